@@ -14,7 +14,9 @@ first updates work on the wide prior cloud and run longer than the steady state,
 headline as `steady_ms_per_frame`).  The timed region is always that whole sequence: without --steps it is 99 steps
 of one frame update; with `--steps K` it is K steps of F = round(99 / K) consecutive frame updates each (the driver's
 `--steps 20`: 20 steps x 5 updates over a 101-frame sequence) -- a step is one pass of the hot path over one batch of
-input, here F frames for all points.  The W warm-up steps run the first W steps of the same sequence, untimed; the
+input, here F frames for all points.  More steps than the sequence has frame updates (K > 99 on C3, F = 1) run it
+again from the prior, lap after lap, the K steps split evenly over the laps: the scene moves under the camera, and a longer sequence would
+carry the tracked points out of the frames.  The W warm-up steps run the first W steps of the same sequence, untimed; the
 state is then re-initialised (untimed) and the K timed steps start from the prior.  `--burn-in B` (> 0) instead times
 K single-frame steps after B untimed updates (the steady-state window used for A/B runs).  The timed region is repeated
 `--repeats` R = 5 times inside the invocation (re-initialised, untimed, in between): `value`, `ms_per_step` and the
@@ -26,10 +28,17 @@ the timed region (glh_gather_moments inside the library; no torch anywhere).  `-
 starts the N ranks itself (children are started before anything touches a GPU); under torchrun
 (RANK / WORLD_SIZE set) every process is one rank.
 
-The default run (C3, one GPU) adds short SECONDARY legs after the headline, each over its whole sequence from the prior
-on the frames already in memory: exact arithmetic at C3 (the arithmetic the oracle tests pin bit for bit), one GPU's
-shard of C4 (1 250 x 10 000), C5 (2 048 x 5 000, two observers + DEM term), C2, and C3 on RGB frames -- `secondary` in
-the JSON line.
+A plain run measures the headline only: it renders the frames, warms up, times the R repetitions of the K steps, writes
+`--dump-outputs` and prints the line.  `--full` adds what takes runs of its own: one more pass of the timed region with
+HIP events around every launch (roofline, per-stage and steady-state figures, the device-copy bandwidth), the API leg
+(glimpse_amd.Tracker.track), the CPU baselines and, on C3 and one GPU, short SECONDARY legs after the headline, each over
+its whole sequence from the prior on the frames already in memory: exact arithmetic at C3 (the arithmetic the oracle
+tests pin bit for bit), one GPU's shard of C4 (1 250 x 10 000), C5 (2 048 x 5 000, two observers + DEM term), C2, C3 on
+RGB frames and the run from image files -- `secondary` in the JSON line.
+
+`--dump-outputs DIR`: rank 0 writes what the last timed step computed -- the posterior means and sigmas of its F frame
+updates for every point, (F, points, 6) float64 each, and the points' status bits -- as DIR/<name>.npy; beyond 64 MB a
+fixed, seeded sample of the points (DIR/points.npy holds their indices).  The inputs depend on the arguments only.
 
 Prints ONE JSON line on rank 0 (keys: DESIGN.md "Measurement") and exits non-zero when the run is unhealthy.
 """
@@ -57,7 +66,7 @@ def parse_args(argv=None):
                     help="timed steps (default: one per frame update of the whole sequence).  With --burn-in 0 the "
                          "timed region is ALWAYS the configuration's whole sequence from the prior: K steps of F "
                          "consecutive frame updates each, F = round((frames - 1) / K) (--steps 20 on the 100-frame C3: 20 "
-                         "steps x 5 updates)")
+                         "steps x 5 updates); more steps than the sequence has frame updates run it again from the prior, in laps")
     ap.add_argument("--frames-per-step", type=int, default=0,
                     help="frame updates per timed step (0 = automatic, see --steps; 1 with --burn-in > 0)")
     ap.add_argument("--warmup", type=int, default=3)
@@ -108,8 +117,14 @@ def parse_args(argv=None):
                          "re-initialised (untimed) in between; `value` / `ms_per_step` are the MEDIAN repetition's, "
                          "`spread` lists min / max / n (boxes of the pool differ by 3-5 %%, one 44-ms sample says little)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the secondary legs of the default run (exact arithmetic at C3, the C4 shard, C5, C2)")
+                    help="skip the secondary legs of a --full run (exact arithmetic at C3, the C4 shard, C5, C2)")
     ap.add_argument("--dump-moments", default=None, help="rank 0 saves the (gathered) posterior history (T, P, 12) here (.npy)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed (posterior means / sigmas of its frame updates, "
+                         "the points' status bits) as DIR/<name>.npy, float64, at most 64 MB in all")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the profiled pass (roofline, per-stage and steady-state figures, "
+                         "device-copy bandwidth), the secondary legs, the API and from-files legs, the CPU baselines")
     return ap.parse_args(argv)
 
 
@@ -288,6 +303,28 @@ def ssd_flops_per_step(O, tile, boxes, status):
         ho = (boxes[o, :, 3] - boxes[o, :, 1] - th + 1)[ok].astype(np.float64)
         total += 3.0 * tw * th * float((wo * ho).sum())
     return total
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, history, status, last):
+    """What a caller of the timed path receives for its last step: the posterior moments of frames `last` .. T-1 of the
+    (T, points, 12) history -- means (columns 0-5) and sigmas (6-11), float64 -- and every point's status bits.  When
+    these exceed DUMP_LIMIT_BYTES, a sample of the points drawn with a fixed seed (the same points for the same
+    arguments); points.npy lists the points written."""
+    os.makedirs(path, exist_ok=True)
+    hist = np.asarray(history[last:], dtype=np.float64)
+    n_frames, n_points = hist.shape[:2]
+    per_point = (n_frames * 12 + 2) * 8  # means + sigmas, status, index
+    fit = (DUMP_LIMIT_BYTES - 4 * 4096) // per_point  # (less room for the .npy headers)
+    pts = np.arange(n_points)
+    if n_points > fit:
+        pts = np.sort(np.random.default_rng(0).choice(n_points, fit, replace=False))
+    out = {"means": hist[:, pts, 0:6], "sigmas": hist[:, pts, 6:12],
+           "point_status": np.asarray(status)[pts].astype(np.float64), "points": pts.astype(np.float64)}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 _SHARED = {}  # name -> ndarray over anonymous shared memory, allocated before the helpers fork
@@ -897,7 +934,13 @@ def worker(args):
             (max(1, round((cfg["frames"] - 1) / K)) if B == 0 else 1)
     if K < 1:
         raise SystemExit("need at least one timed step")
-    T = 1 + B + K * F  # frames of the sequence: frame 0 initialises, then burn-in, then K steps of F updates
+    # The scene moves under the camera and the tracked points with it: a sequence much longer than the configuration's
+    # would carry them out of the frames.  More steps than the sequence has frame updates run it again from the prior,
+    # lap after lap (re-initialised and burnt in, untimed, in between), the K steps split evenly over the laps.
+    n_laps = 1 if K <= cfg["frames"] - 1 else -(-K // max(1, (cfg["frames"] - 1 - B) // F))
+    laps = [K // n_laps + (i < K % n_laps) for i in range(n_laps)]  # steps of each lap
+    T = 1 + B + laps[0] * F  # frames of the sequence: frame 0 initialises, then burn-in, then a lap's steps of F updates
+    last_end = B + laps[-1] * F  # the frame of the last timed update
     W = min(W, (T - 1) // F)
     strong = args.split == "strong"
     if strong:
@@ -919,7 +962,7 @@ def worker(args):
     # frames: rendered once per job (rank 0), shared with the other ranks as memory-mapped files -- by forked helpers,
     # hence BEFORE anything loads the HIP library (the device count below does)
     cores = usable_cores()
-    secondary = (world == 1 and not args.no_secondary and args.workload == "C3" and args.points is None
+    secondary = (args.full and world == 1 and not args.no_secondary and args.workload == "C3" and args.points is None
                  and args.particles is None and args.motion == "cartesian" and args.dem == "constant" and B == 0 and args.channels == 1
                  and args.bits == 8)
     rendered = {}
@@ -971,7 +1014,7 @@ def worker(args):
             ctx.init_templates(o, 0)
         ctx.record_moments(0)
 
-    C = K * F if args.frames_per_call <= 0 else min(args.frames_per_call, K * F)
+    C = T - 1 - B if args.frames_per_call <= 0 else min(args.frames_per_call, T - 1 - B)
 
     def run(first, count):
         """`count` consecutive frame updates from frame `first`: glh_track calls of up to C frames each (the frame
@@ -1005,32 +1048,40 @@ def worker(args):
     R = max(1, args.repeats)
 
     def timed_pass(profiled):
-        initialise()  # back to the prior (untimed)
-        run(1, B)  # burn-in, untimed
-        ctx.sync()
-        ctx.profile_enable(profiled)
-        ctx.profile_reset()
-        group.barrier()
-        t0 = time.perf_counter()
-        run(1 + B, K * F)
-        got = None
-        if world > 1:
+        """The K steps, lap by lap; `profiled`: HIP events around the launches of the first lap."""
+        total, got = 0.0, None
+        for lap, n in enumerate(laps):
+            if lap > 0:
+                ctx.profile_enable(False)
+            initialise()  # back to the prior (untimed)
+            run(1, B)  # burn-in, untimed
             ctx.sync()
-            got = gather()
-        group.barrier()
-        return group.max(time.perf_counter() - t0), got
+            if lap == 0:
+                ctx.profile_enable(profiled)
+                ctx.profile_reset()
+            group.barrier()
+            t0 = time.perf_counter()
+            run(1 + B, n * F)
+            if world > 1 and lap == len(laps) - 1:
+                ctx.sync()
+                got = gather()
+            group.barrier()
+            total += group.max(time.perf_counter() - t0)
+        return total, got
 
     all_elapsed = []
     for _ in range(R):
-        all_elapsed.append(timed_pass(False)[0])
+        e, gathered = timed_pass(False)  # (the gathered history: checked against the state the last pass left)
+        all_elapsed.append(e)
     elapsed = sorted(all_elapsed)[(R - 1) // 2]  # the median repetition (the lower middle one of an even count)
-    profiled_elapsed, gathered = timed_pass(True)  # (the gathered history: checked against the state this last pass left)
-    stage_ms = ctx.profile_get()
-    dom = max(stage_ms, key=lambda k: stage_ms[k][0])
-    launch_ms = ctx.profile_launches(dom)
-    span_ms = ctx.profile_span(dom)
+    if args.full:
+        profiled_elapsed, gathered = timed_pass(True)
+        stage_ms = ctx.profile_get()
+        dom = max(stage_ms, key=lambda k: stage_ms[k][0])
+        launch_ms = ctx.profile_launches(dom)
+        span_ms = ctx.profile_span(dom)
+        ctx.profile_enable(False)
     streams = ctx.last_track_streams() if C > 1 else 1
-    ctx.profile_enable(False)
     _mark("headline timed")
 
     # health of the run: every point must still be tracked by every observer
@@ -1038,11 +1089,6 @@ def worker(args):
     pt_status = ctx.point_status()
     frac_ok = float((status == 0).mean())
     n_err = int((pt_status != 0).sum())
-    # algorithmic bytes / SSD flops of one step, from the search boxes of the last timed step (the smallest tiles
-    # of the sequence: the tile term, ~4 % of the bytes, is if anything understated for the first frames)
-    boxes = ctx.search_boxes()
-    abytes = algorithmic_bytes_per_step(wl.P, wl.N, wl.O, wl.tile, boxes, status, wl.channels * wl.bits // 8)
-    flops = ssd_flops_per_step(wl.O, wl.tile, boxes, status)
     moments_local = ctx.get_moments(0, T)
 
     gathered_ok = None
@@ -1056,6 +1102,9 @@ def worker(args):
     rc = 0
     if rank == 0 and args.dump_moments:
         np.save(args.dump_moments, gathered[0] if world > 1 else moments_local)
+    if rank == 0 and args.dump_outputs:
+        history, point_status = gathered if world > 1 else (moments_local, pt_status)
+        dump_outputs(args.dump_outputs, history[:last_end + 1], point_status, last_end + 1 - F)
     if rank == 0:
         total_points = sum(sizes)
         value = total_points * wl.N * K * F / elapsed
@@ -1073,16 +1122,15 @@ def worker(args):
                        "value_min": total_points * wl.N * K * F / max(all_elapsed),
                        "value_max": total_points * wl.N * K * F / min(all_elapsed),
                        "ms_per_step_all": [round(1e3 * e / K, 5) for e in all_elapsed],
-                       "profiled_pass_ms_per_step": 1e3 * profiled_elapsed / K,
-                       "note": "the n repetitions run without event timers; one more pass of the same region with HIP "
-                               "events around every launch gives the roofline's launch durations and GPU span"},
+                       "note": "the n repetitions run without event timers"},
             "higher_is_better": True,
             "scaling": "strong" if strong else "weak",
             "vs_baseline": None,
             "dtype": "f64",
             "data": "synthetic",
             "config": dict(wl.describe(args.motion), dem=args.dem, rng="device Philox4x32-7",
-                           math=args.math, untimed_launches=W * F + B, untimed_kernel_launches=(W * F + B) * streams,
+                           math=args.math, untimed_launches=W * F + B * len(laps),
+                           untimed_kernel_launches=(W * F + B * len(laps)) * streams, laps=len(laps),
                            parallelism=f"points sharded x{world}",
                            total_points=total_points, frames_per_s=K * F / elapsed, burn_in_steps=B, frames_per_call=C,
                            frame_updates_per_step=F, track_streams=streams,
@@ -1095,13 +1143,23 @@ def worker(args):
                                    + getattr(group, "why_host", "") + ")"}[transport],
             "health": {"observer_ok_fraction": frac_ok, "points_with_error_bits": n_err,
                        "gathered_moments_finite": gathered_ok,
-                       "final_means_finite": bool(np.isfinite(moments_local[T - 1]).all())},
+                       "final_means_finite": bool(np.isfinite(moments_local[last_end]).all())},
         }
+    if rank == 0 and args.full:
+        Kp = laps[0]  # (the steps of the profiled lap: the figures below are per step and frame of that lap)
+        out["spread"]["profiled_pass_ms_per_step"] = 1e3 * profiled_elapsed / K
+        out["spread"]["note"] += ("; one more pass of the same region with HIP events around every launch gives the "
+                                  "roofline's launch durations and GPU span")
+        # algorithmic bytes / SSD flops of one step, from the search boxes of the last timed step (the smallest tiles
+        # of the sequence: the tile term, ~4 % of the bytes, is if anything understated for the first frames)
+        boxes = ctx.search_boxes()
+        abytes = algorithmic_bytes_per_step(wl.P, wl.N, wl.O, wl.tile, boxes, status, wl.channels * wl.bits // 8)
+        flops = ssd_flops_per_step(wl.O, wl.tile, boxes, status)
         tot = sum(ms for ms, _ in stage_ms.values())
         dom_ms, dom_n = stage_ms[dom]
         per_launch_ms = dom_ms / max(dom_n, 1)
-        launches_per_step = dom_n / K
-        launches_per_frame = dom_n / (K * F)
+        launches_per_step = dom_n / Kp
+        launches_per_frame = dom_n / (Kp * F)
         # one launch of the dominant kernel processes P*N particle-frames (SURVEY 8(d) per-unit bytes); `abytes` are
         # the algorithmic bytes of ONE frame update
         kern = KERNEL_OF_STAGE.get(dom, dom)
@@ -1114,7 +1172,7 @@ def worker(args):
         # HBM bytes of a frame from the committed PMC passes: per launch x the launches of a frame (like `achieved`, which
         # is the bytes of a frame over the time of a frame)
         traffic = pmc_traffic_per_frame(wl, kern) if wl.channels == 1 and wl.bits == 8 else None
-        span_per_frame_ms = span_ms / (K * F)
+        span_per_frame_ms = span_ms / (Kp * F)
         per_launch_ach = abytes / launches_per_frame / (per_launch_ms * 1e-3) / 1e9
         ach = abytes / (span_per_frame_ms * 1e-3) / 1e9 if streams > 1 else per_launch_ach
         roof = {"kernel": kern, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS,
@@ -1125,7 +1183,7 @@ def worker(args):
                                "points": wl.P / launches_per_frame},
                 "algorithmic_bytes_per_launch": abytes / launches_per_frame,
                 "algorithmic_bytes_per_particle_frame": abytes / (wl.P * wl.N),
-                "ssd_fp32_tflops": flops / (tot / (K * F) * 1e-3) / 1e12,
+                "ssd_fp32_tflops": flops / (tot / (Kp * F) * 1e-3) / 1e12,
                 # what a float4 copy kernel reaches on this chip (MI355X_MICROARCH.md), and this GPU's own
                 # hipMemcpyDtoD rate ("a measured device-copy ceiling")
                 "achievable_GBps": HBM_ACHIEVABLE_GBS, "frac_of_achievable": ach / HBM_ACHIEVABLE_GBS,
@@ -1156,9 +1214,9 @@ def worker(args):
                                   "source": "profiles/" + sq_file,
                                   "source_run": "committed profile, not measured in this run: a separate rocprofv3 "
                                                 "--pmc SQ_INSTS_VALU pass of this command on the builder's gpurun box"}
-        out["stage_ms_per_step"] = {k: ms / K for k, (ms, _) in stage_ms.items() if ms > 0}
+        out["stage_ms_per_step"] = {k: ms / Kp for k, (ms, _) in stage_ms.items() if ms > 0}
         if len(launch_ms) == dom_n and launches_per_frame == 1:
-            tail = launch_ms[-min(20, K * F):]
+            tail = launch_ms[-min(20, Kp * F):]
             out["steady_ms_per_frame"] = float(tail.mean())
             out["steady_ms_per_step"] = float(tail.mean()) * F
             out["steady_value"] = wl.P * wl.N / (float(tail.mean()) * 1e-3) * world
@@ -1177,7 +1235,7 @@ def worker(args):
             ctx_closed = True
             out["secondary"] = secondary_legs(args, device, T, rendered, seed)
             _mark("secondary legs")
-        if not args.no_api:
+        if args.full and not args.no_api:
             if not ctx_closed:
                 ctx.close()
             ctx_closed = True
@@ -1194,7 +1252,7 @@ def worker(args):
                     except Exception as e:  # noqa: BLE001
                         out["secondary"][f"C3_from_files_{fmt}"] = {"error": repr(e)}
                 _mark("run from files")
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(wl, frames, T, args.cpu_seconds)
                 _mark("CPU baseline, one core")

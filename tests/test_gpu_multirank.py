@@ -82,7 +82,7 @@ def test_bench_two_ranks_on_one_gpu_match_one_rank(tmp_path):
     assert two["health"]["points_with_error_bits"] == 0
     assert two["config"]["total_points"] == 16 and two["config"]["points_per_gpu"] == 8
     assert "host copies" in two["collective"]
-    one = _bench(["--gpus", "1", "--dump-moments", str(tmp_path / "one.npy")] + common)
+    one = _bench(["--gpus", "1", "--full", "--dump-moments", str(tmp_path / "one.npy")] + common)
     assert one["n_gpus"] == 1 and one["config"]["total_points"] == 16
     assert one["roofline"]["kernel"] == "k_point_step" and one["steps"] == 3
     assert one["health"]["final_means_finite"]

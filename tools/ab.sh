@@ -16,7 +16,7 @@ for i in 1 2 3; do
         --*) extra=$v ;;
         *) export $v ;;
       esac
-      python bench.py --no-cpu-baseline --no-api "$@" $extra 2>/dev/null | python -c "
+      python bench.py --full --no-cpu-baseline --no-api "$@" $extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']; print('$v', round(d['ms_per_step'],4), round(r['avg_launch_ms']*r['launches_per_step'],4), 'span', round(r.get('gpu_span_ms_per_frame', 0)*d['config']['frame_updates_per_step'],4), 'streams', r.get('concurrent_launches', 1))"
     )
