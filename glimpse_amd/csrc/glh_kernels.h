@@ -1120,7 +1120,7 @@ __device__ __forceinline__ bool np_sum_f32_block(const float* a, int n, int row_
 // level by one wave (LDS operations of a wave complete in order: a level reads what the level below wrote).
 // `load(i)`: item i of the array (the squares of the normalisation are formed here, not stored); `node`: 256 words,
 // `val`: 256 floats of LDS.  All threads; barriers inside.  (The serial walk above: 35 k and 55 k cycles of a float32 frame's
-// 217 k-cycle tile stage, tools/experiments/r04_jobs/j31_float_split.sh.)
+// 217 k-cycle tile stage, profiles/ab_r04/r4j31_phase_f32_before.txt.)
 constexpr uint32_t NP_NODE_INNER = 0xffffffffu;
 template <typename LOAD>
 __device__ __forceinline__ float np_leaf_8lanes(int off, int len, int sub, LOAD load) {

@@ -495,11 +495,6 @@ GLH_HD bool raster_window_axis(const double* a, double g0, double k, double x, i
 template <bool PAIR>
 GLH_HD bool raster_sample_window(const RasterPatch* p0, const RasterPatch* p1, double x, double y, double& v0, double& v1,
                                  const RasterWin* win = nullptr) {
-#ifdef GLH_ABLATE_SAMPLE  // (diagnostic build: what the samples cost where they stand -- the value is not the raster's)
-  v0 = x * 1e-9 + y * 1e-9;
-  if constexpr (PAIR) v1 = 0.3 + x * 1e-12;
-  return true;
-#endif
   int li, lj;
   double tx, ty;
   const bool okx = raster_window_axis(p0->ax, win ? win->x0 : p0->ax[0], win ? win->kx : p0->fkx, x, li, tx);
@@ -550,12 +545,6 @@ GLH_HD double raster_sample(const RasterDev& r, double x, double y, int order, b
       double v, unused;
       if (raster_sample_window<false>(patch, patch, x, y, v, unused, win)) return v;
     }
-#ifdef GLH_ABLATE_COLD  // (diagnostic build: no general code behind the window -- what its inlined copies cost the hot path)
-    if (patch) {
-      *oob = true;
-      return NAN;
-    }
-#endif
   }
   // (Tried in round 5: this general code as a real function called from the particle loops -- 20 .. 30 inlined copies of it
   // make the raster instantiations 370 KB -- does not compile: a call inside divergent control flow ends in the backend's

@@ -28,29 +28,6 @@
 
 namespace glh {
 
-// Two observers, plain code (round 5, experiment -DGLH_PT_RECOMP=1): observer 1's coordinates and the DEM term are not
-// parked in memory between phase A and phase C (32 + 16 bytes per particle-frame through the uv scratch and the weights
-// scratch) -- phase C re-evolves the particle from its pre-evolve record, like the gather does, and projects it again.
-#ifndef GLH_PT_PRIO
-#define GLH_PT_PRIO 0
-#endif
-#ifndef GLH_PT_RECOMP
-#define GLH_PT_RECOMP 0
-#endif
-#ifndef GLH_PT_PREFETCH2
-#define GLH_PT_PREFETCH2 0
-#endif
-// Tangent models over rasters: phase A parks every particle's evolved height for the gather's re-evolution (1) or the
-// gather samples the surface again (0: an experiment of round 5, now that a sample from the window is ~45 instructions).
-#ifndef GLH_PT_ZPARK
-#define GLH_PT_ZPARK 1
-#endif
-#ifndef GLH_PT_LDS_BARRIERS_A
-#define GLH_PT_LDS_BARRIERS_A 0
-#endif
-
-constexpr int PT_BLK = 512;    // threads per workgroup (TB) for N <= 5120: two workgroups share a CU
-constexpr int PT_BLK_BIG = 1024;  // TB for larger N: c[N] alone is > half the LDS, one 16-wave workgroup per CU
 constexpr int PT_MAX_TILE = 63;  // largest template side the fused kernel handles (rows padded to 64 floats)
 constexpr int PT_NSTAMP = GLH_NSTAMP;
 constexpr int PT_MAX_OBS = 4;    // observers per point in the fused kernel (= MAX_OBS of the library)
@@ -832,7 +809,6 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
   // general instantiation.
   static_assert(!CONTRACT || FAST, "the compile-time contract belongs to the fast arithmetic");
   constexpr bool COMMON = CONTRACT;
-  constexpr bool RECOMP = GLH_PT_RECOMP && NOBS == 2 && PPT > 0 && !SURF;
   const int rng_mode = COMMON ? (int)GLH_RNG_PHILOX : a.rng_mode;
   PT_STAMP(0);
   const uint16_t* uin = COMMON || a.uidx_in ? a.uidx_in + (size_t)pt * N : nullptr;
@@ -1051,13 +1027,8 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
     if constexpr (SURF) {
       bool oob = false;  // (flagged by phase A, which evolved the same particle)
       if (GRID && tangent_pt) {
-#if GLH_PT_ZPARK
         evolve_noise(rng_mode, a.normals, a.seed, a.step, pt, a.pt_base, k, N, n, false);
         evolve_particle<FAST, GRID, true>(x, m, n, tau, tau2, a.surf, &oob, nullptr, z_parked);
-#else
-        evolve_noise(rng_mode, a.normals, a.seed, a.step, pt, a.pt_base, k, N, n, true);
-        evolve_particle<FAST, GRID, false>(x, m, n, tau, tau2, a.surf, &oob, s_patches.get(), 0.0, wins);
-#endif
       } else {
         // (with rasters the tangent models took the branch above, and the other models' step reads no surface: the copy
         // without raster code serves -- the gather of the raster instantiations carries no sampler at all)
@@ -1122,14 +1093,6 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
       }
       if (i < N) {
         double n[3];
-#ifdef GLH_PAD_VALU  // sensitivity probe: this many extra vector instructions per particle (tools/ab.sh pad.so)
-        {
-          uint32_t padv = (uint32_t)i;
-#pragma unroll
-          for (int q = 0; q < GLH_PAD_VALU; ++q) asm volatile("v_xor_b32 %0, %0, %1" : "+v"(padv) : "v"(tid));
-          asm volatile("" ::"v"(padv));
-        }
-#endif
         evolve_noise(rng_mode, a.normals, a.seed, a.step, pt, a.pt_base, i, N, n, third);
         if constexpr (SURF)
           evolve_particle<FAST, GRID>(x, m, n, tau, tau2, a.surf, &raster_oob, s_patches.get(), 0.0, wins);
@@ -1141,9 +1104,7 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
         }
 #pragma unroll
         for (int k = 0; k < 6; ++k) bad |= isnan(x[k]);
-#ifndef GLH_ABLATE_ZP
-        if (GLH_PT_ZPARK && GRID && tangent_pt) ZP[i] = x[2];  // (for the gather's re-evolution: evolve_loaded)
-#endif
+        if (GRID && tangent_pt) ZP[i] = x[2];  // (for the gather's re-evolution: evolve_loaded)
         if (with_term) {
           // CartesianMotion.compute_log_likelihoods (motion.py:181-204) of the evolved particle
           double ll = 0.0;
@@ -1153,7 +1114,7 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
             const double d = m[16] - x[2];
             ll = (1.0 / (2.0 * (zs * zs))) * (d * d);
           }
-          if constexpr (!RECOMP) W[i] = ll;  // (RECOMP: phase C makes the term again from the re-evolved height)
+          W[i] = ll;
         }
         if (with_viewshed) view_bits |= viewshed_bits(a.surf, x[0], x[1]);
 #pragma unroll
@@ -1172,7 +1133,7 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
               c[i] = u;
               V0[i] = v;
             }
-          } else if constexpr (!RECOMP)
+          } else
             reinterpret_cast<double2*>(a.uv)[((size_t)o * a.P + pt) * N + i] = make_double2(u, v);
           if (isnan(u) || isnan(v)) {
             nanf[o] = true;
@@ -1211,13 +1172,7 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
         b[0] = r0; b[1] = r1; b[2] = r2m; b[3] = r3; b[4] = r4;
       }
     }
-#if GLH_PT_LDS_BARRIERS_A
-    // (round 5) LDS only: __syncthreads() also waits for this wave's outstanding memory operations -- here the template
-    // loads issued a few lines up precisely so that they travel WHILE the box is reduced, and the stores of phase A
-    pt_lds_barrier();
-#else
     __syncthreads();
-#endif
     PT_STAMP(18);
     if (tid < NOBS) {
       const int o = tid;
@@ -1257,32 +1212,10 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
       a.obs_status[slot] = st;
     }
     PT_STAMP(19);
-#if GLH_PT_LDS_BARRIERS_A
-    pt_lds_barrier();  // (the box and the status words just stored to memory are for the host: nobody here waits for them)
-#else
     __syncthreads();
-#endif
   }
 
   PT_STAMP(1);
-#if GLH_PT_PRIO
-  {
-    // experiment (round 5): a workgroup whose search tiles are large -- the slow point a launch of one round ends with --
-    // takes issue priority over its neighbour on the compute unit for the rest of its life
-    int area = 0, nok = 0;
-#pragma unroll
-    for (int o = 0; o < NOBS; ++o)
-      if (s_status[o] == GLH_OBS_OK) {
-        area += (s_box[o][2] - s_box[o][0]) * (s_box[o][3] - s_box[o][1]);
-        ++nok;
-      }
-    area = __builtin_amdgcn_readfirstlane(area);
-    const int base = __builtin_amdgcn_readfirstlane(nok) * (a.tw + 8) * (a.th + 8);
-    if (area * 2 > base * 4) __builtin_amdgcn_s_setprio(3);
-    else if (area * 2 > base * 3) __builtin_amdgcn_s_setprio(2);
-    else if (area * 4 > base * 5) __builtin_amdgcn_s_setprio(1);
-  }
-#endif
   // ---------------- B + C per observer, in the reference's order (tracker.py:139-146) ----------
   bool outside = false;
   const bool w_here = NOBS == 1 && !a.has_dem;  // uniform: phase C of observer 0 writes weights, not log likelihoods
@@ -1417,53 +1350,6 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
         }
         c_ready = true;
         w_done = w_here;
-      } else if constexpr (RECOMP) {
-        if (!c_ready) {  // observer 0 was skipped: c[] still holds its parked coordinates
-          for (int i = tid; i < N; i += TB) c[i] = 0.0;
-          c_ready = true;
-        }
-        // The particle again: its pre-evolve record (L2 / Infinity-Cache hot: phase A streamed it), the same noise, the
-        // same step, the same projection as phase A -- the same bits --, and with the evolved height at hand the motion
-        // model's term (tracker.py:143: appended last) and the weight in the same pass.
-        const bool mterm = a.has_dem && motion_term;  // uniform
-        const double zs = m[17];
-        auto rec_of = [&](int i) -> int { return COMMON || uin ? (int)uin[i < N ? i : 0] : (i < N ? i : 0); };
-        int rn = rec_of(tid + TB);
-        double2 nx0, nx1, nx2;
-        {
-          const double2* src = Pin2 + (size_t)rec_of(tid) * rec_stride;
-          nx0 = src[0]; nx1 = src[chunk_stride]; nx2 = src[2 * chunk_stride];
-        }
-#pragma unroll 1
-        for (int i = tid; i < N; i += TB) {
-          asm volatile("" ::: "memory");  // (camera / motion constants from LDS every iteration, as in phase A)
-          double x[6] = {nx0.x, nx0.y, nx1.x, nx1.y, nx2.x, nx2.y};
-          {
-            const double2* src = Pin2 + (size_t)rn * rec_stride;
-            nx0 = src[0]; nx1 = src[chunk_stride]; nx2 = src[2 * chunk_stride];
-            rn = rec_of(i + 2 * TB);
-          }
-          double n[3];
-          evolve_noise(rng_mode, a.normals, a.seed, a.step, pt, a.pt_base, i, N, n, third);
-          evolve_cartesian_m<FAST>(x, m, n, tau, tau2);
-          double u, v;
-          if constexpr (COMMON)
-            project_simple_fast(s_cam[o], x[0], x[1], x[2], u, v);
-          else
-            project_m<FAST>(s_cam[o], a.cam_flags[o], x[0], x[1], x[2], u, v);
-          double ll = c[i];
-          ll += eval(u, v) * scale;
-          if (mterm) {
-            double t = 0.0;
-            if (zs != 0.0) {
-              const double d = m[16] - x[2];
-              t = (1.0 / (2.0 * (zs * zs))) * (d * d);
-            }
-            ll += t;
-          }
-          c[i] = weight_of<FAST>(ll, tab32);
-        }
-        w_done = true;
       } else if constexpr (NOBS > 1) {
         if (!c_ready) {  // observer 0 was skipped: c[] still holds its parked coordinates
           for (int i = tid; i < N; i += TB) c[i] = 0.0;
@@ -1476,24 +1362,6 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
           // operations in the same order as the separate loop below, which then has nothing left to do)
           const bool mterm = a.has_dem && motion_term;  // uniform
           double wn = mterm ? W[tid < N ? tid : 0] : 0.0;
-#if GLH_PT_PREFETCH2
-          // (round 5 experiment: the coordinates and the term of the particle after next are requested as well -- what
-          // the scratch returns comes from memory, a microsecond away under load, and one particle's sampling is less)
-          double2 qn2 = uvp[tid + TB < N ? tid + TB : 0];
-          double wn2 = mterm ? W[tid + TB < N ? tid + TB : 0] : 0.0;
-          for (int i = tid; i < N; i += TB) {
-            const double2 q = qn;
-            const double wi = wn;
-            qn = qn2;
-            wn = wn2;
-            qn2 = uvp[i + 2 * TB < N ? i + 2 * TB : 0];
-            if (mterm) wn2 = W[i + 2 * TB < N ? i + 2 * TB : 0];
-            double ll = c[i];
-            ll += eval(q.x, q.y) * scale;
-            if (mterm) ll += wi;  // (tracker.py:143: appended last)
-            c[i] = weight_of<FAST>(ll, tab32);
-          }
-#else
           for (int i = tid; i < N; i += TB) {
             const double2 q = qn;
             const double wi = wn;
@@ -1504,7 +1372,6 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
             if (mterm) ll += wi;  // (tracker.py:143: appended last)
             c[i] = weight_of<FAST>(ll, tab32);
           }
-#endif
           w_done = true;
         } else {
           for (int i = tid; i < N; i += TB) {
@@ -1756,35 +1623,13 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
   if (outside) flag_point(a.pt_status, a.pt_err_frame, pt, GLH_PT_SAMPLE_OUTSIDE, a.frame);
   if (!w_done) {
     const bool mterm = a.has_dem && motion_term;  // uniform
-    if (RECOMP && mterm) {
-      // (the last observer was skipped on this frame, so its pass did not append the motion model's term: the evolved
-      // height once more, from the record)
-      const double zs = m[17];
-#pragma unroll 1
-      for (int i = tid; i < N; i += TB) {
-        const double2* src = Pin2 + (size_t)(COMMON || uin ? (int)uin[i] : i) * rec_stride;
-        const double2 v0 = src[0], v1 = src[chunk_stride], v2 = src[2 * chunk_stride];
-        double x[6] = {v0.x, v0.y, v1.x, v1.y, v2.x, v2.y};
-        double n[3];
-        evolve_noise(rng_mode, a.normals, a.seed, a.step, pt, a.pt_base, i, N, n, third);
-        evolve_cartesian_m<FAST>(x, m, n, tau, tau2);
-        double ll = c[i], t = 0.0;
-        if (zs != 0.0) {
-          const double d = m[16] - x[2];
-          t = (1.0 / (2.0 * (zs * zs))) * (d * d);
-        }
-        ll += t;
-        c[i] = weight_of<FAST>(ll, tab32);
-      }
-    } else {
-      double wn = mterm ? W[tid < N ? tid : 0] : 0.0;
-      for (int i = tid; i < N; i += TB) {
-        double ll = c[i];
-        const double wi = wn;
-        if (mterm) wn = W[i + TB < N ? i + TB : 0];
-        if (mterm) ll += wi;  // the motion model's term is appended last (tracker.py:143)
-        c[i] = weight_of<FAST>(ll, tab32);  // the weights stay in LDS until the gather of phase E
-      }
+    double wn = mterm ? W[tid < N ? tid : 0] : 0.0;
+    for (int i = tid; i < N; i += TB) {
+      double ll = c[i];
+      const double wi = wn;
+      if (mterm) wn = W[i + TB < N ? i + TB : 0];
+      if (mterm) ll += wi;  // the motion model's term is appended last (tracker.py:143)
+      c[i] = weight_of<FAST>(ll, tab32);  // the weights stay in LDS until the gather of phase E
     }
     __syncthreads();
   }
@@ -2068,18 +1913,12 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
 #pragma unroll
   for (int k = 0; k < 6; ++k) K[k] = s_K[k];
   double s0 = 0.0, s1[6] = {0, 0, 0, 0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0};
-#ifndef GLH_PT_GU
-#define GLH_PT_GU 2
-#endif
   // records in flight per thread.  The general code keeps ONE: with two, its 128 registers spill two record chunks inside this
   // loop (40 B of scratch); one record in flight, none -- TangentCartesianMotion -3.4 %, uint16 frames -3.3 %, over rasters
   // +-0 (profiles/ab_r04/r4j59_ab_gu1.txt).  The plain code has the registers for two (round 3: -1 % against one).
   // The 1 024-thread plain code (C4: one workgroup per CU, nothing else hides its latencies) takes three: -1.5 %, no scratch
   // (r4j71_ab_gu_plain.txt; C3 / C5 at 512 threads: one, two and three within noise).
-#ifndef GLH_PT_GU_SURF
-#define GLH_PT_GU_SURF 1
-#endif
-  constexpr int GU = SURF ? GLH_PT_GU_SURF : (TB >= 1024 ? GLH_PT_GU + 1 : GLH_PT_GU);
+  constexpr int GU = SURF ? 1 : (TB >= 1024 ? 3 : 2);
   // The record index of a survivor, uin[source], is a memory load the record loads depend on: the words of the NEXT
   // iteration (source | copies from the rank table, record index from memory) are fetched while this iteration's
   // records are evolved (C4, whose 16-wave workgroup has its CU to itself: -0.8 %; C3 / C5: -0.2 .. -0.4 %).
@@ -2094,11 +1933,7 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
       const int h = h0 + g * TB;
       sc_n[g] = h < U ? usc[h] : 0u;
       rec_n[g] = COMMON || uin ? (int)uin[sc_n[g] & 0xffffu] : (int)(sc_n[g] & 0xffffu);
-#ifndef GLH_ABLATE_ZP
-      zp_n[g] = GLH_PT_ZPARK && GRID && tangent_pt ? ZP[sc_n[g] & 0xffffu] : 0.0;
-#else
-      zp_n[g] = 0.0;  // (diagnostic build: what the parked heights cost -- wrong results)
-#endif
+      zp_n[g] = GRID && tangent_pt ? ZP[sc_n[g] & 0xffffu] : 0.0;
     }
   };
   fetch_next(tid);

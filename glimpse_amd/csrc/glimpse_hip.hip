@@ -189,9 +189,8 @@ struct glh_ctx {
   hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
   int last_track_streams = 1;  // streams the last glh_track used
   int n_cus = 256;             // compute units of the device (hipDeviceProp: glh_create)
-  bool capturing = false;      // glh_track is recording its frame loop into a hipGraph (no event timers meanwhile)
-  hipGraphExec_t track_graph = nullptr;  // the last captured frame loop (kept until the next one or the context's end)
-  int force_tb = 0;            // experiment (GLH_PT_BIG_FRAMES): this launch runs the 1 024-thread instantiation
+  // diagnostic (GLH_PT_STOP="stamp:frame", read by glh_create): the fused launches of that frame end at that phase stamp
+  int stop_stamp = -1, stop_frame = -1;
   double *sse = nullptr, *sse_copy = nullptr, *ll_dbg = nullptr;
   double* lu = nullptr;
   double* poly = nullptr;
@@ -253,7 +252,7 @@ struct StageTimer {
   hipStream_t s;
   StageTimer(glh_ctx* ctx, int st, hipStream_t on = nullptr) : c(ctx), stage(st), s(on ? on : ctx->stream) {
     c->launches[st]++;
-    if (!c->profiling || c->capturing) return;
+    if (!c->profiling) return;
     auto get = [&]() {
       hipEvent_t e;
       if (!c->pool.empty()) {
@@ -331,7 +330,6 @@ extern "C" int glh_destroy(glh_ctx* c) {
   (void)hipSetDevice(c->cfg.device_id);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   if (c->comm) (void)glh_comm_destroy(c);
-  if (c->track_graph) (void)hipGraphExecDestroy(c->track_graph);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
   for (auto e : c->pin_ev)
     if (e) (void)hipEventDestroy(e);
@@ -408,6 +406,13 @@ extern "C" int glh_create(const glh_config* cfg, glh_ctx** out) {
   {
     int cus = 0;  // (what decides whether a batch is two rounds of workgroups per half: glh_track's two streams)
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, k.device_id) == hipSuccess && cus > 0) c->n_cus = cus;
+  }
+  if (const char* stop = getenv("GLH_PT_STOP")) {  // (tools/phase_counts.sh: one process per setting)
+    int s = -1, f = -1;
+    if (sscanf(stop, "%d:%d", &s, &f) == 2) {
+      c->stop_stamp = s;
+      c->stop_frame = f;
+    }
   }
   const size_t P = k.max_points, N = k.max_particles, O = k.n_observers;
   c->tile_cap = k.max_tile * k.max_tile;
@@ -1526,17 +1531,12 @@ static bool fused_plan(const glh_ctx* c, int* r2_bytes, int mode = -1) {
   const int typical = pt_small_bytes(c->tw, c->th, nb) + 48 * pt_search_ld(48) * 4 + pt_keys_count(48, 48) * 2;
   // (a context with rasters runs the instantiations that keep windows of them in static LDS)
   const int patch = c->rasters[0].z || c->rasters[1].z || c->rasters[2].z ? PT_PATCH_LDS : 0;
-  // experiment (GLH_PT_LDS_HALF=bytes): another bound for the dynamic LDS of a workgroup that shares its compute unit --
-  // 49 152 lets THREE 512-thread workgroups in (with a build at 6 waves per SIMD: -DPT_MINW=6)
-  int lds_shared = PT_LDS_HALF;
-  if (const char* e = getenv("GLH_PT_LDS_HALF")) lds_shared = std::max(16 * 1024, std::min(atoi(e), PT_LDS_HALF));
-  const int lds_half = lds_shared - patch, lds_max = PT_LDS_MAX - patch;
+  const int lds_half = PT_LDS_HALF - patch, lds_max = PT_LDS_MAX - patch;
   int r2;
   if (cN + std::max(r2_min, typical) <= lds_half)
     r2 = lds_half - cN;
   else
     r2 = std::min(lds_max - cN, 72 * 1024);
-  if (getenv("GLH_PT_ONE_BLOCK")) r2 = std::min(lds_max - cN, 100 * 1024);  // experiment: 1 workgroup / CU
   if (mode == 2) r2 = r2_min;  // test hook: typical tiles no longer fit -> HBM workspaces
   if (r2 < r2_min || cN + r2 > lds_max) return false;  // (N beyond ~10 900: the staged kernels take the step)
   *r2_bytes = r2;
@@ -1549,7 +1549,8 @@ static bool fused_plan(const glh_ctx* c, int* r2_bytes, int mode = -1) {
 static int cell_cap(const glh_ctx* c) {
   int r2 = 0;
   if (!fused_plan(c, &r2, c->fused == 2 ? 2 : 1)) return 0;
-  const int tb = c->N > 10 * PT_BLK ? PT_BLK_BIG : PT_BLK;
+  int tb, ppt;
+  pt_shape(c->N, c->cfg.n_observers, &tb, &ppt);
   return std::min(r2 / (GLH_CELL_LD * 8), 2 * tb / 4);
 }
 
@@ -1638,11 +1639,7 @@ static int fused_step(glh_ctx* c, int frame, double tau, const int32_t* images, 
   a.hp_ry = c->hp_ry;
   a.interp_k = c->interp_k;
   a.pt_base = c->pt_base;
-  a.stop_at = -1;
-  if (const char* stop = getenv("GLH_PT_STOP")) {  // diagnostic: "stamp:frame" -- that launch ends at that stamp
-    int k = -1, f = -1;
-    if (sscanf(stop, "%d:%d", &k, &f) == 2 && f == frame) a.stop_at = k;
-  }
+  a.stop_at = c->stop_frame == frame ? c->stop_stamp : -1;
   a.surf = surfaces(c);
   a.nleaves = c->nleaves;
   a.nnodes = c->nnodes;
@@ -1655,18 +1652,9 @@ static int fused_step(glh_ctx* c, int frame, double tau, const int32_t* images, 
                                     pt_align16(4 * pt_plan_ints(c->nleaves, c->nnodes, c->nlevels, c->nroots)),
                                 (size_t)pt_park_bytes());
     const dim3 grid(npts);
-    // N <= 5120: 512 threads, two workgroups per CU; larger N: 1024 threads, one per CU.  u of observer 0 in registers
-    // (PPT per thread) and its v in c[] up to 10240 particles, both parked in LDS / the uv scratch beyond that and with
-    // three or four observers.  Two observers keep observer 0 in registers as well (round 4: the first observer's pass is
-    // peeled off the observer loop, so the registers are dead during the second observer's tile pipeline).
-    const bool big = c->N > 10 * PT_BLK || c->force_tb == PT_BLK_BIG;
-    const int tb = big ? PT_BLK_BIG : PT_BLK;
+    int tb, ppt;
+    pt_shape(c->N, O, &tb, &ppt);
     const dim3 block(tb);
-    int ppt = c->N <= 4 * tb ? 4 : (c->N <= 10 * tb ? 10 : 0);
-    if (big && ppt == 4) ppt = 10;
-    if (O == 2 && ppt == 4) ppt = 10;  // (the library carries <.., 10, 2> only)
-    if (getenv("GLH_PT_UVLDS") || O >= 3) ppt = 0;
-    if (O == 2 && getenv("GLH_PT_PPT0")) ppt = 0;  // diagnostic: the round-3 form (everything through the scratch)
     // the general instantiation: gridded surfaces and / or motion models other than CartesianMotion
     const bool fast = use_fast(c);
     // ... and, in fast arithmetic, everything the common instantiation is not compiled for (glh_point.h: COMMON): it
@@ -1679,17 +1667,12 @@ static int fused_step(glh_ctx* c, int frame, double tau, const int32_t* images, 
     for (int o = 0; o < O; ++o) plain &= c->obs[o].bits == 8;            // ... of 8-bit frames
     const bool rast = c->rasters[0].z || c->rasters[1].z || c->rasters[2].z;  // (the instantiations with the raster samples)
     const bool surf = rast || !c->all_cartesian || (fast && !common) || !plain;
-    int tbv = 512, nobsv = O;
-    if (big) {
-      tbv = 1024;
-      if (ppt != 10) ppt = 0;
-    }
-    c->last_variant[0] = tbv; c->last_variant[1] = ppt; c->last_variant[2] = nobsv;
+    c->last_variant[0] = tb; c->last_variant[1] = ppt; c->last_variant[2] = O;
     c->last_variant[3] = (fast ? 1 : 0) | (surf ? 2 : 0) | (common ? 4 : 0) | (rast ? 8 : 0);
     // codes the library carries (glh_point_variants.h): exact / exact general / fast common / fast general / fast
     // general under the contract
-    const void* kern = pt_kernel(tbv, ppt, nobsv, rast ? 2 : (surf ? 1 : 0), fast, surf ? common : fast);
-    if (!kern) return fail(GLH_E_STATE, "no instantiation of the fused kernel for <%d, %d, %d>", tbv, ppt, nobsv);
+    const void* kern = pt_kernel(tb, ppt, O, rast ? 2 : (surf ? 1 : 0), fast, surf ? common : fast);
+    if (!kern) return fail(GLH_E_STATE, "no instantiation of the fused kernel for <%d, %d, %d>", tb, ppt, O);
     void* kargs[] = {(void*)&a};
     HIPCHK(hipLaunchKernel(kern, grid, block, kargs, lds, on));
   }
@@ -1798,67 +1781,15 @@ extern "C" int glh_track(glh_ctx* c, int n_frames, const int32_t* frames, const 
   if (fused_ok && !c->track_covariances) {
     if (c->track_streams >= 2) ns = c->track_streams;
     else if (c->track_streams == 0 && c->P > c->n_cus) ns = 2;
-    if (const char* e = getenv("GLH_TRACK_STREAMS")) ns = atoi(e) >= 1 && atoi(e) <= 4 ? atoi(e) : ns;
     ns = std::min(ns, c->P);
   }
   c->last_track_streams = ns;
-  // experiment (GLH_PT_BIG_FRAMES=n): the first n frames of the call run the 1 024-thread instantiation with the whole
-  // CU's LDS (the wide search tiles after the prior fit without the HBM workspaces)
-  int big_frames = 0, r2_big = r2_bytes;
-  if (const char* e = getenv("GLH_PT_BIG_FRAMES")) {
-    if (fused_ok && c->N <= 10 * PT_BLK && O <= 2) {
-      big_frames = atoi(e);
-      const int cN = pt_align16(c->N * 8) + pt_align16(4 * pt_plan_ints(c->nleaves, c->nnodes, c->nlevels, c->nroots));
-      const int patch = c->rasters[0].z || c->rasters[1].z || c->rasters[2].z ? PT_PATCH_LDS : 0;
-      r2_big = std::max(r2_bytes, std::min(PT_LDS_MAX - patch - cN, 100 * 1024));
-    }
-  }
   if (ns == 1) {
-    // experiment (GLH_TRACK_GRAPH=1): the frame loop of a one-stream run as ONE hipGraph launch -- small batches (C2,
-    // a GPU's share of C5) spend 15 % of a frame between two launches
-    const bool graph = fused_ok && !c->track_covariances && getenv("GLH_TRACK_GRAPH") && n_frames > 1;
-    if (graph) {
-      HIPCHK(hipSetDevice(c->cfg.device_id));
-      for (int b = 0; b < 2; ++b)  // (nothing may be allocated while the stream is being captured)
-        if (!c->uidx[b]) CHK(dalloc(&c->uidx[b], (size_t)c->cfg.max_points * c->cfg.max_particles));
-      for (int o = 0; o < O; ++o)
-        if (c->obs[o].bits >= 32) CHK(prepare_bins16(c, o, true));
-      CHK(drain_profile(c));
-      if (c->track_graph) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        (void)hipGraphExecDestroy(c->track_graph);
-        c->track_graph = nullptr;
-      }
-      HIPCHK(hipStreamBeginCapture(c->stream, hipStreamCaptureModeRelaxed));
-      c->capturing = true;
-    }
+    // frame by frame through glh_step (fused or staged), covariances recorded after every frame when asked
     int rc = GLH_OK;
     for (int k = 0; k < n_frames && rc == GLH_OK; ++k) {
-      c->force_tb = k < big_frames ? PT_BLK_BIG : 0;
-      if (fused_ok && (graph || big_frames > 0)) {
-        rc = glh_set_frame(c, frames[k]);
-        if (rc == GLH_OK)
-          rc = fused_step(c, frames[k], taus[k], images + (size_t)k * O, GLH_RNG_PHILOX, nullptr, seed,
-                          k < big_frames ? r2_big : r2_bytes);
-      } else {
-        rc = glh_step(c, frames[k], taus[k], images + (size_t)k * O, GLH_RNG_PHILOX, nullptr, nullptr, seed);
-      }
+      rc = glh_step(c, frames[k], taus[k], images + (size_t)k * O, GLH_RNG_PHILOX, nullptr, nullptr, seed);
       if (rc == GLH_OK && c->track_covariances) rc = glh_record_covariances(c, frames[k]);
-    }
-    c->force_tb = 0;
-    if (graph) {
-      c->capturing = false;
-      hipGraph_t g = nullptr;
-      const hipError_t e1 = hipStreamEndCapture(c->stream, &g);
-      if (rc != GLH_OK) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc;
-      }
-      HIPCHK(e1);
-      hipError_t e2 = hipGraphInstantiate(&c->track_graph, g, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(g);
-      HIPCHK(e2);
-      HIPCHK(hipGraphLaunch(c->track_graph, c->stream));
     }
     return rc;
   }
@@ -1880,12 +1811,10 @@ extern "C" int glh_track(glh_ctx* c, int n_frames, const int32_t* frames, const 
     rc = glh_set_frame(c, frames[k]);
     for (int q = 0; q < ns && rc == GLH_OK; ++q) {
       const int p0 = (int)((int64_t)c->P * q / ns), p1 = (int)((int64_t)c->P * (q + 1) / ns);
-      c->force_tb = k < big_frames ? PT_BLK_BIG : 0;
-      rc = fused_step(c, frames[k], taus[k], images + (size_t)k * O, GLH_RNG_PHILOX, nullptr, seed,
-                      k < big_frames ? r2_big : r2_bytes, p0, p1 - p0, on[q], q == ns - 1);
+      rc = fused_step(c, frames[k], taus[k], images + (size_t)k * O, GLH_RNG_PHILOX, nullptr, seed, r2_bytes, p0,
+                      p1 - p0, on[q], q == ns - 1);
     }
   }
-  c->force_tb = 0;
   for (int q = 1; q < ns; ++q) {
     (void)hipEventRecord(c->ev_join[q - 1], on[q]);
     (void)hipStreamWaitEvent(c->stream, c->ev_join[q - 1], 0);

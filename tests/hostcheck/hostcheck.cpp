@@ -8,6 +8,7 @@
 #include "../../glimpse_amd/csrc/glh_host.h"
 #include "../../glimpse_amd/csrc/glh_math.h"
 #include "../../glimpse_amd/csrc/glh_median.h"
+#include "../../glimpse_amd/csrc/glh_point_variants.h"
 
 using namespace glh;
 
@@ -272,4 +273,12 @@ void hc_raster_patch_fast(const double* z, int nx, int ny, const double* gx, con
   }
 }
 int hc_raster_uniform(const double* g, int n, double lo, double hi) { return raster_coordinates_uniform(g, n, lo, hi) ? 1 : 0; }
+
+// the launch shape of the fused step (glh_host.h: pt_shape), and whether the library carries it (glh_point_variants.h)
+void hc_pt_shape(int n, int o, int* tb_ppt) { pt_shape(n, o, &tb_ppt[0], &tb_ppt[1]); }
+int hc_pt_shape_carried(int tb, int ppt, int nobs) {
+#define HC_PT_SHAPE_IS(TB, PPT, NOBS) || (tb == TB && ppt == PPT && nobs == NOBS)
+  return false GLH_PT_SHAPES(HC_PT_SHAPE_IS) ? 1 : 0;
+#undef HC_PT_SHAPE_IS
+}
 }

@@ -18,7 +18,8 @@ OUT = os.path.join(ROOT, "tests", "hostcheck", "_build", "libhostcheck.so")
 @pytest.fixture(scope="module")
 def hc():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    deps = [SRC] + [os.path.join(ROOT, "glimpse_amd", "csrc", f) for f in ("glh_math.h", "glh_median.h", "glh_host.h")]
+    headers = ("glh_math.h", "glh_median.h", "glh_host.h", "glh_point_variants.h")
+    deps = [SRC] + [os.path.join(ROOT, "glimpse_amd", "csrc", f) for f in headers]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", OUT, SRC], check=True)
     lib = C.CDLL(OUT)
@@ -315,3 +316,26 @@ def test_raster_window_serves_the_same_samples(hc):
                                     len(xy), p(fast))
             np.testing.assert_array_equal(fast[:, 0], fast[:, 1])
             np.testing.assert_allclose(fast[:, 0], vals[:, 0], rtol=0, atol=1e-14 * np.abs(z).max())
+
+
+def test_fused_launch_shapes_are_carried_by_the_library(hc):
+    """glh_host.h: pt_shape -- every (threads, PPT, observers) the fused step can launch for 1 .. 32 768 particles and one to
+    four observers is an instantiation glh_point_variants.h carries, and the shapes the tests and the benchmark rely on
+    stay where they are."""
+    out = np.zeros(2, dtype=np.int32)
+
+    def shape(n, o):
+        hc.hc_pt_shape(n, o, p(out))
+        return int(out[0]), int(out[1])
+
+    missing = set()
+    for o in range(1, 5):
+        for n in range(1, 32769):
+            tb, ppt = shape(n, o)
+            if not hc.hc_pt_shape_carried(tb, ppt, o):
+                missing.add((tb, ppt, o))
+    assert not missing, sorted(missing)
+    pinned = {(2000, 1): (512, 4), (5000, 1): (512, 10), (5000, 2): (512, 10), (5000, 3): (512, 0),
+              (10000, 1): (1024, 10), (10500, 1): (1024, 0), (8000, 4): (1024, 0)}
+    for (n, o), want in pinned.items():
+        assert shape(n, o) == want, (n, o)
