@@ -141,6 +141,7 @@ SIGNATURES = {
     "glh_stage_project_directions": (_I, [_I, _P, _P, _I, _P]),
     "glh_stage_project_depth": (_I, [_I, _P, _P, _I, _I, _P, _P]),
     "glh_stage_unproject": (_I, [_I, _P, _P, _I, _P, _I, _I, _P]),
+    "glh_stage_reproject": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
     "glh_stage_template": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "glh_stage_search_tile": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _I, _P]),
     "glh_stage_template_highpass": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _P]),
@@ -713,6 +714,35 @@ def stage_unproject(cam, uv, depth=None, directions=True, device_id=0):
     check(load().glh_stage_unproject(device_id, _ptr(cam), _ptr(uv), len(uv), _ptr(d), 0 if d is None else len(d),
                                      int(bool(directions)), _ptr(xyz)))
     return xyz
+
+
+REPROJECT_METHODS = {"linear": 0, "nearest": 1}
+REPROJECT_DTYPES = {"uint8": (8, 0), "uint16": (16, 0), "float32": (32, 1), "float64": (64, 1)}
+
+
+def stage_reproject(frames, src_cams, dst_cam, dst_size, method="linear", device_id=0, return_kernel_ms=False):
+    """Image.project (image.py:301-361) over a batch: `frames` (n, h, w, channels) of uint8 / uint16 / float32 / float64,
+    one or three channels, each frame with its own camera `src_cams` (n, CAM_LEN), resampled into `dst_cam` (same
+    position), `dst_size` = (width, height) -> (n, height, width, channels) of the frames' dtype.  One library call: the
+    frames' copies overlap their neighbours' kernels.  `return_kernel_ms`: also the summed kernel time (HIP events)."""
+    if method not in REPROJECT_METHODS:
+        raise ValueError(f"Method '{method}' is not defined")
+    frames = np.ascontiguousarray(frames)
+    if frames.ndim != 4:
+        raise ValueError("frames must be (n, rows, cols, channels)")
+    if frames.dtype.name not in REPROJECT_DTYPES:
+        raise TypeError(f"frames of dtype {frames.dtype}: uint8, uint16, float32 or float64")
+    bits, is_float = REPROJECT_DTYPES[frames.dtype.name]
+    n, h, w, ch = frames.shape
+    src_cams = _arr(src_cams, np.float64, (n, CAM_LEN))
+    dst_cam = _arr(dst_cam, np.float64, (CAM_LEN,))
+    dw, dh = (int(v) for v in dst_size)
+    out = np.empty((n, dh, dw, ch), dtype=frames.dtype)
+    ms = C.c_double(0.0)
+    check(load().glh_stage_reproject(device_id, _ptr(frames), bits, is_float, w, h, ch, n, _ptr(src_cams), _ptr(dst_cam),
+                                     dw, dh, REPROJECT_METHODS[method], _ptr(out),
+                                     C.byref(ms) if return_kernel_ms else None))
+    return (out, ms.value) if return_kernel_ms else out
 
 
 def _frame_dims(frame):

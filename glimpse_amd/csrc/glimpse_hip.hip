@@ -100,12 +100,13 @@ enum Stage {
   ST_WEIGHTS,
   ST_RESAMPLE,
   ST_POINT_STEP,
+  ST_REPROJECT,  // (glh_stage_reproject: stateless, reports its own kernel time)
   ST_COUNT
 };
 static const char* kStageNames[ST_COUNT] = {"init_particles", "evolve_project", "moments",
                                             "template_init",  "tileprep",       "ssd",
                                             "spline_fit",     "weights",        "resample",
-                                            "point_step"};
+                                            "point_step",     "reproject"};
 
 // ------------------------------------------------------------------------------------------
 // context
@@ -2385,6 +2386,152 @@ extern "C" int glh_stage_unproject(int dev, const double* cam, const double* uv,
                      du.as<double>(), n, depth ? dd.as<double>() : nullptr, n_depth, directions, dx.as<double>());
   CHK(finish());
   return dx.down(xyz, (size_t)n * 3 * sizeof(double));
+}
+
+// Image.project over a batch of frames.  Three slots, each a pinned input and output staging buffer and a device source
+// and target frame; three streams (upload, kernel, download) chained by events, so that frame k + 1's upload and frame
+// k - 1's download overlap frame k's kernel -- the staging ring of glh_observer_upload_frame_async, in both directions.
+namespace {
+struct ReprojectRing {
+  static constexpr int NSLOT = 3;
+  hipStream_t up = nullptr, run = nullptr, down = nullptr;
+  hipEvent_t uploaded[NSLOT] = {}, computed[NSLOT] = {}, downloaded[NSLOT] = {};
+  std::vector<hipEvent_t> k0, k1;  // around every kernel (timing)
+  uint8_t *pin_in[NSLOT] = {}, *pin_out[NSLOT] = {}, *dev_in[NSLOT] = {}, *dev_out[NSLOT] = {};
+  ~ReprojectRing() {
+    for (hipStream_t s : {up, run, down})
+      if (s) (void)hipStreamSynchronize(s);
+    for (int k = 0; k < NSLOT; ++k) {
+      for (hipEvent_t e : {uploaded[k], computed[k], downloaded[k]})
+        if (e) (void)hipEventDestroy(e);
+      if (pin_in[k]) (void)hipHostFree(pin_in[k]);
+      if (pin_out[k]) (void)hipHostFree(pin_out[k]);
+      if (dev_in[k]) (void)hipFree(dev_in[k]);
+      if (dev_out[k]) (void)hipFree(dev_out[k]);
+    }
+    for (hipEvent_t e : k0) (void)hipEventDestroy(e);
+    for (hipEvent_t e : k1) (void)hipEventDestroy(e);
+    for (hipStream_t s : {up, run, down})
+      if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+template <typename T>
+void launch_reproject(hipStream_t s, int channels, const CamDev* src_cam, const CamDev* dst_cam, const void* src, int sw,
+                      int sh, int dw, int dh, int method, void* out) {
+  const dim3 grid((dw + RPJ_BX - 1) / RPJ_BX, (dh + RPJ_BY - 1) / RPJ_BY), block(RPJ_BX, RPJ_BY);
+  if (channels == 1)
+    hipLaunchKernelGGL((k_reproject<T, 1>), grid, block, 0, s, src_cam, dst_cam, (const T*)src, sw, sh, dw, dh, method,
+                       (T*)out);
+  else
+    hipLaunchKernelGGL((k_reproject<T, 3>), grid, block, 0, s, src_cam, dst_cam, (const T*)src, sw, sh, dw, dh, method,
+                       (T*)out);
+}
+}  // namespace
+
+extern "C" int glh_stage_reproject(int dev, const void* frames, int depth_bits, int is_float, int width, int height,
+                                   int channels, int n_frames, const double* src_cams, const double* dst_cam,
+                                   int dst_width, int dst_height, int method, void* out, double* kernel_ms) {
+  if (!frames || !src_cams || !dst_cam || !out || n_frames < 1) return fail(GLH_E_INVALID, "bad argument");
+  if (!((!is_float && (depth_bits == 8 || depth_bits == 16)) || (is_float && (depth_bits == 32 || depth_bits == 64))))
+    return fail(GLH_E_UNSUPPORTED, "frames of %d bits (%s): uint8, uint16, float32 or float64", depth_bits,
+                is_float ? "float" : "integer");
+  if (channels != 1 && channels != 3) return fail(GLH_E_UNSUPPORTED, "1 or 3 channels");
+  if (method != RPJ_LINEAR && method != RPJ_NEAREST) return fail(GLH_E_UNSUPPORTED, "method %d: 0 linear, 1 nearest", method);
+  // (the interpolator needs two grid points on an axis; the pixel index arithmetic is 32-bit)
+  if (width < 2 || height < 2 || dst_width < 1 || dst_height < 1 || width > 32768 || height > 32768 ||
+      dst_width > 32768 || dst_height > 32768)
+    return fail(GLH_E_INVALID, "frame %d x %d -> %d x %d: a source of at least 2 x 2, at most 32768 on a side", width,
+                height, dst_width, dst_height);
+  if (dst_cam[23] != 0.0) return fail(GLH_E_UNSUPPORTED, "the target is a raster grid, not a camera");
+  if ((int)dst_cam[6] != dst_width || (int)dst_cam[7] != dst_height)
+    return fail(GLH_E_INVALID, "target camera imgsz (%g, %g) != target size (%d, %d)", dst_cam[6], dst_cam[7], dst_width,
+                dst_height);
+  std::vector<CamDev> cams(n_frames + 1);
+  for (int i = 0; i < n_frames; ++i) {
+    const double* v = src_cams + (size_t)i * GLH_CAM_LEN;
+    if (v[23] != 0.0) return fail(GLH_E_UNSUPPORTED, "frame %d is a raster grid, not a camera", i);
+    if ((int)v[6] != width || (int)v[7] != height)
+      return fail(GLH_E_INVALID, "camera %d imgsz (%g, %g) != frame size (%d, %d)", i, v[6], v[7], width, height);
+    if (!(v[0] == dst_cam[0] && v[1] == dst_cam[1] && v[2] == dst_cam[2]))
+      return fail(GLH_E_INVALID, "source camera %d and the target camera have different positions ('xyz')", i);
+    expand_camera(v, &cams[i]);
+  }
+  expand_camera(dst_cam, &cams[n_frames]);
+  HIPCHK(hipSetDevice(dev));
+  const size_t px = (size_t)(depth_bits / 8) * channels;
+  const size_t in_bytes = (size_t)width * height * px, out_bytes = (size_t)dst_width * dst_height * px;
+  DevBuf dcams;
+  CHK(dcams.up(cams.data(), cams.size() * sizeof(CamDev)));
+  ReprojectRing r;
+  const int nslot = n_frames < ReprojectRing::NSLOT ? n_frames : ReprojectRing::NSLOT;
+  HIPCHK(hipStreamCreateWithFlags(&r.up, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&r.run, hipStreamNonBlocking));
+  HIPCHK(hipStreamCreateWithFlags(&r.down, hipStreamNonBlocking));
+  for (int k = 0; k < nslot; ++k) {
+    HIPCHK(hipEventCreateWithFlags(&r.uploaded[k], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&r.computed[k], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&r.downloaded[k], hipEventDisableTiming));
+    HIPCHK(hipHostMalloc((void**)&r.pin_in[k], in_bytes, hipHostMallocDefault));
+    HIPCHK(hipHostMalloc((void**)&r.pin_out[k], out_bytes, hipHostMallocDefault));
+    HIPCHK(hipMalloc((void**)&r.dev_in[k], in_bytes));
+    HIPCHK(hipMalloc((void**)&r.dev_out[k], out_bytes));
+  }
+  if (kernel_ms) {
+    r.k0.resize(n_frames, nullptr);
+    r.k1.resize(n_frames, nullptr);
+    for (int i = 0; i < n_frames; ++i) {
+      HIPCHK(hipEventCreate(&r.k0[i]));
+      HIPCHK(hipEventCreate(&r.k1[i]));
+    }
+  }
+  const uint8_t* in = static_cast<const uint8_t*>(frames);
+  uint8_t* res = static_cast<uint8_t*>(out);
+  const CamDev* dc = dcams.as<CamDev>();
+  auto collect = [&](int frame) {  // the finished frame of this slot, from its pinned buffer to the caller's array
+    const int k = frame % nslot;
+    HIPCHK(hipEventSynchronize(r.downloaded[k]));
+    memcpy(res + (size_t)frame * out_bytes, r.pin_out[k], out_bytes);
+    return (int)GLH_OK;
+  };
+  for (int i = 0; i < n_frames; ++i) {
+    const int k = i % nslot;
+    if (i >= nslot) CHK(collect(i - nslot));  // (its download is over, so its kernel and upload are: the slot is free)
+    memcpy(r.pin_in[k], in + (size_t)i * in_bytes, in_bytes);
+    HIPCHK(hipMemcpyAsync(r.dev_in[k], r.pin_in[k], in_bytes, hipMemcpyHostToDevice, r.up));
+    HIPCHK(hipEventRecord(r.uploaded[k], r.up));
+    HIPCHK(hipStreamWaitEvent(r.run, r.uploaded[k], 0));
+    if (kernel_ms) HIPCHK(hipEventRecord(r.k0[i], r.run));
+    if (depth_bits == 8)
+      launch_reproject<uint8_t>(r.run, channels, dc + i, dc + n_frames, r.dev_in[k], width, height, dst_width, dst_height,
+                                method, r.dev_out[k]);
+    else if (depth_bits == 16)
+      launch_reproject<uint16_t>(r.run, channels, dc + i, dc + n_frames, r.dev_in[k], width, height, dst_width, dst_height,
+                                 method, r.dev_out[k]);
+    else if (depth_bits == 32)
+      launch_reproject<float>(r.run, channels, dc + i, dc + n_frames, r.dev_in[k], width, height, dst_width, dst_height,
+                              method, r.dev_out[k]);
+    else
+      launch_reproject<double>(r.run, channels, dc + i, dc + n_frames, r.dev_in[k], width, height, dst_width, dst_height,
+                               method, r.dev_out[k]);
+    HIPCHK(hipGetLastError());
+    if (kernel_ms) HIPCHK(hipEventRecord(r.k1[i], r.run));
+    HIPCHK(hipEventRecord(r.computed[k], r.run));
+    HIPCHK(hipStreamWaitEvent(r.down, r.computed[k], 0));
+    HIPCHK(hipMemcpyAsync(r.pin_out[k], r.dev_out[k], out_bytes, hipMemcpyDeviceToHost, r.down));
+    HIPCHK(hipEventRecord(r.downloaded[k], r.down));
+  }
+  for (int i = n_frames > nslot ? n_frames - nslot : 0; i < n_frames; ++i) CHK(collect(i));
+  if (kernel_ms) {
+    double total = 0.0;
+    for (int i = 0; i < n_frames; ++i) {
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, r.k0[i], r.k1[i]));
+      total += ms;
+    }
+    *kernel_ms = total;
+  }
+  return GLH_OK;
 }
 
 static int check_box(const int32_t* box, int width, int height) {

@@ -7,10 +7,12 @@ time-lapse camera gives the same samples).  A read at another size than the file
 is GDAL's default RasterIO resampling -- nearest neighbour, destination pixel i from source column
 floor((i + 0.5) * src / dst) -- on the decoded array; GDAL itself is absent here, and for JPEG files it would first pick
 one of the decoder's built-in 1/2, 1/4, 1/8 overviews, which this does not reproduce (parity unpinned for resized
-reads).  EXIF parsing, `project`, `write` and `plot` are out of scope.
+reads).  `project` (image.py:301-361) resamples the frame into another camera on the GPU.  EXIF parsing, `write` and
+`plot` are out of scope.
 """
 import numpy as np
 
+from . import _lib
 from .camera import Camera
 
 
@@ -113,3 +115,29 @@ class Image:
     def inbounds(self, uv):
         """image.py:297-299."""
         return self.cam.inframe(uv)
+
+    def _check_project(self, cam, method, name="Source"):
+        """The argument checks of `project`, made before anything touches the library."""
+        if not all(np.asarray(cam.xyz) == self.cam.xyz):
+            raise ValueError(f"{name} and target cameras have different positions ('xyz')")
+        if method not in ("linear", "nearest"):
+            raise ValueError(f"Method '{method}' is not defined")  # (scipy's RegularGridInterpolator says the same)
+
+    def _project_frame(self):
+        """The pixels `project` samples: `read()` with a third axis."""
+        array = self.read()
+        return array[:, :, None] if array.ndim < 3 else array
+
+    def project(self, cam, method="linear"):
+        """image.py:301-361: this image seen by `cam`, a camera at the same position (another view direction, focal
+        length, distortion or image size) -- every pixel centre of `cam` is cast out as a ray, projected into this
+        image's camera and sampled there with `method` = "linear" (bilinear) or "nearest", as
+        scipy.interpolate.RegularGridInterpolator over the pixel centres does.  Returns (cam.imgsz[1], cam.imgsz[0],
+        channels) in the dtype of the pixels (uint8, uint16, float32 or float64; one or three channels; a one-channel
+        image comes back with a third axis of 1, like the reference).  Target pixels that see nothing of this image are
+        NaN for float pixels.  For integer pixels the reference casts that NaN to the integer dtype, which NumPy calls
+        an invalid cast and which stores 0 on x86: 0 is written here.  One kernel on the GPU (`glh_stage_reproject`);
+        `Observer.project` is the batch form."""
+        self._check_project(cam, method)
+        frame = self._project_frame()
+        return _lib.stage_reproject(frame[None], self.cam.vector24[None], cam.vector24, cam.imgsz, method)[0]

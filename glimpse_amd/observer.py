@@ -109,6 +109,25 @@ class Observer:
         for img in self._pick(index):
             img.array = None
 
+    def project(self, cam, index=slice(None), method="linear"):
+        """`Image.project(cam, method)` of the images `index` selects (a slice, or a list of positions), each through its
+        own camera, as one array (frames, cam.imgsz[1], cam.imgsz[0], channels): a time-lapse whose view direction
+        wanders, stabilised into one camera.  The reference has no such method -- there it is a Python loop over
+        `Image.project`; here the frames go through one library call whose copies overlap its kernels, and every frame
+        equals the per-image call bit for bit.  The images must share one pixel shape and dtype; an image whose camera
+        is not at `cam.xyz` raises the ValueError of `Image.project`, naming the image."""
+        images = self._pick(index)
+        if not images:
+            raise ValueError("No images selected")
+        positions = np.arange(len(self.images))[index]
+        for i, img in zip(positions, images):
+            img._check_project(cam, method, name=f"Source (image {i})")
+        frames = [img._project_frame() for img in images]
+        if len({(f.shape, f.dtype) for f in frames}) != 1:
+            raise ValueError("Images differ in shape or dtype: " + str(sorted({(f.shape, str(f.dtype)) for f in frames})))
+        return _lib.stage_reproject(np.stack(frames), np.stack([img.cam.vector24 for img in images]), cam.vector24,
+                                    cam.imgsz, method)
+
     def subset(self, **kwargs):
         """observer.py:455-464: a new Observer over the images select_datetimes(**kwargs) keeps."""
         keep = select_datetimes(self.datetimes, **kwargs)

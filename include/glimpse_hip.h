@@ -423,6 +423,18 @@ int glh_stage_project_depth(int device_id, const double* cam, const double* xyz,
  * undistortion by the closed form for k1 alone, else 20 Oulu iterations (camera.py:1198-1337).   */
 int glh_stage_unproject(int device_id, const double* cam, const double* uv, int n, const double* depth,
                         int n_depth, int directions, double* xyz);
+/* Image.project (image.py:301-361): n_frames >= 1 frames of one shape [n_frames][height][width][channels], each with its
+ * own camera src_cams [n_frames][GLH_CAM_LEN], resampled into the camera dst_cam at the same position: out
+ * [n_frames][dst_height][dst_width][channels] in the frames' own type.  depth_bits / is_float: 8 / 0, 16 / 0 (unsigned),
+ * 32 / 1, 64 / 1; channels 1 or 3; method 0 = linear, 1 = nearest, on the grid of the source pixel centres as
+ * scipy.interpolate.RegularGridInterpolator(bounds_error=False) evaluates them.  Pixels that see nothing of the frame are
+ * NaN in float frames and 0 in integer frames.  Frames travel through pinned staging buffers on streams of their own, so
+ * that a frame's copies overlap its neighbours' kernels.  kernel_ms (or NULL): the sum of the kernels' durations, from
+ * events.  GLH_E_UNSUPPORTED: a raster grid as camera, another type, channel count or method; GLH_E_INVALID: cameras at
+ * different positions ('xyz'), camera imgsz that differ from the frame sizes.                                            */
+int glh_stage_reproject(int device_id, const void* frames, int depth_bits, int is_float, int width, int height,
+                        int channels, int n_frames, const double* src_cams, const double* dst_cam, int dst_width,
+                        int dst_height, int method, void* out, double* kernel_ms);
 /* Tracker.extract_tile(return_histogram=True) (tracker.py:494-534) on a uint8 frame crop
  * `box` (l,t,r,b): tile float64 [h][w], CDF values/quantiles, n entries.                    */
 int glh_stage_template(int device_id, const uint8_t* frame, int width, int height, int channels,
