@@ -151,6 +151,7 @@ SIGNATURES = {
     "glh_stage_sample_orders": (_I, [_I, _P, _I, _I, _I, _I, _P, _P, _I, _P, _P]),
     "glh_stage_resample": (_I, [_I, _P, _I, _D, _P]),
     "glh_stage_raster_sample": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _D, _D, _D, _D, _P, _I, _I, _P, _P]),
+    "glh_stage_viewshed": (_I, [_I, _P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _D, _D, _P, _P]),
 }
 
 _lib = None
@@ -829,3 +830,66 @@ def stage_raster_sample(raster, xy, order=1, device_id=0):
     check(load().glh_stage_raster_sample(device_id, _ptr(z), nx, ny, _ptr(gx), _ptr(gy), sx, sy, x0, x1, y0, y1,
                                          _ptr(xy), len(xy), int(order), _ptr(vals), _ptr(oob)))
     return vals, oob.astype(bool)
+
+
+VIEWSHED_F64, VIEWSHED_F32 = 0, 1
+VIEWSHED_TIMES = ("upload_ms", "cells_ms", "sort_ms", "sweep_ms", "download_ms", "rings", "launches", "sort_scratch_bytes")
+
+
+def viewshed_correction(correction):
+    """`correction` of Raster.viewshed (raster.py:1322-1325) -> (on, radius, refraction): False / None skip it, True takes
+    the defaults of helpers.elevation_corrections (helpers.py:1771-1773), a dict its keyword arguments (another key is the
+    TypeError the reference's call would raise)."""
+    def elevation_corrections(radius=6.3781e6, refraction=0.13):
+        return True, float(radius), float(refraction)
+
+    if correction is True:
+        correction = {}
+    if isinstance(correction, dict):
+        return elevation_corrections(**correction)
+    return False, 6.3781e6, 0.13
+
+
+def viewshed_dem(array, origin_z):
+    """The DEM as the kernel takes it, (z, dtype flag).  The reference forms `array.ravel() - origin[2]` in whatever dtype
+    NumPy promotes to (raster.py:1320) -- for a float32 DEM that depends on what kind of scalar origin[2] is -- so the
+    promotion is asked of NumPy itself, on one element: float32 stays float32 (the subtraction and the correction's sum
+    are then rounded to float32 on the device too), everything else is computed in float64 (integers convert exactly)."""
+    array = np.asarray(array)
+    if array.dtype.kind not in "iuf" or array.dtype.itemsize > 8 or array.dtype == np.float16:
+        raise TypeError(f"a DEM of dtype {array.dtype}: float64, float32 or integers")
+    probe = (array.ravel()[:1] - origin_z).dtype
+    if probe == np.float32:
+        return np.ascontiguousarray(array, dtype=np.float32), VIEWSHED_F32
+    if probe.kind not in "iuf" or probe.itemsize > 8 or probe == np.float16:
+        raise TypeError(f"a DEM of dtype {array.dtype} less an origin of type {type(origin_z).__name__} is {probe}")
+    return np.ascontiguousarray(array, dtype=np.float64), VIEWSHED_F64
+
+
+def stage_viewshed(raster, origins, correction=None, device_id=0, return_times=False, float32=None):
+    """Raster.viewshed (raster.py:1293-1389) of `raster` from the m positions `origins` (m, 3): bool (m, ny, nx).  The DEM
+    is uploaded once and the m viewsheds are computed one after another.  `float32`: whether the reference's dz would be
+    float32 (None: NumPy's promotion of the DEM with `origins`' own scalar type is asked; Raster.viewshed asks with the
+    caller's origin[2], which may be a Python float).  `return_times`: also a dict of the HIP-event split, summed over the
+    origins (VIEWSHED_TIMES)."""
+    on, radius, refraction = viewshed_correction(correction)
+    origins = np.asarray(origins)
+    if origins.ndim != 2 or origins.shape[1] != 3 or len(origins) < 1:
+        raise ValueError(f"origins must be (m, 3) with m >= 1, got {origins.shape}")
+    if float32 is None:
+        z, flag = viewshed_dem(raster.array, origins[0, 2])
+    else:
+        z = np.ascontiguousarray(raster.array, dtype=np.float32 if float32 else np.float64)
+        flag = VIEWSHED_F32 if float32 else VIEWSHED_F64
+    if z.ndim != 2:
+        raise ValueError(f"a DEM is two-dimensional, got {z.shape}")
+    origins = _arr(origins, np.float64)
+    ny, nx = z.shape
+    x, y = _arr(raster.x, np.float64, (nx,)), _arr(raster.y, np.float64, (ny,))
+    out = np.empty((len(origins), ny, nx), dtype=np.uint8)
+    times = np.zeros(len(VIEWSHED_TIMES))
+    check(load().glh_stage_viewshed(device_id, _ptr(z), flag, nx, ny, _ptr(x), _ptr(y), float(1 / abs(raster.d[0])),
+                                    _ptr(origins), len(origins), int(on), radius, refraction, _ptr(out),
+                                    _ptr(times) if return_times else None))
+    vis = out.view(bool)
+    return (vis, dict(zip(VIEWSHED_TIMES, (float(t) for t in times)))) if return_times else vis

@@ -34,8 +34,10 @@ HEADERS = [
     VARIANTS,
     os.path.join(os.path.dirname(HERE), "include", "glimpse_hip.h"),
 ]
-HOST_HEADERS = [os.path.join(CSRC, "glh_host.h"), os.path.join(CSRC, "glh_comm.h")]
-DEPS = [SRC, INST, *HEADERS, *HOST_HEADERS]
+VIEWSHED = os.path.join(CSRC, "glh_viewshed.hip")  # Raster.viewshed: its kernels and rocPRIM's radix sort
+VIEWSHED_HEADER = os.path.join(CSRC, "glh_viewshed.h")
+HOST_HEADERS = [os.path.join(CSRC, "glh_host.h"), os.path.join(CSRC, "glh_comm.h"), VIEWSHED_HEADER]
+DEPS = [SRC, INST, VIEWSHED, *HEADERS, *HOST_HEADERS]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -82,7 +84,9 @@ def up_to_date():
 def _jobs(extra, objdir=OBJDIR):
     """[(object, command, dependencies)]"""
     cc = hipcc()
-    jobs = [(os.path.join(objdir, "glimpse_hip.o"), [cc, *FLAGS, *extra, "-c", SRC], [SRC, *HEADERS, *HOST_HEADERS])]
+    jobs = [(os.path.join(objdir, "glimpse_hip.o"), [cc, *FLAGS, *extra, "-c", SRC], [SRC, *HEADERS, *HOST_HEADERS]),
+            (os.path.join(objdir, "glh_viewshed.o"), [cc, *FLAGS, *extra, "-c", VIEWSHED],
+             [VIEWSHED, VIEWSHED_HEADER, HEADERS[-1]])]
     for tb, ppt, nobs, s, f, c in variants():
         obj = os.path.join(objdir, f"pt_{tb}_{ppt}_{nobs}_{s}{f}{c}.o")
         defs = [f"-DPT_TB={tb}", f"-DPT_PPT={ppt}", f"-DPT_NOBS={nobs}", f"-DPT_SURF={s}", f"-DPT_FAST={f}",

@@ -17,6 +17,7 @@
 #include "glh_kernels.h"
 #include "glh_point.h"
 #include "glh_point_variants.h"
+#include "glh_viewshed.h"
 
 using namespace glh;
 
@@ -2793,6 +2794,39 @@ extern "C" int glh_stage_raster_sample(int dev, const double* z, int nx, int ny,
   CHK(finish());
   CHK(dv.down(values, (size_t)n * 8));
   return do_.down(oob, (size_t)n);
+}
+
+// Raster.viewshed (raster.py:1293-1389): the arguments are checked here, before a device is touched; the kernels, the sort
+// and the launches are glh_viewshed.hip's.
+extern "C" int glh_stage_viewshed(int dev, const void* z, int z_dtype, int nx, int ny, const double* x, const double* y,
+                                  double inv_cell, const double* origins, int m, int correction, double radius,
+                                  double refraction, uint8_t* visible, double* times_ms) {
+  if (!z || !x || !y || !origins || !visible) return fail(GLH_E_INVALID, "viewshed: null argument");
+  if (nx < 1 || ny < 1 || m < 1) return fail(GLH_E_INVALID, "viewshed: %d x %d cells, %d origins: at least one of each", nx, ny, m);
+  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "viewshed: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", nx, ny);
+  if (z_dtype != GLH_VIEWSHED_F64 && z_dtype != GLH_VIEWSHED_F32)
+    return fail(GLH_E_UNSUPPORTED, "viewshed: z_dtype %d: 0 float64, 1 float32", z_dtype);
+  if (!(std::isfinite(inv_cell) && inv_cell > 0.0)) return fail(GLH_E_INVALID, "viewshed: inverse cell size %g", inv_cell);
+  for (int i = 0; i < nx; ++i)
+    if (!std::isfinite(x[i])) return fail(GLH_E_INVALID, "viewshed: x[%d] is not finite", i);
+  for (int i = 0; i < ny; ++i)
+    if (!std::isfinite(y[i])) return fail(GLH_E_INVALID, "viewshed: y[%d] is not finite", i);
+  for (int i = 0; i < 3 * m; ++i)
+    if (!std::isfinite(origins[i])) return fail(GLH_E_INVALID, "viewshed: origin %d is not finite", i / 3);
+  if (correction && !(std::isfinite(radius) && radius != 0.0 && std::isfinite(refraction)))
+    return fail(GLH_E_INVALID, "viewshed: correction with radius %g, refraction %g", radius, refraction);
+  const ViewshedJob job{dev, z, z_dtype == GLH_VIEWSHED_F32, nx, ny, x, y, inv_cell, origins, m, correction != 0, radius,
+                        refraction, visible, times_ms};
+  for (int o = 0; o < m; ++o) {
+    const double far = viewshed_farthest_cells(job, origins + 3 * o);
+    if (!(far < (double)VS_MAX_RINGS))
+      return fail(GLH_E_UNSUPPORTED, "viewshed: origin %d is %g cells from the DEM's farthest cell (fewer than %d are served)", o,
+                  far, VS_MAX_RINGS);
+  }
+  char msg[512] = "";
+  const int rc = viewshed_run(job, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
 }
 
 extern "C" int glh_stage_resample(int dev, const double* weights, int n, double u, int64_t* idx) {

@@ -6,8 +6,12 @@ Only what `Tracker` / the motion models use is mirrored: the constructor from an
 (raster.py:652-694 with Grid, :25-98), the cell-centre coordinates (`x`, `y`, raster.py:131-165), the
 bounds test (`inbounds_xy`, :313-337) and `sample(xy, order in {0, 1})` at points (:913-1027).  Sampling
 runs on the GPU (`glh_stage_raster_sample`; inside a tracking run the kernels sample the uploaded
-raster themselves).  File I/O (GDAL), resampling, terrain analysis are out of scope.
+raster themselves).  Of the terrain analysis, `viewshed(origin, correction)` (:1293-1389) is served, on the GPU
+(`glh_stage_viewshed`): it makes the `Tracker(viewshed=...)` input from a DEM and a camera position.  File I/O (GDAL),
+resampling, `horizon`, `hillshade`, `fill_crevasses` are out of scope.
 """
+import warnings
+
 import numpy as np
 
 from . import _lib
@@ -106,6 +110,37 @@ class Raster:
         z = np.ascontiguousarray(self.array, dtype=np.float64)
         nx, ny = (int(v) for v in self.size)
         return z, nx, ny, gx, gy, sx, sy, float(self.min[0]), float(self.max[0]), float(self.min[1]), float(self.max[1])
+
+    def viewshed(self, origin, correction=False):
+        """The binary viewshed from a point (raster.py:1293-1389): bool, shape of `array`, True where a cell is seen from
+        `origin` (x, y, z).  `correction`: False / None, True (default arguments) or the arguments of
+        helpers.elevation_corrections (`radius`, `refraction`; helpers.py:1771-1790).  Computed on the GPU
+        (`glh_stage_viewshed`) by the reference's own algorithm -- cells ordered by distance ring and heading, rings swept
+        outwards against the interpolated running maximum of the elevation ratio -- with its quirks: the cell under an
+        origin that sits on a cell centre is never tested (False), a raster whose cells all lie within half a cell of
+        the origin is all True."""
+        if not all(abs(self.d[0]) == abs(self.d)):
+            warnings.warn(
+                "DEM cells not square "
+                + str(tuple(abs(self.d)))
+                + " - "
+                + "may lead to unexpected results"
+            )
+        if not self.inbounds_xy(np.atleast_2d(origin[0:2])):
+            warnings.warn("Origin not in DEM - may lead to unexpected results")
+        _lib.viewshed_correction(correction)  # (a TypeError for an unknown argument comes before anything else)
+        if self.array.ndim != 2:
+            raise ValueError(f"a DEM is two-dimensional, got {self.array.shape}")
+        z, flag = _lib.viewshed_dem(self.array, origin[2])
+        # every cell within half a cell of the origin (ring 0 only): "Single co-located pixel, return all visible"
+        # (raster.py:1339-1345).  The farthest cell is a corner, and the ring number grows with the distance.
+        x, y = self.x, self.y
+        dx = max(abs(x[0] - origin[0]), abs(x[-1] - origin[0]))
+        dy = max(abs(y[0] - origin[1]), abs(y[-1] - origin[1]))
+        if int(np.sqrt(dx ** 2 + dy ** 2) * (1 / abs(self.d[0])) + 0.5) == 0:
+            return np.ones(self.array.shape, dtype=bool)
+        xyz = np.array([[float(origin[0]), float(origin[1]), float(origin[2])]])
+        return _lib.stage_viewshed(self, xyz, correction, float32=flag == _lib.VIEWSHED_F32)[0]
 
     def sample(self, xy, grid=False, order=1, bounds_error=True, fill_value=np.nan):
         """Values at points (n, 2): bilinear (order 1) or nearest cell (order 0) (raster.py:913-1027)."""

@@ -468,6 +468,25 @@ int glh_stage_raster_sample(int device_id, const double* z, int nx, int ny, cons
                             const double* gy, int sx, int sy, double xmin, double xmax, double ymin,
                             double ymax, const double* xy, int n, int order, double* values,
                             uint8_t* oob);
+/* Raster.viewshed(origin, correction) (raster.py:1293-1389) for m >= 1 origins [m][3] over ONE upload of the DEM:
+ * visible [m][ny][nx], 1 = seen from the origin.  z [ny][nx] is Raster.array as float64 (z_dtype GLH_VIEWSHED_F64) or as
+ * float32 (GLH_VIEWSHED_F32: the reference's `array.ravel() - origin[2]` stays float32 -- a float32 DEM and an origin
+ * NumPy does not promote it with -- so the subtraction and the correction's sum are rounded to float32).  x [nx], y [ny]
+ * are Grid.x / Grid.y as NumPy made them (first to last column / row, either direction); inv_cell = 1 / abs(d[0]).
+ * correction != 0 adds helpers.elevation_corrections (helpers.py:1771-1790) with `radius` and `refraction`.  The
+ * reference's algorithm and its quirks: cells ordered by ring (distance in cells, rounded) and heading, rings swept in
+ * ascending order with the previous ring's running maximum interpolated as np.interp(period=2 pi) does; a ring 0 beside
+ * other rings is never processed (the cell under the origin is 0); cells that all lie in ring 0 are all 1.
+ * times_ms (or NULL) [8]: HIP-event milliseconds summed over the origins -- [0] upload, [1] per-cell kernel, [2] sort,
+ * [3] sweep, [4] download -- then [5] rings processed, [6] sweep launches, [7] bytes of the sort's scratch.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, nx, ny or m < 1, nx * ny >= 2^31, coordinates,
+ * origins or inv_cell that are not finite, radius 0), GLH_E_UNSUPPORTED (an unknown z_dtype; an origin more than 2^24
+ * cells from the DEM).  A failed device allocation is GLH_E_NOMEM, with the bytes it asked for in glh_last_error().    */
+#define GLH_VIEWSHED_F64 0
+#define GLH_VIEWSHED_F32 1
+int glh_stage_viewshed(int device_id, const void* z, int z_dtype, int nx, int ny, const double* x, const double* y,
+                       double inv_cell, const double* origins, int m, int correction, double radius,
+                       double refraction, uint8_t* visible, double* times_ms);
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
 
