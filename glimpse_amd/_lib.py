@@ -152,6 +152,8 @@ SIGNATURES = {
     "glh_stage_resample": (_I, [_I, _P, _I, _D, _P]),
     "glh_stage_raster_sample": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _D, _D, _D, _D, _P, _I, _I, _P, _P]),
     "glh_stage_viewshed": (_I, [_I, _P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _D, _D, _P, _P]),
+    "glh_stage_project_dem": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
+    "glh_stage_rasterize": (_I, [_I, _P, _I, _P, _I, _I, _P, _P]),
 }
 
 _lib = None
@@ -893,3 +895,62 @@ def stage_viewshed(raster, origins, correction=None, device_id=0, return_times=F
                                     _ptr(times) if return_times else None))
     vis = out.view(bool)
     return (vis, dict(zip(VIEWSHED_TIMES, (float(t) for t in times)))) if return_times else vis
+
+
+PD_F64, PD_F32, PD_U8, PD_U16 = 0, 1, 2, 3
+PD_DTYPES = {"float64": PD_F64, "float32": PD_F32, "uint8": PD_U8, "uint16": PD_U16}
+PD_TIMES = ("upload_ms", "project_ms", "order_ms", "reduce_ms", "download_ms", "memberships", "kept", "sort_scratch_bytes")
+
+
+def _pd_result(out, times, return_times):
+    return (out, dict(zip(PD_TIMES, (float(t) for t in times)))) if return_times else out
+
+
+def stage_project_dem(cam, z, values, mask, cols, x_coords, rows, y_coords, return_depth=False, device_id=0,
+                      return_times=False):
+    """Camera.project_dem (camera.py:967-1129) for the camera vector `cam` (CAM_LEN): float64 (height, width, layers +
+    return_depth).  `z` (ny, nx): the DEM, float32 as it is, anything else as float64.  `values` (ny, nx, layers) or None:
+    float64, float32, uint8, uint16 travel as they are, bool as uint8, anything else as the float64 np.bincount would
+    make of it.  `mask` (ny, nx) or None.  `cols` / `rows`: the (start, stop) of the tiling's column / row slices
+    (Raster.tile_indices), `x_coords` / `y_coords`: each slice's own coordinates, one slice after another.
+    `return_times`: also a dict of the HIP-event split (PD_TIMES)."""
+    cam = _arr(cam, np.float64, (CAM_LEN,))
+    z = np.asarray(z)
+    z = np.ascontiguousarray(z, dtype=np.float32 if z.dtype == np.float32 else np.float64)
+    ny, nx = z.shape
+    layers, code = 0, PD_F64
+    if values is not None:
+        values = np.asarray(values)
+        if values.dtype == bool:
+            values = values.view(np.uint8)
+        if values.dtype.name not in PD_DTYPES:
+            values = values.astype(np.float64)
+        values = _arr(values, values.dtype, (ny, nx, values.shape[2]))
+        layers, code = values.shape[2], PD_DTYPES[values.dtype.name]
+    if mask is not None:
+        mask = _arr(np.asarray(mask, dtype=bool), bool, (ny, nx)).view(np.uint8)
+    xs, xe = (_arr([c[k] for c in cols], np.int32) for k in (0, 1))
+    ys, ye = (_arr([r[k] for r in rows], np.int32) for k in (0, 1))
+    x_coords = _arr(x_coords, np.float64, (int((xe - xs).sum()),))
+    y_coords = _arr(y_coords, np.float64, (int((ye - ys).sum()),))
+    width, height = int(cam[6]), int(cam[7])
+    out = np.empty((height, width, layers + int(bool(return_depth))))
+    times = np.zeros(len(PD_TIMES))
+    check(load().glh_stage_project_dem(device_id, _ptr(cam), _ptr(z), PD_F32 if z.dtype == np.float32 else PD_F64, nx, ny,
+                                       _ptr(mask), _ptr(values), code, layers, len(xs), _ptr(xs), _ptr(xe), _ptr(x_coords),
+                                       len(ys), _ptr(ys), _ptr(ye), _ptr(y_coords), int(bool(return_depth)), _ptr(out),
+                                       _ptr(times) if return_times else None))
+    return _pd_result(out, times, return_times)
+
+
+def stage_rasterize(keys, values, n_pixels, device_id=0, return_times=False):
+    """helpers.rasterize_points (helpers.py:1617-1698) on the device: `keys` (n,) the pixel of every point, each in
+    [0, n_pixels), `values` (n, d) -> float64 (n_pixels, d) of per-pixel means (the sum in the points' order, times
+    1 / count), NaN where no point falls."""
+    keys = _arr(keys, np.int32)
+    values = _arr(values, np.float64, (len(keys), np.shape(values)[1]))
+    out = np.empty((int(n_pixels), values.shape[1]))
+    times = np.zeros(len(PD_TIMES))
+    check(load().glh_stage_rasterize(device_id, _ptr(keys), len(keys), _ptr(values), values.shape[1], int(n_pixels),
+                                     _ptr(out), _ptr(times) if return_times else None))
+    return _pd_result(out, times, return_times)

@@ -7,7 +7,8 @@ box with the repository snapshot.  -ffp-contract=off keeps float64 expressions
 bit-identical to NumPy's (no implicit FMA); the SSD kernel asks for FMA explicitly.
 
 The library is many translation units compiled in parallel: glimpse_hip.hip (the C ABI and the
-staged kernels) and one object per instantiation of the fused kernel (glh_point_inst.hip with
+staged kernels), glh_viewshed.hip and glh_project_dem.hip (the terrain routines, each with rocPRIM's
+radix sort) and one object per instantiation of the fused kernel (glh_point_inst.hip with
 -DPT_*; the list is csrc/glh_point_variants.h).  Objects are cached in glimpse_amd/lib/obj/ and
 rebuilt when a source they include is newer.
 """
@@ -36,8 +37,10 @@ HEADERS = [
 ]
 VIEWSHED = os.path.join(CSRC, "glh_viewshed.hip")  # Raster.viewshed: its kernels and rocPRIM's radix sort
 VIEWSHED_HEADER = os.path.join(CSRC, "glh_viewshed.h")
-HOST_HEADERS = [os.path.join(CSRC, "glh_host.h"), os.path.join(CSRC, "glh_comm.h"), VIEWSHED_HEADER]
-DEPS = [SRC, INST, VIEWSHED, *HEADERS, *HOST_HEADERS]
+PROJECT_DEM = os.path.join(CSRC, "glh_project_dem.hip")  # Camera.project_dem / rasterize: kernels and the radix sort
+PROJECT_DEM_HEADER = os.path.join(CSRC, "glh_project_dem.h")
+HOST_HEADERS = [os.path.join(CSRC, "glh_host.h"), os.path.join(CSRC, "glh_comm.h"), VIEWSHED_HEADER, PROJECT_DEM_HEADER]
+DEPS = [SRC, INST, VIEWSHED, PROJECT_DEM, *HEADERS, *HOST_HEADERS]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -86,7 +89,9 @@ def _jobs(extra, objdir=OBJDIR):
     cc = hipcc()
     jobs = [(os.path.join(objdir, "glimpse_hip.o"), [cc, *FLAGS, *extra, "-c", SRC], [SRC, *HEADERS, *HOST_HEADERS]),
             (os.path.join(objdir, "glh_viewshed.o"), [cc, *FLAGS, *extra, "-c", VIEWSHED],
-             [VIEWSHED, VIEWSHED_HEADER, HEADERS[-1]])]
+             [VIEWSHED, VIEWSHED_HEADER, HEADERS[-1]]),
+            (os.path.join(objdir, "glh_project_dem.o"), [cc, *FLAGS, *extra, "-c", PROJECT_DEM],
+             [PROJECT_DEM, PROJECT_DEM_HEADER, os.path.join(CSRC, "glh_math.h"), HEADERS[-1]])]
     for tb, ppt, nobs, s, f, c in variants():
         obj = os.path.join(objdir, f"pt_{tb}_{ppt}_{nobs}_{s}{f}{c}.o")
         defs = [f"-DPT_TB={tb}", f"-DPT_PPT={ppt}", f"-DPT_NOBS={nobs}", f"-DPT_SURF={s}", f"-DPT_FAST={f}",

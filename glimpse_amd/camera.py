@@ -5,7 +5,10 @@ state vector `_vector[20]` :101, :128-198).  `xyz_to_uv` (camera.py:591-628) -- 
 half that sits on the Tracker hot path -- runs on the GPU through libglimpse_hip.so; there is no
 CPU fallback for it.  The inverse projection (`uv_to_xyz`, camera.py:630-663, with the k1 closed form
 and the Oulu undistortion, :1198-1337) runs on the GPU as well (`glh_stage_unproject`); it is not on
-the per-frame path.  Calibration / rendering methods are out of scope.
+the per-frame path.  Of the rendering methods, `project_dem` (camera.py:967-1129: the image and the depth map a
+camera records of a DEM) and `rasterize` (:858-883: points to a mean image) are served, on the GPU
+(`glh_stage_project_dem`, `glh_stage_rasterize`); `project_dem` without the per-tile rescaling (`scale_limits` other than
+(1, 1), which fails in the reference itself).  Calibration methods are out of scope.
 """
 import numpy as np
 
@@ -219,3 +222,54 @@ class Camera:
         uv = np.atleast_2d(np.asarray(uv, dtype=float))
         d = None if (isinstance(depth, (int, float)) and depth == 1) else depth
         return _lib.stage_unproject(self.vector24, uv, depth=d, directions=directions)
+
+    # ---- rendering (GPU)
+    def rasterize(self, uv, values):
+        """camera.py:858-883: the image (imgsz[1], imgsz[0]) of the mean of `values` (n,) over the points `uv` (n, 2) that
+        truncate to each pixel, NaN where there is none; `values` (n, d) with d > 1 give (imgsz[1], imgsz[0], d).  The
+        means are helpers.rasterize_points': float64 sums in the points' order times 1 / count, formed on the device
+        (`glh_stage_rasterize`).  A point exactly on the far edge (u == imgsz[0] or v == imgsz[1]), where the reference
+        raises, is out of frame."""
+        uv, values = np.asarray(uv), np.asarray(values)
+        nx, ny = (int(v) for v in self.imgsz)
+        keep = self.inframe(uv) & (uv[:, 0] < nx) & (uv[:, 1] < ny)
+        columns = 1 if values.ndim == 1 else values.shape[1]
+        picked = np.asarray(values[keep], dtype=np.float64).reshape(int(keep.sum()), columns)
+        shape = (ny, nx) if columns == 1 else (ny, nx, columns)
+        if not keep.any():
+            return np.full(shape, np.nan)
+        keys = uv[keep, 1].astype(int) * nx + uv[keep, 0].astype(int)
+        return _lib.stage_rasterize(keys, picked, nx * ny).reshape(shape)
+
+    def project_dem(self, dem, values=None, mask=None, tile_size=(256, 256), tile_overlap=(1, 1), scale=1,
+                    scale_limits=(1, 1), parallel=False, return_depth=False):
+        """camera.py:967-1129: the image (imgsz[1], imgsz[0], layers) this camera records of the `values` (one per cell,
+        2-D or with layers along a third axis) draped over the `dem` (a Raster), with the depth of the surface along the
+        optical axis appended as the last layer when `return_depth`; NaN where no cell lands.  `mask`: the cells to
+        include (default: those with an elevation).  Computed on the GPU (`glh_stage_project_dem`) with the reference's
+        semantics: the DEM is cut into `dem.tile_indices(tile_size, tile_overlap)`; within a tile a pixel is the mean of
+        the cells that truncate to it (float64 sum in row-major order, times 1 / count); across tiles there is no depth
+        test -- the last tile that reaches a pixel overwrites it, so the tiling is part of the answer.  The value layers
+        equal the reference's bit for bit.  `scale` has no effect and `parallel` is ignored; `scale_limits` other than
+        (1, 1) -- the per-tile rescaling, which fails in the reference itself -- is not built.  A cell exactly on the far
+        edge of the frame (u == imgsz[0] or v == imgsz[1]), where the reference raises, is out of frame."""
+        if min(scale_limits) != 1 or max(scale_limits) != 1:
+            raise NotImplementedError("project_dem rescales no tile: scale_limits must be (1, 1)")
+        dem_shape = tuple(int(v) for v in dem.size[::-1])
+        if values is not None:
+            values = np.atleast_3d(values)
+            if values.shape[0:2] != dem_shape:
+                raise ValueError("values does not have the same 2-d shape as dem")
+        elif not return_depth:
+            raise ValueError("values cannot be missing if return_depth is False")
+        if mask is not None and np.shape(mask) != dem_shape:
+            raise ValueError("mask does not have the same 2-d shape as dem")
+        if np.ndim(dem.array) != 2:
+            raise ValueError(f"a DEM is two-dimensional, got {np.shape(dem.array)}")
+        tiles = dem.tile_indices(size=tile_size, overlap=tile_overlap)
+        rows = list(dict.fromkeys((i.start, i.stop) for i, _ in tiles))
+        cols = list(dict.fromkeys((j.start, j.stop) for _, j in tiles))
+        return _lib.stage_project_dem(
+            self.vector24, dem.array, values, mask,
+            cols, np.concatenate([dem._tile_coordinates(0, a, b) for a, b in cols]),
+            rows, np.concatenate([dem._tile_coordinates(1, a, b) for a, b in rows]), return_depth=return_depth)

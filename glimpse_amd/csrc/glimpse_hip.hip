@@ -17,6 +17,7 @@
 #include "glh_kernels.h"
 #include "glh_point.h"
 #include "glh_point_variants.h"
+#include "glh_project_dem.h"
 #include "glh_viewshed.h"
 
 using namespace glh;
@@ -2826,6 +2827,69 @@ extern "C" int glh_stage_viewshed(int dev, const void* z, int z_dtype, int nx, i
   }
   char msg[512] = "";
   const int rc = viewshed_run(job, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+// Camera.project_dem (camera.py:967-1129) and Camera.rasterize (camera.py:858-883): the arguments are checked here, before
+// a device is touched; the kernels, the sort and the launches are glh_project_dem.hip's.
+static int check_pd_axis(const char* name, int n, const int32_t* start, const int32_t* end, int cells) {
+  for (int k = 0; k < n; ++k) {
+    if (start[k] < 0 || end[k] > cells || start[k] >= end[k])
+      return fail(GLH_E_INVALID, "project_dem: %s slice %d is [%d, %d) of %d cells", name, k, start[k], end[k], cells);
+    if (k && (start[k] < start[k - 1] || end[k] <= end[k - 1]))
+      return fail(GLH_E_INVALID, "project_dem: %s slices %d and %d are not ascending", name, k - 1, k);
+  }
+  return GLH_OK;
+}
+
+extern "C" int glh_stage_project_dem(int dev, const double* cam, const void* z, int z_dtype, int nx, int ny,
+                                     const uint8_t* mask, const void* values, int v_dtype, int layers, int n_tx,
+                                     const int32_t* x_start, const int32_t* x_end, const double* x_coords, int n_ty,
+                                     const int32_t* y_start, const int32_t* y_end, const double* y_coords, int return_depth,
+                                     double* out, double* times_ms) {
+  if (!cam || !z || !x_start || !x_end || !x_coords || !y_start || !y_end || !y_coords || !out)
+    return fail(GLH_E_INVALID, "project_dem: null argument");
+  if (nx < 1 || ny < 1 || n_tx < 1 || n_ty < 1)
+    return fail(GLH_E_INVALID, "project_dem: %d x %d cells in %d x %d tiles: at least one of each", nx, ny, n_tx, n_ty);
+  if (layers < 0 || (layers > 0) != (values != nullptr))
+    return fail(GLH_E_INVALID, "project_dem: %d layers %s values", layers, values ? "with" : "without");
+  if (layers == 0 && !return_depth) return fail(GLH_E_INVALID, "project_dem: neither values nor the depth asked for");
+  if (z_dtype != GLH_PD_F64 && z_dtype != GLH_PD_F32)
+    return fail(GLH_E_UNSUPPORTED, "project_dem: z_dtype %d: 0 float64, 1 float32", z_dtype);
+  if (layers && (v_dtype < GLH_PD_F64 || v_dtype > GLH_PD_U16))
+    return fail(GLH_E_UNSUPPORTED, "project_dem: v_dtype %d: 0 float64, 1 float32, 2 uint8, 3 uint16", v_dtype);
+  if (cam[23] != 0.0) return fail(GLH_E_UNSUPPORTED, "project_dem: the camera is a raster grid");
+  const double w = cam[6], h = cam[7];
+  if (!(w >= 1.0 && h >= 1.0 && w == std::floor(w) && h == std::floor(h)))
+    return fail(GLH_E_INVALID, "project_dem: imgsz (%g, %g) is not a positive integer size", w, h);
+  CHK(check_pd_axis("column", n_tx, x_start, x_end, nx));
+  CHK(check_pd_axis("row", n_ty, y_start, y_end, ny));
+  CamDev cd;
+  expand_camera(cam, &cd);
+  const ProjectDemJob job{dev, &cd, (int)w, (int)h, z, z_dtype == GLH_PD_F32, nx, ny, mask, values, layers ? v_dtype : GLH_PD_F64,
+                          layers, PdAxis{n_tx, x_start, x_end, x_coords}, PdAxis{n_ty, y_start, y_end, y_coords},
+                          return_depth != 0, out, times_ms};
+  const int64_t lim = (int64_t)1 << 31;
+  if ((int64_t)nx * ny >= lim || w * h >= (double)(lim - 1) || w * h * (layers + 1) >= 9e15 ||
+      project_dem_memberships(job) >= lim)
+    return fail(GLH_E_UNSUPPORTED, "project_dem: %d x %d cells (%lld with the tiles' overlap) into %g x %g pixels: fewer than "
+                                   "2^31 of each are served (32-bit indices)", nx, ny, (long long)project_dem_memberships(job), w, h);
+  char msg[512] = "";
+  const int rc = project_dem_run(job, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+extern "C" int glh_stage_rasterize(int dev, const int32_t* keys, int n, const double* values, int layers, int n_pixels,
+                                   double* out, double* times_ms) {
+  if (!keys || !values || !out) return fail(GLH_E_INVALID, "rasterize: null argument");
+  if (n < 1 || layers < 1 || n_pixels < 1)
+    return fail(GLH_E_INVALID, "rasterize: %d points, %d layers, %d pixels: at least one of each", n, layers, n_pixels);
+  for (int i = 0; i < n; ++i)
+    if (keys[i] < 0 || keys[i] >= n_pixels)
+      return fail(GLH_E_INVALID, "rasterize: key %d of point %d outside [0, %d)", keys[i], i, n_pixels);
+  const RasterizeJob job{dev, keys, n, values, layers, n_pixels, out, times_ms};
+  char msg[512] = "";
+  const int rc = rasterize_run(job, msg, sizeof msg);
   return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
 }
 

@@ -7,8 +7,10 @@ Only what `Tracker` / the motion models use is mirrored: the constructor from an
 bounds test (`inbounds_xy`, :313-337) and `sample(xy, order in {0, 1})` at points (:913-1027).  Sampling
 runs on the GPU (`glh_stage_raster_sample`; inside a tracking run the kernels sample the uploaded
 raster themselves).  Of the terrain analysis, `viewshed(origin, correction)` (:1293-1389) is served, on the GPU
-(`glh_stage_viewshed`): it makes the `Tracker(viewshed=...)` input from a DEM and a camera position.  File I/O (GDAL),
-resampling, `horizon`, `hillshade`, `fill_crevasses` are out of scope.
+(`glh_stage_viewshed`): it makes the `Tracker(viewshed=...)` input from a DEM and a camera position.
+`tile_indices(size, overlap)` (:581-610) cuts the grid into the tiles `Camera.project_dem` walks; it and the tiles' own
+coordinates (`__getitem__`, :670-693) are computed on the host and handed to the device.  File I/O (GDAL), resampling,
+`horizon`, `hillshade`, `fill_crevasses` are out of scope.
 """
 import warnings
 
@@ -110,6 +112,34 @@ class Raster:
         z = np.ascontiguousarray(self.array, dtype=np.float64)
         nx, ny = (int(v) for v in self.size)
         return z, nx, ny, gx, gy, sx, sy, float(self.min[0]), float(self.max[0]), float(self.min[1]), float(self.max[1])
+
+    def tile_indices(self, size, overlap=(0, 0)):
+        """Grid.tile_indices (raster.py:581-610): (rows, columns) slice pairs that chop the grid into tiles of about
+        `size` = (nx, ny) cells, row-major.  Per axis: round(cells / size) tiles (none rounds to one tile over the whole
+        axis, through the reference's division by zero), cell i in tile floor(i / ceil(cells / tiles)); every tile but
+        the first starts `overlap` cells early, so overlapping cells belong to both neighbours."""
+        axes = []
+        for cells, target, lap in zip((int(v) for v in self.size), size, overlap):
+            tiles = int(np.round(cells / target))
+            with np.errstate(divide="ignore"):
+                label = np.floor(np.arange(cells) / np.ceil(np.float64(cells) / tiles))
+            ends = np.concatenate(([0], np.searchsorted(label, np.unique(label), side="right")))
+            starts = ends.copy()
+            starts[1:-1] -= lap
+            axes.append([slice(int(a), int(b)) for a, b in zip(starts[:-1], ends[1:])])
+        return tuple((i, j) for i in axes[1] for j in axes[0])
+
+    def _tile_coordinates(self, dim, start, stop):
+        """Grid.x (dim 0) or Grid.y (dim 1) of the tile `self[start:stop]` along that axis (raster.py:670-693): a tile of
+        three or more cells is built from the slice of this raster's coordinates and keeps them; a narrower one is built
+        from its outer limits and spaces its own."""
+        c = self._centres(dim)[start:stop]
+        if len(c) >= 3:
+            return c
+        lim = c[[0, -1]] + np.array((-0.5, 0.5)) * self.d[dim]
+        d = (lim[1] - lim[0]) / len(c)
+        value = np.linspace(start=min(lim) + abs(d) / 2, stop=max(lim) - abs(d) / 2, num=len(c))
+        return value[::-1] if d < 0 else value
 
     def viewshed(self, origin, correction=False):
         """The binary viewshed from a point (raster.py:1293-1389): bool, shape of `array`, True where a cell is seen from

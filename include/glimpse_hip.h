@@ -487,6 +487,41 @@ int glh_stage_raster_sample(int device_id, const double* z, int nx, int ny, cons
 int glh_stage_viewshed(int device_id, const void* z, int z_dtype, int nx, int ny, const double* x, const double* y,
                        double inv_cell, const double* origins, int m, int correction, double radius,
                        double refraction, uint8_t* visible, double* times_ms);
+/* Camera.project_dem (camera.py:967-1129) with scale_limits = (1, 1): the image a camera records of a DEM's per-cell
+ * values, and the depth of the DEM along the optical axis.  out [height][width][layers + (return_depth != 0)] float64 with
+ * (width, height) = the camera's imgsz; NaN where no cell lands.  cam [GLH_CAM_LEN] (a camera, not a raster grid).
+ * z [ny][nx] is the DEM as float64 or float32 (z_dtype GLH_PD_F64 / GLH_PD_F32); mask [ny][nx] (0 = skip the cell) or NULL
+ * (every cell; a NaN elevation never projects); values [ny][nx][layers] of v_dtype (GLH_PD_F64, _F32, _U8, _U16), NULL
+ * with layers == 0.  The tiling is the caller's (Grid.tile_indices, raster.py:581-610; the device never re-derives it): the
+ * tiles are the cross product of n_ty row slices [y_start[k], y_end[k]) and n_tx column slices [x_start[k], x_end[k]), in
+ * row-major order; x_coords holds, slice after slice, the x of each column of the slice as the tile's own Grid.x has it
+ * (sum of the widths entries), y_coords likewise per row slice.  A cell takes part in a tile when its mask is set, it lies
+ * in front of the camera and its uv truncate to a pixel of the image (a uv exactly on the far edge, where the reference
+ * raises, is out of frame).  Within a tile a pixel is sum * (1 / count) per layer, the sum in float64 in row-major cell
+ * order as np.bincount forms it; across tiles the last tile that reaches a pixel overwrites the earlier ones (no depth
+ * test).  The value layers are bit for bit the reference's, and two calls give identical bytes.
+ * times_ms (or NULL) [8]: HIP-event milliseconds -- [0] upload, [1] project, [2] order (winners, sort, runs), [3] reduce,
+ * [4] download -- then [5] memberships (cells summed over the tiles), [6] memberships kept, [7] bytes of the sort's scratch.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, sizes < 1, no layer at all, values without layers or
+ * layers without values, slices that are empty, not ascending or outside the DEM, an imgsz that is not a positive
+ * integer), GLH_E_UNSUPPORTED (an unknown dtype code, a raster grid as camera, 2^31 or more memberships, cells or
+ * pixels).  A failed device allocation is GLH_E_NOMEM.                                                                 */
+#define GLH_PD_F64 0
+#define GLH_PD_F32 1
+#define GLH_PD_U8 2
+#define GLH_PD_U16 3
+int glh_stage_project_dem(int device_id, const double* cam, const void* z, int z_dtype, int nx, int ny,
+                          const uint8_t* mask, const void* values, int v_dtype, int layers, int n_tx,
+                          const int32_t* x_start, const int32_t* x_end, const double* x_coords, int n_ty,
+                          const int32_t* y_start, const int32_t* y_end, const double* y_coords, int return_depth,
+                          double* out, double* times_ms);
+/* Camera.rasterize (camera.py:858-883; helpers.rasterize_points, helpers.py:1617-1698): n points, each with its pixel
+ * keys [n] in [0, n_pixels) and values [n][layers] float64, to out [n_pixels][layers]: per pixel sum * (1 / count) with
+ * the sum in the points' order, NaN without a point.  The sort and the reduction are glh_stage_project_dem's.  times_ms as
+ * there ([1] is the index fill; [5] = [6] = n).  GLH_E_INVALID before a device is touched: null pointers, n, layers or
+ * n_pixels < 1, a key outside [0, n_pixels).                                                                          */
+int glh_stage_rasterize(int device_id, const int32_t* keys, int n, const double* values, int layers, int n_pixels,
+                        double* out, double* times_ms);
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
 

@@ -16,6 +16,8 @@ Fixtures:
   g8_c5mini.npz       2 observers (nadir + oblique), dem_sigma > 0, 2 pts x 200 particles
   g27_reproject.npz   Image.project: four dtypes, one / three channels, linear / nearest, six camera pairs (--g27)
   g28_viewshed.npz    Raster.viewshed on seeded exact terrain: 14 cases, results packed, DEMs by SHA-256 (--g28)
+  g29_project_dem.npz Camera.project_dem / Camera.rasterize on seeded exact terrain: the cases' parameters, the images,
+                      the admission margins, Grid.tile_indices; DEMs by SHA-256 (--g29)
 Every g8 file stores frames, cameras, motion parameters, the recorded legacy
 RNG draws (in the reference's order), per-step traces (uv, box, search tile,
 sse, sampled ll, weights, searchsorted indices, particles) and Tracks.means /
@@ -1441,8 +1443,161 @@ def g28_viewshed(path=None):
     np.savez_compressed(path, **out)
     print("g28 ->", path, os.path.getsize(path), "bytes")
 
+# ---- g29: Camera.project_dem, Camera.rasterize ---------------------------------------------------------------------
+# name -> inputs (tests/project_dem_restatement.py: case_inputs), camera, tiling.  DEMs of 96 x 128 cells of 10 m
+# (x 0 .. 1280, y 0 .. 960) into 64 x 48 pixels.  Cameras: "across" stands west of the DEM and looks east over it (pixels
+# are reached by several tiles: the last must win), "inside" stands in the DEM with cells behind it, "far" looks at it
+# from 6 km at a grazing angle (a pixel collects hundreds of cells).
+G29_CAMERAS = {
+    "across": dict(xyz=(-300.0, 470.0, 150.0), viewdir=(90.0, -14.0, 0.0), f=40.0),
+    "inside": dict(xyz=(640.3, 480.7, 60.0), viewdir=(31.0, -24.0, 5.0), f=30.0),
+    "far": dict(xyz=(-6000.0, 481.0, 100.0), viewdir=(90.0, -1.0, 0.0), f=60.0),
+}
+G29_CASES = {
+    "tiles32": dict(camera="across", tile_size=(32, 32), tile_overlap=(1, 1), values="f64x1"),
+    "single_tile": dict(camera="across", tile_size=(256, 256), tile_overlap=(1, 1), values="f64x1"),
+    "tiles40x24_distorted": dict(camera="across", tile_size=(40, 24), tile_overlap=(3, 2), values="f64x3", return_depth=True,
+                                 k=(0.11, -0.04, 0.008, 0.02, -0.006, 0.001), p=(0.004, -0.003), c=(1.7, -2.2)),
+    "inside_depth_only": dict(camera="inside", tile_size=(32, 32), tile_overlap=(0, 0), values="none", return_depth=True,
+                              y="asc"),
+    "far_field": dict(camera="far", tile_size=(128, 48), tile_overlap=(1, 1), values="f64x1", return_depth=True),
+    "correction_holes_f32": dict(camera="across", tile_size=(32, 32), tile_overlap=(1, 1), values="f32x2", holes=True,
+                                 correction={"radius": 3.0e6, "refraction": 0.2}, return_depth=True),
+    "mask_u8_dem32": dict(camera="inside", tile_size=(40, 24), tile_overlap=(1, 1), values="u8x3", mask=True,
+                          dem_dtype="float32"),
+    "u16_y_ascending": dict(camera="across", tile_size=(32, 32), tile_overlap=(3, 2), values="u16x1", y="asc"),
+}
+G29_TILINGS = [((96, 128), (32, 32), (1, 1)), ((96, 128), (40, 24), (3, 2)), ((96, 128), (256, 256), (1, 1)),
+               ((96, 128), (32, 32), (0, 0)), ((3, 3), (256, 256), (1, 1)), ((100, 100), (256, 256), (1, 1)),
+               ((7, 300), (100, 2), (2, 1)), ((5, 4), (2, 2), (1, 1))]
+
+
+def g29_project_dem(path=None):
+    """Camera.project_dem (camera.py:967-1129) and Camera.rasterize (:858-883) of the reference.  A case is admitted
+    only if, for every cell that is masked in, not NaN and in front of the camera, u and v are at least 1e-6 px from
+    every integer and every depth is at least 1e-6 from 0 -- the device's projection is within 1e-9 of the reference's
+    (tests/test_gpu_parity.py), so no cell can change its pixel.  The margins are stored."""
+    from tests import project_dem_restatement as pr
+    from tests import viewshed_terrain as vt
+
+    MARGIN = 1e-6
+    counts_seen = []
+    real_rasterize_points = glimpse.helpers.rasterize_points
+
+    def counting(rows, cols, values, shape=None, a=None):
+        if a is None:
+            idx, n = np.unique(np.ravel_multi_index((rows, cols), shape[0:2]), return_counts=True)
+            counts_seen.append((idx, n))
+        return real_rasterize_points(rows, cols, values, shape=shape, a=a)
+
+    def run(name, seed):
+        c = G29_CASES[name]
+        z, xlim, ylim, values, mask = pr.case_inputs((96, 128), seed, y=c.get("y", "desc"), holes=c.get("holes", False),
+                                                     mask=c.get("mask", False), dem_dtype=c.get("dem_dtype", "float64"),
+                                                     values=c["values"])
+        cc = G29_CAMERAS[c["camera"]]
+        top = float(np.nanmax(z))
+        cam = glimpse.Camera(imgsz=(64, 48), f=cc["f"], c=c.get("c", (0, 0)), k=c.get("k", (0,) * 6), p=c.get("p", (0, 0)),
+                             xyz=(cc["xyz"][0], cc["xyz"][1], top + cc["xyz"][2]), viewdir=cc["viewdir"],
+                             correction=c.get("correction", False))
+        dem = glimpse.Raster(z, x=xlim, y=ylim)
+        counts_seen.clear()
+        glimpse.helpers.rasterize_points = counting
+        try:
+            with warnings.catch_warnings(), np.errstate(all="ignore"):
+                warnings.simplefilter("ignore")
+                img = cam.project_dem(dem, values=values, mask=mask, tile_size=c["tile_size"],
+                                      tile_overlap=c["tile_overlap"], return_depth=c.get("return_depth", False))
+        finally:
+            glimpse.helpers.rasterize_points = real_rasterize_points
+        behind = np.zeros(64 * 48, dtype=np.int64)
+        for idx, n in counts_seen:  # (the last tile's count stays, as its mean does)
+            behind[idx] = n
+        # the margins, over every tile's cells as the reference projects them
+        m_uv, m_depth, on_edge = np.inf, np.inf, 0
+        use = ~np.isnan(z) if mask is None else mask
+        for ij in dem.tile_indices(size=c["tile_size"], overlap=c["tile_overlap"]):
+            tile, tm = dem[ij], use[ij]
+            xyz = glimpse.helpers.grid_to_points((tile.X[tm], tile.Y[tm], tile.array[tm]))
+            with np.errstate(all="ignore"):
+                xy, depth = cam._xyz_to_xy(xyz, return_depth=True)
+                uv = cam._xy_to_uv(xy)
+            ok = ~np.isnan(xyz[:, 2])
+            m_depth = min(m_depth, float(np.min(np.abs(depth[ok]), initial=np.inf)))
+            front = ok & (depth > 0)
+            m_uv = min(m_uv, float(np.min(np.abs(uv[front] - np.round(uv[front])), initial=np.inf)))
+            on_edge += int(np.sum((uv[front, 0] == 64) | (uv[front, 1] == 48)))
+        vec = np.zeros(24)
+        vec[:20] = cam._vector
+        if isinstance(cam.correction, dict):
+            vec[20:23] = 1.0, cam.correction["radius"], cam.correction["refraction"]
+        return z, vec, img, behind.reshape(48, 64), m_uv, m_depth, on_edge
+
+    out, names = {}, sorted(G29_CASES)
+    for name in names:
+        c = G29_CASES[name]
+        for seed in range(2900, 2920):
+            z, vec, img, behind, m_uv, m_depth, on_edge = run(name, seed)
+            ok = m_uv >= MARGIN and m_depth >= MARGIN and on_edge == 0 and np.isfinite(img).any()
+            if name == "far_field":
+                ok = ok and behind.max() > 256
+            print("g29", name, "seed", seed, "uv margin %.3g" % m_uv, "depth margin %.3g" % m_depth, "pixels hit",
+                  int((behind > 0).sum()), "most cells in a pixel", int(behind.max()), "kept" if ok else "dropped")
+            if ok:
+                break
+        else:
+            raise RuntimeError(f"g29 {name}: no seed is admitted")
+        assert m_uv >= MARGIN and m_depth >= MARGIN
+        out[f"{name}__seed"] = np.int64(seed)
+        out[f"{name}__sha256"] = vt.sha256(z)
+        out[f"{name}__cam"] = vec
+        out[f"{name}__image"] = img
+        out[f"{name}__counts"] = behind.astype(np.int32)
+        out[f"{name}__margins"] = np.array([m_uv, m_depth])
+        out[f"{name}__tiling"] = np.array([*c["tile_size"], *c["tile_overlap"]], dtype=np.int64)
+        out[f"{name}__flags"] = np.array([c.get("y", "desc") == "asc", c.get("holes", False), c.get("mask", False),
+                                          c.get("dem_dtype", "float64") == "float32", c.get("return_depth", False)])
+        out[f"{name}__values"] = np.array(c["values"])
+    out["cases"] = np.array(names)
+    assert len({tuple(out[f"{n}__tiling"]) for n in names}) >= 4
+    # the docstring's example: a camera straight above a 3 x 3 raster, one cell per pixel
+    cam = glimpse.Camera(imgsz=3, f=3, xyz=(0, 0, 3), viewdir=(0, -90, 0))
+    Z = np.array([(0.1, 0.2, 0.3), (0.4, 0.5, 0.6), (0.7, 0.8, 0.9)])
+    vals = np.random.default_rng(29).integers(-2 ** 30, 2 ** 30, size=(3, 3)) / 2.0 ** 12
+    out["doctest__values"] = vals
+    out["doctest__image"] = cam.project_dem(glimpse.Raster(Z, x=(-1, 0, 1), y=(1, 0, -1)), values=vals, return_depth=True)
+    assert np.all(out["doctest__image"][:, :, 0] == vals)
+    # Grid.tile_indices
+    for k, (shape, size, overlap) in enumerate(G29_TILINGS):
+        with np.errstate(all="ignore"):
+            tiles = glimpse.Raster(np.zeros(shape)).tile_indices(size=size, overlap=overlap)
+        out[f"tiling{k}__args"] = np.array([*shape, *size, *overlap], dtype=np.int64)
+        out[f"tiling{k}__slices"] = np.array([(i.start, i.stop, j.start, j.stop) for i, j in tiles], dtype=np.int64)
+    out["tilings"] = np.int64(len(G29_TILINGS))
+    # Camera.rasterize: the docstring's example, and seeded points with repeats and two value columns.  The reference's
+    # method writes into a 2-d image and so fails for more than one column; helpers.rasterize_points, which it calls,
+    # serves them on an image with a third axis -- called here the way the method calls it.
+    cam = glimpse.Camera(imgsz=(3, 2), f=1)
+    out["rasterize_doctest__image"] = cam.rasterize(uv=np.array([(0.5, 0.5), (2.5, 1.5), (2.5, 1.5)]),
+                                                    values=np.array([1, 2, 4]))
+    cam = glimpse.Camera(imgsz=(64, 48), f=40)
+    uv, values = pr.rasterize_inputs(2929, 5000, (64, 48))
+    keep = cam.inframe(uv)
+    assert not np.any((uv[keep, 0] == 64) | (uv[keep, 1] == 48)) and 1000 < keep.sum() < 5000
+    a = np.full((48, 64, 2), np.nan)
+    glimpse.helpers.rasterize_points(uv[keep, 1].astype(int), uv[keep, 0].astype(int), values[keep], a=a)
+    out["rasterize_points__image"] = a
+    out["rasterize_points__one_column"] = cam.rasterize(uv=uv, values=values[:, 0])
+    assert np.array_equal(a[:, :, 0], out["rasterize_points__one_column"], equal_nan=True)
+    path = path or os.path.join(OUT, "g29_project_dem.npz")
+    np.savez_compressed(path, **out)
+    print("g29 ->", path, os.path.getsize(path), "bytes")
+
 
 if __name__ == "__main__":
+    if "--g29" in sys.argv:
+        g29_project_dem(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+        sys.exit(0)
     if "--g28" in sys.argv:
         g28_viewshed(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
         sys.exit(0)

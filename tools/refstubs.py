@@ -77,7 +77,9 @@ def install():
             for item in sequence:
                 r = func(*item) if star else func(item)
                 if reduce is not None:
-                    r = reduce(r)
+                    # sharedmem unpacks a tuple result into reduce's arguments (Camera.project_dem returns (idx, means)
+                    # per tile; Tracker.track returns a list, which is passed whole)
+                    r = reduce(*r) if isinstance(r, tuple) else reduce(r)
                 results.append(r)
             return results
 
