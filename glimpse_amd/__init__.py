@@ -10,6 +10,7 @@ glimpse_amd/lib/libglimpse_hip.so, bound with ctypes in glimpse_amd._lib).  Ther
 fallback: build the library with `python -m glimpse_amd.build`.
 """
 from .camera import Camera
+from .filters import gaussian_filter, maximum_filter
 from .image import Image
 from .motion import (CartesianMotion, CylindricalMotion, Motion, TangentCartesianMotion,
                      TangentCylindricalMotion)
@@ -19,5 +20,6 @@ from .tracker import Tracker
 from .tracks import Tracks
 
 __all__ = ["Camera", "Image", "Observer", "Motion", "CartesianMotion", "CylindricalMotion",
-           "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "Tracker", "Tracks"]
+           "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "Tracker", "Tracks", "maximum_filter",
+           "gaussian_filter"]
 __version__ = "0.1.0"

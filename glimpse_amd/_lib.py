@@ -154,6 +154,9 @@ SIGNATURES = {
     "glh_stage_viewshed": (_I, [_I, _P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _D, _D, _P, _P]),
     "glh_stage_project_dem": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "glh_stage_rasterize": (_I, [_I, _P, _I, _P, _I, _I, _P, _P]),
+    "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "glh_stage_gaussian_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
+    "glh_stage_fill_crevasses": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
 }
 
 _lib = None
@@ -954,3 +957,66 @@ def stage_rasterize(keys, values, n_pixels, device_id=0, return_times=False):
     check(load().glh_stage_rasterize(device_id, _ptr(keys), len(keys), _ptr(values), values.shape[1], int(n_pixels),
                                      _ptr(out), _ptr(times) if return_times else None))
     return _pd_result(out, times, return_times)
+
+
+FILTER_F64, FILTER_F32 = 0, 1
+FILTER_TIMES = ("upload_ms", "max_ms", "gauss0_ms", "gauss1_ms", "download_ms")
+
+
+def _filter_array(a, mask):
+    """(a, dtype flag, nx, ny, mask, out) of the filter stages: `a` (ny, nx) float64 / float32, `mask` uint8 (ny, nx) or
+    None; glimpse_amd.filters checks what the caller gave."""
+    if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 2:
+        raise TypeError(f"a two-dimensional float64 or float32 array (got {a.dtype}, {a.ndim} dimensions)")
+    a = np.ascontiguousarray(a)
+    ny, nx = a.shape
+    if mask is not None:
+        mask = _arr(mask, np.uint8, (ny, nx))
+    return a, FILTER_F32 if a.dtype == np.float32 else FILTER_F64, nx, ny, mask, np.empty_like(a)
+
+
+def _filter_weights(w):
+    """(table, radius) of one axis of the Gaussian; (None, 0) for a skipped axis."""
+    if w is None:
+        return None, 0
+    w = _arr(w, np.float64)
+    if w.ndim != 1 or len(w) % 2 != 1:
+        raise ValueError("a weight table has 2 * radius + 1 entries")
+    return w, len(w) // 2
+
+
+def _filter_result(out, times, return_times):
+    return (out, dict(zip(FILTER_TIMES, (float(t) for t in times)))) if return_times else out
+
+
+def stage_max_filter(a, mask, fill, size_y, size_x, mode=0, device_id=0, return_times=False):
+    """helpers.maximum_filter (helpers.py:390-430) with a window of size_y rows x size_x columns and the boundary `mode`
+    (a HIGHPASS_MODES code): a new array.  `return_times`: also a dict of the HIP-event split (FILTER_TIMES)."""
+    a, flag, nx, ny, mask, out = _filter_array(a, mask)
+    times = np.zeros(len(FILTER_TIMES))
+    check(load().glh_stage_max_filter(device_id, _ptr(a), flag, nx, ny, _ptr(mask), int(bool(fill)), int(size_y), int(size_x),
+                                      int(mode), _ptr(out), _ptr(times) if return_times else None))
+    return _filter_result(out, times, return_times)
+
+
+def stage_gaussian_filter(a, mask, fill, w0, w1, mode=0, device_id=0, return_times=False):
+    """helpers.gaussian_filter (helpers.py:347-387) with the weight tables `w0` (along rows) and `w1` (along columns) of
+    glimpse_amd.filters.gaussian_weights; None skips the axis."""
+    a, flag, nx, ny, mask, out = _filter_array(a, mask)
+    (w0, r0), (w1, r1) = _filter_weights(w0), _filter_weights(w1)
+    times = np.zeros(len(FILTER_TIMES))
+    check(load().glh_stage_gaussian_filter(device_id, _ptr(a), flag, nx, ny, _ptr(mask), int(bool(fill)), _ptr(w0), r0,
+                                           _ptr(w1), r1, int(mode), _ptr(out), _ptr(times) if return_times else None))
+    return _filter_result(out, times, return_times)
+
+
+def stage_fill_crevasses(a, mask, fill, size_y, size_x, max_mode, w0, w1, gauss_mode, device_id=0, return_times=False):
+    """Raster.fill_crevasses (raster.py:1266-1291): the Gaussian of the maximum, the same mask and `fill` for both, over
+    one upload and one download."""
+    a, flag, nx, ny, mask, out = _filter_array(a, mask)
+    (w0, r0), (w1, r1) = _filter_weights(w0), _filter_weights(w1)
+    times = np.zeros(len(FILTER_TIMES))
+    check(load().glh_stage_fill_crevasses(device_id, _ptr(a), flag, nx, ny, _ptr(mask), int(bool(fill)), int(size_y),
+                                          int(size_x), int(max_mode), _ptr(w0), r0, _ptr(w1), r1, int(gauss_mode), _ptr(out),
+                                          _ptr(times) if return_times else None))
+    return _filter_result(out, times, return_times)

@@ -19,6 +19,7 @@
 #include "glh_point_variants.h"
 #include "glh_project_dem.h"
 #include "glh_viewshed.h"
+#include "glh_filters.h"
 
 using namespace glh;
 
@@ -2891,6 +2892,76 @@ extern "C" int glh_stage_rasterize(int dev, const int32_t* keys, int n, const do
   char msg[512] = "";
   const int rc = rasterize_run(job, msg, sizeof msg);
   return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+// helpers.maximum_filter, helpers.gaussian_filter (helpers.py:347-430) and Raster.fill_crevasses (raster.py:1266-1291): the
+// arguments are checked here, before a device is touched; the kernels and the launches are glh_filters.hip's.
+static int check_filter_array(const char* who, const void* a, int dtype, int nx, int ny, const void* out) {
+  if (!a || !out) return fail(GLH_E_INVALID, "%s: null argument", who);
+  if (nx < 1 || ny < 1) return fail(GLH_E_INVALID, "%s: %d x %d cells: at least one of each", who, nx, ny);
+  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "%s: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", who, nx, ny);
+  if (dtype != GLH_FILTER_F64 && dtype != GLH_FILTER_F32)
+    return fail(GLH_E_UNSUPPORTED, "%s: dtype %d: 0 float64, 1 float32", who, dtype);
+  return GLH_OK;
+}
+
+static int check_filter_window(const char* who, int size_y, int size_x, int mode) {
+  if (size_y < 1 || size_x < 1) return fail(GLH_E_INVALID, "%s: a window of %d x %d cells", who, size_y, size_x);
+  if (size_y > FL_MAX_WINDOW || size_x > FL_MAX_WINDOW)
+    return fail(GLH_E_UNSUPPORTED, "%s: a window of %d x %d cells: up to %d a side are served", who, size_y, size_x, FL_MAX_WINDOW);
+  if (mode < GLH_HP_REFLECT || mode > GLH_HP_WRAP) return fail(GLH_E_UNSUPPORTED, "%s: boundary mode %d of the maximum", who, mode);
+  return GLH_OK;
+}
+
+static int check_filter_weights(const char* who, const double* w0, int r0, const double* w1, int r1, int mode) {
+  const double* w[2] = {w0, w1};
+  const int r[2] = {r0, r1};
+  for (int ax = 0; ax < 2; ++ax) {
+    if (!w[ax]) continue;
+    if (r[ax] < 0) return fail(GLH_E_INVALID, "%s: radius %d along axis %d", who, r[ax], ax);
+    if (r[ax] > FL_MAX_RADIUS)
+      return fail(GLH_E_UNSUPPORTED, "%s: radius %d along axis %d: up to %d cells are served", who, r[ax], ax, FL_MAX_RADIUS);
+    for (int k = 0; k <= 2 * r[ax]; ++k)
+      if (!std::isfinite(w[ax][k])) return fail(GLH_E_INVALID, "%s: weight %d of axis %d is not finite", who, k, ax);
+    for (int k = 0; k < r[ax]; ++k)
+      if (w[ax][k] != w[ax][2 * r[ax] - k]) return fail(GLH_E_UNSUPPORTED, "%s: the weights of axis %d are not symmetric", who, ax);
+  }
+  if (mode < GLH_HP_REFLECT || mode > GLH_HP_WRAP) return fail(GLH_E_UNSUPPORTED, "%s: boundary mode %d of the Gaussian", who, mode);
+  return GLH_OK;
+}
+
+static int run_filters(const FiltersJob& job) {
+  char msg[512] = "";
+  const int rc = filters_run(job, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+extern "C" int glh_stage_max_filter(int dev, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
+                                    int size_y, int size_x, int mode, void* out, double* times_ms) {
+  CHK(check_filter_array("max_filter", a, dtype, nx, ny, out));
+  CHK(check_filter_window("max_filter", size_y, size_x, mode));
+  return run_filters(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, mode, 0, nullptr, 0,
+                                nullptr, 0, 0, out, times_ms});
+}
+
+extern "C" int glh_stage_gaussian_filter(int dev, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
+                                         const double* w0, int r0, const double* w1, int r1, int mode, void* out,
+                                         double* times_ms) {
+  CHK(check_filter_array("gaussian_filter", a, dtype, nx, ny, out));
+  CHK(check_filter_weights("gaussian_filter", w0, r0, w1, r1, mode));
+  return run_filters(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 0, 1, 1, 0, 1, w0, r0, w1, r1, mode, out,
+                                times_ms});
+}
+
+extern "C" int glh_stage_fill_crevasses(int dev, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
+                                        int size_y, int size_x, int max_mode, const double* w0, int r0, const double* w1,
+                                        int r1, int gauss_mode, void* out, double* times_ms) {
+  CHK(check_filter_array("fill_crevasses", a, dtype, nx, ny, out));
+  CHK(check_filter_window("fill_crevasses", size_y, size_x, max_mode));
+  CHK(check_filter_weights("fill_crevasses", w0, r0, w1, r1, gauss_mode));
+  return run_filters(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, max_mode, 1, w0, r0,
+                                w1, r1, gauss_mode, out, times_ms});
 }
 
 extern "C" int glh_stage_resample(int dev, const double* weights, int n, double u, int64_t* idx) {

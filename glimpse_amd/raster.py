@@ -9,8 +9,9 @@ runs on the GPU (`glh_stage_raster_sample`; inside a tracking run the kernels sa
 raster themselves).  Of the terrain analysis, `viewshed(origin, correction)` (:1293-1389) is served, on the GPU
 (`glh_stage_viewshed`): it makes the `Tracker(viewshed=...)` input from a DEM and a camera position.
 `tile_indices(size, overlap)` (:581-610) cuts the grid into the tiles `Camera.project_dem` walks; it and the tiles' own
-coordinates (`__getitem__`, :670-693) are computed on the host and handed to the device.  File I/O (GDAL), resampling,
-`horizon`, `hillshade`, `fill_crevasses` are out of scope.
+coordinates (`__getitem__`, :670-693) are computed on the host and handed to the device.  `fill_crevasses` (:1266-1291),
+the smoothed surface handed to the motion models, runs on the GPU too (`glh_stage_fill_crevasses`; glimpse_amd/filters.py).
+File I/O (GDAL), resampling, `horizon`, `hillshade` are out of scope.
 """
 import warnings
 
@@ -171,6 +172,19 @@ class Raster:
             return np.ones(self.array.shape, dtype=bool)
         xyz = np.array([[float(origin[0]), float(origin[1]), float(origin[2])]])
         return _lib.stage_viewshed(self, xyz, correction, float32=flag == _lib.VIEWSHED_F32)[0]
+
+    def fill_crevasses(self, maximum={"size": 5}, gaussian={"sigma": 5}, mask=None, fill=False):
+        """A maximum filter of the values, then Gaussian smoothing (raster.py:1266-1291), in place: `array` becomes
+        gaussian_filter(maximum_filter(array, **maximum, mask, fill), **gaussian, mask, fill) of glimpse_amd.filters, bit
+        for bit the reference's.  `mask`: True where a cell is included, or a callable that makes it from `array`; the
+        same mask goes to both filters.  `fill`: excluded cells take interpolated values (NaN where no included cell is
+        in reach) instead of keeping their own.  One library call (`glh_stage_fill_crevasses`): the maximum never leaves
+        the device.  What is served and refused: glimpse_amd/filters.py."""
+        from . import filters
+
+        if callable(mask):
+            mask = mask(self.array)
+        self.array = filters.fill_crevasses(self.array, maximum, gaussian, mask=mask, fill=fill)
 
     def sample(self, xy, grid=False, order=1, bounds_error=True, fill_value=np.nan):
         """Values at points (n, 2): bilinear (order 1) or nearest cell (order 0) (raster.py:913-1027)."""

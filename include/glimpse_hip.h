@@ -522,6 +522,37 @@ int glh_stage_project_dem(int device_id, const double* cam, const void* z, int z
  * n_pixels < 1, a key outside [0, n_pixels).                                                                          */
 int glh_stage_rasterize(int device_id, const int32_t* keys, int n, const double* values, int layers, int n_pixels,
                         double* out, double* times_ms);
+/* helpers.maximum_filter(a, mask, fill, size, mode) (helpers.py:390-430; scipy.ndimage.maximum_filter) of a [ny][nx],
+ * float64 (dtype GLH_FILTER_F64) or float32 (GLH_FILTER_F32), into out [ny][nx] of the same dtype.  The window is size_y
+ * rows x size_x columns, each 1 .. 31 (a tile and its halo live in LDS), reaching size / 2 cells back and size - 1 - size / 2
+ * forward as SciPy centres it; `mode` is the boundary: 0 reflect, 1 nearest, 2 mirror, 3 wrap.  mask [ny][nx] (0 = excluded)
+ * or NULL: an excluded cell counts as the dtype's lowest finite value, and afterwards a's own values are put back at the
+ * excluded cells (fill == 0) or at the cells whose maximum is that lowest value (fill != 0).  A NaN at an included cell is
+ * the caller's to refuse (the comparison `v > m` drops it).
+ * times_ms (or NULL) [5]: HIP-event milliseconds -- [0] upload, [1] maximum, [2] Gaussian along axis 0, [3] along axis 1,
+ * [4] download (the same layout for the three filter stages; a stage that does not run is 0).
+ * Checked before a device is touched: GLH_E_INVALID (null a / out, nx or ny < 1, nx * ny >= 2^31, a window side < 1),
+ * GLH_E_UNSUPPORTED (another dtype or mode, a window side above 31).  A failed device allocation is GLH_E_NOMEM.        */
+#define GLH_FILTER_F64 0
+#define GLH_FILTER_F32 1
+int glh_stage_max_filter(int device_id, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
+                         int size_y, int size_x, int mode, void* out, double* times_ms);
+/* helpers.gaussian_filter(a, mask, fill, ...) (helpers.py:347-387; scipy.ndimage.gaussian_filter, order 0).  w0
+ * [2 * r0 + 1]: the normalised weights along axis 0 (rows) as the host's NumPy makes them, NULL when SciPy skips the axis;
+ * w1 [2 * r1 + 1] likewise along axis 1 (columns).  Radii 0 .. 4096 (the half table is kept in LDS); the tables must be
+ * symmetric, as a Gaussian's are: each pass is SciPy's symmetric form  tmp = in[0] w[0]; for j = -r .. -1: tmp += (in[j] +
+ * in[-j]) w[j], in float64 in that order, rounded to a's dtype after each axis, so the result equals SciPy's in every bit.
+ * With a mask: G(a, 0 at excluded cells) / G(1 at included cells) in a's dtype, a's own values put back at excluded cells
+ * when fill == 0; fill != 0 leaves 0 / 0 = NaN where no included cell is in reach.  `mode` and times_ms as above.
+ * GLH_E_INVALID: as above, a negative radius, a weight that is not finite; GLH_E_UNSUPPORTED: another dtype or mode, a
+ * radius above 4096, weights that are not symmetric.                                                                     */
+int glh_stage_gaussian_filter(int device_id, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
+                              const double* w0, int r0, const double* w1, int r1, int mode, void* out, double* times_ms);
+/* Raster.fill_crevasses (raster.py:1266-1291): the Gaussian of the maximum, both with the ORIGINAL mask and `fill`, over
+ * one upload and one download; the maximum never leaves the device.  Arguments, limits and times_ms as the two above.   */
+int glh_stage_fill_crevasses(int device_id, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
+                             int size_y, int size_x, int max_mode, const double* w0, int r0, const double* w1, int r1,
+                             int gauss_mode, void* out, double* times_ms);
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
 

@@ -18,6 +18,8 @@ Fixtures:
   g28_viewshed.npz    Raster.viewshed on seeded exact terrain: 14 cases, results packed, DEMs by SHA-256 (--g28)
   g29_project_dem.npz Camera.project_dem / Camera.rasterize on seeded exact terrain: the cases' parameters, the images,
                       the admission margins, Grid.tile_indices; DEMs by SHA-256 (--g29)
+  g30_fill_crevasses.npz Raster.fill_crevasses, helpers.maximum_filter, helpers.gaussian_filter on seeded exact terrain
+                      with crevasses: 21 cases, the three outputs of each, inputs by SHA-256 (--g30)
 Every g8 file stores frames, cameras, motion parameters, the recorded legacy
 RNG draws (in the reference's order), per-step traces (uv, box, search tile,
 sse, sampled ll, weights, searchsorted indices, particles) and Tracks.means /
@@ -1594,7 +1596,50 @@ def g29_project_dem(path=None):
     print("g29 ->", path, os.path.getsize(path), "bytes")
 
 
+# ---- g30: Raster.fill_crevasses, helpers.maximum_filter, helpers.gaussian_filter -----------------------------------------
+G30_SEEDS = {name: 3000 + k for k, name in enumerate((
+    "defaults", "holes_keep", "holes_fill", "block_fill", "callable_mask", "float32", "float32_holes_fill", "size_3x7",
+    "size_4", "sigma_2_0", "sigma_1p5_3_truncate_3", "radius_4_9", "mode_reflect", "mode_nearest", "mode_mirror",
+    "mode_wrap", "shorter_than_radius", "one_row", "one_column", "docstring_keep", "docstring_fill"))}
+
+
+def g30_fill_crevasses(path=None):
+    """The reference's own Raster.fill_crevasses (raster.py:1266-1291), helpers.maximum_filter and helpers.gaussian_filter
+    (helpers.py:347-430) on the cases of tests/fill_crevasses_restatement.py: per case the seed, the input's SHA-256 (the
+    inputs are rebuilt by the tests) and the three outputs -- the two helpers each applied to the INPUT with the case's
+    mask and `fill`."""
+    from tests import fill_crevasses_restatement as fr
+    from tests import viewshed_terrain as vt
+
+    assert sorted(G30_SEEDS) == sorted(fr.CASES)
+    out, names = {}, sorted(fr.CASES)
+    for name in names:
+        seed = G30_SEEDS[name]
+        z, maximum, gaussian, mask, fill = fr.build(name, seed)
+        array_mask = fr.resolved(mask, z)
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")  # (scipy.ndimage.filters is a deprecated name; 0 / 0 where nothing is in reach)
+            dem = glimpse.Raster(z.copy())
+            assert dem.fill_crevasses(maximum=maximum, gaussian=gaussian, mask=mask, fill=fill) is None
+            top = glimpse.helpers.maximum_filter(z.copy(), mask=array_mask, fill=fill, **maximum)
+            smooth = glimpse.helpers.gaussian_filter(z.copy(), mask=array_mask, fill=fill, **gaussian)
+        assert dem.array.dtype == z.dtype and dem.array.shape == z.shape
+        out[f"{name}__seed"] = np.int64(seed)
+        out[f"{name}__sha256"] = vt.sha256(z)
+        out[f"{name}__fill_crevasses"] = dem.array
+        out[f"{name}__maximum"] = top
+        out[f"{name}__gaussian"] = smooth
+        print("g30", name, z.shape, z.dtype, "NaN in:", int(np.isnan(z).sum()), "NaN out:", int(np.isnan(dem.array).sum()))
+    out["cases"] = np.array(names)
+    path = path or os.path.join(OUT, "g30_fill_crevasses.npz")
+    np.savez_compressed(path, **out)
+    print("g30 ->", path, os.path.getsize(path), "bytes")
+
+
 if __name__ == "__main__":
+    if "--g30" in sys.argv:
+        g30_fill_crevasses(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+        sys.exit(0)
     if "--g29" in sys.argv:
         g29_project_dem(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
         sys.exit(0)
