@@ -1053,16 +1053,15 @@ __device__ __forceinline__ float np_sum_flat_f32(const float* a, int n) {
 // once to list the leaves (no data touched), 8 lanes per leaf then form its sum exactly as np_pairwise_leaf_f32 does --
 // lane j the accumulator r[j], ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) by three exchange-adds (float addition
 // commutes, so both lanes of a pair hold the same bits), the tail by lane 0 -- and thread 0 walks the recursion again,
-// taking the leaf sums in order.  row_len > 0: the sum of a 2-D strided view as np.add.reduce forms it, out += pairwise(row)
-// row by row; row_len == 0: a flat array in chunks of 8192.  `list`: `cap` words of LDS (a leaf = offset | length << 16:
+// taking the leaf sums in order: a flat array in chunks of 8192 (a strided 2-D view is summed the same way).  `list`: `cap` words of LDS (a leaf = offset | length << 16:
 // offsets below 65 536).  Returns false (nothing done) when the leaves may not fit -- the caller sums serially.
 template <int NT>
-__device__ __forceinline__ bool np_sum_f32_block(const float* a, int n, int row_len, uint32_t* list, int cap, float* result) {
+__device__ __forceinline__ bool np_sum_f32_block(const float* a, int n, uint32_t* list, int cap, float* result) {
   __shared__ int s_nleaf;
   const int tid = threadIdx.x, sub = tid & 7;
-  const int unit = row_len > 0 ? row_len : 8192;
+  const int unit = 8192;
   const int units = (n + unit - 1) / unit;
-  if (!list || n >= 65536 || (long long)units * (unit <= 128 ? 1 : (min(unit, n) + 63) / 64) > cap) return false;  // (uniform)
+  if (!list || n >= 65536 || (long long)units * ((min(unit, n) + 63) / 64) > cap) return false;  // (uniform)
   if (tid == 0) {
     int k = 0;
     for (int o = 0; o < n; o += unit)
@@ -1194,43 +1193,14 @@ __device__ __forceinline__ float np_sum_flat_block(int n, uint32_t* node, float*
   }
   return acc;
 }
-// ... of an h x w strided view, w <= 128: out += pairwise(row), row by row, and a row is one leaf.  The rows' sums by 8
-// lanes each into val[h]; their ordered sum by wave 0, the values passed from lane to lane through v_readlane (64 dependent
-// additions, no memory in the chain).  val: >= h floats of LDS; *out: LDS.  All threads; ends with a barrier.
-template <int NT, typename LOAD>
-__device__ __forceinline__ void np_sum_rows_block(int h, int w, float* val, float* out, LOAD load) {
-  const int tid = threadIdx.x, sub = tid & 7;
-  for (int r0 = 0; r0 < h; r0 += NT / 8) {
-    const int r = r0 + (tid >> 3);
-    if (r < h) {
-      const float res = np_leaf_8lanes(r * w, w, sub, load);
-      if (sub == 0) val[r] = res;
-    }
-  }
-  __syncthreads();
-  if (tid < WAVE) {
-    float acc = 0.0f;
-    for (int c0 = 0; c0 < h; c0 += WAVE) {
-      const int v = c0 + tid < h ? __float_as_int(val[c0 + tid]) : 0;
-#pragma unroll
-      for (int k = 0; k < WAVE; ++k) {
-        if (c0 + k >= h) break;  // (uniform)
-        acc += __int_as_float(__builtin_amdgcn_readlane(v, k));
-      }
-    }
-    if (tid == 0) *out = acc;
-  }
-  __syncthreads();
-}
 
 // helpers.normalize (helpers.py:344) of a float32 box by the whole block with the tile in LDS (the fused kernel's float
 // branch): g[n] receives the gray values, then -- in place -- the normalised ones, (g - mean) * (1 / std) in float32, the two
-// sums in NumPy's order as above.  `words`: 512 words of LDS (tree slots / row sums).  Same bits as normalize_box_float
+// sums in NumPy's order as above.  `words`: 512 words of LDS (tree slots).  Same bits as normalize_box_float
 // below (the staged kernels' form: values as doubles in memory), which it replaces for tiles that fit.  Ends with a barrier.
 template <int NT>
 __device__ __forceinline__ void normalize_box_f32_block(const uint8_t* frame, int width, int channels, const int* box, float* g,
                                                         uint32_t* words, unsigned long long* stp = nullptr) {
-  __shared__ float s_rows;
   const int tid = threadIdx.x;
   const int w = box[2] - box[0], h = box[3] - box[1], n = w * h;
   uint32_t* node = words;
@@ -1267,19 +1237,9 @@ __device__ __forceinline__ void normalize_box_f32_block(const uint8_t* frame, in
   __syncthreads();
   if (stp && tid == 0) stp[(size_t)blockIdx.x * GLH_NSTAMP + 20] = __builtin_amdgcn_s_memtime();
   auto plain = [g](int i) { return g[i]; };
-  float total;
-  if (channels == 1 && w <= 128 && h <= 256) {  // a strided view of the frame: row by row
-    np_sum_rows_block<NT>(h, w, val, &s_rows, plain);
-    total = s_rows;
-  } else if (channels == 1) {  // (rows that split: one tree per row, in order)
-    total = 0.0f;
-    for (int r = 0; r < h; ++r) {
-      total += np_pairwise_block<NT>(r * w, w, node, val, plain);
-      __syncthreads();
-    }
-  } else {  // the channel mean is a new contiguous array
-    total = np_sum_flat_block<NT>(n, node, val, plain);
-  }
+  // (a one-channel tile is a strided view of the frame, the channel mean of a three-channel one a new array: np.add.reduce
+  // sums either through its buffer, flat)
+  const float total = np_sum_flat_block<NT>(n, node, val, plain);
   const float mean = total / (float)n;
   if (stp && tid == 0) stp[(size_t)blockIdx.x * GLH_NSTAMP + 21] = __builtin_amdgcn_s_memtime();
   const float sq = np_sum_flat_block<NT>(n, node, val, [g, mean](int i) {
@@ -1295,9 +1255,9 @@ __device__ __forceinline__ void normalize_box_f32_block(const uint8_t* frame, in
 
 // normalize (helpers.py:344) of the box into y[n]: (a - a.mean()) * (1 / a.std()); all threads; ends with a barrier.
 // float64 frames: block reductions (the last bits of a float64 mean decide nothing).  float32 frames: float32 arithmetic
-// with NumPy's own summation order, on thread 0 -- a one-channel tile is a strided view of the frame, which NumPy sums
-// row by row (out += pairwise(row)); the channel mean of a three-channel tile is a new contiguous array, summed flat;
-// (a - mean)^2 is contiguous either way.  `tmp`: 2 n floats of scratch that may overlap y (not each other).
+// with NumPy's own summation order, on thread 0 -- np.add.reduce takes a one-channel tile, a strided view of the frame,
+// through its buffer and sums it flat, in chunks of 8192 items, like the contiguous channel mean of a three-channel tile and
+// like (a - mean)^2 (NumPy 2.2; tests/test_oracle_golden.py holds this restatement to np.sum on views of many shapes).  `tmp`: 2 n floats of scratch that may overlap y (not each other).
 template <int NT = BLK>
 __device__ __forceinline__ void normalize_box_float(const uint8_t* frame, int width, int channels, int bits, const int* box,
                                                     double* y, float* tmp_g, float* tmp_x2, double* red, bool* const_tile,
@@ -1312,17 +1272,9 @@ __device__ __forceinline__ void normalize_box_float(const uint8_t* frame, int wi
     }
     __syncthreads();
     // (the sums by the whole block when the leaves of NumPy's recursion fit `list`, by thread 0 otherwise: same bits)
-    const bool par_g = np_sum_f32_block<NT>(tmp_g, n, channels == 1 ? w : 0, list, list_cap, &s_sum);
+    const bool par_g = np_sum_f32_block<NT>(tmp_g, n, list, list_cap, &s_sum);
     if (tid == 0) {
-      float acc = s_sum;
-      if (!par_g) {
-        acc = 0.0f;
-        if (channels == 1)
-          for (int r = 0; r < h; ++r) acc += np_pairwise_f32(tmp_g + (size_t)r * w, w);
-        else
-          acc = np_sum_flat_f32(tmp_g, n);
-      }
-      s_mean = acc / (float)n;
+      s_mean = (par_g ? s_sum : np_sum_flat_f32(tmp_g, n)) / (float)n;
     }
     __syncthreads();
     const float mean = s_mean;
@@ -1331,7 +1283,7 @@ __device__ __forceinline__ void normalize_box_float(const uint8_t* frame, int wi
       tmp_x2[idx] = d * d;
     }
     __syncthreads();
-    const bool par_x = np_sum_f32_block<NT>(tmp_x2, n, 0, list, list_cap, &s_sum);
+    const bool par_x = np_sum_f32_block<NT>(tmp_x2, n, list, list_cap, &s_sum);
     if (tid == 0) {
       const float var = (par_x ? s_sum : np_sum_flat_f32(tmp_x2, n)) / (float)n;
       s_inv = 1.0f / sqrtf(var);

@@ -77,13 +77,14 @@ def snap_box(uv, size, imgsz):
     return (nxy * 1.0 + 0.0).flatten().astype(int)
 
 
-def initialize_template(frame, cam, mean_xyz, tile_size):
-    """tracker.py:536-561.  Returns dict(box, duv, tile, histogram)."""
+def initialize_template(frame, cam, mean_xyz, tile_size, highpass_size=(5, 5), highpass_mode="reflect"):
+    """tracker.py:536-561.  Returns dict(box, duv, tile, histogram).  `highpass_size` / `highpass_mode`: Tracker.highpass,
+    which :556 hands on to extract_tile."""
     uv = camera.xyz_to_uv(cam, np.asarray(mean_xyz, dtype=float)[None, 0:3]).ravel()
     box = snap_box(uv, tile_size, cam[6:8])
     template = {"box": box, "duv": uv - box.reshape(2, -1).mean(axis=0), "uv": uv}
     template["tile"], template["histogram"] = extract_tile(
-        frame, box, return_histogram=True
+        frame, box, return_histogram=True, highpass_size=highpass_size, highpass_mode=highpass_mode
     )
     return template
 

@@ -22,11 +22,19 @@ from . import camera, resample, spline, ssd, tiles
 
 
 class Observer(dict):
-    def __init__(self, frames, cams, sigma=0.3, interp=(3, 3), ssd="f64"):
+    def __init__(self, frames, cams, sigma=0.3, interp=(3, 3), ssd="f64", highpass_size=(5, 5),
+                 highpass_mode="reflect"):
         """`interp` = (kx, ky) of Tracker(interpolation=...) (tracker.py:60, :585-590, :623); `ssd`: which
-        restatement of cv2.matchTemplate's accumulation (oracle/ssd.py) -- "f64" or "row_f32"."""
+        restatement of cv2.matchTemplate's accumulation (oracle/ssd.py) -- "f64" or "row_f32"; `highpass_size` /
+        `highpass_mode`: the entries of Tracker(highpass=...) (tracker.py:59, :530), carried here like `interp`."""
+        size = (int(highpass_size),) * 2 if np.isscalar(highpass_size) else tuple(int(v) for v in highpass_size)
         super().__init__(frames=list(frames), cams=np.asarray(cams, dtype=float), sigma=sigma, interp=tuple(interp),
-                         ssd=ssd)
+                         ssd=ssd, highpass_size=size, highpass_mode=highpass_mode)
+
+
+def _highpass(obs):
+    """extract_tile's high-pass arguments of an observer (plain dicts without them: the reference's defaults)."""
+    return {"highpass_size": obs.get("highpass_size", (5, 5)), "highpass_mode": obs.get("highpass_mode", "reflect")}
 
 
 def observer_log_likelihoods(obs, img, template, particles, trace=None):
@@ -47,7 +55,7 @@ def observer_log_likelihoods(obs, img, template, particles, trace=None):
         warnings.warn("Particles too close to or beyond image bounds, skipping image")
         return None
     box = box.ravel()
-    search_tile = tiles.extract_tile(frame, box, histogram=template["histogram"])
+    search_tile = tiles.extract_tile(frame, box, histogram=template["histogram"], **_highpass(obs))
     sse = ssd.match_template_sqdiff(
         search_tile.astype(np.float32), template["tile"].astype(np.float32), accumulate=obs.get("ssd", "f64")
     )
@@ -172,7 +180,7 @@ def track_one(
                 img = matching[i][o]
                 mean = resample.particle_mean(particles, weights)
                 templates[o] = tiles.initialize_template(
-                    observers[o]["frames"][img], observers[o]["cams"][img], mean, tile_size
+                    observers[o]["frames"][img], observers[o]["cams"][img], mean, tile_size, **_highpass(observers[o])
                 )
                 if tr is not None:
                     tr.setdefault("templates", {})[int(o)] = templates[o]

@@ -847,7 +847,7 @@ def test_tracking_on_float64_frames_reproduces_reference(golden):
 def test_tracking_float32_and_multichannel_float_frames_reproduces_reference(golden, tag):
     """float32 frames (one or three channels) and three-channel float64 frames (tracker.py:494-534 works on any dtype):
     the reference normalises a tile in the frame's own dtype -- a float32 mean, standard deviation and scaling, summed in
-    NumPy's order (row by row over the strided view of a one-channel tile, flat over the channel mean of an RGB one) --
+    NumPy's order (flat in chunks of 8192, over the strided view of a one-channel tile as over the channel mean) --
     and so does the device: the template of a float32 frame (tile and sorted distinct values) equals the reference's BIT
     FOR BIT, the tracks follow (g24, reference run under this container's NumPy, same np.random seed)."""
     from tests.test_oracle_golden import float_scenes

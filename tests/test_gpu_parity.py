@@ -54,7 +54,13 @@ def test_stage_tiles_match_reference(lib, golden, name, key):
 def test_stage_ssd_matches_oracle(lib):
     rng = np.random.default_rng(7)
     for (hs, ws, th, tw) in [(19, 18, 15, 15), (40, 52, 15, 15), (64, 64, 31, 31), (35, 90, 31, 31),
-                             (120, 131, 31, 31), (30, 33, 9, 11), (200, 36, 31, 31)]:
+                             (120, 131, 31, 31), (30, 33, 9, 11), (200, 36, 31, 31),
+                             # even and non-square templates; 48, 49 and 63 pixels a side (the padded template rows of
+                             # the fused kernel's big-tile path end at 64 floats); a 63-wide and a 63-high strip
+                             (40, 41, 16, 16), (33, 50, 12, 20), (45, 28, 20, 8), (60, 70, 48, 48), (62, 61, 49, 49),
+                             (75, 80, 63, 63), (20, 90, 7, 63), (90, 20, 63, 7),
+                             # 1 x 1, 2 x 2 and 4 x 4 surfaces
+                             (15, 15, 15, 15), (32, 32, 31, 31), (12, 14, 9, 11)]:
         s = rng.standard_normal((hs, ws)).astype(np.float32)
         t = rng.standard_normal((th, tw)).astype(np.float32)
         want = ossd.match_template_sqdiff(s, t)

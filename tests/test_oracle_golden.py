@@ -556,3 +556,66 @@ def test_oracle_with_other_interpolation_orders(golden, orders, tag):
     res = otracker.track(models, observers, np.arange(6)[:, None], np.ones(5), tile_size=(15, 15))
     np.testing.assert_allclose(res["means"], g[f"k{kx}{ky}_{tag}_means"], rtol=1e-9, atol=1e-10)
     np.testing.assert_allclose(res["sigmas"], g[f"k{kx}{ky}_{tag}_sigmas"], rtol=1e-9, atol=1e-10)
+
+
+@pytest.mark.parametrize("tag,highpass", [("3", dict(highpass_size=(3, 3))), ("7", dict(highpass_size=(7, 7))),
+                                          ("nearest", dict(highpass_size=(5, 5), highpass_mode="nearest")),
+                                          ("mirror", dict(highpass_size=3, highpass_mode="mirror"))])
+def test_oracle_with_other_highpass_windows_and_modes(golden, tag, highpass):
+    """Tracker(highpass={"size": .., "mode": ..}) (tracker.py:59, :530) through a whole track: the oracle's loop, with the
+    window and the boundary mode carried on the Observer, against the reference run with the same seed (g17: 3 x 3 and
+    7 x 7 windows; g26: 'nearest' and 'mirror')."""
+    from oracle import motion as omotion
+    from oracle import tracker as otracker
+
+    g = golden("g17_highpass.npz" if tag in ("3", "7") else "g26_highpass_modes.npz")
+    scene = golden("g15_ragged.npz")
+    T = len(scene["frames"])
+    observers = [otracker.Observer(list(scene["frames"]), np.tile(scene["cam"], (T, 1)), 0.3, **highpass)]
+    models = [omotion.CartesianMotion(xy=xy, xy_sigma=(0.2, 0.2), vxyz=(0.15, 0, 0), vxyz_sigma=(0.2, 0.2, 0.0),
+                                      axyz=(0, 0, 0), axyz_sigma=(0.05, 0.05, 0.0), dem=0.0, dem_sigma=0.0, n=200)
+              for xy in g["e2e_xy"]]
+    np.random.seed(31)
+    res = otracker.track(models, observers, np.arange(T)[:, None], np.ones(T - 1), tile_size=(15, 15))
+    assert all(e is None for e in res["errors"])
+    np.testing.assert_allclose(res["means"], g[f"e2e_means_{tag}"], rtol=1e-9, atol=1e-10)
+    np.testing.assert_allclose(res["sigmas"], g[f"e2e_sigmas_{tag}"], rtol=1e-9, atol=1e-10)
+    # the options act: the default window gives another track
+    default = [otracker.Observer(list(scene["frames"]), np.tile(scene["cam"], (T, 1)), 0.3)]
+    np.random.seed(31)
+    other = otracker.track(models, default, np.arange(T)[:, None], np.ones(T - 1), tile_size=(15, 15))
+    assert not np.allclose(other["means"], g[f"e2e_means_{tag}"], rtol=1e-9, atol=1e-10)
+
+
+def test_numpy_sums_a_strided_float32_view_flat():
+    """The summation order the float32 tile stage restates (glh_kernels.h: normalize_box_float): np.sum of a strided 2-D
+    float32 view of a frame -- a one-channel tile -- equals the pairwise sum of the same items as one flat array in chunks of
+    8192, bit for bit, and is NOT the rows' pairwise sums added in order."""
+    rng = np.random.default_rng(0)
+    frame = rng.random((400, 600)).astype(np.float32)
+
+    def flat(a):
+        x = np.ascontiguousarray(a).ravel()
+        acc = np.float32(0)
+        for s in range(0, len(x), resample.NUMPY_BUFSIZE):
+            acc = np.float32(acc + resample._pairwise_rec(x[s:s + resample.NUMPY_BUFSIZE]))
+        return acc
+
+    def by_rows(a):
+        acc = np.float32(0)
+        for row in a:
+            acc = np.float32(acc + resample._pairwise_rec(row))
+        return acc
+
+    rows_differ = 0
+    for h, w in [(15, 15), (31, 33), (33, 31), (7, 9), (8, 8), (16, 17), (47, 47), (63, 7), (10, 129), (91, 90), (100, 100),
+                 (300, 30)]:
+        for _ in range(6):
+            y0, x0 = rng.integers(0, 100, 2)
+            a = frame[y0:y0 + h, x0:x0 + w]
+            assert not a.flags.c_contiguous
+            total = a.sum()
+            assert total.dtype == np.float32 and flat(a) == total, (h, w)
+            assert a.mean() == np.float32(total / np.float32(h * w))
+            rows_differ += by_rows(a) != total
+    assert rows_differ > 10
