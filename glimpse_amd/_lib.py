@@ -152,6 +152,7 @@ SIGNATURES = {
     "glh_stage_resample": (_I, [_I, _P, _I, _D, _P]),
     "glh_stage_raster_sample": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _D, _D, _D, _D, _P, _I, _I, _P, _P]),
     "glh_stage_viewshed": (_I, [_I, _P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _D, _D, _P, _P]),
+    "glh_stage_horizon": (_I, [_I, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _I, _I, _I, _D, _D, _P, _P, _P]),
     "glh_stage_project_dem": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "glh_stage_rasterize": (_I, [_I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
@@ -898,6 +899,45 @@ def stage_viewshed(raster, origins, correction=None, device_id=0, return_times=F
                                     _ptr(times) if return_times else None))
     vis = out.view(bool)
     return (vis, dict(zip(VIEWSHED_TIMES, (float(t) for t in times)))) if return_times else vis
+
+
+HORIZON_TIMES = ("upload_ms", "kernel_ms", "download_ms")
+
+
+def stage_horizon(raster, origins, starts, ends, correction=None, device_id=0, return_times=False, float32=None):
+    """The device part of Raster.horizon (raster.py:1435-1458) for the m positions `origins` (m, 3) over one upload of the
+    DEM: `starts` (m, 2) the (col, row) of each origin's cell, `ends` (m, n, 2) the (col, row) where each of its n rays
+    leaves the grid.  Returns (cell (m, n, 2) int32 (row, col), -1 where a heading has no horizon point; dz (m, n) of the
+    chosen cells, NaN there).  `float32`: whether dz stays float32, which depends on the type of the caller's origin
+    (Raster.horizon passes viewshed_dem's answer for it); None decides from `origins` as an array, a float64 one unless
+    the caller made it otherwise, so a float32 DEM is then widened.  `return_times`: also a dict of HORIZON_TIMES."""
+    on, radius, refraction = viewshed_correction(correction)
+    origins = np.asarray(origins)
+    if origins.ndim != 2 or origins.shape[1] != 3 or len(origins) < 1:
+        raise ValueError(f"origins must be (m, 3) with m >= 1, got {origins.shape}")
+    if float32 is None:
+        z, flag = viewshed_dem(raster.array, origins[0, 2])
+    else:
+        z = np.ascontiguousarray(raster.array, dtype=np.float32 if float32 else np.float64)
+        flag = VIEWSHED_F32 if float32 else VIEWSHED_F64
+    if z.ndim != 2:
+        raise ValueError(f"a DEM is two-dimensional, got {z.shape}")
+    m = len(origins)
+    origins = _arr(origins, np.float64)
+    starts = _arr(starts, np.int32, (m, 2))
+    ends = _arr(ends, np.int32)
+    if ends.ndim != 3 or ends.shape[0] != m or ends.shape[2] != 2 or ends.shape[1] < 1:
+        raise ValueError(f"ends must be ({m}, n, 2) with n >= 1, got {ends.shape}")
+    n = ends.shape[1]
+    ny, nx = z.shape
+    d = raster.d
+    cell = np.empty((m, n, 2), dtype=np.int32)
+    dz = np.empty((m, n), dtype=np.float64)
+    times = np.zeros(len(HORIZON_TIMES))
+    check(load().glh_stage_horizon(device_id, _ptr(z), flag, nx, ny, float(raster.xlim[0]), float(raster.ylim[0]),
+                                   float(d[0]), float(d[1]), _ptr(origins), _ptr(starts), _ptr(ends), m, n, int(on), radius,
+                                   refraction, _ptr(cell), _ptr(dz), _ptr(times) if return_times else None))
+    return (cell, dz, dict(zip(HORIZON_TIMES, (float(t) for t in times)))) if return_times else (cell, dz)
 
 
 PD_F64, PD_F32, PD_U8, PD_U16 = 0, 1, 2, 3

@@ -18,6 +18,7 @@
 #include "glh_point.h"
 #include "glh_point_variants.h"
 #include "glh_project_dem.h"
+#include "glh_horizon.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
 
@@ -2828,6 +2829,42 @@ extern "C" int glh_stage_viewshed(int dev, const void* z, int z_dtype, int nx, i
   }
   char msg[512] = "";
   const int rc = viewshed_run(job, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+// Raster.horizon (raster.py:1391-1463): the arguments are checked here, before a device is touched; the kernel and the
+// launch are glh_horizon.hip's.
+extern "C" int glh_stage_horizon(int dev, const void* z, int z_dtype, int nx, int ny, double xlim0, double ylim0, double d0,
+                                 double d1, const double* origins, const int32_t* starts, const int32_t* ends, int m, int n,
+                                 int correction, double radius, double refraction, int32_t* cell, double* dz,
+                                 double* times_ms) {
+  if (!z || !origins || !starts || !ends || !cell || !dz) return fail(GLH_E_INVALID, "horizon: null argument");
+  if (nx < 1 || ny < 1 || m < 1 || n < 1)
+    return fail(GLH_E_INVALID, "horizon: %d x %d cells, %d origins, %d headings: at least one of each", nx, ny, m, n);
+  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "horizon: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", nx, ny);
+  if ((int64_t)m * n >= ((int64_t)1 << 24))  // (one workgroup of up to 256 lanes per line: a launch holds fewer than 2^32)
+    return fail(GLH_E_INVALID, "horizon: %d origins x %d headings: fewer than 2^24 lines are served", m, n);
+  if (z_dtype != GLH_VIEWSHED_F64 && z_dtype != GLH_VIEWSHED_F32)
+    return fail(GLH_E_UNSUPPORTED, "horizon: z_dtype %d: 0 float64, 1 float32", z_dtype);
+  if (!(std::isfinite(xlim0) && std::isfinite(ylim0) && std::isfinite(d0) && std::isfinite(d1) && d0 != 0.0 && d1 != 0.0))
+    return fail(GLH_E_INVALID, "horizon: corner (%g, %g), cell size (%g, %g)", xlim0, ylim0, d0, d1);
+  for (int i = 0; i < 3 * m; ++i)
+    if (!std::isfinite(origins[i])) return fail(GLH_E_INVALID, "horizon: origin %d is not finite", i / 3);
+  if (correction && !(std::isfinite(radius) && radius != 0.0 && std::isfinite(refraction)))
+    return fail(GLH_E_INVALID, "horizon: correction with radius %g, refraction %g", radius, refraction);
+  for (int o = 0; o < m; ++o)
+    if (starts[2 * o] < 0 || starts[2 * o] >= nx || starts[2 * o + 1] < 0 || starts[2 * o + 1] >= ny)
+      return fail(GLH_E_INVALID, "horizon: start cell (col %d, row %d) of origin %d is outside the %d x %d grid", starts[2 * o],
+                  starts[2 * o + 1], o, nx, ny);
+  for (int64_t i = 0; i < (int64_t)m * n; ++i)
+    if (ends[2 * i] < 0 || ends[2 * i] >= nx || ends[2 * i + 1] < 0 || ends[2 * i + 1] >= ny)
+      return fail(GLH_E_INVALID, "horizon: end cell (col %d, row %d) of origin %d, heading %d is outside the %d x %d grid",
+                  ends[2 * i], ends[2 * i + 1], (int)(i / n), (int)(i % n), nx, ny);
+  const HorizonJob job{dev, z, z_dtype == GLH_VIEWSHED_F32, nx, ny, xlim0, ylim0, d0, d1, origins, starts, ends, m, n,
+                       correction != 0, radius, refraction, cell, dz, times_ms};
+  char msg[512] = "";
+  const int rc = horizon_run(job, msg, sizeof msg);
   return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
 }
 

@@ -1,5 +1,5 @@
 """`Raster`: the in-memory part of `glimpse.Raster` that the tracking path samples
-(/root/reference/src/glimpse/raster.py): a gridded surface (DEM, DEM uncertainty, viewshed) defined by
+(the reference's src/glimpse/raster.py): a gridded surface (DEM, DEM uncertainty, viewshed) defined by
 its array and outer x / y limits, sampled at points.
 
 Only what `Tracker` / the motion models use is mirrored: the constructor from an array and limits
@@ -7,11 +7,13 @@ Only what `Tracker` / the motion models use is mirrored: the constructor from an
 bounds test (`inbounds_xy`, :313-337) and `sample(xy, order in {0, 1})` at points (:913-1027).  Sampling
 runs on the GPU (`glh_stage_raster_sample`; inside a tracking run the kernels sample the uploaded
 raster themselves).  Of the terrain analysis, `viewshed(origin, correction)` (:1293-1389) is served, on the GPU
-(`glh_stage_viewshed`): it makes the `Tracker(viewshed=...)` input from a DEM and a camera position.
+(`glh_stage_viewshed`): it makes the `Tracker(viewshed=...)` input from a DEM and a camera position.  So is its sibling
+`horizon(origin, headings, correction)` (:1391-1463), the visible horizon as world-coordinate lines for camera calibration
+(`glh_stage_horizon`: one workgroup per heading; the rays' start and end cells are computed on the host).
 `tile_indices(size, overlap)` (:581-610) cuts the grid into the tiles `Camera.project_dem` walks; it and the tiles' own
 coordinates (`__getitem__`, :670-693) are computed on the host and handed to the device.  `fill_crevasses` (:1266-1291),
 the smoothed surface handed to the motion models, runs on the GPU too (`glh_stage_fill_crevasses`; glimpse_amd/filters.py).
-File I/O (GDAL), resampling, `horizon`, `hillshade` are out of scope.
+File I/O (GDAL), resampling, `hillshade`, `gradient` are out of scope.
 """
 import warnings
 
@@ -172,6 +174,94 @@ class Raster:
             return np.ones(self.array.shape, dtype=bool)
         xyz = np.array([[float(origin[0]), float(origin[1]), float(origin[2])]])
         return _lib.stage_viewshed(self, xyz, correction, float32=flag == _lib.VIEWSHED_F32)[0]
+
+    def _snapped_colrow(self, xy):
+        """Grid.xy_to_rowcol(xy, snap=True) (raster.py:478-500 through snap_xy, :343-388) as (col, row): the cell each point
+        falls in, a point on a cell edge in the higher one, an exact hit on the far outer edges in the last one."""
+        corner = np.append(self.xlim[0], self.ylim[0])
+        nxy = (xy - corner) / self.d
+        nxy -= 0.5
+        nxy = np.floor(nxy + 0.5)
+        nxy[xy == np.append(self.xlim[1], self.ylim[1])] -= 1
+        nxy += 0.5
+        snapped = nxy * self.d + corner
+        return ((snapped - corner) / self.d - 0.5).astype(int)
+
+    def _horizon_rays(self, origin, headings):
+        """(start (2,), ends (n, 2)) of Raster.horizon's lines as (col, row) (raster.py:1418-1434): the origin's cell, and
+        per heading (degrees clockwise from north) the cell where the ray leaves the raster's box -- the exits of
+        helpers.intersect_rays_box (helpers.py:955-1001) in two dimensions, snapped.  The end cells are then clamped into
+        the grid: an exit that lies a rounding error outside the box snaps to row or column -1 or `size`, where the
+        reference raises (its snap repairs only exact hits on the far edges)."""
+        headings = np.array(headings, dtype=float)
+        thetas = -(headings - 90) * (np.pi / 180)
+        directions = np.column_stack((np.cos(thetas), np.sin(thetas)))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            invdir = 1 / directions
+            neg = invdir < 0
+            tmin = (np.where(neg[:, 0], self.max[0], self.min[0]) - origin[0]) * invdir[:, 0]
+            tmax = (np.where(neg[:, 0], self.min[0], self.max[0]) - origin[0]) * invdir[:, 0]
+            tymin = (np.where(neg[:, 1], self.max[1], self.min[1]) - origin[1]) * invdir[:, 1]
+            tymax = (np.where(neg[:, 1], self.min[1], self.max[1]) - origin[1]) * invdir[:, 1]
+            misses = (tmin > tymax) | (tymin > tmax)
+            tmax[misses] = np.nan
+            y_first = tymax < tmax
+            tmax[y_first] = tymax[y_first]
+            tmax[tmax < 0] = np.nan
+        xy_ends = np.array((origin[0], origin[1])) + tmax[:, None] * directions
+        if not np.isfinite(xy_ends).all():
+            raise ValueError("a ray from the origin does not leave the raster's box at a finite point")
+        start = self._snapped_colrow(np.array([[origin[0], origin[1]]]))[0]
+        ends = self._snapped_colrow(xy_ends)
+        nx, ny = (int(v) for v in self.size)
+        return start, np.column_stack((np.clip(ends[:, 0], 0, nx - 1), np.clip(ends[:, 1], 0, ny - 1)))
+
+    def _horizon_points(self, origin, headings, correction):
+        """hxyz (n, 3) of Raster.horizon before it is split into runs (raster.py:1436-1459): per heading the horizon point
+        [x, y, z], NaN where the heading has none."""
+        _lib.viewshed_correction(correction)  # (a TypeError for an unknown argument comes before anything else)
+        if self.array.ndim != 2:
+            raise ValueError(f"a DEM is two-dimensional, got {self.array.shape}")
+        z, flag = _lib.viewshed_dem(self.array, origin[2])
+        n = len(headings)
+        if n == 0:
+            return np.full((0, 3), np.nan)
+        origin_xyz = tuple(float(v) for v in origin[0:3])
+        if not self.inbounds_xy(np.atleast_2d(origin_xyz[0:2]))[0]:
+            raise ValueError(f"origin {origin_xyz[0:2]} is outside the raster (x {tuple(self.xlim)}, y {tuple(self.ylim)}): "
+                             "the horizon is computed from a position inside the DEM")
+        start, ends = self._horizon_rays(origin_xyz, headings)
+        cell, dz = _lib.stage_horizon(self, np.array([origin_xyz]), start[None, :], ends[None, :, :], correction,
+                                      float32=flag == _lib.VIEWSHED_F32)
+        cell, dz = cell[0], dz[0]
+        found = cell[:, 0] >= 0
+        hxyz = np.full((n, 3), np.nan)
+        hxyz[found, 0:2] = (cell[found] + 0.5)[:, ::-1] * self.d + np.array((self.xlim[0], self.ylim[0]))
+        hxyz[found, 2] = dz[found]
+        hxyz[:, 2] += origin_xyz[2]
+        return hxyz
+
+    def horizon(self, origin, headings=range(360), correction=False):
+        """The horizon from a point (raster.py:1391-1463): a list of (k, 3) float64 arrays, each an unbroken run of horizon
+        points [x, y, z] in heading order.  `headings`: degrees clockwise from north; `correction` as in `viewshed`.  Per
+        heading the cells of the Bresenham line from the origin's cell to the cell where the ray leaves the raster are
+        taken (the origin's cell skipped, NaN cells ignored), and the horizon point is the centre of the cell of greatest
+        elevation ratio, with its own elevation -- unless that cell is the line's last with a value, which is no horizon.
+        Runs are split where a heading has no point, circularly: the last run joins the first.  The lines are computed on
+        the GPU (`glh_stage_horizon`), bit for bit what the reference computes.  `origin` must lie inside the raster (the
+        reference raises for one outside, too).  One departure: the end cell of every ray is clamped into the grid, where
+        the reference raises for the many headings whose exit lies a rounding error outside the box."""
+        hxyz = self._horizon_points(origin, headings, correction)
+        if len(hxyz) == 0:
+            return []
+        # helpers.boolean_split(hxyz, mask, axis=0, circular=True)[mask[0]::2] (helpers.py:799-803)
+        mask = np.isnan(hxyz[:, 0])
+        cuts = np.nonzero(mask[1:] != mask[:-1])[0] + 1
+        splits = np.split(hxyz, cuts, axis=0)
+        if len(splits) > 1 and mask[0] == mask[-1]:
+            splits[0] = np.concatenate((splits[-1], splits[0]), axis=0)
+            splits.pop(-1)
+        return splits[int(mask[0])::2]
 
     def fill_crevasses(self, maximum={"size": 5}, gaussian={"sigma": 5}, mask=None, fill=False):
         """A maximum filter of the values, then Gaussian smoothing (raster.py:1266-1291), in place: `array` becomes

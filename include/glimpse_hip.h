@@ -487,6 +487,27 @@ int glh_stage_raster_sample(int device_id, const double* z, int nx, int ny, cons
 int glh_stage_viewshed(int device_id, const void* z, int z_dtype, int nx, int ny, const double* x, const double* y,
                        double inv_cell, const double* origins, int m, int correction, double radius,
                        double refraction, uint8_t* visible, double* times_ms);
+/* Raster.horizon(origin, headings, correction) (raster.py:1391-1463) for m >= 1 origins [m][3] with n headings each, over
+ * ONE upload of the DEM.  z, z_dtype (GLH_VIEWSHED_F64 / _F32), correction, radius and refraction as in glh_stage_viewshed;
+ * xlim0, ylim0 = the outer corner of cell (row 0, col 0) and d0, d1 = Grid.d as NumPy made it, with its signs: the centre
+ * of a cell is ((col + 0.5) d0 + xlim0, (row + 0.5) d1 + ylim0) (rowcol_to_xy, raster.py:461-476).  The rays are the
+ * caller's: starts [m][2] = the (col, row) of each origin's cell, ends [m][n][2] = the (col, row) where each ray leaves
+ * the grid (the host keeps NumPy's cos / sin).  Per (origin, heading) the cells of helpers.bresenham_line(start, end)
+ * after the start cell are taken, each with dz = z - origin z (float32 under _F32, widened afterwards) and the ratio
+ * dz / sqrt(dxy) -- (dz + (refraction - 1) dxy / (2 radius)) / sqrt(dxy) with correction -- in float64, operation by
+ * operation as NumPy rounds them.  A NaN dz makes a cell missing.  The horizon cell is the one of greatest ratio, the
+ * first among equals (np.nanargmax), and only if a cell that is not missing lies beyond it.
+ * cell [m][n][2] int32 = its (row, col), -1 -1 where the heading has no horizon point; dz [m][n] = its dz (NaN there).
+ * One workgroup per line, the cell index in closed form, a fixed-order reduction: two calls give the same bytes.
+ * times_ms (or NULL) [3]: HIP-event milliseconds -- [0] upload, [1] kernel, [2] download.
+ * Elevations are finite or NaN: with +-inf in z the choice among cells of ratio -inf or NaN is not np.nanargmax's.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, nx, ny, m or n < 1, nx * ny >= 2^31, m * n >= 2^24
+ * (a launch of one workgroup per line holds fewer than 2^32 lanes), a start or end cell outside the grid, origins, corner
+ * or cell sizes that are not finite, a cell size of 0, radius 0 with correction), GLH_E_UNSUPPORTED (an unknown z_dtype).
+ * A failed device allocation is GLH_E_NOMEM.                                                                            */
+int glh_stage_horizon(int device_id, const void* z, int z_dtype, int nx, int ny, double xlim0, double ylim0, double d0,
+                      double d1, const double* origins, const int32_t* starts, const int32_t* ends, int m, int n,
+                      int correction, double radius, double refraction, int32_t* cell, double* dz, double* times_ms);
 /* Camera.project_dem (camera.py:967-1129) with scale_limits = (1, 1): the image a camera records of a DEM's per-cell
  * values, and the depth of the DEM along the optical axis.  out [height][width][layers + (return_depth != 0)] float64 with
  * (width, height) = the camera's imgsz; NaN where no cell lands.  cam [GLH_CAM_LEN] (a camera, not a raster grid).
