@@ -15,11 +15,11 @@ from .image import Image
 from .motion import (CartesianMotion, CylindricalMotion, Motion, TangentCartesianMotion,
                      TangentCylindricalMotion)
 from .observer import Observer
-from .raster import Raster
+from .raster import Raster, RasterInterpolant
 from .tracker import Tracker
 from .tracks import Tracks
 
 __all__ = ["Camera", "Image", "Observer", "Motion", "CartesianMotion", "CylindricalMotion",
-           "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "Tracker", "Tracks", "maximum_filter",
+           "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "RasterInterpolant", "Tracker", "Tracks", "maximum_filter",
            "gaussian_filter"]
 __version__ = "0.1.0"

@@ -153,6 +153,9 @@ SIGNATURES = {
     "glh_stage_raster_sample": (_I, [_I, _P, _I, _I, _P, _P, _I, _I, _D, _D, _D, _D, _P, _I, _I, _P, _P]),
     "glh_stage_viewshed": (_I, [_I, _P, _I, _I, _I, _P, _P, _D, _P, _I, _I, _D, _D, _P, _P]),
     "glh_stage_horizon": (_I, [_I, _P, _I, _I, _I, _D, _D, _D, _D, _P, _P, _P, _I, _I, _I, _D, _D, _P, _P, _P]),
+    "glh_stage_raster_regrid": (_I, [_I, _P, _P, _I, _P, _I, _P, _P]),
+    "glh_stage_zoom_linear": (_I, [_I, _P, _I, _I, _I, _I, _P, _P]),
+    "glh_stage_raster_interpolate": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P]),
     "glh_stage_project_dem": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "glh_stage_rasterize": (_I, [_I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
@@ -938,6 +941,97 @@ def stage_horizon(raster, origins, starts, ends, correction=None, device_id=0, r
                                    float(d[0]), float(d[1]), _ptr(origins), _ptr(starts), _ptr(ends), m, n, int(on), radius,
                                    refraction, _ptr(cell), _ptr(dz), _ptr(times) if return_times else None))
     return (cell, dz, dict(zip(HORIZON_TIMES, (float(t) for t in times)))) if return_times else (cell, dz)
+
+
+REGRID_TIMES = ("upload_ms", "solve_ms", "evaluate_ms", "download_ms")
+INTERPOLATE_TIMES = ("upload_ms", "regrid_ms", "blend_ms", "download_ms")
+
+
+class RegridSrc(C.Structure):
+    """glh_regrid_src (include/glimpse_hip.h)."""
+    _fields_ = [("z", _P), ("nan_mask", _P), ("nx", C.c_int32), ("ny", C.c_int32), ("gx", _P), ("gy", _P),
+                ("xmin", _D), ("xmax", _D), ("ymin", _D), ("ymax", _D), ("kx", C.c_int32), ("ky", C.c_int32),
+                ("use_zmin", C.c_int32), ("flip_x", C.c_int32), ("flip_y", C.c_int32), ("reserved", C.c_int32), ("zmin", _D)]
+
+
+def regrid_src(z, gx, gy, box, kx, ky, nan_mask=None, zmin=None, flip_x=False, flip_y=False):
+    """(glh_regrid_src, the arrays it points into -- keep them alive for the call).  z (ny, nx) with ascending axes and no
+    NaN (0 under `nan_mask`); gx, gy the ascending cell centres; box = (xmin, xmax, ymin, ymax)."""
+    z = _arr(z, np.float64)
+    if z.ndim != 2:
+        raise ValueError(f"a raster is two-dimensional, got {z.shape}")
+    ny, nx = z.shape
+    gx, gy = _arr(gx, np.float64, (nx,)), _arr(gy, np.float64, (ny,))
+    if nan_mask is not None:
+        nan_mask = _arr(nan_mask, np.uint8, (ny, nx))
+    use_zmin = zmin is not None and not np.isnan(zmin)
+    src = RegridSrc(_ptr(z), _ptr(nan_mask), nx, ny, _ptr(gx), _ptr(gy), float(box[0]), float(box[1]), float(box[2]),
+                    float(box[3]), int(kx), int(ky), int(use_zmin), int(bool(flip_x)), int(bool(flip_y)), 0,
+                    float(zmin) if use_zmin else 0.0)
+    return src, (z, gx, gy, nan_mask)
+
+
+def stage_raster_regrid(src, xo, yo, device_id=0, return_times=False):
+    """glh_stage_raster_regrid: the spline of `src` (regrid_src's pair) on the ascending vectors xo (mx,), yo (my,):
+    float64 (my, mx).  `return_times`: also a dict of REGRID_TIMES."""
+    struct, keep = src
+    xo, yo = _arr(xo, np.float64), _arr(yo, np.float64)
+    if xo.ndim != 1 or yo.ndim != 1:
+        raise ValueError(f"xo and yo are vectors, got {xo.shape} and {yo.shape}")
+    out = np.empty((len(yo), len(xo)), dtype=np.float64)
+    times = np.zeros(len(REGRID_TIMES))
+    check(load().glh_stage_raster_regrid(device_id, C.byref(struct), _ptr(xo), len(xo), _ptr(yo), len(yo), _ptr(out),
+                                         _ptr(times) if return_times else None))
+    del keep
+    return (out, dict(zip(REGRID_TIMES, (float(t) for t in times)))) if return_times else out
+
+
+def stage_zoom_linear(a, shape, device_id=0, return_times=False):
+    """glh_stage_zoom_linear: scipy.ndimage.zoom(a, zoom, order=1) of float64 `a` into `shape` = (my, mx)."""
+    a = _arr(a, np.float64)
+    if a.ndim != 2:
+        raise ValueError(f"a raster is two-dimensional, got {a.shape}")
+    my, mx = (int(v) for v in shape)
+    if my < 1 or mx < 1:
+        raise ValueError(f"the zoomed shape {(my, mx)} has no cells")
+    out = np.empty((my, mx), dtype=np.float64)
+    times = np.zeros(len(REGRID_TIMES))
+    check(load().glh_stage_zoom_linear(device_id, _ptr(a), a.shape[1], a.shape[0], mx, my, _ptr(out),
+                                       _ptr(times) if return_times else None))
+    return (out, dict(zip(REGRID_TIMES, (float(t) for t in times)))) if return_times else out
+
+
+def stage_raster_interpolate(m0, m1, scale, scale2, ratio, s0=None, s1=None, xo=None, yo=None, device_id=0,
+                             return_times=False):
+    """glh_stage_raster_interpolate: (z, sigma or None) of RasterInterpolant._interpolate.  m0, s0: (ny, nx) arrays; m1, s1:
+    arrays of that shape, or regrid_src pairs to be regridded at order 1 onto the ascending centres xo (nx,), yo (ny,).
+    `scale2` = scale ** 2 and `ratio` = nearest_dx / dx as the caller's Python made them."""
+    m0 = _arr(m0, np.float64)
+    if m0.ndim != 2:
+        raise ValueError(f"a raster is two-dimensional, got {m0.shape}")
+    ny, nx = m0.shape
+
+    def second(v):
+        if isinstance(v, tuple):
+            return None, v
+        return _arr(v, np.float64, (ny, nx)), None
+
+    m1, m1_src = second(m1)
+    with_sigma = s0 is not None
+    s1, s1_src = second(s1) if with_sigma else (None, None)
+    s0 = _arr(s0, np.float64, (ny, nx)) if with_sigma else None
+    if m1_src is not None or s1_src is not None:
+        xo, yo = _arr(xo, np.float64, (nx,)), _arr(yo, np.float64, (ny,))
+    else:
+        xo = yo = None
+    z = np.empty((ny, nx), dtype=np.float64)
+    sigma = np.empty((ny, nx), dtype=np.float64) if with_sigma else None
+    times = np.zeros(len(INTERPOLATE_TIMES))
+    check(load().glh_stage_raster_interpolate(
+        device_id, nx, ny, _ptr(m0), _ptr(m1), C.byref(m1_src[0]) if m1_src else None, _ptr(s0), _ptr(s1),
+        C.byref(s1_src[0]) if s1_src else None, _ptr(xo), _ptr(yo), float(scale), float(scale2), 1 / 3, float(ratio), _ptr(z),
+        _ptr(sigma), _ptr(times) if return_times else None))
+    return (z, sigma, dict(zip(INTERPOLATE_TIMES, (float(t) for t in times)))) if return_times else (z, sigma)
 
 
 PD_F64, PD_F32, PD_U8, PD_U16 = 0, 1, 2, 3

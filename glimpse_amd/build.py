@@ -8,7 +8,8 @@ bit-identical to NumPy's (no implicit FMA); the SSD kernel asks for FMA explicit
 
 The library is many translation units compiled in parallel: glimpse_hip.hip (the C ABI and the
 staged kernels), glh_viewshed.hip and glh_project_dem.hip (the terrain routines, each with rocPRIM's
-radix sort), glh_horizon.hip (Raster.horizon), glh_filters.hip (the maximum and Gaussian filters of Raster.fill_crevasses) and one object per instantiation of the fused kernel (glh_point_inst.hip with
+radix sort), glh_horizon.hip (Raster.horizon), glh_regrid.hip (Raster.sample(grid=True), resize,
+RasterInterpolant), glh_filters.hip (the maximum and Gaussian filters of Raster.fill_crevasses) and one object per instantiation of the fused kernel (glh_point_inst.hip with
 -DPT_*; the list is csrc/glh_point_variants.h).  Objects are cached in glimpse_amd/lib/obj/ and
 rebuilt when a source they include is newer.
 """
@@ -39,13 +40,16 @@ VIEWSHED = os.path.join(CSRC, "glh_viewshed.hip")  # Raster.viewshed: its kernel
 VIEWSHED_HEADER = os.path.join(CSRC, "glh_viewshed.h")
 HORIZON = os.path.join(CSRC, "glh_horizon.hip")  # Raster.horizon: one workgroup per heading's line
 HORIZON_HEADER = os.path.join(CSRC, "glh_horizon.h")
+REGRID = os.path.join(CSRC, "glh_regrid.hip")  # Raster.sample(grid=True) / resize / RasterInterpolant: solves and evaluation
+REGRID_HEADER = os.path.join(CSRC, "glh_regrid.h")
+REGRID_HOST_HEADER = os.path.join(CSRC, "glh_regrid_host.h")  # its per-axis host arithmetic (also compiled by tests/hostcheck)
 PROJECT_DEM = os.path.join(CSRC, "glh_project_dem.hip")  # Camera.project_dem / rasterize: kernels and the radix sort
 PROJECT_DEM_HEADER = os.path.join(CSRC, "glh_project_dem.h")
 FILTERS = os.path.join(CSRC, "glh_filters.hip")  # maximum_filter / gaussian_filter / Raster.fill_crevasses
 FILTERS_HEADER = os.path.join(CSRC, "glh_filters.h")
 HOST_HEADERS = [os.path.join(CSRC, "glh_host.h"), os.path.join(CSRC, "glh_comm.h"), VIEWSHED_HEADER, HORIZON_HEADER,
-                PROJECT_DEM_HEADER, FILTERS_HEADER]
-DEPS = [SRC, INST, VIEWSHED, HORIZON, PROJECT_DEM, FILTERS, *HEADERS, *HOST_HEADERS]
+                REGRID_HEADER, REGRID_HOST_HEADER, PROJECT_DEM_HEADER, FILTERS_HEADER]
+DEPS = [SRC, INST, VIEWSHED, HORIZON, REGRID, PROJECT_DEM, FILTERS, *HEADERS, *HOST_HEADERS]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -97,6 +101,8 @@ def _jobs(extra, objdir=OBJDIR):
              [VIEWSHED, VIEWSHED_HEADER, HEADERS[-1]]),
             (os.path.join(objdir, "glh_horizon.o"), [cc, *FLAGS, *extra, "-c", HORIZON],
              [HORIZON, HORIZON_HEADER, HEADERS[-1]]),
+            (os.path.join(objdir, "glh_regrid.o"), [cc, *FLAGS, *extra, "-c", REGRID],
+             [REGRID, REGRID_HEADER, REGRID_HOST_HEADER, HEADERS[-1]]),
             (os.path.join(objdir, "glh_project_dem.o"), [cc, *FLAGS, *extra, "-c", PROJECT_DEM],
              [PROJECT_DEM, PROJECT_DEM_HEADER, os.path.join(CSRC, "glh_math.h"), HEADERS[-1]]),
             (os.path.join(objdir, "glh_filters.o"), [cc, *FLAGS, *extra, "-c", FILTERS],

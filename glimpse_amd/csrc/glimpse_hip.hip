@@ -19,6 +19,7 @@
 #include "glh_point_variants.h"
 #include "glh_project_dem.h"
 #include "glh_horizon.h"
+#include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
 
@@ -2865,6 +2866,104 @@ extern "C" int glh_stage_horizon(int dev, const void* z, int z_dtype, int nx, in
                        correction != 0, radius, refraction, cell, dz, times_ms};
   char msg[512] = "";
   const int rc = horizon_run(job, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+// Raster.sample(grid=True) / resample, Raster.resize and RasterInterpolant (raster.py:1042-1083, :1178-1187, :1673-1700):
+// the arguments are checked here, before a device is touched; the factoring, the kernels and the launches are
+// glh_regrid.hip's.
+static int check_regrid_outputs(const char* who, const double* xo, int mx, const double* yo, int my) {
+  if (!xo || !yo) return fail(GLH_E_INVALID, "%s: null output coordinates", who);
+  if (mx < 1 || my < 1) return fail(GLH_E_INVALID, "%s: %d x %d output coordinates: at least one of each", who, mx, my);
+  if ((int64_t)mx * my >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "%s: %d x %d output cells: fewer than 2^31 are served", who, mx, my);
+  for (int i = 0; i < mx; ++i)
+    if (!std::isfinite(xo[i]) || (i && xo[i] < xo[i - 1]))
+      return fail(GLH_E_INVALID, "%s: output x %d is not finite or decreases: the vectors are sorted ascending", who, i);
+  for (int i = 0; i < my; ++i)
+    if (!std::isfinite(yo[i]) || (i && yo[i] < yo[i - 1]))
+      return fail(GLH_E_INVALID, "%s: output y %d is not finite or decreases: the vectors are sorted ascending", who, i);
+  return GLH_OK;
+}
+
+static int check_regrid_axis(const char* who, const char* axis, const double* g, int n, int k, double lo, double hi) {
+  if (k < 1 || k > RG_MAX_K) return fail(GLH_E_INVALID, "%s: order %d along %s: 1 .. 5 are served", who, k, axis);
+  if (n <= k) return fail(GLH_E_INVALID, "%s: %d cells along %s: order %d needs more than %d", who, n, axis, k, k);
+  if (!(std::isfinite(lo) && std::isfinite(hi) && lo < hi)) return fail(GLH_E_INVALID, "%s: box (%g, %g) along %s", who, lo, hi, axis);
+  for (int i = 0; i < n; ++i)
+    if (!std::isfinite(g[i]) || (i && !(g[i] > g[i - 1])))
+      return fail(GLH_E_INVALID, "%s: cell centre %d along %s is not finite or not above the one before: the vectors are "
+                                 "sorted strictly ascending", who, i, axis);
+  if (g[0] < lo || g[n - 1] > hi)
+    return fail(GLH_E_INVALID, "%s: the cell centres along %s (%g .. %g) leave the box (%g, %g)", who, axis, g[0], g[n - 1], lo, hi);
+  return GLH_OK;
+}
+
+static int check_regrid_src(const char* who, const glh_regrid_src* s, bool order1_only, RegridSource& out) {
+  if (!s || !s->z || !s->gx || !s->gy) return fail(GLH_E_INVALID, "%s: null argument", who);
+  if (s->nx < 1 || s->ny < 1 || (int64_t)s->nx * s->ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "%s: %d x %d cells: at least one, fewer than 2^31", who, s->nx, s->ny);
+  int rc = check_regrid_axis(who, "x", s->gx, s->nx, s->kx, s->xmin, s->xmax);
+  if (rc != GLH_OK) return rc;
+  rc = check_regrid_axis(who, "y", s->gy, s->ny, s->ky, s->ymin, s->ymax);
+  if (rc != GLH_OK) return rc;
+  if (order1_only && (s->kx != 1 || s->ky != 1))
+    return fail(GLH_E_UNSUPPORTED, "%s: orders (%d, %d): the interpolant regrids at order 1", who, s->kx, s->ky);
+  if (s->nan_mask && (s->kx != 1 || s->ky != 1))
+    return fail(GLH_E_UNSUPPORTED, "%s: a NaN mask with orders (%d, %d): NaN cells are served at order 1 only (above it one "
+                                   "NaN cell reaches every sample of the global fit)", who, s->kx, s->ky);
+  const size_t cells = (size_t)s->nx * s->ny;
+  for (size_t i = 0; i < cells; ++i)
+    if (!std::isfinite(s->z[i])) return fail(GLH_E_INVALID, "%s: cell %zu is not finite (NaN cells go into nan_mask)", who, i);
+  out = RegridSource{s->z, s->nan_mask, s->nx, s->ny, s->gx, s->gy, s->xmin, s->xmax, s->ymin, s->ymax, s->kx, s->ky,
+                     s->use_zmin != 0, s->zmin, s->flip_x != 0, s->flip_y != 0};
+  return GLH_OK;
+}
+
+extern "C" int glh_stage_raster_regrid(int dev, const glh_regrid_src* src, const double* xo, int mx, const double* yo, int my,
+                                       double* out, double* times_ms) {
+  if (!out) return fail(GLH_E_INVALID, "raster_regrid: null argument");
+  RegridSource s{};
+  int rc = check_regrid_src("raster_regrid", src, false, s);
+  if (rc != GLH_OK) return rc;
+  rc = check_regrid_outputs("raster_regrid", xo, mx, yo, my);
+  if (rc != GLH_OK) return rc;
+  char msg[512] = "";
+  rc = regrid_run(RegridJob{dev, s, xo, yo, mx, my, out, times_ms}, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+extern "C" int glh_stage_zoom_linear(int dev, const double* a, int nx, int ny, int mx, int my, double* out, double* times_ms) {
+  if (!a || !out) return fail(GLH_E_INVALID, "zoom_linear: null argument");
+  if (nx < 1 || ny < 1 || mx < 1 || my < 1)
+    return fail(GLH_E_INVALID, "zoom_linear: %d x %d cells into %d x %d: at least one of each", nx, ny, mx, my);
+  if ((int64_t)nx * ny >= ((int64_t)1 << 31) || (int64_t)mx * my >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "zoom_linear: %d x %d cells into %d x %d: fewer than 2^31 are served", nx, ny, mx, my);
+  char msg[512] = "";
+  const int rc = zoom_run(ZoomJob{dev, a, nx, ny, mx, my, out, times_ms}, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+extern "C" int glh_stage_raster_interpolate(int dev, int nx, int ny, const double* m0, const double* m1,
+                                            const glh_regrid_src* m1_src, const double* s0, const double* s1,
+                                            const glh_regrid_src* s1_src, const double* xo, const double* yo, double scale,
+                                            double scale2, double third, double ratio, double* z, double* sigma,
+                                            double* times_ms) {
+  if (!m0 || !z || (!m1 && !m1_src)) return fail(GLH_E_INVALID, "raster_interpolate: null argument");
+  if (sigma && (!s0 || (!s1 && !s1_src))) return fail(GLH_E_INVALID, "raster_interpolate: sigma asked for without both inputs");
+  if (nx < 1 || ny < 1 || (int64_t)nx * ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "raster_interpolate: %d x %d cells: at least one, fewer than 2^31", nx, ny);
+  RegridSource ms{}, ss{};
+  const bool regrid_m = m1_src != nullptr, regrid_s = sigma && s1_src != nullptr;
+  int rc;
+  if (regrid_m && (rc = check_regrid_src("raster_interpolate (means)", m1_src, true, ms)) != GLH_OK) return rc;
+  if (regrid_s && (rc = check_regrid_src("raster_interpolate (sigmas)", s1_src, true, ss)) != GLH_OK) return rc;
+  if ((regrid_m || regrid_s) && (rc = check_regrid_outputs("raster_interpolate", xo, nx, yo, ny)) != GLH_OK) return rc;
+  const InterpolateJob job{dev, nx, ny, m0, regrid_m ? nullptr : m1, regrid_m ? &ms : nullptr, sigma ? s0 : nullptr,
+                           regrid_s ? nullptr : s1, regrid_s ? &ss : nullptr, xo, yo, scale, scale2, third, ratio, z, sigma,
+                           times_ms};
+  char msg[512] = "";
+  rc = interpolate_run(job, msg, sizeof msg);
   return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
 }
 

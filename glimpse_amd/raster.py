@@ -13,13 +13,77 @@ raster themselves).  Of the terrain analysis, `viewshed(origin, correction)` (:1
 `tile_indices(size, overlap)` (:581-610) cuts the grid into the tiles `Camera.project_dem` walks; it and the tiles' own
 coordinates (`__getitem__`, :670-693) are computed on the host and handed to the device.  `fill_crevasses` (:1266-1291),
 the smoothed surface handed to the motion models, runs on the GPU too (`glh_stage_fill_crevasses`; glimpse_amd/filters.py).
-File I/O (GDAL), resampling, `hillshade`, `gradient` are out of scope.
+Resampling is served on the GPU as well: `sample(xy, grid=True, order 1 .. 5)` (:961-999, :1042-1070), the interpolating
+`RectBivariateSpline` of the reference evaluated on a grid (`glh_stage_raster_regrid`: banded LU factors made on the host,
+one kernel substituting down the columns, one along the rows through LDS tiles, one evaluating), `resample(grid)`
+(:1072-1083), `resize(scale)` (:1178-1187, `glh_stage_zoom_linear`), and `RasterInterpolant` (:1528-1771), the DEM and
+its uncertainty for a day between two DEMs (`glh_stage_raster_interpolate`: the regridding of the second raster and the
+blend in one call).  Their host-only companions are restated here: `copy`, `grid` (a `Grid`, equal to another by shape and
+limits), `box2d`, `crop_extent` / `crop`.
+File I/O (GDAL), `hillshade`, `gradient`, `rasterize_polygons`, `fill_circle` and rasters with a singleton dimension (the
+reference's 1-D `interp1d` path) are out of scope.
 """
+import copy
+import datetime
+import numbers
 import warnings
+from pathlib import Path
 
 import numpy as np
 
-from . import _lib
+from . import _lib, helpers
+
+
+class SplineOrderError(Exception):
+    """`sample(grid=True)` with an order outside 1 .. 5.  The reference hands the order to FITPACK, whose f2py wrapper raises
+    its module's own `error`, a direct subclass of Exception: neither a ValueError nor a NotImplementedError, and so is
+    this."""
+
+
+class Grid:
+    """Grid (raster.py:23-610) as far as RasterInterpolant needs it: dimensions `size` (nx, ny) and outer limits; two
+    grids are equal when their shapes and limits are (raster.py:60-66)."""
+
+    def __init__(self, size, x=None, y=None):
+        self.size = np.atleast_1d(size)
+        self.xlim = Raster._limits(x, self.size[0])
+        self.ylim = Raster._limits(y, self.size[1])
+
+    def __eq__(self, other):
+        return bool(self.shape == other.shape and (self.xlim == other.xlim).all() and (self.ylim == other.ylim).all())
+
+    __hash__ = None
+
+    @property
+    def shape(self):
+        return int(self.size[1]), int(self.size[0])
+
+    @property
+    def d(self):
+        return np.hstack((np.diff(self.xlim), np.diff(self.ylim))) / self.size
+
+    @property
+    def min(self):
+        return np.array((min(self.xlim), min(self.ylim)))
+
+    @property
+    def max(self):
+        return np.array((max(self.xlim), max(self.ylim)))
+
+    @property
+    def box2d(self):
+        return np.hstack((self.min, self.max))
+
+    @property
+    def x(self):
+        return Raster._centres(self, 0)
+
+    @property
+    def y(self):
+        return Raster._centres(self, 1)
+
+    def copy(self):
+        return Grid(self.size.copy(), x=self.xlim.copy(), y=self.ylim.copy())
 
 
 class Raster:
@@ -276,9 +340,179 @@ class Raster:
             mask = mask(self.array)
         self.array = filters.fill_crevasses(self.array, maximum, gaussian, mask=mask, fill=fill)
 
+    # ---- host-only companions of the resampling (restated from the reference)
+    def _set_array(self, array):
+        self.array = np.atleast_2d(array)
+        ny, nx = self.array.shape[:2]
+        self.size = np.array((nx, ny))
+
+    def copy(self):
+        """raster.py:904-911."""
+        return self.__class__(self.array.copy(), x=self.xlim.copy(), y=self.ylim.copy(), datetime=copy.copy(self.datetime))
+
+    @property
+    def shape(self):
+        return self.array.shape
+
+    @property
+    def grid(self):
+        """The raster's Grid (raster.py:884-887)."""
+        return Grid(self.size, x=self.xlim, y=self.ylim)
+
+    @property
+    def box2d(self):
+        """(xmin, ymin, xmax, ymax) (raster.py:134-137)."""
+        return np.hstack((self.min, self.max))
+
+    def crop_extent(self, xlim=None, ylim=None):
+        """Grid.crop_extent (raster.py:526-574): the outer limits (xlim, ylim) and the first and last (rows, cols) of the
+        cells a crop to the box keeps: the box is cut to the raster's, its corners snap to the cells they fall in, and a
+        far corner that lies exactly on an inner cell edge snaps down, into the cell before it."""
+        if xlim is None:
+            xlim = self.xlim
+        if ylim is None:
+            ylim = self.ylim
+        box = helpers.intersect_boxes(np.vstack((np.hstack((min(xlim), min(ylim), max(xlim), max(ylim))),
+                                                 np.hstack((self.min[0:2], self.max[0:2])))))
+        xlim = box[0::2]
+        if self.xlim[0] > self.xlim[1]:
+            xlim = xlim[::-1]
+        ylim = box[1::2]
+        if self.ylim[0] > self.ylim[1]:
+            ylim = ylim[::-1]
+        xy = np.column_stack((xlim, ylim))
+        rowcol = self._snapped_colrow(xy)[:, ::-1].copy()
+        bottom_right = np.append(self.xlim[1], self.ylim[1])
+        is_edge = (bottom_right - xy[1, :]) % self.d == 0
+        is_outer_edge = xy[1, :] == bottom_right
+        snap_down = is_edge & ~is_outer_edge
+        rowcol[1, snap_down[::-1]] -= 1
+        new_xy = (rowcol + 0.5)[:, ::-1] * self.d + np.array((self.xlim[0], self.ylim[0]))
+        new_xlim = new_xy[:, 0] + np.array([-0.5, 0.5]) * self.d[0]
+        new_ylim = new_xy[:, 1] + np.array([-0.5, 0.5]) * self.d[1]
+        return new_xlim, new_ylim, rowcol[:, 0], rowcol[:, 1]
+
+    def crop(self, xlim=None, ylim=None, zlim=None):
+        """Crop in place (raster.py:1149-1176): to the cells of `crop_extent(xlim, ylim)`; values outside `zlim` become NaN
+        (an integer array is cast to float, with the reference's warning)."""
+        if xlim is not None or ylim is not None:
+            xlim, ylim, rows, cols = self.crop_extent(xlim=xlim, ylim=ylim)
+            self._set_array(self.array[rows[0]:rows[1] + 1, cols[0]:cols[1] + 1])
+            self.xlim = xlim
+            self.ylim = ylim
+        if zlim is not None:
+            outbounds = (self.array < min(zlim)) | (self.array > max(zlim))
+            if np.count_nonzero(outbounds) and not issubclass(self.array.dtype.type, np.floating):
+                warnings.warn("array cast to float to accommodate NaN")
+                self.array = self.array.astype(float)
+            self.array[outbounds] = np.nan
+
+    def resize(self, scale, order=1):
+        """Resize `array` in place by the fraction `scale` (raster.py:1178-1187): scipy.ndimage.zoom(array, scale, order=1),
+        on the GPU (`glh_stage_zoom_linear`).  The limits stay, so the cell size changes.  Only order 1 and floating
+        arrays are built."""
+        if order != 1:
+            raise NotImplementedError(f"resize with order {order}: only order 1 is built")
+        if not issubclass(self.array.dtype.type, np.floating):
+            raise NotImplementedError(f"resize of a {self.array.dtype} array: only floating arrays are built")
+        if self.array.ndim != 2:
+            raise ValueError(f"a raster is two-dimensional, got {self.array.shape}")
+        shape = tuple(int(round(n * float(scale))) for n in self.array.shape)
+        self._set_array(_lib.stage_zoom_linear(self.array, shape).astype(self.array.dtype, copy=False))
+
+    def resample(self, grid, **kwargs):
+        """Resample in place onto the cell centres of `grid`, anything with x, y, xlim, ylim (raster.py:1072-1083);
+        `kwargs` go to `sample`."""
+        array = self.sample((grid.x, grid.y), grid=True, **kwargs)
+        self._set_array(array)
+        self.xlim, self.ylim = self._limits(grid.xlim, 0), self._limits(grid.ylim, 0)
+
+    def _grid_source(self, xy, order, bounds_error, fill_value):
+        """The host part of `sample(xy, grid=True)` (raster.py:961-999, :1042-1070), in the reference's order: the bounds
+        test first, then the shape, the order and the NaN cells.  Returns (source, xo, yo, xout, yout): the
+        _lib.regrid_src of this raster with its axes flipped to ascending and the output directions taken from the first
+        two requested coordinates; the ascending coordinates; the out-of-bounds columns and rows (None without a test).
+        `source` is None for a 1 x 1 raster (a constant)."""
+        x, y = (np.atleast_1d(np.asarray(v, dtype=float)) for v in xy)
+        if x.ndim != 1 or y.ndim != 1:
+            raise ValueError(f"with grid=True the coordinates are two vectors, got {x.shape} and {y.shape}")
+        xout = yout = None
+        if bounds_error or fill_value is not None:
+            xout = ~((x >= self.min[0]) & (x <= self.max[0]))
+            yout = ~((y >= self.min[1]) & (y <= self.max[1]))
+            if bounds_error and (xout.any() or yout.any()):
+                raise ValueError("Some of the sampling coordinates are out of bounds")
+        if self.array.ndim != 2:
+            raise ValueError(f"a raster is two-dimensional, got {self.array.shape}")
+        singleton = int((self.size == 1).sum())
+        if singleton == 2:
+            return None, x, y, xout, yout
+        if singleton == 1:
+            raise NotImplementedError("a raster with one singleton dimension is sampled in 1-D by the reference "
+                                      "(scipy.interpolate.interp1d): the 1-D case is not built")
+        if not isinstance(order, numbers.Integral) or not 1 <= order <= 5:
+            raise SplineOrderError(f"order {order!r} with grid=True: the spline orders 1 .. 5 are served (order 0 is point "
+                                   "sampling: grid=False)")
+        nx, ny = (int(v) for v in self.size)
+        if nx <= order or ny <= order:
+            raise ValueError(f"order {order} needs more than {order} cells on each axis, the raster has {nx} x {ny}")
+        sx, sy = (1 if v > 0 else -1 for v in self.d)
+        z = np.asarray(self.array[::sy, ::sx], dtype=np.float64)
+        is_nan = np.isnan(z)
+        nan_mask = None
+        zmin = None
+        if is_nan.any():
+            if order != 1:
+                raise ValueError(f"the raster has {int(is_nan.sum())} NaN cells: they are served at order 1 only.  Above it "
+                                 "the fit is global: the reference's stand-in value for a NaN cell rings through every "
+                                 "sample, and most of them come back NaN")
+            nan_mask = is_nan
+            z = np.where(is_nan, 0.0, z)
+            if not is_nan.all():
+                zmin = float(np.min(self.array[::sy, ::sx][~is_nan]))
+        else:
+            zmin = float(np.min(self.array))
+        if not np.isfinite(z).all():
+            raise ValueError("the raster holds infinite values: a spline through them is not defined")
+        xdir = 1 if len(x) < 2 or x[1] > x[0] else -1
+        ydir = 1 if len(y) < 2 or y[1] > y[0] else -1
+        xo, yo = x[::xdir], y[::ydir]
+        if (np.diff(xo) <= 0).any() or (np.diff(yo) <= 0).any() or not (np.isfinite(xo).all() and np.isfinite(yo).all()):
+            raise ValueError("x and y must be strictly increasing or strictly decreasing when `grid` is True")
+        source = _lib.regrid_src(z, self.x[::sx], self.y[::sy], (self.min[0], self.max[0], self.min[1], self.max[1]),
+                                 order, order, nan_mask=nan_mask, zmin=zmin, flip_x=xdir < 0, flip_y=ydir < 0)
+        return source, xo, yo, xout, yout
+
+    def _sample_grid(self, xy, order, bounds_error, fill_value):
+        source, x, y, xout, yout = self._grid_source(xy, order, bounds_error, fill_value)
+        if source is None:
+            samples = np.full((len(y), len(x)), float(self.array.flat[0]))
+        else:
+            samples = _lib.stage_raster_regrid(source, x, y)
+        if not bounds_error and fill_value is not None:
+            samples[yout, :] = fill_value
+            samples[:, xout] = fill_value
+        return samples
+
     def sample(self, xy, grid=False, order=1, bounds_error=True, fill_value=np.nan):
-        """Values at points (n, 2): bilinear (order 1) or nearest cell (order 0) (raster.py:913-1027)."""
-        if grid or order not in (0, 1):
+        """Values at points (n, 2): bilinear (order 1) or nearest cell (order 0) (raster.py:913-1027).
+
+        With `grid=True`, `xy` = (x (n,), y (m,)) coordinate vectors and the result is float64 (m, n): the reference's
+        interpolating scipy.interpolate.RectBivariateSpline of `order` 1 .. 5 over the raster's outer limits, evaluated on
+        the grid on the GPU (`glh_stage_raster_regrid`).  The bounds test runs first, per axis.  A descending raster axis is
+        flipped; the result follows the order of the requested coordinates, which are strictly monotonic (their direction
+        is read off the first two).  `bounds_error=False`: out-of-bounds rows and columns take `fill_value`, or with
+        `fill_value=None` the spline's value at the nearest limit (FITPACK clamps).  As in the reference, samples below
+        the raster's minimum come back NaN (that is how it marks the reach of a NaN cell, and it also blanks a spline's
+        undershoot).  A 1 x 1 raster returns its constant (as (m, n), where the reference returns (n, m)); a raster with one
+        singleton dimension is not built.  NaN cells are served at order 1 only, by a rule that is local where the
+        reference's stand-in value is not: a sample is NaN exactly when a cell of nonzero weight in its support is NaN --
+        the two neighbouring cells per axis, and in the end segment, where the first coefficient is extrapolated from
+        cells 0 and 1, both of them.  (The reference's own answer differs from this only where a NaN sits in the second or
+        second-to-last cell of a line, through float64 overflow of the stand-in.)"""
+        if grid:
+            return self._sample_grid(xy, order, bounds_error, fill_value)
+        if order not in (0, 1):
             raise NotImplementedError("only point sampling with order 0 or 1 is built")
         xy = np.atleast_2d(np.asarray(xy, dtype=float))
         values, oob = _lib.stage_raster_sample(self, xy, order)
@@ -287,3 +521,170 @@ class Raster:
                 raise ValueError("Some of the sampling coordinates are out of bounds")
             values[oob] = fill_value
         return values
+
+
+class RasterInterpolant:
+    """Interpolation of a raster time series (raster.py:1528-1771): `means` and `sigmas` hold Rasters or numbers (infinite
+    rasters; `sigmas=None` is 0), `x` their coordinates, numbers or datetimes (default: the means' `datetime`).  A call
+    takes the two rasters nearest `xi`, crops them to their common box, brings the second onto the first's grid
+    (`Raster.resample`, order 1) and blends them linearly in `xi`; with `return_sigma` the two uncertainty rasters are
+    propagated the same way.  The regridding and the blend are one library call (`glh_stage_raster_interpolate`) in
+    float64 (float32 rasters are widened, where the reference blends them in float32).  A path among the means or sigmas
+    raises NotImplementedError: file I/O is out of scope.
+
+    The reference's quirks are kept: `d` resizes by `d / mean|d|`, which REFINES a raster asked for a coarser cell (a 10 m
+    raster with d=20 comes back at 5 m); `d` and the limits are compared by exact float equality; the returned rasters
+    carry `means[0]`'s limits."""
+
+    def __init__(self, means, sigmas=None, x=None):
+        self.means = means
+        if x is None:
+            x = [raster.datetime for raster in means]
+        self.x = np.asarray(x)
+        self.sigmas = sigmas
+
+    def _parse_as_raster(self, obj, xi=None, d=None, xlim=None, ylim=None):
+        """raster.py:1555-1592."""
+        t = xi if isinstance(xi, datetime.datetime) else None
+        if isinstance(obj, numbers.Number):
+            if xlim is None:
+                xlim = (-np.inf, np.inf)
+            if ylim is None:
+                ylim = (-np.inf, np.inf)
+            return Raster(obj, x=xlim, y=ylim, datetime=t)
+        if isinstance(obj, Raster):
+            d_change = d is not None and d != np.abs(obj.d).mean()
+            xlim_change = xlim is not None and sorted(xlim) != sorted(obj.xlim)
+            ylim_change = ylim is not None and sorted(ylim) != sorted(obj.ylim)
+            if any((d_change, xlim_change, ylim_change)):
+                obj = obj.copy()
+            if xlim_change or ylim_change:
+                obj.crop(xlim=xlim, ylim=ylim)
+            if d_change:
+                scale = d / np.abs(obj.d).mean()
+                obj.resize(scale)
+            return obj
+        if isinstance(obj, (str, Path)):
+            raise NotImplementedError(f"a raster file ({obj}): file I/O is out of scope, read it into a Raster first")
+        raise ValueError("Cannot cast as Raster: " + str(type(obj)))
+
+    def _read_mean(self, index, d=None, xlim=None, ylim=None, zlim=None, fun=None, **kwargs):
+        """raster.py:1594-1614: `fun` is called on a copy, on the host."""
+        xi = self.x[index]
+        obj = self.means[index]
+        raster = self._parse_as_raster(obj, xi, d=d, xlim=xlim, ylim=ylim)
+        if (zlim is not None or fun is not None) and raster is obj:
+            raster = raster.copy()
+        if zlim is not None:
+            raster.crop(zlim=zlim)
+        if fun is not None:
+            fun(raster, **kwargs)
+        return raster
+
+    def _read_sigma(self, index, d=None, xlim=None, ylim=None):
+        """raster.py:1616-1629."""
+        xi = self.x[index]
+        obj = 0 if self.sigmas is None else self.sigmas[index]
+        return self._parse_as_raster(obj, xi, d=d, xlim=xlim, ylim=ylim)
+
+    def _read_mean_grid(self, index):
+        """raster.py:1631-1640."""
+        obj = self.means[index]
+        if isinstance(obj, Raster):
+            return obj.grid
+        if isinstance(obj, (str, Path)):
+            raise NotImplementedError(f"a raster file ({obj}): file I/O is out of scope, read it into a Raster first")
+        if isinstance(obj, numbers.Number):
+            return Grid((1, 1), x=(-np.inf, np.inf), y=(-np.inf, np.inf))
+        raise ValueError("Cannot cast as Grid: " + str(type(obj)))
+
+    def nearest(self, xi, extrapolate=False):
+        """Indices of the two nearest rasters, in the order of their coordinates (raster.py:1642-1671): one on either side
+        of `xi`, or with `extrapolate` the two nearest wherever they lie."""
+        dx = self.x - xi
+        zero = type(dx[0])(0)
+        if extrapolate:
+            i, j = abs(dx).argsort()[:2]
+        else:
+            before = np.where(dx <= zero)[0]
+            after = np.where(dx >= zero)[0]
+            if not before.size or not after.size:
+                raise ValueError("Not bounded on both sides by a Raster")
+            i = before[np.argmin(abs(dx[before]))]
+            j = after[np.argmin(dx[after])]
+        ij = [i, j]
+        ij.sort(key=lambda index: self.x[index])
+        return tuple(ij)
+
+    @staticmethod
+    def _second(pair, originals):
+        """What the blend takes for the second raster of `pair`: its array when the grids are equal, else the source of its
+        regridding onto the first's grid (Raster.resample with the default arguments, raster.py:1757-1760), with the
+        ascending centres of that grid.  A raster that is not two-dimensional in extent (a number) is resampled here."""
+        first, second = pair
+        if first.grid == second.grid:
+            return second.array, None, None
+        if (second.size > 1).all():
+            source, xo, yo, _, _ = second._grid_source((first.x, first.y), 1, True, np.nan)
+            return source, xo, yo
+        if any(second is o for o in originals):
+            second = second.copy()
+        second.resample(first)
+        return second.array, None, None
+
+    def _interpolate(self, means, x, xi, sigmas=None):
+        """raster.py:1673-1700, the arrays' arithmetic on the device in the reference's operation order."""
+        dx = x[1] - x[0]
+        scale = (xi - x[0]) / dx
+        t = xi if isinstance(xi, datetime.datetime) else None
+        m1, xo, yo = self._second(means, self.means)
+        m0 = np.asarray(means[0].array, dtype=np.float64)
+        if not isinstance(m1, tuple):
+            m0, m1 = (np.ascontiguousarray(a) for a in np.broadcast_arrays(m0, np.asarray(m1, dtype=np.float64)))
+        s0 = s1 = None
+        scale2 = ratio = 0.0
+        if sigmas is not None:
+            scale2 = scale ** 2
+            nearest_dx = np.min(np.abs(np.subtract(xi, x)))
+            ratio = nearest_dx / dx
+            if sigmas[0].grid != sigmas[1].grid and sigmas[0].grid != means[0].grid:
+                # the sigmas have a grid of their own: regrid them in a call of their own
+                if self.sigmas is not None and any(sigmas[1] is o for o in self.sigmas):
+                    sigmas[1] = sigmas[1].copy()
+                sigmas[1].resample(sigmas[0])
+            s1, sxo, syo = self._second(sigmas, self.sigmas if self.sigmas is not None else ())
+            if isinstance(s1, tuple):
+                xo, yo = sxo, syo
+                s0 = np.asarray(sigmas[0].array, dtype=np.float64)
+                if s0.shape != m0.shape:
+                    raise ValueError(f"the sigma rasters ({s0.shape}) and the mean rasters ({m0.shape}) differ in shape")
+            else:
+                s0 = np.ascontiguousarray(np.broadcast_to(np.asarray(sigmas[0].array, dtype=np.float64), m0.shape))
+                s1 = np.ascontiguousarray(np.broadcast_to(np.asarray(s1, dtype=np.float64), m0.shape))
+        z, sigma = _lib.stage_raster_interpolate(m0, m1, scale, scale2, ratio, s0=s0, s1=s1, xo=xo, yo=yo)
+        raster = means[0].__class__(z, x=means[0].xlim, y=means[0].ylim, datetime=t)
+        if sigmas is not None:
+            return raster, raster.__class__(sigma, x=means[0].xlim, y=means[0].ylim, datetime=t)
+        return raster
+
+    def __call__(self, xi, d=None, xlim=None, ylim=None, zlim=None, return_sigma=False, extrapolate=False, fun=None,
+                 **kwargs):
+        """The raster interpolated at `xi`, and with `return_sigma` its standard deviation (raster.py:1702-1771).  `d`:
+        target cell size (default: the largest of the two rasters); `xlim`, `ylim`: crop bounds (default: the rasters'
+        intersection); `zlim`: values of the means outside it become NaN; `fun(raster, **kwargs)` modifies each mean in
+        place before the blend."""
+        ij = self.nearest(xi, extrapolate=extrapolate)
+        grids = [self._read_mean_grid(k) for k in ij]
+        if d is None:
+            d = np.max(np.abs(np.stack([grid.d for grid in grids])))
+        if xlim is None:
+            xlim = (-np.inf, np.inf)
+        if ylim is None:
+            ylim = (-np.inf, np.inf)
+        boxes = [grid.box2d for grid in grids]
+        boxes.append([min(xlim), min(ylim), max(xlim), max(ylim)])
+        box = helpers.intersect_boxes(boxes)
+        xlim, ylim = box[0::2], box[1::2]
+        means = [self._read_mean(k, d=d, xlim=xlim, ylim=ylim, zlim=zlim, fun=fun, **kwargs) for k in ij]
+        sigmas = [self._read_sigma(k, d=d, xlim=xlim, ylim=ylim) for k in ij] if return_sigma else None
+        return self._interpolate(means=means, sigmas=sigmas, x=self.x[list(ij)], xi=xi)

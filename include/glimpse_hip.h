@@ -574,6 +574,60 @@ int glh_stage_gaussian_filter(int device_id, const void* a, int dtype, int nx, i
 int glh_stage_fill_crevasses(int device_id, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
                              int size_y, int size_x, int max_mode, const double* w0, int r0, const double* w1, int r1,
                              int gauss_mode, void* out, double* times_ms);
+/* ---- regridding: Raster.sample(grid=True) / resample, Raster.resize, RasterInterpolant ("regrid", since
+ * glh_stage_resample is particle resampling) ------------------------------------------------------------------------------
+ * A raster as the source of a spline evaluation.  z [ny][nx] float64 with rows and columns in ASCENDING coordinate order
+ * (the caller flips a descending axis); gx [nx], gy [ny] its strictly ascending cell centres; xmin .. ymax the box = the
+ * raster's outer limits, half a cell beyond the outermost centres: the end knots sit there, not on the outermost centres
+ * as in the tracker's spline kernels, so the spline extrapolates in that half cell and arguments beyond the box are
+ * clamped to it (FITPACK's fpbisp).  kx, ky in 1 .. 5.  Per axis the knots are FITPACK regrid's for s = 0: k + 1 at
+ * either limit, between them the centres x[(k+1)/2 .. n-(k+1)/2-1] (k odd) or the midpoints (x[i] + x[i+1]) / 2,
+ * i = k/2 .. n-k/2-2 (k even).  nan_mask [ny][nx] (or NULL; kx == ky == 1 only): 1 where the cell is NaN, z holding any
+ * finite value there; a sample is NaN when a coefficient of nonzero weight has a masked cell in its support (its own
+ * cell, and for the first / last coefficient of a line the neighbour it is extrapolated from).  use_zmin: samples below
+ * zmin become NaN (raster.py:1068).  flip_x / flip_y: output column j holds coordinate xo[mx - 1 - j] (row i: yo).      */
+typedef struct glh_regrid_src {
+  const double* z;
+  const uint8_t* nan_mask;
+  int32_t nx, ny;
+  const double* gx;
+  const double* gy;
+  double xmin, xmax, ymin, ymax;
+  int32_t kx, ky;
+  int32_t use_zmin;
+  int32_t flip_x, flip_y;
+  int32_t reserved;
+  double zmin;
+} glh_regrid_src;
+/* scipy.interpolate.RectBivariateSpline(gy, gx, z, bbox, kx, ky, s=0)(yo, xo, grid=True) (raster.py:1056-1067): out
+ * [my][mx] float64, the interpolating tensor-product spline of `src` on the non-decreasing coordinate vectors xo [mx],
+ * yo [my].  The per-axis banded collocation matrices (k diagonals on either side) are factored by LU without pivoting on
+ * the host; one kernel substitutes down the columns (a thread per column), one along the rows (tiles transposed through
+ * LDS), one evaluates (a thread per output cell, (ky+1)(kx+1) terms, rows outer).  Order 1 on an axis of three or more
+ * cells launches no solve: the first and last coefficient of a line have a closed form.  float64 throughout, no
+ * contraction, fixed summation orders: two calls give the same bytes.
+ * times_ms (or NULL) [4]: HIP-event milliseconds -- [0] upload, [1] solve, [2] evaluate, [3] download.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, n <= k on an axis, k outside 1 .. 5, mx or my < 1,
+ * nx * ny or mx * my >= 2^31, centres not strictly ascending or outside the box, outputs decreasing, values not finite),
+ * GLH_E_UNSUPPORTED (a nan_mask with an order above 1).  A failed device allocation is GLH_E_NOMEM.                     */
+int glh_stage_raster_regrid(int device_id, const glh_regrid_src* src, const double* xo, int mx, const double* yo, int my,
+                            double* out, double* times_ms);
+/* scipy.ndimage.zoom(a, zoom, order=1) of float64 a [ny][nx] into out [my][mx] (the caller rounds n * zoom): output index
+ * i samples input coordinate c = i (n_in - 1) / (n_out - 1) (0 when n_out == 1); i0 = floor(c), t = c - i0, and
+ * out = a00 (1-ty)(1-tx) + a01 (1-ty) tx + a10 ty (1-tx) + a11 ty tx summed in that order.  times_ms as above ([1] is 0).
+ * GLH_E_INVALID: null pointers, a dimension < 1, nx * ny or mx * my >= 2^31.                                           */
+int glh_stage_zoom_linear(int device_id, const double* a, int nx, int ny, int mx, int my, double* out, double* times_ms);
+/* RasterInterpolant._interpolate (raster.py:1681-1698) over one upload and one download: z = m0 + (m1 - m0) scale and,
+ * when sigma is not NULL, sigma = sqrt(s0^2 + scale2 (s0^2 + s1^2) + ((third (m1 - m0)) ratio)^2), operation by operation
+ * in that order (the caller passes scale2 = scale ** 2, third = 1 / 3 and ratio = nearest_dx / dx as its own Python made
+ * them).  m0, s0, z, sigma [ny][nx].  The second mean is m1 [ny][nx], or, when m1_src is not NULL, m1_src regridded at
+ * order 1 onto the ascending centres xo [nx], yo [ny] of the first's grid (Raster.resample; its flip_x / flip_y say how
+ * the first's array runs); likewise s1 / s1_src.  times_ms [4]: upload, regrid, blend, download.
+ * Checks as glh_stage_raster_regrid; a source must have kx == ky == 1.                                                   */
+int glh_stage_raster_interpolate(int device_id, int nx, int ny, const double* m0, const double* m1,
+                                 const glh_regrid_src* m1_src, const double* s0, const double* s1,
+                                 const glh_regrid_src* s1_src, const double* xo, const double* yo, double scale,
+                                 double scale2, double third, double ratio, double* z, double* sigma, double* times_ms);
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
 

@@ -22,6 +22,8 @@ Fixtures:
                       with crevasses: 21 cases, the three outputs of each, inputs by SHA-256 (--g30)
   g31_horizon.npz     Raster.horizon on seeded exact terrain, heading by heading: 12 cases, the headings the reference
                       raises on, the points, the runs, a few helpers.bresenham_line outputs; DEMs by SHA-256 (--g31)
+  g32_regrid.npz      Raster.sample(grid=True) at orders 1 .. 5, resample, resize, crop_extent and RasterInterpolant of
+                      the reference on the cases of tests/regrid_restatement.py; inputs by SHA-256 (--g32)
 Every g8 file stores frames, cameras, motion parameters, the recorded legacy
 RNG draws (in the reference's order), per-step traces (uv, box, search tile,
 sse, sampled ll, weights, searchsorted indices, particles) and Tracks.means /
@@ -1730,7 +1732,104 @@ def g31_horizon(path=None):
     print("g31 ->", path, os.path.getsize(path), "bytes")
 
 
+# ---- g32: Raster.sample(grid=True) / resample / resize / crop_extent, RasterInterpolant ---------------------------------
+def g32_regrid(path=None):
+    """The reference's own Raster.sample(grid=True), resample, resize, crop_extent and RasterInterpolant on the cases of
+    tests/regrid_restatement.py.  Inputs are rebuilt by the tests from seeds and pinned here by SHA-256.  Per sample case:
+    the output (float64 (len(y), len(x)); the 1 x 1 case as the reference shapes it).  Per zoom: the resized array.  Per
+    crop box: crop_extent's limits and indices.  Per interpolant case: nearest's indices, the mean (and sigma) arrays and
+    their limits.  Also what the reference raises for order 0 with grid=True (its class name and bases), and nearest's
+    answers on a numeric and a datetime series."""
+    import datetime
+
+    from tests import regrid_restatement as rr
+    from tests import viewshed_terrain as vt
+
+    out = {}
+    for name in sorted(rr.SAMPLE_CASES):
+        z, xlim, ylim, xy, kwargs = rr.build(name)
+        raster = glimpse.Raster(z.copy(), x=xlim, y=ylim)
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            samples = raster.sample(xy, grid=True, **kwargs)
+        assert vt.sha256(raster.array).tobytes() == vt.sha256(z).tobytes()  # (the stand-in values are taken out again)
+        out[f"{name}__sha256"] = vt.sha256(z)
+        out[f"{name}__out"] = np.asarray(samples)
+        print("g32", name, z.shape, z.dtype, "->", samples.shape, "NaN:", int(np.isnan(samples).sum()))
+    # Raster.resample onto another raster's grid, order 1 (the default) and 3
+    z, xlim, ylim, _, _ = rr.build("small_k3")
+    for order in (1, 3):
+        raster = glimpse.Raster(z.copy(), x=xlim, y=ylim)
+        target = glimpse.Raster(np.zeros((9, 14)), x=(rr.X0 + 12.0, rr.X0 + 152.0), y=(rr.Y0 + 121.0, rr.Y0 + 13.0))
+        with np.errstate(all="ignore"):
+            raster.resample(target, order=order)
+        out[f"resample_k{order}__out"] = raster.array
+        out[f"resample_k{order}__limits"] = np.concatenate((raster.xlim, raster.ylim))
+    a = rr.zoom_input()
+    out["zoom__sha256"] = vt.sha256(a)
+    for zoom in rr.ZOOMS:
+        raster = glimpse.Raster(a.copy(), x=(rr.X0, rr.X0 + 310.0), y=(rr.Y0 + 230.0, rr.Y0))
+        raster.resize(zoom)
+        out[f"zoom_{zoom}__out"] = raster.array
+        print("g32 zoom", zoom, a.shape, "->", raster.array.shape)
+    xlim, ylim = rr.limits(rr.CROP_SHAPE)
+    raster = glimpse.Raster(np.zeros(rr.CROP_SHAPE), x=xlim, y=ylim)
+    for k, (bx, by) in enumerate(rr.CROP_BOXES):
+        cx, cy, rows, cols = raster.crop_extent(xlim=bx, ylim=by)
+        out[f"crop{k}__limits"] = np.concatenate((cx, cy))
+        out[f"crop{k}__rowcol"] = np.concatenate((rows, cols)).astype(np.int64)
+    try:
+        raster.sample((raster.x, raster.y), grid=True, order=0)
+        raise RuntimeError("order 0 with grid=True did not raise")
+    except Exception as e:  # noqa: BLE001 (f2py's module error: a class of its own)
+        out["order0__raises"] = np.array([type(e).__name__] + [b.__name__ for b in type(e).__bases__])
+    for name in sorted(rr.INTERPOLANT_CASES):
+        means, sigmas, x, call = rr.interpolant_inputs(name)
+        digest = vt.sha256(np.concatenate([m[0].ravel() for m in means]
+                                          + ([s[0].ravel() for s in sigmas] if isinstance(sigmas, list)
+                                             and not np.isscalar(sigmas[0]) else [])))
+        as_raster = lambda v: v if np.isscalar(v) else glimpse.Raster(v[0].copy(), x=v[1], y=v[2])  # noqa: E731
+        interpolant = glimpse.RasterInterpolant([as_raster(m) for m in means],
+                                                None if sigmas is None else [as_raster(v) for v in sigmas], x=x)
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            result = interpolant(**call)
+        ij = interpolant.nearest(call["xi"], extrapolate=call.get("extrapolate", False))
+        mean, sigma = result if isinstance(result, tuple) else (result, None)
+        out[f"{name}__sha256"] = digest
+        out[f"{name}__ij"] = np.array(ij, dtype=np.int64)
+        out[f"{name}__z"] = mean.array
+        out[f"{name}__limits"] = np.concatenate((mean.xlim, mean.ylim))
+        if sigma is not None:
+            out[f"{name}__sigma"] = sigma.array
+        print("g32 interpolant", name, "ij", ij, "->", mean.array.shape, mean.array.dtype, "NaN:",
+              int(np.isnan(mean.array).sum()))
+    # nearest (raster.py:1642-1671) on a numeric and a datetime series: (xi as a number of days, extrapolate, i, j), -1 -1
+    # where it raises "Not bounded on both sides by a Raster"
+    rows = []
+    for series, make in (([0.0, 10.0, 30.0, 31.0], float), (rr.DATETIMES, lambda v: rr.T0 + datetime.timedelta(days=v))):
+        interpolant = glimpse.RasterInterpolant([0, 0, 0, 0][:len(series)], x=series)
+        for xi in (-3.0, 0.0, 4.0, 5.0, 10.0, 25.0, 30.5, 45.0):
+            for extrapolate in (False, True):
+                try:
+                    ij = interpolant.nearest(make(xi), extrapolate=extrapolate)
+                except ValueError as e:
+                    assert str(e) == "Not bounded on both sides by a Raster"
+                    ij = (-1, -1)
+                rows.append((len(series), xi, float(extrapolate), ij[0], ij[1]))
+    out["nearest"] = np.array(rows, dtype=np.float64)
+    out["sample_cases"] = np.array(sorted(rr.SAMPLE_CASES))
+    out["interpolant_cases"] = np.array(sorted(rr.INTERPOLANT_CASES))
+    path = path or os.path.join(OUT, "g32_regrid.npz")
+    np.savez_compressed(path, **out)
+    print("g32 ->", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < 400_000
+
+
 if __name__ == "__main__":
+    if "--g32" in sys.argv:
+        g32_regrid(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+        sys.exit(0)
     if "--g31" in sys.argv:
         g31_horizon(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
         sys.exit(0)
