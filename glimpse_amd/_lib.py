@@ -161,6 +161,9 @@ SIGNATURES = {
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "glh_stage_gaussian_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_fill_crevasses": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
+    "glh_stage_gradient": (_I, [_I, _P, _I, _I, _I, _D, _D, _P, _P, _P]),
+    "glh_stage_hillshade": (_I, [_I, _P, _I, _I, _I, _D, _D, _D, _P, _D, _P, _P]),
+    "glh_stage_polygon_mask": (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
 }
 
 _lib = None
@@ -1154,3 +1157,57 @@ def stage_fill_crevasses(a, mask, fill, size_y, size_x, max_mode, w0, w1, gauss_
                                           int(size_x), int(max_mode), _ptr(w0), r0, _ptr(w1), r1, int(gauss_mode), _ptr(out),
                                           _ptr(times) if return_times else None))
     return _filter_result(out, times, return_times)
+
+
+TERRAIN_F64, TERRAIN_F32 = 0, 1
+GRADIENT_TIMES = ("upload_ms", "kernel_ms", "download_ms")
+HILLSHADE_TIMES = ("upload_ms", "stencil_ms", "reduce_ms", "normalise_ms", "download_ms")
+POLYGON_MASK_TIMES = ("upload_ms", "kernels_ms", "download_ms")
+
+
+def _terrain_array(z):
+    """(z, dtype flag, nx, ny) of the gradient and hillshade stages: `z` (ny, nx) float64 / float32; glimpse_amd.raster
+    checks and widens what the caller gave."""
+    if z.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or z.ndim != 2:
+        raise TypeError(f"a two-dimensional float64 or float32 array (got {z.dtype}, {z.ndim} dimensions)")
+    z = np.ascontiguousarray(z)
+    return z, TERRAIN_F32 if z.dtype == np.float32 else TERRAIN_F64, z.shape[1], z.shape[0]
+
+
+def _terrain_result(out, names, times, return_times):
+    return (out, dict(zip(names, (float(t) for t in times)))) if return_times else out
+
+
+def stage_gradient(z, d0, d1, device_id=0, return_times=False):
+    """Raster.gradient (raster.py:1465-1474): (dzdx, dzdy) of `z` (ny, nx) with the signed cell sizes d0 (x) and d1 (y),
+    each of z's dtype.  `return_times`: also a dict of the HIP-event split (GRADIENT_TIMES)."""
+    z, flag, nx, ny = _terrain_array(z)
+    dzdx, dzdy = np.empty_like(z), np.empty_like(z)
+    times = np.zeros(5)
+    check(load().glh_stage_gradient(device_id, _ptr(z), flag, nx, ny, float(d0), float(d1), _ptr(dzdx), _ptr(dzdy),
+                                    _ptr(times) if return_times else None))
+    return _terrain_result((dzdx, dzdy), GRADIENT_TIMES, times, return_times)
+
+
+def stage_hillshade(z, d0, d1, vert_exag, direction, fraction, device_id=0, return_times=False):
+    """matplotlib's LightSource.hillshade (Raster.hillshade, raster.py:1249-1264) of `z` (ny, nx): float64 (ny, nx).  d0,
+    d1: the spacings of the gradient along x and y (dy already negated); `direction` (3,) towards the light."""
+    z, flag, nx, ny = _terrain_array(z)
+    direction = _arr(direction, np.float64, (3,))
+    out = np.empty((ny, nx))
+    times = np.zeros(5)
+    check(load().glh_stage_hillshade(device_id, _ptr(z), flag, nx, ny, float(d0), float(d1), float(vert_exag), _ptr(direction),
+                                     float(fraction), _ptr(out), _ptr(times) if return_times else None))
+    return _terrain_result(out, HILLSHADE_TIMES, times, return_times)
+
+
+def stage_polygon_mask(xy, ring_off, n_polygons, n_holes, nx, ny, device_id=0, return_times=False):
+    """helpers.polygons_to_mask (helpers.py:1701-1768) by the stated even-odd rule: `xy` (n, 2) the vertices of all rings
+    in continuous cell coordinates, `ring_off` (rings + 1,) their offsets, the polygon rings first -> bool (ny, nx)."""
+    ring_off = _arr(ring_off, np.int32, (int(n_polygons) + int(n_holes) + 1,))
+    xy = _arr(xy, np.float64, (int(ring_off[-1]), 2))
+    out = np.empty((int(ny), int(nx)), dtype=np.uint8)
+    times = np.zeros(5)
+    check(load().glh_stage_polygon_mask(device_id, _ptr(xy), len(xy), _ptr(ring_off), int(n_polygons), int(n_holes), int(nx),
+                                        int(ny), _ptr(out), _ptr(times) if return_times else None))
+    return _terrain_result(out.view(bool), POLYGON_MASK_TIMES, times, return_times)

@@ -9,7 +9,8 @@ bit-identical to NumPy's (no implicit FMA); the SSD kernel asks for FMA explicit
 The library is many translation units compiled in parallel: glimpse_hip.hip (the C ABI and the
 staged kernels), glh_viewshed.hip and glh_project_dem.hip (the terrain routines, each with rocPRIM's
 radix sort), glh_horizon.hip (Raster.horizon), glh_regrid.hip (Raster.sample(grid=True), resize,
-RasterInterpolant), glh_filters.hip (the maximum and Gaussian filters of Raster.fill_crevasses) and one object per instantiation of the fused kernel (glh_point_inst.hip with
+RasterInterpolant), glh_filters.hip (the maximum and Gaussian filters of Raster.fill_crevasses), glh_terrain.hip
+(Raster.gradient, Raster.hillshade, polygon masks) and one object per instantiation of the fused kernel (glh_point_inst.hip with
 -DPT_*; the list is csrc/glh_point_variants.h).  Objects are cached in glimpse_amd/lib/obj/ and
 rebuilt when a source they include is newer.
 """
@@ -47,9 +48,11 @@ PROJECT_DEM = os.path.join(CSRC, "glh_project_dem.hip")  # Camera.project_dem / 
 PROJECT_DEM_HEADER = os.path.join(CSRC, "glh_project_dem.h")
 FILTERS = os.path.join(CSRC, "glh_filters.hip")  # maximum_filter / gaussian_filter / Raster.fill_crevasses
 FILTERS_HEADER = os.path.join(CSRC, "glh_filters.h")
+TERRAIN = os.path.join(CSRC, "glh_terrain.hip")  # Raster.gradient / hillshade / helpers.polygons_to_mask
+TERRAIN_HEADER = os.path.join(CSRC, "glh_terrain.h")
 HOST_HEADERS = [os.path.join(CSRC, "glh_host.h"), os.path.join(CSRC, "glh_comm.h"), VIEWSHED_HEADER, HORIZON_HEADER,
-                REGRID_HEADER, REGRID_HOST_HEADER, PROJECT_DEM_HEADER, FILTERS_HEADER]
-DEPS = [SRC, INST, VIEWSHED, HORIZON, REGRID, PROJECT_DEM, FILTERS, *HEADERS, *HOST_HEADERS]
+                REGRID_HEADER, REGRID_HOST_HEADER, PROJECT_DEM_HEADER, FILTERS_HEADER, TERRAIN_HEADER]
+DEPS = [SRC, INST, VIEWSHED, HORIZON, REGRID, PROJECT_DEM, FILTERS, TERRAIN, *HEADERS, *HOST_HEADERS]
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -106,7 +109,9 @@ def _jobs(extra, objdir=OBJDIR):
             (os.path.join(objdir, "glh_project_dem.o"), [cc, *FLAGS, *extra, "-c", PROJECT_DEM],
              [PROJECT_DEM, PROJECT_DEM_HEADER, os.path.join(CSRC, "glh_math.h"), HEADERS[-1]]),
             (os.path.join(objdir, "glh_filters.o"), [cc, *FLAGS, *extra, "-c", FILTERS],
-             [FILTERS, FILTERS_HEADER, os.path.join(CSRC, "glh_math.h"), HEADERS[-1]])]
+             [FILTERS, FILTERS_HEADER, os.path.join(CSRC, "glh_math.h"), HEADERS[-1]]),
+            (os.path.join(objdir, "glh_terrain.o"), [cc, *FLAGS, *extra, "-c", TERRAIN],
+             [TERRAIN, TERRAIN_HEADER, HEADERS[-1]])]
     for tb, ppt, nobs, s, f, c in variants():
         obj = os.path.join(objdir, f"pt_{tb}_{ppt}_{nobs}_{s}{f}{c}.o")
         defs = [f"-DPT_TB={tb}", f"-DPT_PPT={ppt}", f"-DPT_NOBS={nobs}", f"-DPT_SURF={s}", f"-DPT_FAST={f}",

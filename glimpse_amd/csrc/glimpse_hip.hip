@@ -22,6 +22,7 @@
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
+#include "glh_terrain.h"
 
 using namespace glh;
 
@@ -3098,6 +3099,70 @@ extern "C" int glh_stage_fill_crevasses(int dev, const void* a, int dtype, int n
   CHK(check_filter_weights("fill_crevasses", w0, r0, w1, r1, gauss_mode));
   return run_filters(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, max_mode, 1, w0, r0,
                                 w1, r1, gauss_mode, out, times_ms});
+}
+
+// Raster.gradient, Raster.hillshade (raster.py:1465-1474, :1249-1264) and helpers.polygons_to_mask (helpers.py:1701-1768):
+// the arguments are checked here, before a device is touched; the kernels and the launches are glh_terrain.hip's.
+static int check_terrain_grid(const char* who, int nx, int ny, int least) {
+  if (nx < least || ny < least) return fail(GLH_E_INVALID, "%s: %d x %d cells: at least %d on each axis", who, nx, ny, least);
+  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "%s: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", who, nx, ny);
+  return GLH_OK;
+}
+
+static int check_terrain_dem(const char* who, int dtype, double d0, double d1) {
+  if (!std::isfinite(d0) || !std::isfinite(d1) || d0 == 0.0 || d1 == 0.0)
+    return fail(GLH_E_INVALID, "%s: cell sizes (%g, %g): finite and not zero", who, d0, d1);
+  if (dtype != GLH_TERRAIN_F64 && dtype != GLH_TERRAIN_F32)
+    return fail(GLH_E_UNSUPPORTED, "%s: dtype %d: 0 float64, 1 float32", who, dtype);
+  return GLH_OK;
+}
+
+extern "C" int glh_stage_gradient(int dev, const void* z, int dtype, int nx, int ny, double d0, double d1, void* dzdx,
+                                  void* dzdy, double* times_ms) {
+  if (!z || !dzdx || !dzdy) return fail(GLH_E_INVALID, "gradient: null argument");
+  CHK(check_terrain_grid("gradient", nx, ny, 2));
+  CHK(check_terrain_dem("gradient", dtype, d0, d1));
+  char msg[512] = "";
+  const int rc = gradient_run(GradientJob{dev, z, dtype == GLH_TERRAIN_F32, nx, ny, d0, d1, dzdx, dzdy, times_ms}, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+extern "C" int glh_stage_hillshade(int dev, const void* z, int dtype, int nx, int ny, double d0, double d1, double vert_exag,
+                                   const double* direction, double fraction, double* out, double* times_ms) {
+  if (!z || !direction || !out) return fail(GLH_E_INVALID, "hillshade: null argument");
+  CHK(check_terrain_grid("hillshade", nx, ny, 2));
+  CHK(check_terrain_dem("hillshade", dtype, d0, d1));
+  if (!std::isfinite(vert_exag) || !std::isfinite(fraction) || !std::isfinite(direction[0]) || !std::isfinite(direction[1]) ||
+      !std::isfinite(direction[2]))
+    return fail(GLH_E_INVALID, "hillshade: vert_exag %g, fraction %g, direction (%g, %g, %g): all finite", vert_exag, fraction,
+                direction[0], direction[1], direction[2]);
+  char msg[512] = "";
+  const HillshadeJob job{dev, z, dtype == GLH_TERRAIN_F32, nx, ny, d0, d1, vert_exag, {direction[0], direction[1], direction[2]},
+                         fraction, out, times_ms};
+  const int rc = hillshade_run(job, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+}
+
+extern "C" int glh_stage_polygon_mask(int dev, const double* xy, int n_vertices, const int32_t* ring_off, int n_polygons,
+                                      int n_holes, int nx, int ny, uint8_t* out, double* times_ms) {
+  if (!xy || !ring_off || !out) return fail(GLH_E_INVALID, "polygon_mask: null argument");
+  CHK(check_terrain_grid("polygon_mask", nx, ny, 1));
+  if (n_vertices < 1 || n_polygons < 1 || n_holes < 0 || (int64_t)n_polygons + n_holes >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "polygon_mask: %d vertices, %d polygon rings, %d hole rings", n_vertices, n_polygons, n_holes);
+  const int rings = n_polygons + n_holes;
+  if (ring_off[0] != 0 || ring_off[rings] != n_vertices)
+    return fail(GLH_E_INVALID, "polygon_mask: the ring offsets run from %d to %d, not from 0 to %d", ring_off[0], ring_off[rings],
+                n_vertices);
+  for (int k = 0; k < rings; ++k)
+    if ((int64_t)ring_off[k + 1] - ring_off[k] < 3 || ring_off[k + 1] > n_vertices)
+      return fail(GLH_E_INVALID, "polygon_mask: ring %d has %lld vertices: at least three", k,
+                  (long long)ring_off[k + 1] - ring_off[k]);
+  for (int64_t i = 0; i < 2 * (int64_t)n_vertices; ++i)
+    if (!std::isfinite(xy[i])) return fail(GLH_E_INVALID, "polygon_mask: vertex %lld is not finite", (long long)(i / 2));
+  char msg[512] = "";
+  const int rc = polygon_mask_run(PolygonMaskJob{dev, xy, ring_off, n_polygons, n_holes, nx, ny, out, times_ms}, msg, sizeof msg);
+  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
 }
 
 extern "C" int glh_stage_resample(int dev, const double* weights, int n, double u, int64_t* idx) {

@@ -20,8 +20,13 @@ one kernel substituting down the columns, one along the rows through LDS tiles, 
 its uncertainty for a day between two DEMs (`glh_stage_raster_interpolate`: the regridding of the second raster and the
 blend in one call).  Their host-only companions are restated here: `copy`, `grid` (a `Grid`, equal to another by shape and
 limits), `box2d`, `crop_extent` / `crop`.
-File I/O (GDAL), `hillshade`, `gradient`, `rasterize_polygons`, `fill_circle` and rasters with a singleton dimension (the
-reference's 1-D `interp1d` path) are out of scope.
+The rest of the raster tooling is served too: `gradient` (:1465-1474, `glh_stage_gradient`) and `hillshade` (:1249-1264,
+`glh_stage_hillshade`: matplotlib's LightSource.hillshade without matplotlib) are one stencil kernel each over the DEM;
+`rasterize_polygons` (:1121-1147) makes masks with `helpers.polygons_to_mask` (`glh_stage_polygon_mask`), by a stated
+even-odd rule on cell centres where the reference calls GDAL; `rasterize` (:1103-1119) takes its per-cell means from
+`glh_stage_rasterize`.  `fill_circle`, `shift`, `data_extent` and `crop_to_data` are restated on the host.
+File I/O (GDAL), `plot`, masked arrays and rasters with a singleton dimension (the reference's 1-D `interp1d` path) are out
+of scope.
 """
 import copy
 import datetime
@@ -339,6 +344,135 @@ class Raster:
         if callable(mask):
             mask = mask(self.array)
         self.array = filters.fill_crevasses(self.array, maximum, gaussian, mask=mask, fill=fill)
+
+    # ---- terrain tooling: gradient, hillshade, masks (raster.py:1103-1147, :1189-1264, :1465-1525)
+    def _terrain_values(self, what):
+        """`array` as the gradient kernels take it: two-dimensional with two or more cells on each axis (np.gradient's
+        ValueError otherwise), float64 or float32; integers and bool are widened to float64 as np.gradient does."""
+        a = self.array
+        if a.ndim != 2:
+            raise ValueError(f"a raster is two-dimensional, got {a.shape}")
+        if min(a.shape) < 2:
+            raise ValueError("Shape of array too small to calculate a numerical gradient, at least (edge_order + 1) "
+                             "elements are required.")
+        if a.dtype.kind in "biu":
+            return a.astype(np.float64)
+        if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)):
+            raise NotImplementedError(f"{what} of a {a.dtype} array: float64 and float32 are built (integers are widened)")
+        return a
+
+    def gradient(self):
+        """(dzdx, dzdy): the derivatives of `array` with respect to x and y (raster.py:1465-1474),
+        np.gradient(array, d[1], d[0]) with the signed cell sizes, on the GPU (`glh_stage_gradient`): central differences
+        (f[i+1] - f[i-1]) / (2 h) inside, one-sided (f[1] - f[0]) / h at the two ends of a line.  A float64 array comes
+        back bit for bit NumPy's; a float32 array comes back float32 (the difference in float32, the quotient against
+        the float64 cell size rounded to float32, as NumPy 2 does); integers and bool are widened to float64."""
+        z = self._terrain_values("gradient")
+        d = self.d
+        return _lib.stage_gradient(z, d[0], d[1])
+
+    def hillshade(self, azimuth=315, altitude=45, **kwargs):
+        """The illumination of the surface, float64 in [0, 1] in the shape of `array` (raster.py:1249-1264):
+        matplotlib.colors.LightSource(azimuth, altitude).hillshade(array, dx=d[0], dy=d[1], **kwargs) with `kwargs` among
+        `vert_exag` and `fraction`, on the GPU (`glh_stage_hillshade`) and without matplotlib.  `azimuth`: degrees clockwise
+        from north; `altitude`: degrees above the horizon.  The normal of vert_exag * array (gradients with dy negated)
+        is dotted with the light direction; the intensity is scaled by `fraction`, stretched from its own minimum and
+        maximum to [0, 1] when they differ by more than 1e-6, and clipped.  matplotlib's quirks are kept: with any NaN
+        cell nothing is stretched, and a NaN cell makes its four edge neighbours NaN, not itself.  It differs from
+        matplotlib's bytes only through the three-term dot product (summed left to right here, BLAS there): by at most
+        a few 2^-52 of the stretch.  `dx` or `dy` among the kwargs is the TypeError the reference raises; masked arrays
+        (a Raster holds a plain array) and LightSource.shade are not built."""
+        for name in ("dx", "dy"):
+            if name in kwargs:
+                raise TypeError(f"hillshade() got multiple values for keyword argument '{name}'")
+        unknown = sorted(set(kwargs) - {"vert_exag", "fraction"})
+        if unknown:
+            raise TypeError(f"hillshade() got an unexpected keyword argument '{unknown[0]}'")
+        z = self._terrain_values("hillshade")
+        az, alt = np.radians(90 - azimuth), np.radians(altitude)
+        direction = np.array([np.cos(az) * np.cos(alt), np.sin(az) * np.cos(alt), np.sin(alt)])
+        d = self.d
+        return _lib.stage_hillshade(z, d[0], -d[1], float(kwargs.get("vert_exag", 1)), direction,
+                                    float(kwargs.get("fraction", 1.0)))
+
+    def rasterize(self, xy, values):
+        """A copy of `array` with the mean of the `values` (n,) of the points `xy` (n, 2) that fall in each cell written
+        over it (raster.py:1103-1119); cells without a point keep their value, points outside the raster are dropped.  The
+        points snap to cells on the host; the means are helpers.rasterize_points' on the GPU (`glh_stage_rasterize`: the
+        sum in the points' order times 1 / count) and are written to the cells that received a point, so a mean of NaN
+        values is told from no point."""
+        xy = np.atleast_2d(np.asarray(xy, dtype=float))
+        values = np.asarray(values)
+        if values.ndim != 1 or len(values) != len(xy):
+            raise ValueError(f"one value per point: {len(xy)} points, values of shape {values.shape}")
+        if self.array.ndim != 2:
+            raise ValueError(f"a raster is two-dimensional, got {self.array.shape}")
+        inside = self.inbounds_xy(xy)
+        array = self.array.copy()
+        if not inside.any():
+            return array
+        colrow = self._snapped_colrow(xy[inside])
+        cells, labels = np.unique(colrow[:, 1] * int(self.size[0]) + colrow[:, 0], return_inverse=True)
+        means = _lib.stage_rasterize(labels.ravel(), values[inside].astype(np.float64)[:, None], len(cells))[:, 0]
+        array.flat[cells] = means
+        return array
+
+    def rasterize_polygons(self, polygons, holes=None):
+        """Boolean array in the shape of `array`: the cells inside `polygons` [[(x, y), ...], ...] and outside `holes`
+        (raster.py:1121-1147), on the GPU through helpers.polygons_to_mask, whose even-odd rule on cell centres stands in
+        for GDAL's.  The vertices go to continuous cell coordinates on the host, as the reference's xy_to_rowcol does."""
+        corner = np.append(self.xlim[0], self.ylim[0])
+        to_cells = lambda rings, what: [((ring - corner) / self.d - 0.5) + 0.5  # noqa: E731
+                                        for ring in helpers.polygon_rings(rings, what)]
+        return helpers.polygons_to_mask(to_cells(polygons, "polygon"), self.size,
+                                        holes=None if holes is None else to_cells(holes, "hole"))
+
+    def shift(self, dx=None, dy=None, dz=None):
+        """Shift the position in place (raster.py:1189-1219)."""
+        if dx is not None:
+            self.xlim = self.xlim + dx
+        if dy is not None:
+            self.ylim = self.ylim + dy
+        if dz is not None:
+            self.array += dz
+
+    def fill_circle(self, center, radius, value=np.nan):
+        """Fill a circle around `center` (x, y) with `value`, in place (raster.py:1221-1247): the cells on and inside
+        helpers.bresenham_circle around the centre's cell, `radius` / d[0] cells wide (rounded), rows and columns clipped
+        to the grid.  On the host.  A raster whose x decreases along the array has a negative radius in cells, which is
+        bresenham_circle's ValueError, as in the reference."""
+        col, row = self._snapped_colrow(np.atleast_2d(np.asarray(center, dtype=float)[0:2]))[0]
+        r = np.round(radius / self.d[0])
+        xyi = helpers.bresenham_circle((col, row), r).astype(int)
+        nx, ny = (int(v) for v in self.size)
+        ind = []
+        for yi in np.unique(xyi[:, 1]):
+            if not -1 < yi < ny:
+                continue
+            xb = xyi[xyi[:, 1] == yi, 0]
+            xi = np.arange(max(xb.min(), 0), min(xb.max(), nx - 1) + 1)
+            ind.append(yi * nx + xi)
+        self.array.flat[np.concatenate(ind) if ind else np.zeros(0, dtype=int)] = value
+
+    def data_extent(self):
+        """(row slice, column slice) of the region bounding all cells that are not NaN (raster.py:1492-1514); ValueError
+        when every cell is NaN."""
+        data = ~np.isnan(self.array)
+        data_row, data_col = np.any(data, axis=1), np.any(data, axis=0)
+        if not data_row.any():
+            raise ValueError("No non-missing values present")
+        first_row, last_row = np.argmax(data_row), data_row.size - np.argmax(data_row[::-1])
+        first_col, last_col = np.argmax(data_col), data_col.size - np.argmax(data_col[::-1])
+        return slice(first_row, last_row), slice(first_col, last_col)
+
+    def crop_to_data(self):
+        """Crop in place to `data_extent()` (raster.py:1516-1525): the limits are put half a cell beyond the first and last
+        kept cell centre."""
+        rows, cols = self.data_extent()
+        x, y, d = self.x[cols], self.y[rows], self.d
+        self._set_array(self.array[rows, cols])
+        self.xlim = x[[0, -1]] + np.array((-0.5, 0.5)) * d[0]
+        self.ylim = y[[0, -1]] + np.array((-0.5, 0.5)) * d[1]
 
     # ---- host-only companions of the resampling (restated from the reference)
     def _set_array(self, array):

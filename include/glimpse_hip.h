@@ -574,6 +574,46 @@ int glh_stage_gaussian_filter(int device_id, const void* a, int dtype, int nx, i
 int glh_stage_fill_crevasses(int device_id, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
                              int size_y, int size_x, int max_mode, const double* w0, int r0, const double* w1, int r1,
                              int gauss_mode, void* out, double* times_ms);
+/* ---- terrain: Raster.gradient, Raster.hillshade, helpers.polygons_to_mask -------------------------------------------------
+ * Raster.gradient (raster.py:1465-1474; np.gradient(array, d[1], d[0])) of z [ny][nx], float64 (dtype GLH_TERRAIN_F64) or
+ * float32 (GLH_TERRAIN_F32), with the signed cell sizes d0 (along x, the columns) and d1 (along y, the rows), into dzdx and
+ * dzdy [ny][nx] of the same dtype: along a line with spacing h, (f[i+1] - f[i-1]) / (2 h) inside and (f[1] - f[0]) / h,
+ * (f[n-1] - f[n-2]) / h at the two ends.  The difference is formed in z's dtype, the quotient in float64 and rounded to z's
+ * dtype, as NumPy does with a float64 spacing: float64 results equal NumPy's in every bit.  One stencil kernel.
+ * times_ms (or NULL) [5]: HIP-event milliseconds -- [0] upload, [1] the kernel, [2] download, the rest 0.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, nx or ny < 2, nx * ny >= 2^31, a cell size that is zero
+ * or not finite), GLH_E_UNSUPPORTED (another dtype).  A failed device allocation is GLH_E_NOMEM.                          */
+#define GLH_TERRAIN_F64 0
+#define GLH_TERRAIN_F32 1
+int glh_stage_gradient(int device_id, const void* z, int dtype, int nx, int ny, double d0, double d1, void* dzdx, void* dzdy,
+                       double* times_ms);
+/* Raster.hillshade (raster.py:1249-1264; matplotlib.colors.LightSource.hillshade) into out [ny][nx] float64.  d0, d1: the
+ * spacings the gradient takes along x and y (the caller hands matplotlib's: dx = d[0], dy = -d[1]); `direction` [3] the unit
+ * vector towards the light as the host's NumPy makes it.  Per cell: e_dx, e_dy the gradients (as above) of vert_exag * z,
+ * the product in z's dtype; the normal (-e_dx, -e_dy, 1) over sqrt((n0^2 + n1^2) + n2^2); I = n0 l0 + n1 l1 + n2 l2 summed
+ * left to right.  imin, imax over all cells (NaN when any cell is NaN: then nothing is normalised); I *= fraction; if
+ * imax - imin > 1e-6, I = (I - imin) / (imax - imin); I clipped to [0, 1], NaN kept.  A stencil kernel stores I and one
+ * (min, max, saw-NaN) partial per workgroup, one workgroup folds the partials in a fixed order, a third kernel scales,
+ * normalises and clips in place; no floating-point atomics, so two calls give the same bytes.
+ * times_ms [5]: [0] upload, [1] stencil, [2] reduction, [3] normalisation, [4] download.
+ * Checks as glh_stage_gradient; also GLH_E_INVALID for a vert_exag, fraction or direction that is not finite.          */
+int glh_stage_hillshade(int device_id, const void* z, int dtype, int nx, int ny, double d0, double d1, double vert_exag,
+                        const double* direction, double fraction, double* out, double* times_ms);
+/* helpers.polygons_to_mask (helpers.py:1701-1768) by a stated rule (the reference calls GDAL, which is not pinned): out
+ * [ny][nx] uint8, 1 inside.  xy [n_vertices][2]: the rings' vertices (x, y) in continuous cell coordinates, the top-left
+ * corner of cell (row 0, column 0) at (0, 0); ring k is vertices ring_off[k] .. ring_off[k + 1] - 1, closed implicitly; the
+ * first n_polygons rings are polygons, the n_holes after them holes.  Per ring, even-odd on the cell centres
+ * (c + 0.5, r + 0.5): an edge with y1 != y2 crosses row r when min(y1, y2) <= r + 0.5 < max(y1, y2), at
+ * x = x1 + (cy - y1) * (x2 - x1) / (y2 - y1) in float64 in that order, and toggles every cell of the row with c + 0.5 > x.
+ * The polygons' cells of odd parity are set, one ring after another; then the holes' are cleared.  Per ring, within its
+ * bounding rows and columns: a thread per (row, edge) toggles the bit of the first toggled column (atomicXor on 32-bit
+ * words), a wave per row turns the bits into parities by a prefix XOR and writes the cells.
+ * times_ms [5]: [0] upload and clearing, [1] the kernels of all rings, [2] download, the rest 0.
+ * GLH_E_INVALID before a device is touched: null pointers, nx or ny < 1, nx * ny >= 2^31, n_vertices or n_polygons < 1,
+ * n_holes < 0, offsets that do not run from 0 to n_vertices, a ring of fewer than three vertices, a vertex that is not
+ * finite.  GLH_E_UNSUPPORTED: a ring whose rows x edges exceed one launch (2^39 pairs).                                   */
+int glh_stage_polygon_mask(int device_id, const double* xy, int n_vertices, const int32_t* ring_off, int n_polygons,
+                           int n_holes, int nx, int ny, uint8_t* out, double* times_ms);
 /* ---- regridding: Raster.sample(grid=True) / resample, Raster.resize, RasterInterpolant ("regrid", since
  * glh_stage_resample is particle resampling) ------------------------------------------------------------------------------
  * A raster as the source of a spline evaluation.  z [ny][nx] float64 with rows and columns in ASCENDING coordinate order

@@ -24,6 +24,8 @@ Fixtures:
                       raises on, the points, the runs, a few helpers.bresenham_line outputs; DEMs by SHA-256 (--g31)
   g32_regrid.npz      Raster.sample(grid=True) at orders 1 .. 5, resample, resize, crop_extent and RasterInterpolant of
                       the reference on the cases of tests/regrid_restatement.py; inputs by SHA-256 (--g32)
+  g33_terrain.npz     Raster.gradient, hillshade, fill_circle, rasterize, shift, data_extent and crop_to_data of the
+                      reference on the cases of tests/terrain_restatement.py; DEMs by SHA-256 (--g33)
 Every g8 file stores frames, cameras, motion parameters, the recorded legacy
 RNG draws (in the reference's order), per-step traces (uv, box, search tile,
 sse, sampled ll, weights, searchsorted indices, particles) and Tracks.means /
@@ -1826,7 +1828,82 @@ def g32_regrid(path=None):
     assert os.path.getsize(path) < 400_000
 
 
+# ---- g33: Raster.gradient / hillshade / fill_circle / rasterize / shift / data_extent / crop_to_data ---------------------
+def g33_terrain(path=None):
+    """The reference's own Raster.gradient and Raster.hillshade (raster.py:1465-1474, :1249-1264; NumPy's gradient and
+    matplotlib's LightSource) on the cases of tests/terrain_restatement.py -- the DEMs are rebuilt by the tests from seeds
+    and pinned here by SHA-256 -- and its host-only fill_circle, rasterize, shift, data_extent and crop_to_data
+    (raster.py:1103-1119, :1189-1247, :1492-1525) on that module's small cases.  rasterize_polygons is not here: the
+    reference calls GDAL, which is not installed; the mask is pinned to a stated rule (glimpse_amd/helpers.py)."""
+    from tests import terrain_restatement as tr
+    from tests import viewshed_terrain as vt
+
+    out = {}
+    for name in tr.GOLDEN_CASES:
+        z, xlim, ylim, kwargs = tr.build(name)
+        raster = glimpse.Raster(z.copy(), x=xlim, y=ylim)
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            dzdx, dzdy = raster.gradient()
+            shade = raster.hillshade(**kwargs)
+        assert shade.dtype == np.float64 and shade.shape == z.shape and dzdx.shape == z.shape
+        out[f"{name}__sha256"] = vt.sha256(z)
+        out[f"{name}__dzdx"] = dzdx
+        out[f"{name}__dzdy"] = dzdy
+        out[f"{name}__hillshade"] = shade
+        print("g33", name, z.dtype, "->", dzdx.dtype, "hillshade NaN:", int(np.isnan(shade).sum()), "at 0 / 1:",
+              int((shade == 0).sum()), int((shade == 1).sum()))
+    for name, (xlim, ylim, centre, radius) in sorted(tr.CIRCLES.items()):
+        raster = glimpse.Raster(np.zeros(tr.CIRCLE_SHAPE), x=xlim, y=ylim)
+        assert raster.fill_circle(centre, radius) is None
+        out[f"circle_{name}"] = raster.array
+        print("g33 circle", name, "radius in cells", np.round(radius / raster.d[0]), "filled:", int(np.isnan(raster.array).sum()))
+    raster = glimpse.Raster(np.arange(180).reshape(tr.CIRCLE_SHAPE), x=tr.CIRCLE_X, y=tr.CIRCLE_Y_DESC)
+    raster.fill_circle((72.0, 63.0), 30.0, value=-7)
+    out["circle_int_value"] = raster.array
+    try:
+        glimpse.Raster(np.zeros(tr.CIRCLE_SHAPE), x=tr.CIRCLE_X_DESC, y=tr.CIRCLE_Y_DESC).fill_circle((72.0, 63.0), 20.0)
+        raise RuntimeError("fill_circle with a negative d[0] did not raise")
+    except ValueError as e:
+        out["circle_negative_d0__raises"] = np.array([type(e).__name__])
+    for dtype in ("float64", "float32", "int64"):
+        array, xlim, ylim, xy, values = tr.rasterize_case(dtype)
+        raster = glimpse.Raster(array.copy(), x=xlim, y=ylim)
+        result = raster.rasterize(xy, values)
+        assert np.array_equal(raster.array, array) and result.dtype == array.dtype
+        out[f"rasterize_{dtype}"] = result
+        print("g33 rasterize", dtype, "cells written:", int((~((result == array) | (result != result))).sum()), "NaN:",
+              int(np.sum(result != result)))
+    z, xlim, ylim = tr.holey()
+    raster = glimpse.Raster(z.copy(), x=xlim, y=ylim)
+    rows, cols = raster.data_extent()
+    out["extent"] = np.array([rows.start, rows.stop, cols.start, cols.stop], dtype=np.int64)
+    raster.crop_to_data()
+    out["crop_to_data__array"] = raster.array
+    out["crop_to_data__limits"] = np.concatenate((raster.xlim, raster.ylim)).astype(np.float64)
+    try:
+        glimpse.Raster(np.full((3, 4), np.nan)).data_extent()
+        raise RuntimeError("data_extent of an all-NaN raster did not raise")
+    except ValueError as e:
+        out["extent_all_nan__raises"] = np.array([str(e)])
+    raster = glimpse.Raster(z.copy(), x=np.array(xlim), y=np.array(ylim))
+    raster.shift(1.5, -2.0, 3.25)
+    out["shift__array"] = raster.array
+    out["shift__limits"] = np.concatenate((raster.xlim, raster.ylim)).astype(np.float64)
+    raster.shift(dy=0.5)
+    out["shift_dy__limits"] = np.concatenate((raster.xlim, raster.ylim)).astype(np.float64)
+    out["holey__sha256"] = vt.sha256(z)
+    out["cases"] = np.array(tr.GOLDEN_CASES)
+    path = path or os.path.join(OUT, "g33_terrain.npz")
+    np.savez_compressed(path, **out)
+    print("g33 ->", path, os.path.getsize(path), "bytes")
+    assert os.path.getsize(path) < 200_000
+
+
 if __name__ == "__main__":
+    if "--g33" in sys.argv:
+        g33_terrain(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
+        sys.exit(0)
     if "--g32" in sys.argv:
         g32_regrid(sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None)
         sys.exit(0)
