@@ -844,7 +844,29 @@ def stage_raster_sample(raster, xy, order=1, device_id=0):
     return vals, oob.astype(bool)
 
 
-VIEWSHED_F64, VIEWSHED_F32 = 0, 1
+# the dtype flag of a float array: GLH_VIEWSHED_*, GLH_PD_*, GLH_FILTER_* and GLH_TERRAIN_* of the header number them alike
+F64, F32 = 0, 1
+VIEWSHED_F64, VIEWSHED_F32 = F64, F32
+
+
+def _timed(result, names, times, return_times, extend=False):
+    """What a stage returns: `result`, and with `return_times` the dict of `names` -> the leading `times` after it
+    (`extend`: as one more item of the tuple `result`)."""
+    if not return_times:
+        return result
+    split = dict(zip(names, (float(t) for t in times)))
+    return (*result, split) if extend else (result, split)
+
+
+def _float_array(a):
+    """(a, dtype flag, nx, ny) of `a` (ny, nx) float64 / float32 as a stage takes it; the callers in glimpse_amd check and
+    widen what their caller gave."""
+    if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 2:
+        raise TypeError(f"a two-dimensional float64 or float32 array (got {a.dtype}, {a.ndim} dimensions)")
+    a = np.ascontiguousarray(a)
+    return a, F32 if a.dtype == np.float32 else F64, a.shape[1], a.shape[0]
+
+
 VIEWSHED_TIMES = ("upload_ms", "cells_ms", "sort_ms", "sweep_ms", "download_ms", "rings", "launches", "sort_scratch_bytes")
 
 
@@ -878,13 +900,9 @@ def viewshed_dem(array, origin_z):
     return np.ascontiguousarray(array, dtype=np.float64), VIEWSHED_F64
 
 
-def stage_viewshed(raster, origins, correction=None, device_id=0, return_times=False, float32=None):
-    """Raster.viewshed (raster.py:1293-1389) of `raster` from the m positions `origins` (m, 3): bool (m, ny, nx).  The DEM
-    is uploaded once and the m viewsheds are computed one after another.  `float32`: whether the reference's dz would be
-    float32 (None: NumPy's promotion of the DEM with `origins`' own scalar type is asked; Raster.viewshed asks with the
-    caller's origin[2], which may be a Python float).  `return_times`: also a dict of the HIP-event split, summed over the
-    origins (VIEWSHED_TIMES)."""
-    on, radius, refraction = viewshed_correction(correction)
+def _dem_and_origins(raster, origins, float32):
+    """(z, dtype flag, origins) of stage_viewshed and stage_horizon: the DEM of `raster` in the dtype `float32` decides
+    (None: viewshed_dem asks NumPy with the first origin's z), and the (m, 3) positions as float64."""
     origins = np.asarray(origins)
     if origins.ndim != 2 or origins.shape[1] != 3 or len(origins) < 1:
         raise ValueError(f"origins must be (m, 3) with m >= 1, got {origins.shape}")
@@ -895,7 +913,17 @@ def stage_viewshed(raster, origins, correction=None, device_id=0, return_times=F
         flag = VIEWSHED_F32 if float32 else VIEWSHED_F64
     if z.ndim != 2:
         raise ValueError(f"a DEM is two-dimensional, got {z.shape}")
-    origins = _arr(origins, np.float64)
+    return z, flag, _arr(origins, np.float64)
+
+
+def stage_viewshed(raster, origins, correction=None, device_id=0, return_times=False, float32=None):
+    """Raster.viewshed (raster.py:1293-1389) of `raster` from the m positions `origins` (m, 3): bool (m, ny, nx).  The DEM
+    is uploaded once and the m viewsheds are computed one after another.  `float32`: whether the reference's dz would be
+    float32 (None: NumPy's promotion of the DEM with `origins`' own scalar type is asked; Raster.viewshed asks with the
+    caller's origin[2], which may be a Python float).  `return_times`: also a dict of the HIP-event split, summed over the
+    origins (VIEWSHED_TIMES)."""
+    on, radius, refraction = viewshed_correction(correction)
+    z, flag, origins = _dem_and_origins(raster, origins, float32)
     ny, nx = z.shape
     x, y = _arr(raster.x, np.float64, (nx,)), _arr(raster.y, np.float64, (ny,))
     out = np.empty((len(origins), ny, nx), dtype=np.uint8)
@@ -903,8 +931,7 @@ def stage_viewshed(raster, origins, correction=None, device_id=0, return_times=F
     check(load().glh_stage_viewshed(device_id, _ptr(z), flag, nx, ny, _ptr(x), _ptr(y), float(1 / abs(raster.d[0])),
                                     _ptr(origins), len(origins), int(on), radius, refraction, _ptr(out),
                                     _ptr(times) if return_times else None))
-    vis = out.view(bool)
-    return (vis, dict(zip(VIEWSHED_TIMES, (float(t) for t in times)))) if return_times else vis
+    return _timed(out.view(bool), VIEWSHED_TIMES, times, return_times)
 
 
 HORIZON_TIMES = ("upload_ms", "kernel_ms", "download_ms")
@@ -918,18 +945,8 @@ def stage_horizon(raster, origins, starts, ends, correction=None, device_id=0, r
     (Raster.horizon passes viewshed_dem's answer for it); None decides from `origins` as an array, a float64 one unless
     the caller made it otherwise, so a float32 DEM is then widened.  `return_times`: also a dict of HORIZON_TIMES."""
     on, radius, refraction = viewshed_correction(correction)
-    origins = np.asarray(origins)
-    if origins.ndim != 2 or origins.shape[1] != 3 or len(origins) < 1:
-        raise ValueError(f"origins must be (m, 3) with m >= 1, got {origins.shape}")
-    if float32 is None:
-        z, flag = viewshed_dem(raster.array, origins[0, 2])
-    else:
-        z = np.ascontiguousarray(raster.array, dtype=np.float32 if float32 else np.float64)
-        flag = VIEWSHED_F32 if float32 else VIEWSHED_F64
-    if z.ndim != 2:
-        raise ValueError(f"a DEM is two-dimensional, got {z.shape}")
+    z, flag, origins = _dem_and_origins(raster, origins, float32)
     m = len(origins)
-    origins = _arr(origins, np.float64)
     starts = _arr(starts, np.int32, (m, 2))
     ends = _arr(ends, np.int32)
     if ends.ndim != 3 or ends.shape[0] != m or ends.shape[2] != 2 or ends.shape[1] < 1:
@@ -943,7 +960,7 @@ def stage_horizon(raster, origins, starts, ends, correction=None, device_id=0, r
     check(load().glh_stage_horizon(device_id, _ptr(z), flag, nx, ny, float(raster.xlim[0]), float(raster.ylim[0]),
                                    float(d[0]), float(d[1]), _ptr(origins), _ptr(starts), _ptr(ends), m, n, int(on), radius,
                                    refraction, _ptr(cell), _ptr(dz), _ptr(times) if return_times else None))
-    return (cell, dz, dict(zip(HORIZON_TIMES, (float(t) for t in times)))) if return_times else (cell, dz)
+    return _timed((cell, dz), HORIZON_TIMES, times, return_times, extend=True)
 
 
 REGRID_TIMES = ("upload_ms", "solve_ms", "evaluate_ms", "download_ms")
@@ -986,7 +1003,7 @@ def stage_raster_regrid(src, xo, yo, device_id=0, return_times=False):
     check(load().glh_stage_raster_regrid(device_id, C.byref(struct), _ptr(xo), len(xo), _ptr(yo), len(yo), _ptr(out),
                                          _ptr(times) if return_times else None))
     del keep
-    return (out, dict(zip(REGRID_TIMES, (float(t) for t in times)))) if return_times else out
+    return _timed(out, REGRID_TIMES, times, return_times)
 
 
 def stage_zoom_linear(a, shape, device_id=0, return_times=False):
@@ -1001,7 +1018,7 @@ def stage_zoom_linear(a, shape, device_id=0, return_times=False):
     times = np.zeros(len(REGRID_TIMES))
     check(load().glh_stage_zoom_linear(device_id, _ptr(a), a.shape[1], a.shape[0], mx, my, _ptr(out),
                                        _ptr(times) if return_times else None))
-    return (out, dict(zip(REGRID_TIMES, (float(t) for t in times)))) if return_times else out
+    return _timed(out, REGRID_TIMES, times, return_times)
 
 
 def stage_raster_interpolate(m0, m1, scale, scale2, ratio, s0=None, s1=None, xo=None, yo=None, device_id=0,
@@ -1034,16 +1051,12 @@ def stage_raster_interpolate(m0, m1, scale, scale2, ratio, s0=None, s1=None, xo=
         device_id, nx, ny, _ptr(m0), _ptr(m1), C.byref(m1_src[0]) if m1_src else None, _ptr(s0), _ptr(s1),
         C.byref(s1_src[0]) if s1_src else None, _ptr(xo), _ptr(yo), float(scale), float(scale2), 1 / 3, float(ratio), _ptr(z),
         _ptr(sigma), _ptr(times) if return_times else None))
-    return (z, sigma, dict(zip(INTERPOLATE_TIMES, (float(t) for t in times)))) if return_times else (z, sigma)
+    return _timed((z, sigma), INTERPOLATE_TIMES, times, return_times, extend=True)
 
 
-PD_F64, PD_F32, PD_U8, PD_U16 = 0, 1, 2, 3
+PD_F64, PD_F32, PD_U8, PD_U16 = F64, F32, 2, 3
 PD_DTYPES = {"float64": PD_F64, "float32": PD_F32, "uint8": PD_U8, "uint16": PD_U16}
 PD_TIMES = ("upload_ms", "project_ms", "order_ms", "reduce_ms", "download_ms", "memberships", "kept", "sort_scratch_bytes")
-
-
-def _pd_result(out, times, return_times):
-    return (out, dict(zip(PD_TIMES, (float(t) for t in times)))) if return_times else out
 
 
 def stage_project_dem(cam, z, values, mask, cols, x_coords, rows, y_coords, return_depth=False, device_id=0,
@@ -1080,7 +1093,7 @@ def stage_project_dem(cam, z, values, mask, cols, x_coords, rows, y_coords, retu
                                        _ptr(mask), _ptr(values), code, layers, len(xs), _ptr(xs), _ptr(xe), _ptr(x_coords),
                                        len(ys), _ptr(ys), _ptr(ye), _ptr(y_coords), int(bool(return_depth)), _ptr(out),
                                        _ptr(times) if return_times else None))
-    return _pd_result(out, times, return_times)
+    return _timed(out, PD_TIMES, times, return_times)
 
 
 def stage_rasterize(keys, values, n_pixels, device_id=0, return_times=False):
@@ -1093,23 +1106,20 @@ def stage_rasterize(keys, values, n_pixels, device_id=0, return_times=False):
     times = np.zeros(len(PD_TIMES))
     check(load().glh_stage_rasterize(device_id, _ptr(keys), len(keys), _ptr(values), values.shape[1], int(n_pixels),
                                      _ptr(out), _ptr(times) if return_times else None))
-    return _pd_result(out, times, return_times)
+    return _timed(out, PD_TIMES, times, return_times)
 
 
-FILTER_F64, FILTER_F32 = 0, 1
+FILTER_F64, FILTER_F32 = F64, F32
 FILTER_TIMES = ("upload_ms", "max_ms", "gauss0_ms", "gauss1_ms", "download_ms")
 
 
 def _filter_array(a, mask):
     """(a, dtype flag, nx, ny, mask, out) of the filter stages: `a` (ny, nx) float64 / float32, `mask` uint8 (ny, nx) or
     None; glimpse_amd.filters checks what the caller gave."""
-    if a.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or a.ndim != 2:
-        raise TypeError(f"a two-dimensional float64 or float32 array (got {a.dtype}, {a.ndim} dimensions)")
-    a = np.ascontiguousarray(a)
-    ny, nx = a.shape
+    a, flag, nx, ny = _float_array(a)
     if mask is not None:
         mask = _arr(mask, np.uint8, (ny, nx))
-    return a, FILTER_F32 if a.dtype == np.float32 else FILTER_F64, nx, ny, mask, np.empty_like(a)
+    return a, flag, nx, ny, mask, np.empty_like(a)
 
 
 def _filter_weights(w):
@@ -1122,10 +1132,6 @@ def _filter_weights(w):
     return w, len(w) // 2
 
 
-def _filter_result(out, times, return_times):
-    return (out, dict(zip(FILTER_TIMES, (float(t) for t in times)))) if return_times else out
-
-
 def stage_max_filter(a, mask, fill, size_y, size_x, mode=0, device_id=0, return_times=False):
     """helpers.maximum_filter (helpers.py:390-430) with a window of size_y rows x size_x columns and the boundary `mode`
     (a HIGHPASS_MODES code): a new array.  `return_times`: also a dict of the HIP-event split (FILTER_TIMES)."""
@@ -1133,7 +1139,7 @@ def stage_max_filter(a, mask, fill, size_y, size_x, mode=0, device_id=0, return_
     times = np.zeros(len(FILTER_TIMES))
     check(load().glh_stage_max_filter(device_id, _ptr(a), flag, nx, ny, _ptr(mask), int(bool(fill)), int(size_y), int(size_x),
                                       int(mode), _ptr(out), _ptr(times) if return_times else None))
-    return _filter_result(out, times, return_times)
+    return _timed(out, FILTER_TIMES, times, return_times)
 
 
 def stage_gaussian_filter(a, mask, fill, w0, w1, mode=0, device_id=0, return_times=False):
@@ -1144,7 +1150,7 @@ def stage_gaussian_filter(a, mask, fill, w0, w1, mode=0, device_id=0, return_tim
     times = np.zeros(len(FILTER_TIMES))
     check(load().glh_stage_gaussian_filter(device_id, _ptr(a), flag, nx, ny, _ptr(mask), int(bool(fill)), _ptr(w0), r0,
                                            _ptr(w1), r1, int(mode), _ptr(out), _ptr(times) if return_times else None))
-    return _filter_result(out, times, return_times)
+    return _timed(out, FILTER_TIMES, times, return_times)
 
 
 def stage_fill_crevasses(a, mask, fill, size_y, size_x, max_mode, w0, w1, gauss_mode, device_id=0, return_times=False):
@@ -1156,49 +1162,37 @@ def stage_fill_crevasses(a, mask, fill, size_y, size_x, max_mode, w0, w1, gauss_
     check(load().glh_stage_fill_crevasses(device_id, _ptr(a), flag, nx, ny, _ptr(mask), int(bool(fill)), int(size_y),
                                           int(size_x), int(max_mode), _ptr(w0), r0, _ptr(w1), r1, int(gauss_mode), _ptr(out),
                                           _ptr(times) if return_times else None))
-    return _filter_result(out, times, return_times)
+    return _timed(out, FILTER_TIMES, times, return_times)
 
 
-TERRAIN_F64, TERRAIN_F32 = 0, 1
+TERRAIN_F64, TERRAIN_F32 = F64, F32
+TR_TIMES = 5  # entries of times_ms that every terrain stage writes (csrc/glh_terrain.h), whatever it names of them
 GRADIENT_TIMES = ("upload_ms", "kernel_ms", "download_ms")
 HILLSHADE_TIMES = ("upload_ms", "stencil_ms", "reduce_ms", "normalise_ms", "download_ms")
 POLYGON_MASK_TIMES = ("upload_ms", "kernels_ms", "download_ms")
 
 
-def _terrain_array(z):
-    """(z, dtype flag, nx, ny) of the gradient and hillshade stages: `z` (ny, nx) float64 / float32; glimpse_amd.raster
-    checks and widens what the caller gave."""
-    if z.dtype not in (np.dtype(np.float64), np.dtype(np.float32)) or z.ndim != 2:
-        raise TypeError(f"a two-dimensional float64 or float32 array (got {z.dtype}, {z.ndim} dimensions)")
-    z = np.ascontiguousarray(z)
-    return z, TERRAIN_F32 if z.dtype == np.float32 else TERRAIN_F64, z.shape[1], z.shape[0]
-
-
-def _terrain_result(out, names, times, return_times):
-    return (out, dict(zip(names, (float(t) for t in times)))) if return_times else out
-
-
 def stage_gradient(z, d0, d1, device_id=0, return_times=False):
     """Raster.gradient (raster.py:1465-1474): (dzdx, dzdy) of `z` (ny, nx) with the signed cell sizes d0 (x) and d1 (y),
     each of z's dtype.  `return_times`: also a dict of the HIP-event split (GRADIENT_TIMES)."""
-    z, flag, nx, ny = _terrain_array(z)
+    z, flag, nx, ny = _float_array(z)
     dzdx, dzdy = np.empty_like(z), np.empty_like(z)
-    times = np.zeros(5)
+    times = np.zeros(max(len(GRADIENT_TIMES), TR_TIMES))
     check(load().glh_stage_gradient(device_id, _ptr(z), flag, nx, ny, float(d0), float(d1), _ptr(dzdx), _ptr(dzdy),
                                     _ptr(times) if return_times else None))
-    return _terrain_result((dzdx, dzdy), GRADIENT_TIMES, times, return_times)
+    return _timed((dzdx, dzdy), GRADIENT_TIMES, times, return_times)
 
 
 def stage_hillshade(z, d0, d1, vert_exag, direction, fraction, device_id=0, return_times=False):
     """matplotlib's LightSource.hillshade (Raster.hillshade, raster.py:1249-1264) of `z` (ny, nx): float64 (ny, nx).  d0,
     d1: the spacings of the gradient along x and y (dy already negated); `direction` (3,) towards the light."""
-    z, flag, nx, ny = _terrain_array(z)
+    z, flag, nx, ny = _float_array(z)
     direction = _arr(direction, np.float64, (3,))
     out = np.empty((ny, nx))
-    times = np.zeros(5)
+    times = np.zeros(max(len(HILLSHADE_TIMES), TR_TIMES))
     check(load().glh_stage_hillshade(device_id, _ptr(z), flag, nx, ny, float(d0), float(d1), float(vert_exag), _ptr(direction),
                                      float(fraction), _ptr(out), _ptr(times) if return_times else None))
-    return _terrain_result(out, HILLSHADE_TIMES, times, return_times)
+    return _timed(out, HILLSHADE_TIMES, times, return_times)
 
 
 def stage_polygon_mask(xy, ring_off, n_polygons, n_holes, nx, ny, device_id=0, return_times=False):
@@ -1207,7 +1201,7 @@ def stage_polygon_mask(xy, ring_off, n_polygons, n_holes, nx, ny, device_id=0, r
     ring_off = _arr(ring_off, np.int32, (int(n_polygons) + int(n_holes) + 1,))
     xy = _arr(xy, np.float64, (int(ring_off[-1]), 2))
     out = np.empty((int(ny), int(nx)), dtype=np.uint8)
-    times = np.zeros(5)
+    times = np.zeros(max(len(POLYGON_MASK_TIMES), TR_TIMES))
     check(load().glh_stage_polygon_mask(device_id, _ptr(xy), len(xy), _ptr(ring_off), int(n_polygons), int(n_holes), int(nx),
                                         int(ny), _ptr(out), _ptr(times) if return_times else None))
-    return _terrain_result(out.view(bool), POLYGON_MASK_TIMES, times, return_times)
+    return _timed(out.view(bool), POLYGON_MASK_TIMES, times, return_times)

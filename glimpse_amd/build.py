@@ -6,13 +6,11 @@ The shared library is written in-tree (glimpse_amd/lib/) so that it travels to t
 box with the repository snapshot.  -ffp-contract=off keeps float64 expressions
 bit-identical to NumPy's (no implicit FMA); the SSD kernel asks for FMA explicitly.
 
-The library is many translation units compiled in parallel: glimpse_hip.hip (the C ABI and the
-staged kernels), glh_viewshed.hip and glh_project_dem.hip (the terrain routines, each with rocPRIM's
-radix sort), glh_horizon.hip (Raster.horizon), glh_regrid.hip (Raster.sample(grid=True), resize,
-RasterInterpolant), glh_filters.hip (the maximum and Gaussian filters of Raster.fill_crevasses), glh_terrain.hip
-(Raster.gradient, Raster.hillshade, polygon masks) and one object per instantiation of the fused kernel (glh_point_inst.hip with
--DPT_*; the list is csrc/glh_point_variants.h).  Objects are cached in glimpse_amd/lib/obj/ and
-rebuilt when a source they include is newer.
+The library is many translation units compiled in parallel: the files of SOURCES (glimpse_hip.hip is the C ABI and the
+staged kernels; every glh_*.hip beside it is one device stage of Raster / Camera, described at its head) and one object
+per instantiation of the fused kernel (glh_point_inst.hip with -DPT_*; the list is csrc/glh_point_variants.h).  Objects are
+cached in glimpse_amd/lib/obj/ and rebuilt when their source, or a header it includes (read from its #include "..."
+lines, followed through the headers), is newer.
 """
 import os
 import re
@@ -23,36 +21,30 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SRC = os.path.join(CSRC, "glimpse_hip.hip")
 INST = os.path.join(CSRC, "glh_point_inst.hip")
 VARIANTS = os.path.join(CSRC, "glh_point_variants.h")
 LIBDIR = os.path.join(HERE, "lib")
 OBJDIR = os.path.join(LIBDIR, "obj")
 LIB = os.path.join(LIBDIR, "libglimpse_hip.so")
-HEADERS = [
-    os.path.join(CSRC, "glh_kernels.h"),
-    os.path.join(CSRC, "glh_point.h"),
-    os.path.join(CSRC, "glh_math.h"),
-    os.path.join(CSRC, "glh_median.h"),
-    VARIANTS,
-    os.path.join(os.path.dirname(HERE), "include", "glimpse_hip.h"),
-]
-VIEWSHED = os.path.join(CSRC, "glh_viewshed.hip")  # Raster.viewshed: its kernels and rocPRIM's radix sort
-VIEWSHED_HEADER = os.path.join(CSRC, "glh_viewshed.h")
-HORIZON = os.path.join(CSRC, "glh_horizon.hip")  # Raster.horizon: one workgroup per heading's line
-HORIZON_HEADER = os.path.join(CSRC, "glh_horizon.h")
-REGRID = os.path.join(CSRC, "glh_regrid.hip")  # Raster.sample(grid=True) / resize / RasterInterpolant: solves and evaluation
-REGRID_HEADER = os.path.join(CSRC, "glh_regrid.h")
-REGRID_HOST_HEADER = os.path.join(CSRC, "glh_regrid_host.h")  # its per-axis host arithmetic (also compiled by tests/hostcheck)
-PROJECT_DEM = os.path.join(CSRC, "glh_project_dem.hip")  # Camera.project_dem / rasterize: kernels and the radix sort
-PROJECT_DEM_HEADER = os.path.join(CSRC, "glh_project_dem.h")
-FILTERS = os.path.join(CSRC, "glh_filters.hip")  # maximum_filter / gaussian_filter / Raster.fill_crevasses
-FILTERS_HEADER = os.path.join(CSRC, "glh_filters.h")
-TERRAIN = os.path.join(CSRC, "glh_terrain.hip")  # Raster.gradient / hillshade / helpers.polygons_to_mask
-TERRAIN_HEADER = os.path.join(CSRC, "glh_terrain.h")
-HOST_HEADERS = [os.path.join(CSRC, "glh_host.h"), os.path.join(CSRC, "glh_comm.h"), VIEWSHED_HEADER, HORIZON_HEADER,
-                REGRID_HEADER, REGRID_HOST_HEADER, PROJECT_DEM_HEADER, FILTERS_HEADER, TERRAIN_HEADER]
-DEPS = [SRC, INST, VIEWSHED, HORIZON, REGRID, PROJECT_DEM, FILTERS, TERRAIN, *HEADERS, *HOST_HEADERS]
+# one object each, beside the fused kernel's instantiations; what each is for is at the head of the file
+SOURCES = ["glimpse_hip.hip", "glh_viewshed.hip", "glh_horizon.hip", "glh_regrid.hip", "glh_project_dem.hip",
+           "glh_filters.hip", "glh_terrain.hip"]
+
+
+def includes(path, seen=None):
+    """`path` and every file of the repository it includes with #include "...", directly or through another."""
+    seen = [] if seen is None else seen
+    path = os.path.normpath(path)
+    if path not in seen:
+        seen.append(path)
+        for name in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(path).read(), re.M):
+            includes(os.path.join(os.path.dirname(path), name), seen)
+    return seen
+
+
+# source -> itself and its headers: what its objects are rebuilt for
+TABLE = {src: includes(os.path.join(CSRC, src)) for src in [*SOURCES, os.path.basename(INST)]}
+DEPS = sorted({dep for deps in TABLE.values() for dep in deps})
 FLAGS = [
     "--offload-arch=gfx950",
     "-O3",
@@ -99,24 +91,13 @@ def up_to_date():
 def _jobs(extra, objdir=OBJDIR):
     """[(object, command, dependencies)]"""
     cc = hipcc()
-    jobs = [(os.path.join(objdir, "glimpse_hip.o"), [cc, *FLAGS, *extra, "-c", SRC], [SRC, *HEADERS, *HOST_HEADERS]),
-            (os.path.join(objdir, "glh_viewshed.o"), [cc, *FLAGS, *extra, "-c", VIEWSHED],
-             [VIEWSHED, VIEWSHED_HEADER, HEADERS[-1]]),
-            (os.path.join(objdir, "glh_horizon.o"), [cc, *FLAGS, *extra, "-c", HORIZON],
-             [HORIZON, HORIZON_HEADER, HEADERS[-1]]),
-            (os.path.join(objdir, "glh_regrid.o"), [cc, *FLAGS, *extra, "-c", REGRID],
-             [REGRID, REGRID_HEADER, REGRID_HOST_HEADER, HEADERS[-1]]),
-            (os.path.join(objdir, "glh_project_dem.o"), [cc, *FLAGS, *extra, "-c", PROJECT_DEM],
-             [PROJECT_DEM, PROJECT_DEM_HEADER, os.path.join(CSRC, "glh_math.h"), HEADERS[-1]]),
-            (os.path.join(objdir, "glh_filters.o"), [cc, *FLAGS, *extra, "-c", FILTERS],
-             [FILTERS, FILTERS_HEADER, os.path.join(CSRC, "glh_math.h"), HEADERS[-1]]),
-            (os.path.join(objdir, "glh_terrain.o"), [cc, *FLAGS, *extra, "-c", TERRAIN],
-             [TERRAIN, TERRAIN_HEADER, HEADERS[-1]])]
+    jobs = [(os.path.join(objdir, src[:-4] + ".o"), [cc, *FLAGS, *extra, "-c", os.path.join(CSRC, src)], TABLE[src])
+            for src in SOURCES]
     for tb, ppt, nobs, s, f, c in variants():
         obj = os.path.join(objdir, f"pt_{tb}_{ppt}_{nobs}_{s}{f}{c}.o")
         defs = [f"-DPT_TB={tb}", f"-DPT_PPT={ppt}", f"-DPT_NOBS={nobs}", f"-DPT_SURF={s}", f"-DPT_FAST={f}",
                 f"-DPT_CON={c}"]
-        jobs.append((obj, [cc, *FLAGS, *extra, *defs, "-c", INST], [INST, *HEADERS]))
+        jobs.append((obj, [cc, *FLAGS, *extra, *defs, "-c", INST], TABLE[os.path.basename(INST)]))
     return jobs
 
 

@@ -33,7 +33,7 @@ struct FiltersJob {
   double* times_ms;  // [FL_TIMES] or null
 };
 
-// Runs the job; a GLH_* status, with the message in err on failure.
-int filters_run(const FiltersJob& job, char* err, size_t err_cap);
+// Runs the job; a GLH_* status, with the message left for glh_last_error() on failure (glh_stage.h: fail).
+int filters_run(const FiltersJob& job);
 
 }  // namespace glh

@@ -32,6 +32,7 @@
 #include "../../include/glimpse_hip.h"
 #include "glh_math.h"
 #include "glh_filters.h"
+#include "glh_stage.h"
 
 namespace glh {
 namespace {
@@ -190,48 +191,6 @@ __global__ void __launch_bounds__(FL_TB) k_fl_gauss(FlGaussArgs p) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-struct Buf {
-  void* p = nullptr;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-struct Err {
-  char* msg;
-  size_t cap;
-  int fail(int code, const char* fmt, ...) const {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, cap, fmt, ap);
-    va_end(ap);
-    return code;
-  }
-};
-
-#define FL_HIP(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) return err.fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-#define FL_ALLOC(buf, bytes)                                                                                  \
-  do {                                                                                                        \
-    const size_t b_ = (bytes) ? (size_t)(bytes) : 1;                                                          \
-    hipError_t e_ = hipMalloc(&(buf).p, b_);                                                                  \
-    if (e_ != hipSuccess) {                                                                                   \
-      (void)hipGetLastError();                                                                                \
-      return err.fail(GLH_E_NOMEM, "filters: hipMalloc(%zu) failed: %s", b_, hipGetErrorString(e_));           \
-    }                                                                                                         \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[6] = {};
-  ~Events() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
 struct Pass {
   int axis;
   const double* w;  // device
@@ -240,72 +199,71 @@ struct Pass {
 
 }  // namespace
 
-int filters_run(const FiltersJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int filters_run(const FiltersJob& j) {
   const size_t n = (size_t)j.nx * j.ny, bytes = n * (j.f32 ? 4 : 8);
   const bool masked = j.mask != nullptr;
-  FL_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernels)
-  Events ev;
-  for (hipEvent_t& e : ev.e) FL_HIP(hipEventCreate(&e));
+  StageEvents<6> ev;
+  CHK(ev.create());
 
   // the Gaussian's passes: axis 0, then axis 1; with both axes skipped one pass with the weight 1 (x * 1.0 is x) still
   // divides and puts back, as the reference's gaussian_filter does around SciPy's copy
   static const double one = 1.0;
   const double* host_w[2] = {j.w0, j.w1};
   const int radius[2] = {j.r0, j.r1};
-  Buf da, dm, dmax, dxf, dxs, dout, dw[2], done;
+  DevBuf da, dm, dmax, dxf, dxs, dout, dw[2], done;
   Pass pass[2];
   int n_pass = 0;
-  FL_ALLOC(da, bytes);
-  if (masked) FL_ALLOC(dm, n);
-  FL_ALLOC(dout, bytes);
-  if (j.do_max && j.do_gauss) FL_ALLOC(dmax, bytes);
+  CHK(da.alloc(bytes));
+  if (masked) CHK(dm.alloc(n));
+  CHK(dout.alloc(bytes));
+  if (j.do_max && j.do_gauss) CHK(dmax.alloc(bytes));
   if (j.do_gauss) {
     for (int ax = 0; ax < 2; ++ax)
       if (host_w[ax]) {
-        FL_ALLOC(dw[ax], (size_t)(2 * radius[ax] + 1) * 8);
-        pass[n_pass++] = Pass{ax, static_cast<const double*>(dw[ax].p), radius[ax]};
+        CHK(dw[ax].alloc((size_t)(2 * radius[ax] + 1) * 8));
+        pass[n_pass++] = Pass{ax, dw[ax].as<const double>(), radius[ax]};
       }
     if (n_pass == 0) {
-      FL_ALLOC(done, 8);
-      pass[n_pass++] = Pass{1, static_cast<const double*>(done.p), 0};
+      CHK(done.alloc(8));
+      pass[n_pass++] = Pass{1, done.as<const double>(), 0};
     }
     if (n_pass == 2) {
-      FL_ALLOC(dxf, bytes);
-      if (masked) FL_ALLOC(dxs, bytes);
+      CHK(dxf.alloc(bytes));
+      if (masked) CHK(dxs.alloc(bytes));
     }
   }
 
-  FL_HIP(hipEventRecord(ev.e[0], s));
-  FL_HIP(hipMemcpy(da.p, j.a, bytes, hipMemcpyHostToDevice));
-  if (masked) FL_HIP(hipMemcpy(dm.p, j.mask, n, hipMemcpyHostToDevice));
+  CHK(ev.record(0, s));
+  HIPCHK(hipMemcpy(da.p, j.a, bytes, hipMemcpyHostToDevice));
+  if (masked) HIPCHK(hipMemcpy(dm.p, j.mask, n, hipMemcpyHostToDevice));
   for (int ax = 0; ax < 2; ++ax)
-    if (dw[ax].p) FL_HIP(hipMemcpy(dw[ax].p, host_w[ax], (size_t)(2 * radius[ax] + 1) * 8, hipMemcpyHostToDevice));
-  if (done.p) FL_HIP(hipMemcpy(done.p, &one, 8, hipMemcpyHostToDevice));
-  FL_HIP(hipEventRecord(ev.e[1], s));
+    if (dw[ax].p) HIPCHK(hipMemcpy(dw[ax].p, host_w[ax], (size_t)(2 * radius[ax] + 1) * 8, hipMemcpyHostToDevice));
+  if (done.p) HIPCHK(hipMemcpy(done.p, &one, 8, hipMemcpyHostToDevice));
+  CHK(ev.record(1, s));
 
   const void* cur = da.p;
   if (j.do_max) {
     void* dst = j.do_gauss ? dmax.p : dout.p;
     const int tiles_x = (j.nx + FL_TW - 1) / FL_TW, tiles_y = (j.ny + FL_TH - 1) / FL_TH;
-    const FlMaxArgs ma{da.p, static_cast<const uint8_t*>(dm.p), dst, j.nx, j.ny, j.size_y, j.size_x, j.max_mode, j.fill, tiles_x};
+    const FlMaxArgs ma{da.p, dm.as<const uint8_t>(), dst, j.nx, j.ny, j.size_y, j.size_x, j.max_mode, j.fill, tiles_x};
     const size_t lds = (size_t)(FL_TH + j.size_y - 1 + FL_TH) * (FL_TW + j.size_x - 1) * (j.f32 ? 4 : 8);
     const dim3 grid((unsigned)((size_t)tiles_x * tiles_y));
     if (j.f32)
       hipLaunchKernelGGL(k_fl_max<float>, grid, dim3(FL_TB), lds, s, ma);
     else
       hipLaunchKernelGGL(k_fl_max<double>, grid, dim3(FL_TB), lds, s, ma);
-    FL_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     cur = dst;
   }
-  FL_HIP(hipEventRecord(ev.e[2], s));
+  CHK(ev.record(2, s));
   int timed_axis[2] = {-1, -1};  // which event pair holds which axis
   const void* own = cur;         // the Gaussian's own input: what it puts back at excluded cells
   const void* cur_s = nullptr;
   for (int k = 0; k < n_pass; ++k) {
     const bool last = k == n_pass - 1;
-    const FlGaussArgs ga{cur, cur_s, static_cast<const uint8_t*>(dm.p), own, last ? dout.p : dxf.p, last ? nullptr : dxs.p,
+    const FlGaussArgs ga{cur, cur_s, dm.as<const uint8_t>(), own, last ? dout.p : dxf.p, last ? nullptr : dxs.p,
                          pass[k].w, pass[k].r, j.nx, j.ny, pass[k].axis, j.gauss_mode, k == 0, last, j.fill};
     const dim3 grid((unsigned)((n + FL_TB - 1) / FL_TB));
     const size_t lds = (size_t)(pass[k].r + 1) * 8;
@@ -320,25 +278,21 @@ int filters_run(const FiltersJob& j, char* errbuf, size_t errcap) {
       else
         hipLaunchKernelGGL((k_fl_gauss<double, false>), grid, dim3(FL_TB), lds, s, ga);
     }
-    FL_HIP(hipGetLastError());
+    HIPCHK(hipGetLastError());
     cur = dxf.p;
     cur_s = dxs.p;
     timed_axis[k] = pass[k].axis;
-    FL_HIP(hipEventRecord(ev.e[3 + k], s));
+    CHK(ev.record(3 + k, s));
   }
-  for (int k = n_pass; k < 2; ++k) FL_HIP(hipEventRecord(ev.e[3 + k], s));
-  FL_HIP(hipMemcpy(j.out, dout.p, bytes, hipMemcpyDeviceToHost));
-  FL_HIP(hipEventRecord(ev.e[5], s));
-  FL_HIP(hipEventSynchronize(ev.e[5]));
+  for (int k = n_pass; k < 2; ++k) CHK(ev.record(3 + k, s));
+  CHK(dout.down(j.out, bytes));
+  CHK(ev.record(5, s));
+  HIPCHK(hipEventSynchronize(ev.e[5]));
   if (j.times_ms) {
-    float f[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int k = 0; k < 5; ++k) (void)hipEventElapsedTime(&f[k], ev.e[k], ev.e[k + 1]);
-    for (int k = 0; k < FL_TIMES; ++k) j.times_ms[k] = 0.0;
-    j.times_ms[0] = f[0];
-    j.times_ms[1] = f[1];
+    ev.report(j.times_ms, 2, FL_TIMES);  // upload, max; then the Gaussian's spans by axis, and the download
     for (int k = 0; k < 2; ++k)
-      if (timed_axis[k] >= 0) j.times_ms[2 + timed_axis[k]] += f[2 + k];
-    j.times_ms[4] = f[4];
+      if (timed_axis[k] >= 0) j.times_ms[2 + timed_axis[k]] += ev.ms(2 + k, 3 + k);
+    j.times_ms[4] = ev.ms(4, 5);
   }
   return GLH_OK;
 }

@@ -25,7 +25,7 @@ struct HorizonJob {
   double* times_ms;  // [HZ_TIMES] or null
 };
 
-// Runs the job; a GLH_* status, with the message in err on failure.
-int horizon_run(const HorizonJob& job, char* err, size_t err_cap);
+// Runs the job; a GLH_* status, with the message left for glh_last_error() on failure (glh_stage.h: fail).
+int horizon_run(const HorizonJob& job);
 
 }  // namespace glh

@@ -28,6 +28,7 @@
 
 #include "../../include/glimpse_hip.h"
 #include "glh_horizon.h"
+#include "glh_stage.h"
 
 namespace glh {
 namespace {
@@ -157,56 +158,9 @@ __global__ void __launch_bounds__(TB) k_horizon(HzArgs a) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-struct Buf {
-  void* p = nullptr;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-struct Err {
-  char* msg;
-  size_t cap;
-  int fail(int code, const char* fmt, ...) const {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, cap, fmt, ap);
-    va_end(ap);
-    return code;
-  }
-};
-
-#define HZ_HIP(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) return err.fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-#define HZ_ALLOC(buf, bytes)                                                                                  \
-  do {                                                                                                        \
-    const size_t b_ = (bytes);                                                                                \
-    hipError_t e_ = hipMalloc(&(buf).p, b_);                                                                  \
-    if (e_ != hipSuccess) {                                                                                   \
-      (void)hipGetLastError();                                                                                \
-      return err.fail(GLH_E_NOMEM, "horizon: hipMalloc(%zu) failed: %s", b_, hipGetErrorString(e_));           \
-    }                                                                                                         \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[4] = {};
-  ~Events() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
 }  // namespace
 
-int horizon_run(const HorizonJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int horizon_run(const HorizonJob& j) {
   const size_t cells = (size_t)j.nx * j.ny, lines = (size_t)j.m * j.n;
   // the longest line of the job chooses the workgroup: a line has max(|dx|, |dy|) cells after its start
   int longest = 0;
@@ -217,41 +171,37 @@ int horizon_run(const HorizonJob& j, char* errbuf, size_t errcap) {
       const int len = ax > ay ? ax : ay;
       if (len > longest) longest = len;
     }
-  HZ_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernel)
-  Events ev;
-  for (hipEvent_t& e : ev.e) HZ_HIP(hipEventCreate(&e));
+  StageEvents<HZ_TIMES + 1> ev;
+  CHK(ev.create());
   const size_t zbytes = cells * (j.f32 ? 4 : 8);
-  Buf dz, dorg, dstart, dend, dcell, dout;
-  HZ_ALLOC(dz, zbytes);
-  HZ_ALLOC(dorg, (size_t)j.m * 24);
-  HZ_ALLOC(dstart, (size_t)j.m * 8);
-  HZ_ALLOC(dend, lines * 8);
-  HZ_ALLOC(dcell, lines * 8);
-  HZ_ALLOC(dout, lines * 8);
-  HZ_HIP(hipEventRecord(ev.e[0], s));
-  HZ_HIP(hipMemcpy(dz.p, j.z, zbytes, hipMemcpyHostToDevice));
-  HZ_HIP(hipMemcpy(dorg.p, j.origins, (size_t)j.m * 24, hipMemcpyHostToDevice));
-  HZ_HIP(hipMemcpy(dstart.p, j.starts, (size_t)j.m * 8, hipMemcpyHostToDevice));
-  HZ_HIP(hipMemcpy(dend.p, j.ends, lines * 8, hipMemcpyHostToDevice));
-  HZ_HIP(hipEventRecord(ev.e[1], s));
+  DevBuf dz, dorg, dstart, dend, dcell, dout;
+  CHK(dz.alloc(zbytes));
+  CHK(dorg.alloc((size_t)j.m * 24));
+  CHK(dstart.alloc((size_t)j.m * 8));
+  CHK(dend.alloc(lines * 8));
+  CHK(dcell.alloc(lines * 8));
+  CHK(dout.alloc(lines * 8));
+  CHK(ev.record(0, s));
+  HIPCHK(hipMemcpy(dz.p, j.z, zbytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dorg.p, j.origins, (size_t)j.m * 24, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dstart.p, j.starts, (size_t)j.m * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dend.p, j.ends, lines * 8, hipMemcpyHostToDevice));
+  CHK(ev.record(1, s));
   const HzArgs a{dz.p, j.nx, j.ny, j.f32, j.correction, j.n, j.xlim0, j.ylim0, j.d0, j.d1, j.refraction - 1.0, 2.0 * j.radius,
                  dorg.as<double>(), dstart.as<int32_t>(), dend.as<int32_t>(), dcell.as<int32_t>(), dout.as<double>()};
   if (longest <= HZ_SHORT)
     hipLaunchKernelGGL(k_horizon<HZ_WAVE>, dim3((unsigned)lines), dim3(HZ_WAVE), 0, s, a);
   else
     hipLaunchKernelGGL(k_horizon<4 * HZ_WAVE>, dim3((unsigned)lines), dim3(4 * HZ_WAVE), 0, s, a);
-  HZ_HIP(hipGetLastError());
-  HZ_HIP(hipEventRecord(ev.e[2], s));
-  HZ_HIP(hipMemcpy(j.cell, dcell.p, lines * 8, hipMemcpyDeviceToHost));
-  HZ_HIP(hipMemcpy(j.dz, dout.p, lines * 8, hipMemcpyDeviceToHost));
-  HZ_HIP(hipEventRecord(ev.e[3], s));
-  HZ_HIP(hipEventSynchronize(ev.e[3]));
-  if (j.times_ms)
-    for (int k = 0; k < HZ_TIMES; ++k) {
-      float f = 0.f;
-      j.times_ms[k] = hipEventElapsedTime(&f, ev.e[k], ev.e[k + 1]) == hipSuccess ? (double)f : 0.0;
-    }
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(2, s));
+  CHK(dcell.down(j.cell, lines * 8));
+  CHK(dout.down(j.dz, lines * 8));
+  CHK(ev.record(3, s));
+  HIPCHK(hipEventSynchronize(ev.e[3]));
+  ev.report(j.times_ms, HZ_TIMES, HZ_TIMES);
   return GLH_OK;
 }
 

@@ -49,8 +49,8 @@ struct RasterizeJob {
 
 // Cells of every tile together (a cell counts once per tile it belongs to); what the device indexes with 32 bits.
 int64_t project_dem_memberships(const ProjectDemJob& job);
-// Each runs its job; a GLH_* status, with the message in err on failure.
-int project_dem_run(const ProjectDemJob& job, char* err, size_t err_cap);
-int rasterize_run(const RasterizeJob& job, char* err, size_t err_cap);
+// Each runs its job; a GLH_* status, with the message left for glh_last_error() on failure (glh_stage.h: fail).
+int project_dem_run(const ProjectDemJob& job);
+int rasterize_run(const RasterizeJob& job);
 
 }  // namespace glh

@@ -32,6 +32,7 @@
 #include "../../include/glimpse_hip.h"
 #include "glh_math.h"
 #include "glh_project_dem.h"
+#include "glh_stage.h"
 
 namespace glh {
 namespace {
@@ -208,98 +209,44 @@ __global__ void __launch_bounds__(PD_TB) k_pd_reduce(PdReduceArgs a) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-struct Buf {
-  void* p = nullptr;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-struct Err {
-  char* msg;
-  size_t cap;
-  int fail(int code, const char* fmt, ...) const {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, cap, fmt, ap);
-    va_end(ap);
-    return code;
-  }
-};
-
-#define PD_HIP(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) return err.fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-#define PD_ALLOC(buf, bytes)                                                                                  \
-  do {                                                                                                        \
-    const size_t b_ = (bytes) ? (size_t)(bytes) : 1;                                                          \
-    hipError_t e_ = hipMalloc(&(buf).p, b_);                                                                  \
-    if (e_ != hipSuccess) {                                                                                   \
-      (void)hipGetLastError();                                                                                \
-      return err.fail(GLH_E_NOMEM, "project_dem: hipMalloc(%zu) failed: %s", b_, hipGetErrorString(e_));       \
-    }                                                                                                         \
-  } while (0)
-#define PD_UPLOAD(buf, src, bytes)                                                                            \
-  do {                                                                                                        \
-    PD_ALLOC(buf, bytes);                                                                                     \
-    PD_HIP(hipMemcpy((buf).p, src, bytes, hipMemcpyHostToDevice));                                            \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[6] = {};
-  ~Events() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
 unsigned blocks_for(int64_t n) { return (unsigned)((n + PD_TB - 1) / PD_TB); }
 
 // Stages 2 (from the sort on) and 3, the download and the times: what project_dem and rasterize share.  key [n] holds a
 // pixel or npix, idx [n] the items; ev.e[0 .. 2] are recorded (upload began, upload done, keys done).
-int order_reduce_download(const Err& err, hipStream_t s, Events& ev, uint32_t* key, uint32_t* idx, uint32_t n,
+int order_reduce_download(hipStream_t s, StageEvents<6>& ev, uint32_t* key, uint32_t* idx, uint32_t n,
                           uint32_t npix, PdReduceArgs ra, double* out, double* times_ms, double items, const uint32_t* kept) {
-  Buf ks, order, run_start, run_end, dout, temp;
-  PD_ALLOC(ks, (size_t)n * 4);
-  PD_ALLOC(order, (size_t)n * 4);
-  PD_ALLOC(run_start, (size_t)npix * 4);
-  PD_ALLOC(run_end, (size_t)npix * 4);
-  PD_ALLOC(dout, (size_t)ra.total * 8);
+  DevBuf ks, order, run_start, run_end, dout, temp;
+  CHK(ks.alloc((size_t)n * 4));
+  CHK(order.alloc((size_t)n * 4));
+  CHK(run_start.alloc((size_t)npix * 4));
+  CHK(run_end.alloc((size_t)npix * 4));
+  CHK(dout.alloc((size_t)ra.total * 8));
   int bits = 1;
   while ((1ull << bits) <= npix) ++bits;  // (npix itself, "no pixel", sorts last)
   size_t tbytes = 0;
-  PD_HIP(rocprim::radix_sort_pairs(nullptr, tbytes, key, ks.as<uint32_t>(), idx, order.as<uint32_t>(), n, 0, bits, s));
-  PD_ALLOC(temp, tbytes);
-  PD_HIP(rocprim::radix_sort_pairs(temp.p, tbytes, key, ks.as<uint32_t>(), idx, order.as<uint32_t>(), n, 0, bits, s));
-  PD_HIP(hipMemsetAsync(run_start.p, 0, (size_t)npix * 4, s));
-  PD_HIP(hipMemsetAsync(run_end.p, 0, (size_t)npix * 4, s));
+  HIPCHK(rocprim::radix_sort_pairs(nullptr, tbytes, key, ks.as<uint32_t>(), idx, order.as<uint32_t>(), n, 0, bits, s));
+  CHK(temp.alloc(tbytes));
+  HIPCHK(rocprim::radix_sort_pairs(temp.p, tbytes, key, ks.as<uint32_t>(), idx, order.as<uint32_t>(), n, 0, bits, s));
+  HIPCHK(hipMemsetAsync(run_start.p, 0, (size_t)npix * 4, s));
+  HIPCHK(hipMemsetAsync(run_end.p, 0, (size_t)npix * 4, s));
   hipLaunchKernelGGL(k_pd_runs, dim3(blocks_for(n)), dim3(PD_TB), 0, s, ks.as<uint32_t>(), n, npix,
                      run_start.as<uint32_t>(), run_end.as<uint32_t>());
-  PD_HIP(hipGetLastError());
-  PD_HIP(hipEventRecord(ev.e[3], s));
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(3, s));
   ra.run_start = run_start.as<uint32_t>();
   ra.run_end = run_end.as<uint32_t>();
   ra.order = order.as<uint32_t>();
   ra.out = dout.as<double>();
   hipLaunchKernelGGL(k_pd_reduce, dim3(blocks_for(ra.total)), dim3(PD_TB), 0, s, ra);
-  PD_HIP(hipGetLastError());
-  PD_HIP(hipEventRecord(ev.e[4], s));
-  PD_HIP(hipMemcpy(out, dout.p, (size_t)ra.total * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(4, s));
+  CHK(dout.down(out, (size_t)ra.total * 8));
   uint32_t h_kept = n;
-  if (kept) PD_HIP(hipMemcpy(&h_kept, kept, 4, hipMemcpyDeviceToHost));
-  PD_HIP(hipEventRecord(ev.e[5], s));
-  PD_HIP(hipEventSynchronize(ev.e[5]));
+  if (kept) HIPCHK(hipMemcpy(&h_kept, kept, 4, hipMemcpyDeviceToHost));
+  CHK(ev.record(5, s));
+  HIPCHK(hipEventSynchronize(ev.e[5]));
   if (times_ms) {
-    for (int k = 0; k < 5; ++k) {
-      float f = 0.f;
-      times_ms[k] = hipEventElapsedTime(&f, ev.e[k], ev.e[k + 1]) == hipSuccess ? (double)f : 0.0;
-    }
+    ev.report(times_ms, 5, 5);
     times_ms[5] = items;
     times_ms[6] = (double)h_kept;
     times_ms[7] = (double)tbytes;
@@ -329,8 +276,7 @@ int64_t project_dem_memberships(const ProjectDemJob& j) {
   return sx * sy;
 }
 
-int project_dem_run(const ProjectDemJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int project_dem_run(const ProjectDemJob& j) {
   std::vector<int32_t> col_slice, row_slice, xt, yt;
   lay_out(j.tx, col_slice, xt);
   lay_out(j.ty, row_slice, yt);
@@ -341,41 +287,41 @@ int project_dem_run(const ProjectDemJob& j, char* errbuf, size_t errcap) {
   const int nl = j.layers + (j.return_depth ? 1 : 0);
   static const size_t v_size[] = {8, 4, 1, 2};  // GLH_PD_F64, _F32, _U8, _U16
 
-  PD_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernels)
-  Events ev;
-  for (hipEvent_t& e : ev.e) PD_HIP(hipEventCreate(&e));
-  Buf dz, dmask, dvals, dxc, dyc, dcs, drs, dxt, dyt, key, idx, cell, depth, winner, kept;
-  PD_HIP(hipEventRecord(ev.e[0], s));
-  PD_UPLOAD(dz, j.z, ncell * (j.z_f32 ? 4 : 8));
-  if (j.mask) PD_UPLOAD(dmask, j.mask, ncell);
-  if (j.layers) PD_UPLOAD(dvals, j.values, ncell * j.layers * v_size[j.v_dtype]);
-  PD_UPLOAD(dxc, j.tx.coords, (size_t)SX * 8);
-  PD_UPLOAD(dyc, j.ty.coords, (size_t)SY * 8);
-  PD_UPLOAD(dcs, col_slice.data(), (size_t)SX * 4);
-  PD_UPLOAD(drs, row_slice.data(), (size_t)SY * 4);
-  PD_UPLOAD(dxt, xt.data(), xt.size() * 4);
-  PD_UPLOAD(dyt, yt.data(), yt.size() * 4);
-  PD_ALLOC(key, (size_t)M * 4);
-  PD_ALLOC(idx, (size_t)M * 4);
-  PD_ALLOC(cell, (size_t)M * 4);
-  if (j.return_depth) PD_ALLOC(depth, (size_t)M * 8);
-  PD_ALLOC(winner, (size_t)npix * 4);
-  PD_ALLOC(kept, 4);
-  PD_HIP(hipEventRecord(ev.e[1], s));
+  StageEvents<6> ev;
+  CHK(ev.create());
+  DevBuf dz, dmask, dvals, dxc, dyc, dcs, drs, dxt, dyt, key, idx, cell, depth, winner, kept;
+  CHK(ev.record(0, s));
+  CHK(dz.up(j.z, ncell * (j.z_f32 ? 4 : 8)));
+  if (j.mask) CHK(dmask.up(j.mask, ncell));
+  if (j.layers) CHK(dvals.up(j.values, ncell * j.layers * v_size[j.v_dtype]));
+  CHK(dxc.up(j.tx.coords, (size_t)SX * 8));
+  CHK(dyc.up(j.ty.coords, (size_t)SY * 8));
+  CHK(dcs.up(col_slice.data(), (size_t)SX * 4));
+  CHK(drs.up(row_slice.data(), (size_t)SY * 4));
+  CHK(dxt.up(xt.data(), xt.size() * 4));
+  CHK(dyt.up(yt.data(), yt.size() * 4));
+  CHK(key.alloc((size_t)M * 4));
+  CHK(idx.alloc((size_t)M * 4));
+  CHK(cell.alloc((size_t)M * 4));
+  if (j.return_depth) CHK(depth.alloc((size_t)M * 8));
+  CHK(winner.alloc((size_t)npix * 4));
+  CHK(kept.alloc(4));
+  CHK(ev.record(1, s));
 
   const PdGeom g{dcs.as<int32_t>(), drs.as<int32_t>(), dxt.as<int32_t>(), dyt.as<int32_t>(), SX, SY, j.tx.n};
-  PD_HIP(hipMemsetAsync(winner.p, 0, (size_t)npix * 4, s));
-  PD_HIP(hipMemsetAsync(kept.p, 0, 4, s));
+  HIPCHK(hipMemsetAsync(winner.p, 0, (size_t)npix * 4, s));
+  HIPCHK(hipMemsetAsync(kept.p, 0, 4, s));
   PdProjectArgs pa{*j.cam, cam_flags(*j.cam), j.width, j.height, g, dxc.as<double>(), dyc.as<double>(), dz.p, j.z_f32, j.nx,
                    dmask.as<uint8_t>(), key.as<uint32_t>(), cell.as<uint32_t>(), depth.as<double>(), winner.as<uint32_t>(),
                    npix};
   hipLaunchKernelGGL(k_pd_project, dim3(blocks_for(M)), dim3(PD_TB), 0, s, pa);
-  PD_HIP(hipGetLastError());
-  PD_HIP(hipEventRecord(ev.e[2], s));
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(2, s));
   hipLaunchKernelGGL(k_pd_keep_winners, dim3(blocks_for(M)), dim3(PD_TB), 0, s, g, j.nx, key.as<uint32_t>(),
                      winner.as<uint32_t>(), npix, idx.as<uint32_t>(), kept.as<uint32_t>());
-  PD_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
 
   PdReduceArgs ra{};
   ra.cell = cell.as<uint32_t>();
@@ -385,33 +331,32 @@ int project_dem_run(const ProjectDemJob& j, char* errbuf, size_t errcap) {
   ra.depth = depth.as<double>();
   ra.nl = nl;
   ra.total = (int64_t)npix * nl;
-  return order_reduce_download(err, s, ev, key.as<uint32_t>(), idx.as<uint32_t>(), (uint32_t)M, npix, ra, j.out, j.times_ms,
+  return order_reduce_download(s, ev, key.as<uint32_t>(), idx.as<uint32_t>(), (uint32_t)M, npix, ra, j.out, j.times_ms,
                                (double)M, kept.as<uint32_t>());
 }
 
-int rasterize_run(const RasterizeJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int rasterize_run(const RasterizeJob& j) {
   const uint32_t n = (uint32_t)j.n, npix = (uint32_t)j.n_pixels;
-  PD_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;
-  Events ev;
-  for (hipEvent_t& e : ev.e) PD_HIP(hipEventCreate(&e));
-  Buf key, idx, dvals;
-  PD_HIP(hipEventRecord(ev.e[0], s));
-  PD_UPLOAD(key, j.keys, (size_t)n * 4);  // (checked to lie in [0, n_pixels): the bits of a uint32 pixel)
-  PD_UPLOAD(dvals, j.values, (size_t)n * j.layers * 8);
-  PD_ALLOC(idx, (size_t)n * 4);
-  PD_HIP(hipEventRecord(ev.e[1], s));
+  StageEvents<6> ev;
+  CHK(ev.create());
+  DevBuf key, idx, dvals;
+  CHK(ev.record(0, s));
+  CHK(key.up(j.keys, (size_t)n * 4));  // (checked to lie in [0, n_pixels): the bits of a uint32 pixel)
+  CHK(dvals.up(j.values, (size_t)n * j.layers * 8));
+  CHK(idx.alloc((size_t)n * 4));
+  CHK(ev.record(1, s));
   hipLaunchKernelGGL(k_pd_iota, dim3(blocks_for(n)), dim3(PD_TB), 0, s, idx.as<uint32_t>(), n);
-  PD_HIP(hipGetLastError());
-  PD_HIP(hipEventRecord(ev.e[2], s));
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(2, s));
   PdReduceArgs ra{};
   ra.values = dvals.p;
   ra.v_dtype = GLH_PD_F64;
   ra.layers = j.layers;
   ra.nl = j.layers;
   ra.total = (int64_t)npix * j.layers;
-  return order_reduce_download(err, s, ev, key.as<uint32_t>(), idx.as<uint32_t>(), n, npix, ra, j.out, j.times_ms, (double)n,
+  return order_reduce_download(s, ev, key.as<uint32_t>(), idx.as<uint32_t>(), n, npix, ra, j.out, j.times_ms, (double)n,
                                nullptr);
 }
 

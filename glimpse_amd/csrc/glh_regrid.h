@@ -75,9 +75,9 @@ int regrid_basis(const double* t, int n, int k, double x, double* h);
 // a pivot is 0 (neither happens for sites inside the box).
 bool regrid_factor(const double* x, int n, const double* t, int k, std::vector<double>& lu);
 
-// Run the jobs; a GLH_* status, with the message in err on failure.
-int regrid_run(const RegridJob& job, char* err, size_t err_cap);
-int zoom_run(const ZoomJob& job, char* err, size_t err_cap);
-int interpolate_run(const InterpolateJob& job, char* err, size_t err_cap);
+// Run the jobs; a GLH_* status, with the message left for glh_last_error() on failure (glh_stage.h: fail).
+int regrid_run(const RegridJob& job);
+int zoom_run(const ZoomJob& job);
+int interpolate_run(const InterpolateJob& job);
 
 }  // namespace glh

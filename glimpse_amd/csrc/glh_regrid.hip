@@ -34,6 +34,7 @@
 
 #include "../../include/glimpse_hip.h"
 #include "glh_regrid.h"
+#include "glh_stage.h"
 #include "glh_regrid_host.h"
 
 namespace glh {
@@ -256,66 +257,6 @@ __global__ void __launch_bounds__(256) k_blend(const double* __restrict__ m0, co
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-struct Buf {
-  void* p = nullptr;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-struct Err {
-  char* msg;
-  size_t cap;
-  int fail(int code, const char* fmt, ...) const {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, cap, fmt, ap);
-    va_end(ap);
-    return code;
-  }
-};
-
-#define RG_HIP(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) return err.fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-#define RG_ALLOC(buf, bytes)                                                                                  \
-  do {                                                                                                        \
-    const size_t b_ = (bytes);                                                                                \
-    hipError_t e_ = hipMalloc(&(buf).p, b_ ? b_ : 8);                                                         \
-    if (e_ != hipSuccess) {                                                                                   \
-      (void)hipGetLastError();                                                                                \
-      return err.fail(GLH_E_NOMEM, "regrid: hipMalloc(%zu) failed: %s", b_, hipGetErrorString(e_));            \
-    }                                                                                                         \
-  } while (0)
-#define RG_UPLOAD(buf, src, bytes)                                                                            \
-  do {                                                                                                        \
-    RG_ALLOC(buf, bytes);                                                                                     \
-    RG_HIP(hipMemcpy((buf).p, (src), (bytes), hipMemcpyHostToDevice));                                        \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[RG_TIMES + 1] = {};
-  ~Events() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
-int report_times(const Events& ev, double* times_ms) {
-  if (times_ms)
-    for (int k = 0; k < RG_TIMES; ++k) {
-      float f = 0.f;
-      times_ms[k] = hipEventElapsedTime(&f, ev.e[k], ev.e[k + 1]) == hipSuccess ? (double)f : 0.0;
-    }
-  return GLH_OK;
-}
-
 // What the host prepares for one axis.
 struct AxisPlan {
   int n = 0, k = 0, m = 0;
@@ -357,24 +298,24 @@ void launch_rows(double* w, int nx, int ny, const double* lu, hipStream_t s) {
 // null stream; e_solve / e_eval are recorded before the solve and before the evaluation when given.  The device buffers
 // live until this returns (hipFree waits for the kernels).
 int regrid_on_device(const RegridSource& src, const double* xo, int mx, const double* yo, int my, double* d_out,
-                     hipEvent_t e_solve, hipEvent_t e_eval, const Err& err) {
+                     hipEvent_t e_solve, hipEvent_t e_eval) {
   hipStream_t s = nullptr;
   AxisPlan px, py;
   if (!plan_axis(src.gx, src.nx, src.xmin, src.xmax, src.kx, xo, mx, px) ||
       !plan_axis(src.gy, src.ny, src.ymin, src.ymax, src.ky, yo, my, py))
-    return err.fail(GLH_E_INVALID, "regrid: the collocation matrix of the cell centres could not be factored within its band "
-                                   "(are the centres inside the box, half a cell from its limits?)");
+    return fail(GLH_E_INVALID, "regrid: the collocation matrix of the cell centres could not be factored within its band "
+                               "(are the centres inside the box, half a cell from its limits?)");
   const size_t cells = (size_t)src.nx * src.ny;
-  Buf dc, dnan, dlux, dluy, dlx, dly, dhx, dhy;
-  RG_UPLOAD(dc, src.z, cells * 8);
-  if (src.nan) RG_UPLOAD(dnan, src.nan, cells);
-  if (!px.closed) RG_UPLOAD(dlux, px.lu.data(), px.lu.size() * 8);
-  if (!py.closed) RG_UPLOAD(dluy, py.lu.data(), py.lu.size() * 8);
-  RG_UPLOAD(dlx, px.l.data(), (size_t)mx * 4);
-  RG_UPLOAD(dly, py.l.data(), (size_t)my * 4);
-  RG_UPLOAD(dhx, px.h.data(), px.h.size() * 8);
-  RG_UPLOAD(dhy, py.h.data(), py.h.size() * 8);
-  if (e_solve) RG_HIP(hipEventRecord(e_solve, s));
+  DevBuf dc, dnan, dlux, dluy, dlx, dly, dhx, dhy;
+  CHK(dc.up(src.z, cells * 8));
+  if (src.nan) CHK(dnan.up(src.nan, cells));
+  if (!px.closed) CHK(dlux.up(px.lu.data(), px.lu.size() * 8));
+  if (!py.closed) CHK(dluy.up(py.lu.data(), py.lu.size() * 8));
+  CHK(dlx.up(px.l.data(), (size_t)mx * 4));
+  CHK(dly.up(py.l.data(), (size_t)my * 4));
+  CHK(dhx.up(px.h.data(), px.h.size() * 8));
+  CHK(dhy.up(py.h.data(), py.h.size() * 8));
+  if (e_solve) HIPCHK(hipEventRecord(e_solve, s));
   double* w = dc.as<double>();
   if (py.closed) {
     hipLaunchKernelGGL(k_ends_cols, dim3((unsigned)((src.nx + RG_WAVE - 1) / RG_WAVE)), dim3(RG_WAVE), 0, s, w, src.nx, src.ny,
@@ -389,7 +330,7 @@ int regrid_on_device(const RegridSource& src, const double* xo, int mx, const do
       default: launch_cols<5>(w, src.nx, src.ny, lu, s); break;
     }
   }
-  RG_HIP(hipGetLastError());
+  HIPCHK(hipGetLastError());
   if (px.closed) {
     hipLaunchKernelGGL(k_ends_rows, dim3((unsigned)((src.ny + RG_WAVE - 1) / RG_WAVE)), dim3(RG_WAVE), 0, s, w, src.nx, src.ny,
                        px.ends);
@@ -403,106 +344,99 @@ int regrid_on_device(const RegridSource& src, const double* xo, int mx, const do
       default: launch_rows<5>(w, src.nx, src.ny, lu, s); break;
     }
   }
-  RG_HIP(hipGetLastError());
-  if (e_eval) RG_HIP(hipEventRecord(e_eval, s));
+  HIPCHK(hipGetLastError());
+  if (e_eval) HIPCHK(hipEventRecord(e_eval, s));
   const RgEval a{w,  dnan.as<uint8_t>(), src.nx, src.ny, src.kx, src.ky, dlx.as<int32_t>(), dhx.as<double>(),
                  dly.as<int32_t>(), dhy.as<double>(), mx, my, src.use_zmin, src.zmin, src.flip_x, src.flip_y, d_out};
   const size_t outs = (size_t)mx * my;
   hipLaunchKernelGGL(k_eval, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, a);
-  RG_HIP(hipGetLastError());
-  RG_HIP(hipStreamSynchronize(s));
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(s));
   return GLH_OK;
 }
 
 }  // namespace
 
-int regrid_run(const RegridJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
-  RG_HIP(hipSetDevice(j.device));
+int regrid_run(const RegridJob& j) {
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;
-  Events ev;
-  for (hipEvent_t& e : ev.e) RG_HIP(hipEventCreate(&e));
+  StageEvents<RG_TIMES + 1> ev;
+  CHK(ev.create());
   const size_t outs = (size_t)j.mx * j.my;
-  Buf dout;
-  RG_ALLOC(dout, outs * 8);
-  RG_HIP(hipEventRecord(ev.e[0], s));
-  const int rc = regrid_on_device(j.src, j.xo, j.mx, j.yo, j.my, dout.as<double>(), ev.e[1], ev.e[2], err);
-  if (rc != GLH_OK) return rc;
-  RG_HIP(hipEventRecord(ev.e[3], s));
-  RG_HIP(hipMemcpy(j.out, dout.p, outs * 8, hipMemcpyDeviceToHost));
-  RG_HIP(hipEventRecord(ev.e[4], s));
-  RG_HIP(hipEventSynchronize(ev.e[4]));
-  return report_times(ev, j.times_ms);
+  DevBuf dout;
+  CHK(dout.alloc(outs * 8));
+  CHK(ev.record(0, s));
+  CHK(regrid_on_device(j.src, j.xo, j.mx, j.yo, j.my, dout.as<double>(), ev.e[1], ev.e[2]));
+  CHK(ev.record(3, s));
+  CHK(dout.down(j.out, outs * 8));
+  CHK(ev.record(4, s));
+  HIPCHK(hipEventSynchronize(ev.e[4]));
+  ev.report(j.times_ms, RG_TIMES, RG_TIMES);
+  return GLH_OK;
 }
 
-int zoom_run(const ZoomJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
-  RG_HIP(hipSetDevice(j.device));
+int zoom_run(const ZoomJob& j) {
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;
-  Events ev;
-  for (hipEvent_t& e : ev.e) RG_HIP(hipEventCreate(&e));
+  StageEvents<RG_TIMES + 1> ev;
+  CHK(ev.create());
   const size_t cells = (size_t)j.nx * j.ny, outs = (size_t)j.mx * j.my;
-  Buf da, dout;
-  RG_ALLOC(dout, outs * 8);
-  RG_HIP(hipEventRecord(ev.e[0], s));
-  RG_UPLOAD(da, j.a, cells * 8);
-  RG_HIP(hipEventRecord(ev.e[1], s));
-  RG_HIP(hipEventRecord(ev.e[2], s));  // (no solve)
+  DevBuf da, dout;
+  CHK(dout.alloc(outs * 8));
+  CHK(ev.record(0, s));
+  CHK(da.up(j.a, cells * 8));
+  CHK(ev.record(1, s));
+  CHK(ev.record(2, s));  // (no solve)
   const double sx = j.mx > 1 ? (double)(j.nx - 1) / (double)(j.mx - 1) : 0.0;
   const double sy = j.my > 1 ? (double)(j.ny - 1) / (double)(j.my - 1) : 0.0;
   hipLaunchKernelGGL(k_zoom_linear, dim3((unsigned)((outs + 255) / 256)), dim3(256), 0, s, da.as<double>(), j.nx, j.ny, j.mx,
                      j.my, sx, sy, dout.as<double>());
-  RG_HIP(hipGetLastError());
-  RG_HIP(hipEventRecord(ev.e[3], s));
-  RG_HIP(hipMemcpy(j.out, dout.p, outs * 8, hipMemcpyDeviceToHost));
-  RG_HIP(hipEventRecord(ev.e[4], s));
-  RG_HIP(hipEventSynchronize(ev.e[4]));
-  return report_times(ev, j.times_ms);
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(3, s));
+  CHK(dout.down(j.out, outs * 8));
+  CHK(ev.record(4, s));
+  HIPCHK(hipEventSynchronize(ev.e[4]));
+  ev.report(j.times_ms, RG_TIMES, RG_TIMES);
+  return GLH_OK;
 }
 
-int interpolate_run(const InterpolateJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
-  RG_HIP(hipSetDevice(j.device));
+int interpolate_run(const InterpolateJob& j) {
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;
-  Events ev;
-  for (hipEvent_t& e : ev.e) RG_HIP(hipEventCreate(&e));
+  StageEvents<RG_TIMES + 1> ev;
+  CHK(ev.create());
   const size_t cells = (size_t)j.nx * j.ny;
-  Buf dm0, dm1, ds0, ds1, dz, dsig;
-  RG_ALLOC(dz, cells * 8);
-  if (j.sigma) RG_ALLOC(dsig, cells * 8);
-  RG_HIP(hipEventRecord(ev.e[0], s));
-  RG_UPLOAD(dm0, j.m0, cells * 8);
+  DevBuf dm0, dm1, ds0, ds1, dz, dsig;
+  CHK(dz.alloc(cells * 8));
+  if (j.sigma) CHK(dsig.alloc(cells * 8));
+  CHK(ev.record(0, s));
+  CHK(dm0.up(j.m0, cells * 8));
   if (j.m1_src)
-    RG_ALLOC(dm1, cells * 8);
+    CHK(dm1.alloc(cells * 8));
   else
-    RG_UPLOAD(dm1, j.m1, cells * 8);
+    CHK(dm1.up(j.m1, cells * 8));
   if (j.sigma) {
-    RG_UPLOAD(ds0, j.s0, cells * 8);
+    CHK(ds0.up(j.s0, cells * 8));
     if (j.s1_src)
-      RG_ALLOC(ds1, cells * 8);
+      CHK(ds1.alloc(cells * 8));
     else
-      RG_UPLOAD(ds1, j.s1, cells * 8);
+      CHK(ds1.up(j.s1, cells * 8));
   }
-  RG_HIP(hipEventRecord(ev.e[1], s));  // (the sources of the regridding are uploaded within the next span)
-  if (j.m1_src) {
-    const int rc = regrid_on_device(*j.m1_src, j.xo, j.nx, j.yo, j.ny, dm1.as<double>(), nullptr, nullptr, err);
-    if (rc != GLH_OK) return rc;
-  }
-  if (j.sigma && j.s1_src) {
-    const int rc = regrid_on_device(*j.s1_src, j.xo, j.nx, j.yo, j.ny, ds1.as<double>(), nullptr, nullptr, err);
-    if (rc != GLH_OK) return rc;
-  }
-  RG_HIP(hipEventRecord(ev.e[2], s));
+  CHK(ev.record(1, s));  // (the sources of the regridding are uploaded within the next span)
+  if (j.m1_src) CHK(regrid_on_device(*j.m1_src, j.xo, j.nx, j.yo, j.ny, dm1.as<double>(), nullptr, nullptr));
+  if (j.sigma && j.s1_src) CHK(regrid_on_device(*j.s1_src, j.xo, j.nx, j.yo, j.ny, ds1.as<double>(), nullptr, nullptr));
+  CHK(ev.record(2, s));
   hipLaunchKernelGGL(k_blend, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, dm0.as<double>(), dm1.as<double>(),
                      ds0.as<double>(), ds1.as<double>(), cells, j.scale, j.scale2, j.third, j.ratio, dz.as<double>(),
                      j.sigma ? dsig.as<double>() : nullptr);
-  RG_HIP(hipGetLastError());
-  RG_HIP(hipEventRecord(ev.e[3], s));
-  RG_HIP(hipMemcpy(j.z, dz.p, cells * 8, hipMemcpyDeviceToHost));
-  if (j.sigma) RG_HIP(hipMemcpy(j.sigma, dsig.p, cells * 8, hipMemcpyDeviceToHost));
-  RG_HIP(hipEventRecord(ev.e[4], s));
-  RG_HIP(hipEventSynchronize(ev.e[4]));
-  return report_times(ev, j.times_ms);
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(3, s));
+  CHK(dz.down(j.z, cells * 8));
+  if (j.sigma) CHK(dsig.down(j.sigma, cells * 8));
+  CHK(ev.record(4, s));
+  HIPCHK(hipEventSynchronize(ev.e[4]));
+  ev.report(j.times_ms, RG_TIMES, RG_TIMES);
+  return GLH_OK;
 }
 
 }  // namespace glh

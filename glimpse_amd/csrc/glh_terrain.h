@@ -43,9 +43,9 @@ struct PolygonMaskJob {
   double* times_ms;
 };
 
-// Each runs its job; a GLH_* status, with the message in err on failure.
-int gradient_run(const GradientJob& job, char* err, size_t err_cap);
-int hillshade_run(const HillshadeJob& job, char* err, size_t err_cap);
-int polygon_mask_run(const PolygonMaskJob& job, char* err, size_t err_cap);
+// Each runs its job; a GLH_* status, with the message left for glh_last_error() on failure (glh_stage.h: fail).
+int gradient_run(const GradientJob& job);
+int hillshade_run(const HillshadeJob& job);
+int polygon_mask_run(const PolygonMaskJob& job);
 
 }  // namespace glh

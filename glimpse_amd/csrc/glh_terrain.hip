@@ -40,6 +40,7 @@
 
 #include "../../include/glimpse_hip.h"
 #include "glh_terrain.h"
+#include "glh_stage.h"
 
 namespace glh {
 namespace {
@@ -274,74 +275,21 @@ __global__ void __launch_bounds__(TR_TB) k_pm_fill(PmRingArgs p) {
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-struct Buf {
-  void* p = nullptr;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-};
-
-struct Err {
-  char* msg;
-  size_t cap;
-  int fail(int code, const char* fmt, ...) const {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, cap, fmt, ap);
-    va_end(ap);
-    return code;
-  }
-};
-
-#define TR_HIP(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) return err.fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-#define TR_ALLOC(buf, bytes)                                                                                  \
-  do {                                                                                                        \
-    const size_t b_ = (bytes) ? (size_t)(bytes) : 1;                                                          \
-    hipError_t e_ = hipMalloc(&(buf).p, b_);                                                                  \
-    if (e_ != hipSuccess) {                                                                                   \
-      (void)hipGetLastError();                                                                                \
-      return err.fail(GLH_E_NOMEM, "terrain: hipMalloc(%zu) failed: %s", b_, hipGetErrorString(e_));           \
-    }                                                                                                         \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[TR_TIMES + 1] = {};
-  ~Events() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
-// times_ms[k] = the time between events k and k + 1, for the first `n` intervals; the rest 0
-void tr_times(const Events& ev, int n, double* times_ms) {
-  if (!times_ms) return;
-  for (int k = 0; k < TR_TIMES; ++k) {
-    float f = 0.f;
-    if (k < n) (void)hipEventElapsedTime(&f, ev.e[k], ev.e[k + 1]);
-    times_ms[k] = f;
-  }
-}
-
 }  // namespace
 
-int gradient_run(const GradientJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int gradient_run(const GradientJob& j) {
   const size_t n = (size_t)j.nx * j.ny, bytes = n * (j.f32 ? 4 : 8);
-  TR_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernels)
-  Events ev;
-  for (hipEvent_t& e : ev.e) TR_HIP(hipEventCreate(&e));
-  Buf dz, dx, dy;
-  TR_ALLOC(dz, bytes);
-  TR_ALLOC(dx, bytes);
-  TR_ALLOC(dy, bytes);
-  TR_HIP(hipEventRecord(ev.e[0], s));
-  TR_HIP(hipMemcpy(dz.p, j.z, bytes, hipMemcpyHostToDevice));
-  TR_HIP(hipEventRecord(ev.e[1], s));
+  StageEvents<TR_TIMES + 1> ev;
+  CHK(ev.create());
+  DevBuf dz, dx, dy;
+  CHK(dz.alloc(bytes));
+  CHK(dx.alloc(bytes));
+  CHK(dy.alloc(bytes));
+  CHK(ev.record(0, s));
+  HIPCHK(hipMemcpy(dz.p, j.z, bytes, hipMemcpyHostToDevice));
+  CHK(ev.record(1, s));
   TrStencilArgs a{};
   a.z = dz.p;
   a.nx = j.nx;
@@ -356,36 +304,35 @@ int gradient_run(const GradientJob& j, char* errbuf, size_t errcap) {
     hipLaunchKernelGGL(k_tr_gradient<float>, grid, dim3(TR_TB), 0, s, a);
   else
     hipLaunchKernelGGL(k_tr_gradient<double>, grid, dim3(TR_TB), 0, s, a);
-  TR_HIP(hipGetLastError());
-  TR_HIP(hipEventRecord(ev.e[2], s));
-  TR_HIP(hipMemcpy(j.dzdx, dx.p, bytes, hipMemcpyDeviceToHost));
-  TR_HIP(hipMemcpy(j.dzdy, dy.p, bytes, hipMemcpyDeviceToHost));
-  TR_HIP(hipEventRecord(ev.e[3], s));
-  TR_HIP(hipEventSynchronize(ev.e[3]));
-  tr_times(ev, 3, j.times_ms);
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(2, s));
+  CHK(dx.down(j.dzdx, bytes));
+  CHK(dy.down(j.dzdy, bytes));
+  CHK(ev.record(3, s));
+  HIPCHK(hipEventSynchronize(ev.e[3]));
+  ev.report(j.times_ms, 3, TR_TIMES);
   return GLH_OK;
 }
 
-int hillshade_run(const HillshadeJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int hillshade_run(const HillshadeJob& j) {
   const size_t n = (size_t)j.nx * j.ny, bytes = n * (j.f32 ? 4 : 8);
-  TR_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;
-  Events ev;
-  for (hipEvent_t& e : ev.e) TR_HIP(hipEventCreate(&e));
+  StageEvents<TR_TIMES + 1> ev;
+  CHK(ev.create());
   TrStencilArgs a{};
   a.nx = j.nx;
   a.ny = j.ny;
   a.tiles_x = (j.nx + TR_TW - 1) / TR_TW;
   a.tiles = a.tiles_x * ((j.ny + TR_TH - 1) / TR_TH);
-  Buf dz, draw, dpart, dstats;
-  TR_ALLOC(dz, bytes);
-  TR_ALLOC(draw, n * 8);
-  TR_ALLOC(dpart, (size_t)a.tiles * 3 * 8);
-  TR_ALLOC(dstats, 2 * 8);
-  TR_HIP(hipEventRecord(ev.e[0], s));
-  TR_HIP(hipMemcpy(dz.p, j.z, bytes, hipMemcpyHostToDevice));
-  TR_HIP(hipEventRecord(ev.e[1], s));
+  DevBuf dz, draw, dpart, dstats;
+  CHK(dz.alloc(bytes));
+  CHK(draw.alloc(n * 8));
+  CHK(dpart.alloc((size_t)a.tiles * 3 * 8));
+  CHK(dstats.alloc(2 * 8));
+  CHK(ev.record(0, s));
+  HIPCHK(hipMemcpy(dz.p, j.z, bytes, hipMemcpyHostToDevice));
+  CHK(ev.record(1, s));
   a.z = dz.p;
   a.hx = j.d0;
   a.hy = j.d1;
@@ -393,30 +340,29 @@ int hillshade_run(const HillshadeJob& j, char* errbuf, size_t errcap) {
   a.l0 = j.direction[0];
   a.l1 = j.direction[1];
   a.l2 = j.direction[2];
-  a.raw = static_cast<double*>(draw.p);
-  a.part = static_cast<double*>(dpart.p);
+  a.raw = draw.as<double>();
+  a.part = dpart.as<double>();
   if (j.f32)
     hipLaunchKernelGGL(k_tr_intensity<float>, dim3((unsigned)a.tiles), dim3(TR_TB), 0, s, a);
   else
     hipLaunchKernelGGL(k_tr_intensity<double>, dim3((unsigned)a.tiles), dim3(TR_TB), 0, s, a);
-  TR_HIP(hipGetLastError());
-  TR_HIP(hipEventRecord(ev.e[2], s));
-  hipLaunchKernelGGL(k_tr_reduce, dim3(1), dim3(TR_TB), 0, s, a.part, a.tiles, static_cast<double*>(dstats.p));
-  TR_HIP(hipGetLastError());
-  TR_HIP(hipEventRecord(ev.e[3], s));
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(2, s));
+  hipLaunchKernelGGL(k_tr_reduce, dim3(1), dim3(TR_TB), 0, s, a.part, a.tiles, dstats.as<double>());
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(3, s));
   hipLaunchKernelGGL(k_tr_normalise, dim3((unsigned)((n + TR_TB - 1) / TR_TB)), dim3(TR_TB), 0, s, a.raw, n,
-                     static_cast<const double*>(dstats.p), j.fraction);
-  TR_HIP(hipGetLastError());
-  TR_HIP(hipEventRecord(ev.e[4], s));
-  TR_HIP(hipMemcpy(j.out, draw.p, n * 8, hipMemcpyDeviceToHost));
-  TR_HIP(hipEventRecord(ev.e[5], s));
-  TR_HIP(hipEventSynchronize(ev.e[5]));
-  tr_times(ev, 5, j.times_ms);
+                     dstats.as<const double>(), j.fraction);
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(4, s));
+  CHK(draw.down(j.out, n * 8));
+  CHK(ev.record(5, s));
+  HIPCHK(hipEventSynchronize(ev.e[5]));
+  ev.report(j.times_ms, 5, TR_TIMES);
   return GLH_OK;
 }
 
-int polygon_mask_run(const PolygonMaskJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int polygon_mask_run(const PolygonMaskJob& j) {
   const size_t n = (size_t)j.nx * j.ny;
   const int rings = j.n_polygons + j.n_holes, wpr = (j.nx + 31) / 32;
   const size_t n_vertices = (size_t)j.ring_off[rings];
@@ -446,40 +392,40 @@ int polygon_mask_run(const PolygonMaskJob& j, char* errbuf, size_t errcap) {
       r.rb0 = r0 > 0.0 ? (int)r0 : 0;
       r.rb1 = r1 < (double)(j.ny - 1) ? (int)r1 : j.ny - 1;
       if (((size_t)(r.rb1 - r.rb0 + 1) * nv + TR_TB - 1) / TR_TB > 0x7fffffffull)
-        return err.fail(GLH_E_UNSUPPORTED, "polygon_mask: ring %d: %d rows x %d edges is more than one launch holds", k,
-                        r.rb1 - r.rb0 + 1, nv);
+        return fail(GLH_E_UNSUPPORTED, "polygon_mask: ring %d: %d rows x %d edges is more than one launch holds", k,
+                    r.rb1 - r.rb0 + 1, nv);
       ++n_live;
     }
     ring[k] = r;
   }
-  TR_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;
-  Events ev;
-  for (hipEvent_t& e : ev.e) TR_HIP(hipEventCreate(&e));
-  Buf dxy, dbits, dout;
-  TR_ALLOC(dxy, n_vertices * 16);
-  TR_ALLOC(dbits, (size_t)j.ny * wpr * 4);
-  TR_ALLOC(dout, n);
-  TR_HIP(hipEventRecord(ev.e[0], s));
-  if (n_live) TR_HIP(hipMemcpy(dxy.p, j.xy, n_vertices * 16, hipMemcpyHostToDevice));
-  TR_HIP(hipMemsetAsync(dbits.p, 0, (size_t)j.ny * wpr * 4, s));
-  TR_HIP(hipMemsetAsync(dout.p, 0, n, s));
-  TR_HIP(hipEventRecord(ev.e[1], s));
+  StageEvents<TR_TIMES + 1> ev;
+  CHK(ev.create());
+  DevBuf dxy, dbits, dout;
+  CHK(dxy.alloc(n_vertices * 16));
+  CHK(dbits.alloc((size_t)j.ny * wpr * 4));
+  CHK(dout.alloc(n));
+  CHK(ev.record(0, s));
+  if (n_live) HIPCHK(hipMemcpy(dxy.p, j.xy, n_vertices * 16, hipMemcpyHostToDevice));
+  HIPCHK(hipMemsetAsync(dbits.p, 0, (size_t)j.ny * wpr * 4, s));
+  HIPCHK(hipMemsetAsync(dout.p, 0, n, s));
+  CHK(ev.record(1, s));
   for (int k = 0; k < rings; ++k) {
     const Ring& r = ring[k];
     if (r.rb1 < r.rb0 || r.cb1 < r.cb0) continue;
     const int nrows = r.rb1 - r.rb0 + 1;
-    const PmRingArgs a{static_cast<const double*>(dxy.p), r.v0, r.nv, r.rb0, nrows, r.cb0, r.cb1, wpr, j.nx,
-                       static_cast<uint32_t*>(dbits.p), static_cast<uint8_t*>(dout.p), k >= j.n_polygons};
+    const PmRingArgs a{dxy.as<const double>(), r.v0, r.nv, r.rb0, nrows, r.cb0, r.cb1, wpr, j.nx,
+                       dbits.as<uint32_t>(), dout.as<uint8_t>(), k >= j.n_polygons};
     hipLaunchKernelGGL(k_pm_cross, dim3((unsigned)(((size_t)nrows * r.nv + TR_TB - 1) / TR_TB)), dim3(TR_TB), 0, s, a);
     hipLaunchKernelGGL(k_pm_fill, dim3((unsigned)((nrows + TR_TB / 64 - 1) / (TR_TB / 64))), dim3(TR_TB), 0, s, a);
   }
-  TR_HIP(hipGetLastError());
-  TR_HIP(hipEventRecord(ev.e[2], s));
-  TR_HIP(hipMemcpy(j.out, dout.p, n, hipMemcpyDeviceToHost));
-  TR_HIP(hipEventRecord(ev.e[3], s));
-  TR_HIP(hipEventSynchronize(ev.e[3]));
-  tr_times(ev, 3, j.times_ms);
+  HIPCHK(hipGetLastError());
+  CHK(ev.record(2, s));
+  CHK(dout.down(j.out, n));
+  CHK(ev.record(3, s));
+  HIPCHK(hipEventSynchronize(ev.e[3]));
+  ev.report(j.times_ms, 3, TR_TIMES);
   return GLH_OK;
 }
 

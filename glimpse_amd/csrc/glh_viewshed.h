@@ -29,7 +29,7 @@ struct ViewshedJob {
 
 // Distance (in cells, + 0.5: the ring number before truncation) of the DEM's farthest corner from an origin.
 double viewshed_farthest_cells(const ViewshedJob& job, const double* origin);
-// Runs the job; a GLH_* status, with the message in err on failure.
-int viewshed_run(const ViewshedJob& job, char* err, size_t err_cap);
+// Runs the job; a GLH_* status, with the message left for glh_last_error() on failure (glh_stage.h: fail).
+int viewshed_run(const ViewshedJob& job);
 
 }  // namespace glh

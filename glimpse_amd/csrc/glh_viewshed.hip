@@ -25,6 +25,7 @@
 
 #include "../../include/glimpse_hip.h"
 #include "glh_viewshed.h"
+#include "glh_stage.h"
 
 namespace glh {
 namespace {
@@ -209,52 +210,6 @@ __global__ void __launch_bounds__(VS_TB) k_vs_ring(VsSweepArgs a, int k, size_t 
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------
-struct Buf {
-  void* p = nullptr;
-  ~Buf() {
-    if (p) (void)hipFree(p);
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
-struct Err {
-  char* msg;
-  size_t cap;
-  int fail(int code, const char* fmt, ...) const {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(msg, cap, fmt, ap);
-    va_end(ap);
-    return code;
-  }
-};
-
-#define VS_HIP(expr)                                                                                          \
-  do {                                                                                                        \
-    hipError_t e_ = (expr);                                                                                   \
-    if (e_ != hipSuccess) return err.fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-#define VS_ALLOC(buf, bytes)                                                                                  \
-  do {                                                                                                        \
-    const size_t b_ = (bytes) ? (size_t)(bytes) : 1;                                                          \
-    hipError_t e_ = hipMalloc(&(buf).p, b_);                                                                  \
-    if (e_ != hipSuccess) {                                                                                   \
-      (void)hipGetLastError();                                                                                \
-      return err.fail(GLH_E_NOMEM, "viewshed: hipMalloc(%zu) failed: %s", b_, hipGetErrorString(e_));          \
-    }                                                                                                         \
-  } while (0)
-
-struct Events {
-  hipEvent_t e[6] = {};
-  ~Events() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
-};
-
 }  // namespace
 
 double viewshed_farthest_cells(const ViewshedJob& j, const double* origin) {
@@ -269,62 +224,57 @@ double viewshed_farthest_cells(const ViewshedJob& j, const double* origin) {
   return far;
 }
 
-int viewshed_run(const ViewshedJob& j, char* errbuf, size_t errcap) {
-  const Err err{errbuf, errcap};
+int viewshed_run(const ViewshedJob& j) {
   const size_t n = (size_t)j.nx * j.ny;
   // the ring numbers of every origin fit a histogram sized before anything is allocated
   int nbins = 1;
   for (int o = 0; o < j.m; ++o) {
     const double far = viewshed_farthest_cells(j, j.origins + 3 * o);
     if (!(far < (double)VS_MAX_RINGS))
-      return err.fail(GLH_E_UNSUPPORTED, "viewshed: origin %d is %g cells from the farthest cell (fewer than %d are served)",
-                      o, far, VS_MAX_RINGS);
+      return fail(GLH_E_UNSUPPORTED, "viewshed: origin %d is %g cells from the farthest cell (fewer than %d are served)",
+                  o, far, VS_MAX_RINGS);
     if ((int)far + 2 > nbins) nbins = (int)far + 2;
   }
-  VS_HIP(hipSetDevice(j.device));
+  HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernels)
-  Events ev;
-  for (hipEvent_t& e : ev.e) VS_HIP(hipEventCreate(&e));
+  StageEvents<6> ev;
+  CHK(ev.create());
   const size_t zbytes = n * (j.f32 ? 4 : 8);
-  Buf dz, dx, dy, hkey, kbuf, elev, ring, idxa, idxb, rka, rkb, es, ms, vis, hist, flags, small, temp;
-  VS_ALLOC(dz, zbytes);
-  VS_ALLOC(dx, (size_t)j.nx * 8);
-  VS_ALLOC(dy, (size_t)j.ny * 8);
-  VS_ALLOC(hkey, n * 8);
-  VS_ALLOC(kbuf, n * 8);  // the first sort's sorted keys, then the sorted headings
-  VS_ALLOC(elev, n * 8);
-  VS_ALLOC(ring, n * 4);
-  VS_ALLOC(idxa, n * 4);
-  VS_ALLOC(idxb, n * 4);
-  VS_ALLOC(rka, n * 4);
-  VS_ALLOC(rkb, n * 4);
-  VS_ALLOC(es, n * 8);
-  VS_ALLOC(ms, n * 8);
-  VS_ALLOC(vis, n);
-  VS_ALLOC(hist, (size_t)nbins * 4);
-  VS_ALLOC(flags, 4);  // the per-cell kernel's error word
+  DevBuf dz, dx, dy, hkey, kbuf, elev, ring, idxa, idxb, rka, rkb, es, ms, vis, hist, flags, small, temp;
+  CHK(dz.alloc(zbytes));
+  CHK(dx.alloc((size_t)j.nx * 8));
+  CHK(dy.alloc((size_t)j.ny * 8));
+  CHK(hkey.alloc(n * 8));
+  CHK(kbuf.alloc(n * 8));  // the first sort's sorted keys, then the sorted headings
+  CHK(elev.alloc(n * 8));
+  CHK(ring.alloc(n * 4));
+  CHK(idxa.alloc(n * 4));
+  CHK(idxb.alloc(n * 4));
+  CHK(rka.alloc(n * 4));
+  CHK(rkb.alloc(n * 4));
+  CHK(es.alloc(n * 8));
+  CHK(ms.alloc(n * 8));
+  CHK(vis.alloc(n));
+  CHK(hist.alloc((size_t)nbins * 4));
+  CHK(flags.alloc(4));  // the per-cell kernel's error word
   int ring_bits = 1;
   while ((1ll << ring_bits) < nbins) ++ring_bits;
   size_t t1 = 0, t2 = 0;
-  VS_HIP(rocprim::radix_sort_pairs(nullptr, t1, hkey.as<uint64_t>(), kbuf.as<uint64_t>(), idxa.as<uint32_t>(),
+  HIPCHK(rocprim::radix_sort_pairs(nullptr, t1, hkey.as<uint64_t>(), kbuf.as<uint64_t>(), idxa.as<uint32_t>(),
                                    idxb.as<uint32_t>(), n, 0, 64, s));
-  VS_HIP(rocprim::radix_sort_pairs(nullptr, t2, rka.as<uint32_t>(), rkb.as<uint32_t>(), idxb.as<uint32_t>(),
+  HIPCHK(rocprim::radix_sort_pairs(nullptr, t2, rka.as<uint32_t>(), rkb.as<uint32_t>(), idxb.as<uint32_t>(),
                                    idxa.as<uint32_t>(), n, 0, ring_bits, s));
   const size_t tbytes = t1 > t2 ? t1 : t2;
-  VS_ALLOC(temp, tbytes);
+  CHK(temp.alloc(tbytes));
 
   double t_ms[5] = {0, 0, 0, 0, 0};
-  auto lap = [&](int which, hipEvent_t a, hipEvent_t b) {
-    float f = 0.f;
-    if (hipEventElapsedTime(&f, a, b) == hipSuccess) t_ms[which] += f;
-  };
-  VS_HIP(hipEventRecord(ev.e[0], s));
-  VS_HIP(hipMemcpy(dz.p, j.z, zbytes, hipMemcpyHostToDevice));
-  VS_HIP(hipMemcpy(dx.p, j.x, (size_t)j.nx * 8, hipMemcpyHostToDevice));
-  VS_HIP(hipMemcpy(dy.p, j.y, (size_t)j.ny * 8, hipMemcpyHostToDevice));
-  VS_HIP(hipEventRecord(ev.e[1], s));
-  VS_HIP(hipEventSynchronize(ev.e[1]));
-  lap(0, ev.e[0], ev.e[1]);
+  CHK(ev.record(0, s));
+  HIPCHK(hipMemcpy(dz.p, j.z, zbytes, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dx.p, j.x, (size_t)j.nx * 8, hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(dy.p, j.y, (size_t)j.ny * 8, hipMemcpyHostToDevice));
+  CHK(ev.record(1, s));
+  HIPCHK(hipEventSynchronize(ev.e[1]));
+  t_ms[0] += ev.ms(0, 1);
 
   std::vector<uint32_t> h_hist(nbins);
   std::vector<size_t> r_start, r_end;
@@ -335,31 +285,31 @@ int viewshed_run(const ViewshedJob& j, char* errbuf, size_t errcap) {
     const double* org = j.origins + 3 * o;
     uint8_t* out = j.visible + (size_t)o * n;
     // ---- 1: per cell
-    VS_HIP(hipEventRecord(ev.e[0], s));
-    VS_HIP(hipMemsetAsync(hist.p, 0, (size_t)nbins * 4, s));
-    VS_HIP(hipMemsetAsync(flags.p, 0, 4, s));
+    CHK(ev.record(0, s));
+    HIPCHK(hipMemsetAsync(hist.p, 0, (size_t)nbins * 4, s));
+    HIPCHK(hipMemsetAsync(flags.p, 0, 4, s));
     VsCellArgs ca{dz.p, dx.as<double>(), dy.as<double>(), j.nx, j.ny, j.f32, j.correction, j.inv_d, org[0], org[1], org[2],
                   j.refraction - 1.0, 2.0 * j.radius, hkey.as<uint64_t>(), elev.as<double>(), ring.as<uint32_t>(),
                   idxa.as<uint32_t>(), hist.as<uint32_t>(), nbins, flags.as<int>()};
     hipLaunchKernelGGL(k_vs_cells, dim3((j.nx + VS_TB - 1) / VS_TB, j.ny), dim3(VS_TB), 0, s, ca);
-    VS_HIP(hipGetLastError());
-    VS_HIP(hipEventRecord(ev.e[1], s));
+    HIPCHK(hipGetLastError());
+    CHK(ev.record(1, s));
     // ---- 2: np.lexsort((heading, ring)): stable by heading, then stable by ring
-    VS_HIP(rocprim::radix_sort_pairs(temp.p, t1, hkey.as<uint64_t>(), kbuf.as<uint64_t>(), idxa.as<uint32_t>(),
+    HIPCHK(rocprim::radix_sort_pairs(temp.p, t1, hkey.as<uint64_t>(), kbuf.as<uint64_t>(), idxa.as<uint32_t>(),
                                      idxb.as<uint32_t>(), n, 0, 64, s));
     hipLaunchKernelGGL(k_vs_gather_ring, dim3(nblocks), dim3(VS_TB), 0, s, ring.as<uint32_t>(), idxb.as<uint32_t>(),
                        rka.as<uint32_t>(), n);
-    VS_HIP(rocprim::radix_sort_pairs(temp.p, t2, rka.as<uint32_t>(), rkb.as<uint32_t>(), idxb.as<uint32_t>(),
+    HIPCHK(rocprim::radix_sort_pairs(temp.p, t2, rka.as<uint32_t>(), rkb.as<uint32_t>(), idxb.as<uint32_t>(),
                                      idxa.as<uint32_t>(), n, 0, ring_bits, s));
     hipLaunchKernelGGL(k_vs_gather_sorted, dim3(nblocks), dim3(VS_TB), 0, s, hkey.as<uint64_t>(), elev.as<double>(),
                        idxa.as<uint32_t>(), kbuf.as<double>(), es.as<double>(), n);
-    VS_HIP(hipGetLastError());
-    VS_HIP(hipEventRecord(ev.e[2], s));
+    HIPCHK(hipGetLastError());
+    CHK(ev.record(2, s));
     // the ring sizes come back once, to shape the launches
     int kernel_err = 0;
-    VS_HIP(hipMemcpy(h_hist.data(), hist.p, (size_t)nbins * 4, hipMemcpyDeviceToHost));
-    VS_HIP(hipMemcpy(&kernel_err, flags.p, 4, hipMemcpyDeviceToHost));
-    if (kernel_err) return err.fail(GLH_E_INVALID, "viewshed: a ring number beyond the %d the corners allow", nbins);
+    CHK(hist.down(h_hist.data(), (size_t)nbins * 4));
+    CHK(flags.down(&kernel_err, 4));
+    if (kernel_err) return fail(GLH_E_INVALID, "viewshed: a ring number beyond the %d the corners allow", nbins);
     // the processed rings: every non-empty ring but ring 0 (raster.py:1333-1346: with a ring 0 `rings` starts at ring 1)
     r_start.clear();
     r_end.clear();
@@ -371,19 +321,19 @@ int viewshed_run(const ViewshedJob& j, char* errbuf, size_t errcap) {
       }
       at += h_hist[b];
     }
-    if (at != n) return err.fail(GLH_E_HIP, "viewshed: the ring histogram counts %zu of %zu cells", at, n);
+    if (at != n) return fail(GLH_E_HIP, "viewshed: the ring histogram counts %zu of %zu cells", at, n);
     const int nr = (int)r_start.size();
-    VS_HIP(hipEventRecord(ev.e[3], s));
+    CHK(ev.record(3, s));
     if (nr == 0) {
       // "Single co-located pixel, return all visible" (raster.py:1344-1345)
-      VS_HIP(hipMemsetAsync(vis.p, 1, n, s));
+      HIPCHK(hipMemsetAsync(vis.p, 1, n, s));
     } else {
-      VS_HIP(hipMemsetAsync(vis.p, 0, n, s));  // (ring 0 beside other rings is never processed: it stays False)
+      HIPCHK(hipMemsetAsync(vis.p, 0, n, s));  // (ring 0 beside other rings is never processed: it stays False)
       // per ring: rot preset to the ring's size ("no non-negative heading"), flag, two counters
       preset.assign((size_t)4 * nr, 0);
       for (int k = 0; k < nr; ++k) preset[k] = (int)(r_end[k] - r_start[k]);
-      VS_ALLOC(small, (size_t)16 * nr);
-      VS_HIP(hipMemcpy(small.p, preset.data(), (size_t)16 * nr, hipMemcpyHostToDevice));
+      CHK(small.alloc((size_t)16 * nr));
+      HIPCHK(hipMemcpy(small.p, preset.data(), (size_t)16 * nr, hipMemcpyHostToDevice));
       VsSweepArgs sa{kbuf.as<double>(), es.as<double>(), ms.as<double>(), idxa.as<uint32_t>(), vis.as<uint8_t>(),
                      small.as<int>(), small.as<int>() + nr, small.as<uint32_t>() + 2 * nr, small.as<uint32_t>() + 3 * nr};
       for (int k = 0; k < nr; ++k) {
@@ -391,20 +341,20 @@ int viewshed_run(const ViewshedJob& j, char* errbuf, size_t errcap) {
         hipLaunchKernelGGL(k_vs_ring, dim3((unsigned)((cnt + VS_TB - 1) / VS_TB)), dim3(VS_TB), 0, s, sa, k,
                            k ? r_start[k - 1] : r_start[k], r_start[k], r_end[k]);
       }
-      VS_HIP(hipGetLastError());
+      HIPCHK(hipGetLastError());
     }
-    VS_HIP(hipEventRecord(ev.e[4], s));
-    VS_HIP(hipMemcpy(out, vis.p, n, hipMemcpyDeviceToHost));
-    VS_HIP(hipEventRecord(ev.e[5], s));
-    VS_HIP(hipEventSynchronize(ev.e[5]));
+    CHK(ev.record(4, s));
+    CHK(vis.down(out, n));
+    CHK(ev.record(5, s));
+    HIPCHK(hipEventSynchronize(ev.e[5]));
     if (small.p) {
-      VS_HIP(hipFree(small.p));
+      HIPCHK(hipFree(small.p));
       small.p = nullptr;
     }
-    lap(1, ev.e[0], ev.e[1]);
-    lap(2, ev.e[1], ev.e[2]);
-    lap(3, ev.e[3], ev.e[4]);
-    lap(4, ev.e[4], ev.e[5]);
+    t_ms[1] += ev.ms(0, 1);
+    t_ms[2] += ev.ms(1, 2);
+    t_ms[3] += ev.ms(3, 4);
+    t_ms[4] += ev.ms(4, 5);
     rings_done += nr;
     launches += nr;
   }

@@ -23,6 +23,7 @@
 #include "glh_viewshed.h"
 #include "glh_filters.h"
 #include "glh_terrain.h"
+#include "glh_stage.h"
 
 using namespace glh;
 
@@ -62,7 +63,7 @@ static std::vector<std::pair<const void*, int>> pt_all_kernels() {
 // ------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
 
-static int fail(int code, const char* fmt, ...) {
+int glh::fail(int code, const char* fmt, ...) {
   char buf[512];
   va_list ap;
   va_start(ap, fmt);
@@ -71,20 +72,6 @@ static int fail(int code, const char* fmt, ...) {
   g_err = buf;
   return code;
 }
-
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                  __LINE__);                                                                 \
-  } while (0)
-
-#define CHK(expr)          \
-  do {                     \
-    int rc_ = (expr);      \
-    if (rc_ != GLH_OK) return rc_; \
-  } while (0)
 
 // LDS plan of the fused kernel (glh_point.h): c[N] + region 2
 constexpr int PT_LDS_MAX = 152 * 1024;   // dynamic LDS of one workgroup (static <= 5 KB on top, 160 KB per CU)
@@ -2309,31 +2296,6 @@ extern "C" int glh_get_gathered(glh_ctx* c, double* out, uint32_t* status) {
 // stateless stage hooks (parity tests): explicit inputs -> one kernel -> outputs
 // ------------------------------------------------------------------------------------------
 namespace {
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int alloc(size_t bytes) {
-    if (bytes == 0) bytes = 1;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) return fail(GLH_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    return GLH_OK;
-  }
-  int up(const void* src, size_t bytes) {
-    CHK(alloc(bytes));
-    HIPCHK(hipMemcpy(p, src, bytes, hipMemcpyHostToDevice));
-    return GLH_OK;
-  }
-  int down(void* dst, size_t bytes) {
-    HIPCHK(hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost));
-    return GLH_OK;
-  }
-  template <typename T>
-  T* as() {
-    return (T*)p;
-  }
-};
 int finish() {
   HIPCHK(hipGetLastError());
   HIPCHK(hipDeviceSynchronize());
@@ -2801,26 +2763,50 @@ extern "C" int glh_stage_raster_sample(int dev, const double* z, int nx, int ny,
   return do_.down(oob, (size_t)n);
 }
 
+// What the stages below check alike, before a device is touched (`who` is the stage's name: every message begins with it).
+static int check_grid(const char* who, int nx, int ny, int least) {
+  if (nx < least || ny < least) return fail(GLH_E_INVALID, "%s: %d x %d cells: at least %d on each axis", who, nx, ny, least);
+  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "%s: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", who, nx, ny);
+  return GLH_OK;
+}
+
+// (GLH_VIEWSHED_*, GLH_PD_*, GLH_FILTER_* and GLH_TERRAIN_* number the two float types alike)
+static_assert(GLH_VIEWSHED_F64 == 0 && GLH_PD_F64 == 0 && GLH_FILTER_F64 == 0 && GLH_TERRAIN_F64 == 0, "float64 is 0");
+static_assert(GLH_VIEWSHED_F32 == 1 && GLH_PD_F32 == 1 && GLH_FILTER_F32 == 1 && GLH_TERRAIN_F32 == 1, "float32 is 1");
+static int check_float_dtype(const char* who, const char* what, int dtype) {
+  if (dtype != 0 && dtype != 1) return fail(GLH_E_UNSUPPORTED, "%s: %s %d: 0 float64, 1 float32", who, what, dtype);
+  return GLH_OK;
+}
+
+static int check_origins(const char* who, const double* origins, int m) {
+  for (int i = 0; i < 3 * m; ++i)
+    if (!std::isfinite(origins[i])) return fail(GLH_E_INVALID, "%s: origin %d is not finite", who, i / 3);
+  return GLH_OK;
+}
+
+static int check_correction(const char* who, int correction, double radius, double refraction) {
+  if (correction && !(std::isfinite(radius) && radius != 0.0 && std::isfinite(refraction)))
+    return fail(GLH_E_INVALID, "%s: correction with radius %g, refraction %g", who, radius, refraction);
+  return GLH_OK;
+}
+
 // Raster.viewshed (raster.py:1293-1389): the arguments are checked here, before a device is touched; the kernels, the sort
 // and the launches are glh_viewshed.hip's.
 extern "C" int glh_stage_viewshed(int dev, const void* z, int z_dtype, int nx, int ny, const double* x, const double* y,
                                   double inv_cell, const double* origins, int m, int correction, double radius,
                                   double refraction, uint8_t* visible, double* times_ms) {
   if (!z || !x || !y || !origins || !visible) return fail(GLH_E_INVALID, "viewshed: null argument");
-  if (nx < 1 || ny < 1 || m < 1) return fail(GLH_E_INVALID, "viewshed: %d x %d cells, %d origins: at least one of each", nx, ny, m);
-  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
-    return fail(GLH_E_INVALID, "viewshed: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", nx, ny);
-  if (z_dtype != GLH_VIEWSHED_F64 && z_dtype != GLH_VIEWSHED_F32)
-    return fail(GLH_E_UNSUPPORTED, "viewshed: z_dtype %d: 0 float64, 1 float32", z_dtype);
+  if (m < 1) return fail(GLH_E_INVALID, "viewshed: %d origins: at least one", m);
+  CHK(check_grid("viewshed", nx, ny, 1));
+  CHK(check_float_dtype("viewshed", "z_dtype", z_dtype));
   if (!(std::isfinite(inv_cell) && inv_cell > 0.0)) return fail(GLH_E_INVALID, "viewshed: inverse cell size %g", inv_cell);
   for (int i = 0; i < nx; ++i)
     if (!std::isfinite(x[i])) return fail(GLH_E_INVALID, "viewshed: x[%d] is not finite", i);
   for (int i = 0; i < ny; ++i)
     if (!std::isfinite(y[i])) return fail(GLH_E_INVALID, "viewshed: y[%d] is not finite", i);
-  for (int i = 0; i < 3 * m; ++i)
-    if (!std::isfinite(origins[i])) return fail(GLH_E_INVALID, "viewshed: origin %d is not finite", i / 3);
-  if (correction && !(std::isfinite(radius) && radius != 0.0 && std::isfinite(refraction)))
-    return fail(GLH_E_INVALID, "viewshed: correction with radius %g, refraction %g", radius, refraction);
+  CHK(check_origins("viewshed", origins, m));
+  CHK(check_correction("viewshed", correction, radius, refraction));
   const ViewshedJob job{dev, z, z_dtype == GLH_VIEWSHED_F32, nx, ny, x, y, inv_cell, origins, m, correction != 0, radius,
                         refraction, visible, times_ms};
   for (int o = 0; o < m; ++o) {
@@ -2829,9 +2815,7 @@ extern "C" int glh_stage_viewshed(int dev, const void* z, int z_dtype, int nx, i
       return fail(GLH_E_UNSUPPORTED, "viewshed: origin %d is %g cells from the DEM's farthest cell (fewer than %d are served)", o,
                   far, VS_MAX_RINGS);
   }
-  char msg[512] = "";
-  const int rc = viewshed_run(job, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  return viewshed_run(job);
 }
 
 // Raster.horizon (raster.py:1391-1463): the arguments are checked here, before a device is touched; the kernel and the
@@ -2841,20 +2825,15 @@ extern "C" int glh_stage_horizon(int dev, const void* z, int z_dtype, int nx, in
                                  int correction, double radius, double refraction, int32_t* cell, double* dz,
                                  double* times_ms) {
   if (!z || !origins || !starts || !ends || !cell || !dz) return fail(GLH_E_INVALID, "horizon: null argument");
-  if (nx < 1 || ny < 1 || m < 1 || n < 1)
-    return fail(GLH_E_INVALID, "horizon: %d x %d cells, %d origins, %d headings: at least one of each", nx, ny, m, n);
-  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
-    return fail(GLH_E_INVALID, "horizon: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", nx, ny);
+  if (m < 1 || n < 1) return fail(GLH_E_INVALID, "horizon: %d origins, %d headings: at least one of each", m, n);
+  CHK(check_grid("horizon", nx, ny, 1));
   if ((int64_t)m * n >= ((int64_t)1 << 24))  // (one workgroup of up to 256 lanes per line: a launch holds fewer than 2^32)
     return fail(GLH_E_INVALID, "horizon: %d origins x %d headings: fewer than 2^24 lines are served", m, n);
-  if (z_dtype != GLH_VIEWSHED_F64 && z_dtype != GLH_VIEWSHED_F32)
-    return fail(GLH_E_UNSUPPORTED, "horizon: z_dtype %d: 0 float64, 1 float32", z_dtype);
+  CHK(check_float_dtype("horizon", "z_dtype", z_dtype));
   if (!(std::isfinite(xlim0) && std::isfinite(ylim0) && std::isfinite(d0) && std::isfinite(d1) && d0 != 0.0 && d1 != 0.0))
     return fail(GLH_E_INVALID, "horizon: corner (%g, %g), cell size (%g, %g)", xlim0, ylim0, d0, d1);
-  for (int i = 0; i < 3 * m; ++i)
-    if (!std::isfinite(origins[i])) return fail(GLH_E_INVALID, "horizon: origin %d is not finite", i / 3);
-  if (correction && !(std::isfinite(radius) && radius != 0.0 && std::isfinite(refraction)))
-    return fail(GLH_E_INVALID, "horizon: correction with radius %g, refraction %g", radius, refraction);
+  CHK(check_origins("horizon", origins, m));
+  CHK(check_correction("horizon", correction, radius, refraction));
   for (int o = 0; o < m; ++o)
     if (starts[2 * o] < 0 || starts[2 * o] >= nx || starts[2 * o + 1] < 0 || starts[2 * o + 1] >= ny)
       return fail(GLH_E_INVALID, "horizon: start cell (col %d, row %d) of origin %d is outside the %d x %d grid", starts[2 * o],
@@ -2865,9 +2844,7 @@ extern "C" int glh_stage_horizon(int dev, const void* z, int z_dtype, int nx, in
                   ends[2 * i], ends[2 * i + 1], (int)(i / n), (int)(i % n), nx, ny);
   const HorizonJob job{dev, z, z_dtype == GLH_VIEWSHED_F32, nx, ny, xlim0, ylim0, d0, d1, origins, starts, ends, m, n,
                        correction != 0, radius, refraction, cell, dz, times_ms};
-  char msg[512] = "";
-  const int rc = horizon_run(job, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  return horizon_run(job);
 }
 
 // Raster.sample(grid=True) / resample, Raster.resize and RasterInterpolant (raster.py:1042-1083, :1178-1187, :1673-1700):
@@ -2902,12 +2879,9 @@ static int check_regrid_axis(const char* who, const char* axis, const double* g,
 
 static int check_regrid_src(const char* who, const glh_regrid_src* s, bool order1_only, RegridSource& out) {
   if (!s || !s->z || !s->gx || !s->gy) return fail(GLH_E_INVALID, "%s: null argument", who);
-  if (s->nx < 1 || s->ny < 1 || (int64_t)s->nx * s->ny >= ((int64_t)1 << 31))
-    return fail(GLH_E_INVALID, "%s: %d x %d cells: at least one, fewer than 2^31", who, s->nx, s->ny);
-  int rc = check_regrid_axis(who, "x", s->gx, s->nx, s->kx, s->xmin, s->xmax);
-  if (rc != GLH_OK) return rc;
-  rc = check_regrid_axis(who, "y", s->gy, s->ny, s->ky, s->ymin, s->ymax);
-  if (rc != GLH_OK) return rc;
+  CHK(check_grid(who, s->nx, s->ny, 1));
+  CHK(check_regrid_axis(who, "x", s->gx, s->nx, s->kx, s->xmin, s->xmax));
+  CHK(check_regrid_axis(who, "y", s->gy, s->ny, s->ky, s->ymin, s->ymax));
   if (order1_only && (s->kx != 1 || s->ky != 1))
     return fail(GLH_E_UNSUPPORTED, "%s: orders (%d, %d): the interpolant regrids at order 1", who, s->kx, s->ky);
   if (s->nan_mask && (s->kx != 1 || s->ky != 1))
@@ -2925,24 +2899,16 @@ extern "C" int glh_stage_raster_regrid(int dev, const glh_regrid_src* src, const
                                        double* out, double* times_ms) {
   if (!out) return fail(GLH_E_INVALID, "raster_regrid: null argument");
   RegridSource s{};
-  int rc = check_regrid_src("raster_regrid", src, false, s);
-  if (rc != GLH_OK) return rc;
-  rc = check_regrid_outputs("raster_regrid", xo, mx, yo, my);
-  if (rc != GLH_OK) return rc;
-  char msg[512] = "";
-  rc = regrid_run(RegridJob{dev, s, xo, yo, mx, my, out, times_ms}, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  CHK(check_regrid_src("raster_regrid", src, false, s));
+  CHK(check_regrid_outputs("raster_regrid", xo, mx, yo, my));
+  return regrid_run(RegridJob{dev, s, xo, yo, mx, my, out, times_ms});
 }
 
 extern "C" int glh_stage_zoom_linear(int dev, const double* a, int nx, int ny, int mx, int my, double* out, double* times_ms) {
   if (!a || !out) return fail(GLH_E_INVALID, "zoom_linear: null argument");
-  if (nx < 1 || ny < 1 || mx < 1 || my < 1)
-    return fail(GLH_E_INVALID, "zoom_linear: %d x %d cells into %d x %d: at least one of each", nx, ny, mx, my);
-  if ((int64_t)nx * ny >= ((int64_t)1 << 31) || (int64_t)mx * my >= ((int64_t)1 << 31))
-    return fail(GLH_E_INVALID, "zoom_linear: %d x %d cells into %d x %d: fewer than 2^31 are served", nx, ny, mx, my);
-  char msg[512] = "";
-  const int rc = zoom_run(ZoomJob{dev, a, nx, ny, mx, my, out, times_ms}, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  CHK(check_grid("zoom_linear", nx, ny, 1));
+  CHK(check_grid("zoom_linear (output)", mx, my, 1));
+  return zoom_run(ZoomJob{dev, a, nx, ny, mx, my, out, times_ms});
 }
 
 extern "C" int glh_stage_raster_interpolate(int dev, int nx, int ny, const double* m0, const double* m1,
@@ -2952,20 +2918,16 @@ extern "C" int glh_stage_raster_interpolate(int dev, int nx, int ny, const doubl
                                             double* times_ms) {
   if (!m0 || !z || (!m1 && !m1_src)) return fail(GLH_E_INVALID, "raster_interpolate: null argument");
   if (sigma && (!s0 || (!s1 && !s1_src))) return fail(GLH_E_INVALID, "raster_interpolate: sigma asked for without both inputs");
-  if (nx < 1 || ny < 1 || (int64_t)nx * ny >= ((int64_t)1 << 31))
-    return fail(GLH_E_INVALID, "raster_interpolate: %d x %d cells: at least one, fewer than 2^31", nx, ny);
+  CHK(check_grid("raster_interpolate", nx, ny, 1));
   RegridSource ms{}, ss{};
   const bool regrid_m = m1_src != nullptr, regrid_s = sigma && s1_src != nullptr;
-  int rc;
-  if (regrid_m && (rc = check_regrid_src("raster_interpolate (means)", m1_src, true, ms)) != GLH_OK) return rc;
-  if (regrid_s && (rc = check_regrid_src("raster_interpolate (sigmas)", s1_src, true, ss)) != GLH_OK) return rc;
-  if ((regrid_m || regrid_s) && (rc = check_regrid_outputs("raster_interpolate", xo, nx, yo, ny)) != GLH_OK) return rc;
+  if (regrid_m) CHK(check_regrid_src("raster_interpolate (means)", m1_src, true, ms));
+  if (regrid_s) CHK(check_regrid_src("raster_interpolate (sigmas)", s1_src, true, ss));
+  if (regrid_m || regrid_s) CHK(check_regrid_outputs("raster_interpolate", xo, nx, yo, ny));
   const InterpolateJob job{dev, nx, ny, m0, regrid_m ? nullptr : m1, regrid_m ? &ms : nullptr, sigma ? s0 : nullptr,
                            regrid_s ? nullptr : s1, regrid_s ? &ss : nullptr, xo, yo, scale, scale2, third, ratio, z, sigma,
                            times_ms};
-  char msg[512] = "";
-  rc = interpolate_run(job, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  return interpolate_run(job);
 }
 
 // Camera.project_dem (camera.py:967-1129) and Camera.rasterize (camera.py:858-883): the arguments are checked here, before
@@ -2992,8 +2954,7 @@ extern "C" int glh_stage_project_dem(int dev, const double* cam, const void* z, 
   if (layers < 0 || (layers > 0) != (values != nullptr))
     return fail(GLH_E_INVALID, "project_dem: %d layers %s values", layers, values ? "with" : "without");
   if (layers == 0 && !return_depth) return fail(GLH_E_INVALID, "project_dem: neither values nor the depth asked for");
-  if (z_dtype != GLH_PD_F64 && z_dtype != GLH_PD_F32)
-    return fail(GLH_E_UNSUPPORTED, "project_dem: z_dtype %d: 0 float64, 1 float32", z_dtype);
+  CHK(check_float_dtype("project_dem", "z_dtype", z_dtype));
   if (layers && (v_dtype < GLH_PD_F64 || v_dtype > GLH_PD_U16))
     return fail(GLH_E_UNSUPPORTED, "project_dem: v_dtype %d: 0 float64, 1 float32, 2 uint8, 3 uint16", v_dtype);
   if (cam[23] != 0.0) return fail(GLH_E_UNSUPPORTED, "project_dem: the camera is a raster grid");
@@ -3012,9 +2973,7 @@ extern "C" int glh_stage_project_dem(int dev, const double* cam, const void* z, 
       project_dem_memberships(job) >= lim)
     return fail(GLH_E_UNSUPPORTED, "project_dem: %d x %d cells (%lld with the tiles' overlap) into %g x %g pixels: fewer than "
                                    "2^31 of each are served (32-bit indices)", nx, ny, (long long)project_dem_memberships(job), w, h);
-  char msg[512] = "";
-  const int rc = project_dem_run(job, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  return project_dem_run(job);
 }
 
 extern "C" int glh_stage_rasterize(int dev, const int32_t* keys, int n, const double* values, int layers, int n_pixels,
@@ -3026,21 +2985,15 @@ extern "C" int glh_stage_rasterize(int dev, const int32_t* keys, int n, const do
     if (keys[i] < 0 || keys[i] >= n_pixels)
       return fail(GLH_E_INVALID, "rasterize: key %d of point %d outside [0, %d)", keys[i], i, n_pixels);
   const RasterizeJob job{dev, keys, n, values, layers, n_pixels, out, times_ms};
-  char msg[512] = "";
-  const int rc = rasterize_run(job, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  return rasterize_run(job);
 }
 
 // helpers.maximum_filter, helpers.gaussian_filter (helpers.py:347-430) and Raster.fill_crevasses (raster.py:1266-1291): the
 // arguments are checked here, before a device is touched; the kernels and the launches are glh_filters.hip's.
 static int check_filter_array(const char* who, const void* a, int dtype, int nx, int ny, const void* out) {
   if (!a || !out) return fail(GLH_E_INVALID, "%s: null argument", who);
-  if (nx < 1 || ny < 1) return fail(GLH_E_INVALID, "%s: %d x %d cells: at least one of each", who, nx, ny);
-  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
-    return fail(GLH_E_INVALID, "%s: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", who, nx, ny);
-  if (dtype != GLH_FILTER_F64 && dtype != GLH_FILTER_F32)
-    return fail(GLH_E_UNSUPPORTED, "%s: dtype %d: 0 float64, 1 float32", who, dtype);
-  return GLH_OK;
+  CHK(check_grid(who, nx, ny, 1));
+  return check_float_dtype(who, "dtype", dtype);
 }
 
 static int check_filter_window(const char* who, int size_y, int size_x, int mode) {
@@ -3068,17 +3021,11 @@ static int check_filter_weights(const char* who, const double* w0, int r0, const
   return GLH_OK;
 }
 
-static int run_filters(const FiltersJob& job) {
-  char msg[512] = "";
-  const int rc = filters_run(job, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
-}
-
 extern "C" int glh_stage_max_filter(int dev, const void* a, int dtype, int nx, int ny, const uint8_t* mask, int fill,
                                     int size_y, int size_x, int mode, void* out, double* times_ms) {
   CHK(check_filter_array("max_filter", a, dtype, nx, ny, out));
   CHK(check_filter_window("max_filter", size_y, size_x, mode));
-  return run_filters(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, mode, 0, nullptr, 0,
+  return filters_run(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, mode, 0, nullptr, 0,
                                 nullptr, 0, 0, out, times_ms});
 }
 
@@ -3087,7 +3034,7 @@ extern "C" int glh_stage_gaussian_filter(int dev, const void* a, int dtype, int 
                                          double* times_ms) {
   CHK(check_filter_array("gaussian_filter", a, dtype, nx, ny, out));
   CHK(check_filter_weights("gaussian_filter", w0, r0, w1, r1, mode));
-  return run_filters(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 0, 1, 1, 0, 1, w0, r0, w1, r1, mode, out,
+  return filters_run(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 0, 1, 1, 0, 1, w0, r0, w1, r1, mode, out,
                                 times_ms});
 }
 
@@ -3097,57 +3044,43 @@ extern "C" int glh_stage_fill_crevasses(int dev, const void* a, int dtype, int n
   CHK(check_filter_array("fill_crevasses", a, dtype, nx, ny, out));
   CHK(check_filter_window("fill_crevasses", size_y, size_x, max_mode));
   CHK(check_filter_weights("fill_crevasses", w0, r0, w1, r1, gauss_mode));
-  return run_filters(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, max_mode, 1, w0, r0,
+  return filters_run(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, max_mode, 1, w0, r0,
                                 w1, r1, gauss_mode, out, times_ms});
 }
 
 // Raster.gradient, Raster.hillshade (raster.py:1465-1474, :1249-1264) and helpers.polygons_to_mask (helpers.py:1701-1768):
 // the arguments are checked here, before a device is touched; the kernels and the launches are glh_terrain.hip's.
-static int check_terrain_grid(const char* who, int nx, int ny, int least) {
-  if (nx < least || ny < least) return fail(GLH_E_INVALID, "%s: %d x %d cells: at least %d on each axis", who, nx, ny, least);
-  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
-    return fail(GLH_E_INVALID, "%s: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", who, nx, ny);
-  return GLH_OK;
-}
-
-static int check_terrain_dem(const char* who, int dtype, double d0, double d1) {
+static int check_terrain_dem(const char* who, int nx, int ny, int dtype, double d0, double d1) {
+  CHK(check_grid(who, nx, ny, 2));
   if (!std::isfinite(d0) || !std::isfinite(d1) || d0 == 0.0 || d1 == 0.0)
     return fail(GLH_E_INVALID, "%s: cell sizes (%g, %g): finite and not zero", who, d0, d1);
-  if (dtype != GLH_TERRAIN_F64 && dtype != GLH_TERRAIN_F32)
-    return fail(GLH_E_UNSUPPORTED, "%s: dtype %d: 0 float64, 1 float32", who, dtype);
-  return GLH_OK;
+  return check_float_dtype(who, "dtype", dtype);
 }
 
 extern "C" int glh_stage_gradient(int dev, const void* z, int dtype, int nx, int ny, double d0, double d1, void* dzdx,
                                   void* dzdy, double* times_ms) {
   if (!z || !dzdx || !dzdy) return fail(GLH_E_INVALID, "gradient: null argument");
-  CHK(check_terrain_grid("gradient", nx, ny, 2));
-  CHK(check_terrain_dem("gradient", dtype, d0, d1));
-  char msg[512] = "";
-  const int rc = gradient_run(GradientJob{dev, z, dtype == GLH_TERRAIN_F32, nx, ny, d0, d1, dzdx, dzdy, times_ms}, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  CHK(check_terrain_dem("gradient", nx, ny, dtype, d0, d1));
+  return gradient_run(GradientJob{dev, z, dtype == GLH_TERRAIN_F32, nx, ny, d0, d1, dzdx, dzdy, times_ms});
 }
 
 extern "C" int glh_stage_hillshade(int dev, const void* z, int dtype, int nx, int ny, double d0, double d1, double vert_exag,
                                    const double* direction, double fraction, double* out, double* times_ms) {
   if (!z || !direction || !out) return fail(GLH_E_INVALID, "hillshade: null argument");
-  CHK(check_terrain_grid("hillshade", nx, ny, 2));
-  CHK(check_terrain_dem("hillshade", dtype, d0, d1));
+  CHK(check_terrain_dem("hillshade", nx, ny, dtype, d0, d1));
   if (!std::isfinite(vert_exag) || !std::isfinite(fraction) || !std::isfinite(direction[0]) || !std::isfinite(direction[1]) ||
       !std::isfinite(direction[2]))
     return fail(GLH_E_INVALID, "hillshade: vert_exag %g, fraction %g, direction (%g, %g, %g): all finite", vert_exag, fraction,
                 direction[0], direction[1], direction[2]);
-  char msg[512] = "";
   const HillshadeJob job{dev, z, dtype == GLH_TERRAIN_F32, nx, ny, d0, d1, vert_exag, {direction[0], direction[1], direction[2]},
                          fraction, out, times_ms};
-  const int rc = hillshade_run(job, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  return hillshade_run(job);
 }
 
 extern "C" int glh_stage_polygon_mask(int dev, const double* xy, int n_vertices, const int32_t* ring_off, int n_polygons,
                                       int n_holes, int nx, int ny, uint8_t* out, double* times_ms) {
   if (!xy || !ring_off || !out) return fail(GLH_E_INVALID, "polygon_mask: null argument");
-  CHK(check_terrain_grid("polygon_mask", nx, ny, 1));
+  CHK(check_grid("polygon_mask", nx, ny, 1));
   if (n_vertices < 1 || n_polygons < 1 || n_holes < 0 || (int64_t)n_polygons + n_holes >= ((int64_t)1 << 31))
     return fail(GLH_E_INVALID, "polygon_mask: %d vertices, %d polygon rings, %d hole rings", n_vertices, n_polygons, n_holes);
   const int rings = n_polygons + n_holes;
@@ -3160,9 +3093,7 @@ extern "C" int glh_stage_polygon_mask(int dev, const double* xy, int n_vertices,
                   (long long)ring_off[k + 1] - ring_off[k]);
   for (int64_t i = 0; i < 2 * (int64_t)n_vertices; ++i)
     if (!std::isfinite(xy[i])) return fail(GLH_E_INVALID, "polygon_mask: vertex %lld is not finite", (long long)(i / 2));
-  char msg[512] = "";
-  const int rc = polygon_mask_run(PolygonMaskJob{dev, xy, ring_off, n_polygons, n_holes, nx, ny, out, times_ms}, msg, sizeof msg);
-  return rc == GLH_OK ? GLH_OK : fail(rc, "%s", msg);
+  return polygon_mask_run(PolygonMaskJob{dev, xy, ring_off, n_polygons, n_holes, nx, ny, out, times_ms});
 }
 
 extern "C" int glh_stage_resample(int dev, const double* weights, int n, double u, int64_t* idx) {
