@@ -4,6 +4,7 @@ Drop-in names for that path only (see DESIGN.md for scope):
 
     from glimpse_amd import Camera, Image, Observer, CartesianMotion, Tracker, Tracks
     (+ CylindricalMotion, TangentCartesianMotion, TangentCylindricalMotion)
+    from glimpse_amd.optimize import ObserverCameras, RotationMatchesXYZ   # orienting an image sequence
 
 The compute runs in hand-written HIP kernels behind a C ABI (include/glimpse_hip.h,
 glimpse_amd/lib/libglimpse_hip.so, bound with ctypes in glimpse_amd._lib).  There is no CPU
@@ -14,12 +15,15 @@ from .filters import gaussian_filter, maximum_filter
 from .image import Image
 from .motion import (CartesianMotion, CylindricalMotion, Motion, TangentCartesianMotion,
                      TangentCylindricalMotion)
+from . import optimize
 from .observer import Observer
+from .optimize import Matches, ObserverCameras, RotationMatches, RotationMatchesXY, RotationMatchesXYZ
 from .raster import Raster, RasterInterpolant
 from .tracker import Tracker
 from .tracks import Tracks
 
 __all__ = ["Camera", "Image", "Observer", "Motion", "CartesianMotion", "CylindricalMotion",
            "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "RasterInterpolant", "Tracker", "Tracks", "maximum_filter",
-           "gaussian_filter"]
+           "gaussian_filter", "optimize", "Matches", "RotationMatches", "RotationMatchesXY", "RotationMatchesXYZ",
+           "ObserverCameras"]
 __version__ = "0.1.0"

@@ -164,6 +164,10 @@ SIGNATURES = {
     "glh_stage_gradient": (_I, [_I, _P, _I, _I, _I, _D, _D, _P, _P, _P]),
     "glh_stage_hillshade": (_I, [_I, _P, _I, _I, _I, _D, _D, _D, _P, _D, _P, _P]),
     "glh_stage_polygon_mask": (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
+    "glh_stage_uv_to_xy": (_I, [_I, _P, _P, _I, _P]),
+    "glh_orient_create": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "glh_orient_eval": (_I, [_P, _P, _P, _P, _P, _P]),
+    "glh_orient_destroy": (_I, [_P]),
 }
 
 _lib = None
@@ -729,6 +733,16 @@ def stage_unproject(cam, uv, depth=None, directions=True, device_id=0):
     return xyz
 
 
+def stage_uv_to_xy(cam, uv, device_id=0):
+    """Camera._uv_to_xy (camera.py:1510-1519): uv (n, 2) -> normalised camera coordinates (n, 2)."""
+    cam = _arr(cam, np.float64, (CAM_LEN,))
+    uv = _arr(uv, np.float64)
+    xy = np.empty((len(uv), 2))
+    if len(uv):
+        check(load().glh_stage_uv_to_xy(device_id, _ptr(cam), _ptr(uv), len(uv), _ptr(xy)))
+    return xy
+
+
 REPROJECT_METHODS = {"linear": 0, "nearest": 1}
 REPROJECT_DTYPES = {"uint8": (8, 0), "uint16": (16, 0), "float32": (32, 1), "float64": (64, 1)}
 
@@ -1205,3 +1219,53 @@ def stage_polygon_mask(xy, ring_off, n_polygons, n_holes, nx, ny, device_id=0, r
     check(load().glh_stage_polygon_mask(device_id, _ptr(xy), len(xy), _ptr(ring_off), int(n_polygons), int(n_holes), int(nx),
                                         int(ny), _ptr(out), _ptr(times) if return_times else None))
     return _timed(out.view(bool), POLYGON_MASK_TIMES, times, return_times)
+
+
+ORIENT_TIMES = ("upload", "map", "reduce", "download")
+
+
+class Orient:
+    """The matches of an image sequence on the device (glh_orient_create): uploaded once, evaluated at many view
+    directions (optimize.ObserverCameras.fit).  `pair_i`, `pair_j` (n_pairs,): the images of every pair; `pair_offset`
+    (n_pairs + 1,): pair p's matches are rows pair_offset[p] .. pair_offset[p + 1] of `xy_i`, `xy_j` (N, 2), the
+    normalised camera coordinates of a match in image i and in image j."""
+
+    def __init__(self, n_images, pair_i, pair_j, pair_offset, xy_i, xy_j, device_id=0):
+        self.n_images = int(n_images)
+        self._h = C.c_void_p()
+        pair_i, pair_j = _arr(pair_i, np.int32), _arr(pair_j, np.int32)
+        pair_offset = _arr(pair_offset, np.int64, (len(pair_i) + 1,))
+        xy_i, xy_j = _arr(xy_i, np.float64).reshape(-1, 2), _arr(xy_j, np.float64).reshape(-1, 2)
+        # (the library is not told N: the rows the offsets name must exist; what else is wrong with them it reports)
+        if pair_i.ndim != 1 or pair_j.shape != pair_i.shape or len(xy_i) != len(xy_j) or len(xy_i) < pair_offset.max():
+            raise ValueError("pair_i / pair_j (n_pairs,) and xy_i / xy_j (N, 2) with N >= pair_offset.max()")
+        check(load().glh_orient_create(int(device_id), self.n_images, len(pair_i), _ptr(pair_i), _ptr(pair_j),
+                                       _ptr(pair_offset), _ptr(xy_i), _ptr(xy_j), C.byref(self._h)))
+
+    def eval(self, R, Rprime, return_times=False):
+        """(objective, gradient (n_images, 3)) of the matches at the rotation matrices `R` (n_images, 3, 3) and their
+        derivatives `Rprime` (n_images, 3, 3, 3) ([r][w][k], Camera.Rprime)."""
+        if not self._h:
+            raise GlhError(-4, "the handle is closed")
+        R = _arr(R, np.float64, (self.n_images, 3, 3))
+        Rprime = _arr(Rprime, np.float64, (self.n_images, 3, 3, 3))
+        objective, gradient, times = C.c_double(0.0), np.empty((self.n_images, 3)), np.zeros(len(ORIENT_TIMES))
+        check(load().glh_orient_eval(self._h, _ptr(R), _ptr(Rprime), C.byref(objective), _ptr(gradient), _ptr(times)))
+        return _timed((objective.value, gradient), ORIENT_TIMES, times, return_times, extend=True)
+
+    def close(self):
+        if self._h:
+            handle, self._h = self._h, C.c_void_p()
+            check(load().glh_orient_destroy(handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

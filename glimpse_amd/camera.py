@@ -8,7 +8,9 @@ and the Oulu undistortion, :1198-1337) runs on the GPU as well (`glh_stage_unpro
 the per-frame path.  Of the rendering methods, `project_dem` (camera.py:967-1129: the image and the depth map a
 camera records of a DEM) and `rasterize` (:858-883: points to a mean image) are served, on the GPU
 (`glh_stage_project_dem`, `glh_stage_rasterize`); `project_dem` without the per-tile rescaling (`scale_limits` other than
-(1, 1), which fails in the reference itself).  Calibration methods are out of scope.
+(1, 1), which fails in the reference itself).  `Rprime` and the camera-coordinate halves of the projection (`_uv_to_xy`
+on the GPU, `_xy_to_uv`, `_xy_to_xyz`, `_xyz_to_xy` on the host) serve `glimpse_amd.optimize`; the other calibration
+methods are out of scope.
 """
 import numpy as np
 
@@ -28,6 +30,39 @@ def _fmt(value, length, default=None, dtype=float):
         fill = v[-1] if default is None else default
         return np.concatenate((v, np.full(length - len(v), fill, dtype=dtype)))
     return v[:length]
+
+
+def rotations(viewdirs):
+    """`Camera.R` (n, 3, 3) and `Camera.Rprime` (n, 3, 3, 3) of the view directions `viewdirs` (n, 3) at once, every entry
+    by the expression of camera.py:263-280 and :290-329 in its order, so that they equal the properties bit for bit
+    (optimize.ObserverCameras evaluates all images' per callback)."""
+    rad = np.deg2rad(np.asarray(viewdirs, dtype=float).reshape(-1, 3))
+    C, S = np.cos(rad).T, np.sin(rad).T
+    zero = np.zeros(rad.shape[0])
+    R = np.array([
+        [C[0] * C[2] + S[0] * S[1] * S[2], C[0] * S[1] * S[2] - C[2] * S[0], -C[1] * S[2]],
+        [C[2] * S[0] * S[1] - C[0] * S[2], S[0] * S[2] + C[0] * C[2] * S[1], -C[1] * C[2]],
+        [C[1] * S[0], C[0] * C[1], S[1]],
+    ])
+    # [w][r][k] as the reference writes it down, stacked along axis 1 into [r][w][k]
+    Rprime = np.array([
+        [
+            [C[0] * S[1] * S[2] - S[0] * C[2], S[0] * S[2] + C[0] * S[1] * C[2], C[0] * C[1]],
+            [-S[0] * S[1] * S[2] - C[0] * C[2], C[0] * S[2] - S[0] * S[1] * C[2], -S[0] * C[1]],
+            [zero, zero, zero],
+        ],
+        [
+            [S[0] * C[1] * S[2], S[0] * C[1] * C[2], -S[0] * S[1]],
+            [C[0] * C[1] * S[2], C[0] * C[1] * C[2], -C[0] * S[1]],
+            [S[1] * S[2], S[1] * C[2], C[1]],
+        ],
+        [
+            [S[0] * S[1] * C[2] - C[0] * S[2], -S[0] * S[1] * S[2] - C[0] * C[2], zero],
+            [S[0] * S[2] + C[0] * S[1] * C[2], S[0] * C[2] - C[0] * S[1] * S[2], zero],
+            [-C[1] * C[2], C[1] * S[2], zero],
+        ],
+    ])
+    return np.ascontiguousarray(R.transpose(2, 0, 1)), np.ascontiguousarray(Rprime.transpose(3, 1, 0, 2)) * (np.pi / 180)
 
 
 class Camera:
@@ -105,6 +140,11 @@ class Camera:
     def R(self):
         """camera.py:239-280."""
         return synth.rotation_matrix(self.viewdir)
+
+    @property
+    def Rprime(self):
+        """camera.py:283-329: the derivative of `R` with respect to `viewdir`, (3, 3, 3) as [r][w][k]."""
+        return rotations(self.viewdir)[1][0]
 
     @property
     def vector24(self):
@@ -222,6 +262,70 @@ class Camera:
         uv = np.atleast_2d(np.asarray(uv, dtype=float))
         d = None if (isinstance(depth, (int, float)) and depth == 1) else depth
         return _lib.stage_unproject(self.vector24, uv, depth=d, directions=directions)
+
+    # ---- the halves of the projection either side of the camera coordinates (camera.py:1138-1196, :1435-1519)
+    def _distort(self, xy):
+        """camera.py:1180-1196 with :1138-1178 on the host (a companion of the classes in `optimize`; `xyz_to_uv`'s own
+        distortion is the projection kernel's)."""
+        xy = np.asarray(xy, dtype=float)
+        if not (self.k.any() or self.p.any()):
+            return xy
+        r2 = np.sum(xy ** 2, axis=1)
+        dxy = xy.copy()
+        if self.k.any():
+            def series(k):  # 1 + k[0] r2 + k[1] r2 r2 + k[2] r2 r2 r2 over the terms whose k is set, left to right
+                total = np.ones(len(r2))
+                for i in range(3):
+                    if k[i]:
+                        term = k[i] * r2
+                        for _ in range(i):
+                            term = term * r2
+                        total = total + term
+                return total
+
+            dr = series(self.k[0:3])
+            if self.k[3:6].any():
+                dr = dr / series(self.k[3:6])
+            dxy = dxy * np.reshape(dr, (-1, 1))
+        if self.p.any():
+            xty = xy[:, 0] * xy[:, 1]
+            dtx = 2 * xty * self.p[0] + self.p[1] * (r2 + 2 * xy[:, 0] ** 2)
+            dty = self.p[0] * (r2 + 2 * xy[:, 1] ** 2) + 2 * xty * self.p[1]
+            dxy = dxy + np.column_stack((dtx, dty))
+        return dxy
+
+    def _xyz_to_xy(self, xyz, directions=False, return_depth=False):
+        """camera.py:1435-1470 on the host, without the elevation correction (`optimize` passes ray directions)."""
+        xyz = np.atleast_2d(np.asarray(xyz, dtype=float))
+        if not directions and isinstance(self.correction, dict):
+            raise NotImplementedError("_xyz_to_xy with an elevation correction: use xyz_to_uv")
+        R = self.R
+        d = xyz if directions else xyz - self.xyz
+        xyz_c = np.column_stack([R[r, 0] * d[:, 0] + R[r, 1] * d[:, 1] + R[r, 2] * d[:, 2] for r in range(3)])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            xy = xyz_c[:, 0:2] / xyz_c[:, 2:3]
+        xy[xyz_c[:, 2] <= 0] = np.nan
+        return (xy, xyz_c[:, 2]) if return_depth else xy
+
+    def _xy_to_xyz(self, xy, directions=True, depth=1):
+        """camera.py:1472-1497 on the host: R.T[:, 0:2] @ xy + R.T[:, 2], term by term."""
+        xy = np.atleast_2d(np.asarray(xy, dtype=float))
+        R = self.R
+        xyz = np.column_stack([(R[0, k] * xy[:, 0] + R[1, k] * xy[:, 1]) + R[2, k] for k in range(3)])
+        if not isinstance(depth, (int, float)) or depth != 1:
+            xyz *= np.atleast_1d(depth).reshape(-1, 1)
+        if not directions:
+            xyz += self.xyz
+        return xyz
+
+    def _xy_to_uv(self, xy):
+        """camera.py:1499-1508 on the host."""
+        return self._distort(xy) * self.f + (self.imgsz / 2 + self.c)
+
+    def _uv_to_xy(self, uv):
+        """camera.py:1510-1519 on the device (`glh_stage_uv_to_xy`): `uv_to_xyz` stopped before the rotation -- the
+        closed form for k1 alone, else the Oulu fixed point, 20 iterations."""
+        return _lib.stage_uv_to_xy(self.vector24, np.atleast_2d(np.asarray(uv, dtype=float)))
 
     # ---- rendering (GPU)
     def rasterize(self, uv, values):

@@ -19,6 +19,7 @@
 #include "glh_point_variants.h"
 #include "glh_project_dem.h"
 #include "glh_horizon.h"
+#include "glh_orient.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
@@ -2845,6 +2846,67 @@ extern "C" int glh_stage_horizon(int dev, const void* z, int z_dtype, int nx, in
   const HorizonJob job{dev, z, z_dtype == GLH_VIEWSHED_F32, nx, ny, xlim0, ylim0, d0, d1, origins, starts, ends, m, n,
                        correction != 0, radius, refraction, cell, dz, times_ms};
   return horizon_run(job);
+}
+
+// optimize.ObserverCameras.fit's objective and gradient (optimize.py:2047-2072) and Camera._uv_to_xy (camera.py:1510-1519):
+// the arguments are checked here, before a device is touched; the kernels and the launches are glh_orient.hip's.
+struct glh_orient {
+  OrientHandle* h;
+};
+
+extern "C" int glh_orient_create(int dev, int n_images, int n_pairs, const int32_t* pair_i, const int32_t* pair_j,
+                                 const int64_t* pair_offset, const double* xy_i, const double* xy_j, glh_orient** handle) {
+  if (!handle) return fail(GLH_E_INVALID, "orient: null handle pointer");
+  *handle = nullptr;
+  if (n_images < 1 || n_pairs < 0) return fail(GLH_E_INVALID, "orient: %d images, %d pairs", n_images, n_pairs);
+  if (n_images >= (1 << 24) || n_pairs >= (1 << 30))
+    return fail(GLH_E_INVALID, "orient: %d images, %d pairs: fewer than 2^24 images and 2^30 pairs are served", n_images, n_pairs);
+  if (!pair_offset || (n_pairs && (!pair_i || !pair_j))) return fail(GLH_E_INVALID, "orient: null pair arrays");
+  if (pair_offset[0] != 0) return fail(GLH_E_INVALID, "orient: pair_offset[0] is %lld, not 0", (long long)pair_offset[0]);
+  int64_t chunks = 0;
+  for (int p = 0; p < n_pairs; ++p) {
+    if (pair_offset[p + 1] < pair_offset[p])
+      return fail(GLH_E_INVALID, "orient: pair_offset decreases at pair %d (%lld after %lld)", p, (long long)pair_offset[p + 1],
+                  (long long)pair_offset[p]);
+    if (pair_i[p] < 0 || pair_i[p] >= n_images || pair_j[p] < 0 || pair_j[p] >= n_images)
+      return fail(GLH_E_INVALID, "orient: pair %d joins images %d and %d of %d", p, pair_i[p], pair_j[p], n_images);
+    chunks += (pair_offset[p + 1] - pair_offset[p] + OR_CHUNK - 1) / OR_CHUNK;
+  }
+  if (chunks >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "orient: %lld matches: fewer than 2^31 chunks of %d are served", (long long)pair_offset[n_pairs],
+                OR_CHUNK);
+  if (pair_offset[n_pairs] > 0 && (!xy_i || !xy_j)) return fail(GLH_E_INVALID, "orient: null match coordinates");
+  glh_orient* g = new (std::nothrow) glh_orient{nullptr};
+  if (!g) return fail(GLH_E_NOMEM, "orient: no memory for a handle");
+  const int rc = orient_create(dev, n_images, n_pairs, pair_i, pair_j, pair_offset, xy_i, xy_j, &g->h);
+  if (rc != GLH_OK) {
+    delete g;
+    return rc;
+  }
+  *handle = g;
+  return GLH_OK;
+}
+
+extern "C" int glh_orient_eval(glh_orient* handle, const double* R, const double* Rprime, double* objective, double* gradient,
+                               double* times_ms) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "orient: null handle");
+  if (!R || !Rprime || !objective || !gradient) return fail(GLH_E_INVALID, "orient: null argument");
+  return orient_eval(handle->h, R, Rprime, objective, gradient, times_ms);
+}
+
+extern "C" int glh_orient_destroy(glh_orient* handle) {
+  if (!handle) return GLH_OK;
+  orient_destroy(handle->h);
+  delete handle;
+  return GLH_OK;
+}
+
+extern "C" int glh_stage_uv_to_xy(int dev, const double* cam, const double* uv, int n, double* xy) {
+  if (!cam || !uv || !xy || n <= 0) return fail(GLH_E_INVALID, "uv_to_xy: bad argument");
+  if (cam[23] != 0.0) return fail(GLH_E_UNSUPPORTED, "uv_to_xy of a raster grid is not built");
+  CamDev cd;
+  expand_camera(cam, &cd);
+  return uv_to_xy_run(dev, cd, uv, n, xy);
 }
 
 // Raster.sample(grid=True) / resample, Raster.resize and RasterInterpolant (raster.py:1042-1083, :1178-1187, :1673-1700):

@@ -668,6 +668,33 @@ int glh_stage_raster_interpolate(int device_id, int nx, int ny, const double* m0
                                  const glh_regrid_src* m1_src, const double* s0, const double* s1,
                                  const glh_regrid_src* s1_src, const double* xo, const double* yo, double scale,
                                  double scale2, double third, double ratio, double* z, double* sigma, double* times_ms);
+/* Camera._uv_to_xy (camera.py:1510-1519): uv [n][2] -> normalised camera coordinates xy [n][2]; the undistortion of
+ * glh_stage_unproject (closed form for k1 alone, else 20 Oulu iterations), stopped before the rotation.               */
+int glh_stage_uv_to_xy(int device_id, const double* cam, const double* uv, int n, double* xy);
+
+/* ---- optimize.ObserverCameras.fit: the objective and its gradient (optimize.py:2047-2072) ----------------------------
+ * A handle holds the point matches of a sequence on the device; they are uploaded once and evaluated at many view
+ * directions.  n_pairs >= 0 image pairs (pair_i[p], pair_j[p]), each an index into the n_images >= 1 images; the matches
+ * of pair p are rows pair_offset[p] .. pair_offset[p + 1] (int64 [n_pairs + 1], from 0, not decreasing) of xy_i and xy_j
+ * [N][2]: the normalised camera coordinates of a match in image i and in image j.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, n_images < 1, 2^24 images or 2^30 pairs or more,
+ * offsets that do not start at 0 or decrease, an image index outside 0 .. n_images - 1, 2^31 chunks or more).           */
+typedef struct glh_orient glh_orient;
+int glh_orient_create(int device_id, int n_images, int n_pairs, const int32_t* pair_i, const int32_t* pair_j,
+                      const int64_t* pair_offset, const double* xy_i, const double* xy_j, glh_orient** handle);
+/* One evaluation at the rotation matrices R [n_images][9] (Camera.R, row-major) and their derivatives Rprime
+ * [n_images][27] (Camera.Rprime, [r][w][k]), both made by the caller.  Per match of pair (i, j), with x^ = [x, y, 1]:
+ * d_i = R_i^T x^_i times 1 / sqrt((a^2 + b^2) + c^2), d_j likewise, e = d_i - d_j; *objective = sum |e|;
+ * g[w] = sum_r sign(e[r]) (Rprime_i[r][w] . x^_i) is added to gradient[i] and subtracted from gradient[j]
+ * (gradient [n_images][3]; the reference's own formula: Rprime of image i only, no derivative of the normalisation).
+ * float64, no contraction, no atomics: the order of every sum depends on the pair sizes alone, so two
+ * evaluations give the same bytes.  times_ms (or NULL) [4]: HIP-event milliseconds -- [0] upload of R and Rprime, [1]
+ * the map kernel, [2] the reduce kernel, [3] download.                                                               */
+int glh_orient_eval(glh_orient* handle, const double* R, const double* Rprime, double* objective, double* gradient,
+                    double* times_ms);
+/* Frees the handle and its device memory (NULL: nothing).                                                              */
+int glh_orient_destroy(glh_orient* handle);
+
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
 
