@@ -364,33 +364,7 @@ def test_fused_step_evolves_every_motion_model_like_the_staged_kernels(gridded, 
         assert (fused["p"][tangent][..., 5] == 0).all()
 
 
-def _multi_observer_case(O, T=4, P=3, N=1500, seed=5):
-    """O stations around one scene (a nadir camera with k1-k3, the oblique station of C5, a second nadir station off to
-    the side with another focal length, a second oblique station), points every one of them sees."""
-    from glimpse_amd import synth
-
-    imgsz = (512, 512)
-    cams = [synth.nadir_camera(imgsz, f=1000.0, height=100.0, k=(0.05, -0.01, 0.002, 0, 0, 0)),
-            synth.pack_camera(imgsz=imgsz, f=1200.0, k=(0.03, 0, 0), xyz=(40, -30, 90), viewdir=(-53.13, -60.9, 0)),
-            synth.nadir_camera(imgsz, f=850.0, height=110.0, k=(0.02, 0, 0, 0, 0, 0), xyz_offset=(4.0, -3.0)),
-            synth.pack_camera(imgsz=imgsz, f=1100.0, k=(0, 0, 0), xyz=(-35, 25, 95), viewdir=(125.5, -65.6, 0))][:O]
-    scene = synth.default_scene(cams[0], seed=seed, velocity=(0.15, 0.0), n_frames=T, margin=60.0)
-    frames = [[scene.render(cam, float(t)) for t in range(T)] for cam in cams]
-    rng = np.random.default_rng(seed)
-    xy = []
-    while len(xy) < P:
-        cand = rng.uniform(-6, 6, 2)
-        uv = [synth.project(cam, np.array([[cand[0], cand[1], 0.0]]))[0] for cam in cams]
-        if all(90 < u[0] < imgsz[0] - 90 and 90 < u[1] < imgsz[1] - 90 for u in uv):
-            xy.append(cand)
-    params = np.zeros((P, 18))
-    params[:, 0:2] = xy
-    params[:, 2:4] = 0.15
-    params[:, 4:7] = (0.15, 0.0, 0.0)
-    params[:, 7:10] = (0.1, 0.1, 0.03)
-    params[:, 13:16] = (0.04, 0.04, 0.01)
-    params[:, 17] = 0.4
-    return dict(cams=cams, frames=frames, params=params, imgsz=imgsz, T=T, P=P, N=N, sigmas=[0.3, 0.45, 0.35, 0.5][:O])
+from tests.launch_shape_cases import multi_observer_case as _multi_observer_case  # noqa: E402  (shared with test_gpu_launch_shapes.py)
 
 
 @pytest.mark.parametrize("O", [3, 4])
