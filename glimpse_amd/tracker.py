@@ -16,6 +16,7 @@ gives the reference's particles, indices and posteriors.  `rng="philox"` draws o
 import datetime
 import operator
 import os
+import time
 import warnings as _warnings
 
 import numpy as np
@@ -25,7 +26,7 @@ from .motion import (CartesianMotion, CylindricalMotion, ModelBlock, _RowView, T
                      params_table)
 from .raster import Raster
 from .timeutil import _US, _offsets_us, nearest_in_sorted  # noqa: F401  (re-exported)
-from .tracks import Tracks
+from .tracks import Tracks, merge_parts
 
 _ERRORS = (
     (_lib.PT_NAN, ValueError, "Some particles have missing (NaN) values"),
@@ -180,16 +181,12 @@ class _FrameFeed:
         return self.tracker.observers[job[0]].images[job[1]]
 
     def _pixels(self, job):
-        import time
-
         t0 = time.perf_counter()
         obs = self.tracker.observers[job[0]]
         a = np.ascontiguousarray(obs.images[job[1]].read(cache=obs.cache))  # (dtype checked by the upload)
         return a, time.perf_counter() - t0
 
     def _to_device(self, k, a, seconds):
-        import time
-
         job = self.jobs[k][0]
         self.stats["decode_seconds"] += seconds
         t0 = time.perf_counter()
@@ -200,8 +197,6 @@ class _FrameFeed:
         self.done[k] = True
 
     def _wait(self, fn):
-        import time
-
         t0 = time.perf_counter()
         out = fn()
         self.stats["waits"] += 1
@@ -216,8 +211,6 @@ class _FrameFeed:
 
     def _pump_processes(self, until):
         """Keep the decoders fed; upload what they have finished; block until jobs [pos, until] are on the device."""
-        import time
-
         pool = self.procs
         while True:
             self._reclaim()
@@ -310,6 +303,239 @@ class _FrameFeed:
             if self.pos < len(self.jobs):
                 self.procs.drain()  # (a run that ended early: nothing of it stays in the ring)
             self.procs = None
+
+
+def _blank(arrays, p, frame):
+    """Row `p` of every array that is there is NaN from `frame` on: a failed track ends where it failed."""
+    for a in arrays:
+        if a is not None:
+            a[p, frame:] = np.nan
+
+
+def _failures(status, err_frame, arrays):
+    """The device's status words as results: per track the exception of the first bit set, in `_ERRORS` order (None
+    for a track that ran through), and its rows of `arrays` blanked from the frame where it failed."""
+    errors = [None] * len(status)
+    for p in np.nonzero(status)[0]:
+        errors[p] = next((cls(msg) for bit, cls, msg in _ERRORS if status[p] & bit), None)
+        _blank(arrays, p, int(err_frame[p]))
+    return errors
+
+
+class _Plan:
+    """Which tracks start, run and end at which time step, and which frames ONE fused launch can take: everything the
+    frame loop decides from `has` (T, O: observer o has an image at step t), `observer_mask` (P, O), the templates'
+    time steps and the resampling method -- computed once, before the loop, without a device."""
+
+    def __init__(self, has, observer_mask, template_indices, resample_method):
+        # per-track [first, last] window (tracker.py:321-325)
+        observed = (has[None, :, :] & observer_mask[:, None, :]).any(axis=2)  # (P, T)
+        first = observed.argmax(axis=1)
+        last = len(has) - 1 - observed[:, ::-1].argmax(axis=1)
+        empty = ~observed.any(axis=1)
+        first[empty], last[empty] = 0, -1
+        self.first, self.last, self.empty = first, last, empty
+        self.lo, self.hi = int(first[~empty].min()) if (~empty).any() else 0, int(last.max())
+        self.uniform = bool(observer_mask.all()) and bool((first == first[0]).all()) and bool((last == last[0]).all())
+        self.systematic = resample_method == "systematic"
+        # common[i]: every track is running and no template starts at frame i -- ONE fused launch does evolve +
+        # likelihood + resample + moments (glh_step)
+        steps = np.arange(len(has))
+        self.common = ((first[:, None] < steps) & (steps <= last[:, None])).all(axis=0) \
+            & ~np.isin(steps, template_indices) & (self.uniform and self.systematic)
+
+    def starting(self, i):
+        return (self.first == i) & ~self.empty
+
+    def running(self, i):
+        return (self.first < i) & (i <= self.last)
+
+    def run_end(self, i, through):
+        """The last frame of the run of common frames that starts at `i` and ends by `through` (and the sequence)."""
+        j, limit = i, min(self.hi, through)
+        while j + 1 <= limit and self.common[j + 1]:
+            j += 1
+        return j
+
+
+class _BatchRun:
+    """The frame loop (tracker.py:326-357) for all tracks of one device batch at once: `execute` makes attempts (one `run`
+    on the device RNG, the replay loop on the np.random stream) until no search tile outgrows automatic workspaces.
+    `ctx`, `dim`: the context in use and its workspace side; `warn_log`, `out_particles`, `out_weights`: of the last run."""
+
+    def __init__(self, tracker, plan, motion_models, matching, has, template_indices, taus, ctx, dim, observer_mask, opts):
+        self.tracker, self.plan, self.models, self.matching, self.has = tracker, plan, motion_models, matching, has
+        self.template_indices, self.taus, self.ctx, self.dim = template_indices, taus, ctx, dim
+        self.observer_mask, self.tile_size = observer_mask, opts["tile_size"]  # (the mask as a (P, O) array)
+        self.return_covariances, self.return_particles = opts["return_covariances"], opts["return_particles"]
+        self.rng, self.seed, self.point_offset = opts["rng"], opts["seed"], opts["point_offset"]
+        self.ntracks, self.n, self.ntimes = len(motion_models), motion_models[0].n, len(matching)
+        self.method = tracker.resample_method
+        self.images = [[m if m is not None else -1 for m in row] for row in matching]  # (per time step, -1: none)
+        self.warn_log = {}  # track -> its warnings (most tracks have none)
+        self.outgrown = False  # a search tile did not fit the workspaces (this attempt)
+        self.out_particles = self.out_weights = None
+
+    def execute(self):
+        """(point status, point error frame) of the attempt that stands."""
+        state0 = np.random.get_state() if self.rng == "numpy" else None
+        while True:
+            self.outgrown = False
+            out = self.attempt(state0)
+            if not self.outgrown or self.tracker.max_search_dim is not None:
+                break
+            # an automatic workspace was too small for some search tile (that observer was skipped on that frame):
+            # nothing of this attempt is kept -- same draws, larger workspaces, within what the kernels take and the
+            # device's memory allows (beyond that the run stands as it is, with its 'observer skipped' warnings).  Only
+            # the context of this shape remembers the size: a diverging track does not enlarge later, unrelated runs.
+            grown = self.tracker._fit_dim(2 * self.dim, self.tracker._dim_limit(self.ntracks))
+            if grown <= self.dim:
+                break
+            try:
+                # (the context in use stays until the larger one exists: if that cannot be made, its results stand)
+                bigger = self.tracker._context(self.ntracks, self.n, self.ntimes, self.tile_size, grown, keep_old=True)
+            except (_lib.GlhError, MemoryError):
+                break
+            self.ctx, self.dim = bigger, grown
+        return out
+
+    def attempt(self, state0):
+        """One pass over the sequence: `run(None)` on the device RNG, or the replay loop on the np.random stream."""
+        if self.rng == "philox":
+            return self.run(None)
+        # The reference stops drawing for a track at the frame where it fails, which shifts
+        # the stream of the tracks after it: replay until the assumed consumption is consistent.
+        first, last, models = self.plan.first, self.plan.last, self.models
+        stops = np.stack((last, last, last), axis=1)
+        for _ in range(self.ntracks + 1):
+            np.random.set_state(state0)
+            draws = self.tracker._draw_numpy(self.ntracks, self.n, first, last, stops,
+                                             per_particle_u=not self.plan.systematic, models=models)
+            status, err_frame = out = self.run(draws)
+            new_stops = np.stack((last, last, last), axis=1)
+            for p in np.nonzero(status)[0]:
+                e = int(err_frame[p])
+                # a dem / dem_sigma raster that does not cover the initial positions raises inside
+                # initialize_particles right after randn(n, 2) (motion.py:158): nothing else is drawn
+                gridded = isinstance(models[p].dem, Raster) or isinstance(models[p].dem_sigma, Raster)
+                if e == first[p] and status[p] & _lib.PT_RASTER_OOB and gridded:
+                    new_stops[p, 2] = -1
+                new_stops[p, 0] = e
+                new_stops[p, 1] = e if (status[p] & _lib.PT_RESAMPLE_CLAMP and not status[p] & 0x77) else e - 1
+            if (new_stops == stops).all():
+                break
+            stops = new_stops
+        return out
+
+    def set_active(self, mask):
+        self.ctx.set_active(None if (self.plan.uniform and mask.all()) else mask.astype(np.uint8))
+
+    def note_skips(self, running, status):
+        for o in range(len(status)):
+            for p in np.nonzero(running & (status[o] == _lib.OBS_OUT_OF_BOUNDS))[0]:
+                self.warn_log.setdefault(int(p), []).append(UserWarning(_OOB_WARNING))
+            for p in np.nonzero(running & (status[o] == _lib.OBS_TILE_TOO_LARGE))[0]:
+                self.outgrown = True
+                self.warn_log.setdefault(int(p), []).append(RuntimeWarning(
+                    f"search tile exceeds max_search_dim={self.dim}; observer {o} skipped"))
+
+    def configure(self, draws):
+        """A new sequence on the context in use; returns its frame feed."""
+        ctx, mask = self.ctx, self.observer_mask
+        ctx.begin_sequence(self.ntracks, self.n, self.tile_size)
+        feed = self.tracker._frame_feed(ctx, self.matching)  # (frames from files are decoded while the frames before them are tracked)
+        self.tracker._upload_surfaces(ctx, self.models)
+        ctx.set_motion(params_table(self.models))
+        ctx.set_observer_mask(None if mask.all() else mask.astype(np.uint8))
+        ctx.set_point_offset(self.point_offset)
+        # device-RNG runs have no reference stream to be bit-exact with: fast arithmetic (GLH_MATH_FAST)
+        ctx.set_math("fast" if draws is None else "exact")
+        ctx.track_covariances(bool(self.return_covariances))  # (runs of frames in one call record them on the way)
+        self.warn_log.clear()
+        shape = (self.ntracks, self.ntimes, self.n)
+        self.out_particles = np.full(shape + (6,), np.nan) if self.return_particles else None
+        self.out_weights = np.full(shape, np.nan) if self.return_particles else None
+        return feed
+
+    def run(self, draws):
+        """Every frame of the sequence, for all tracks at once; returns (point status, point error frame)."""
+        ctx, plan = self.ctx, self.plan
+        feed = self.configure(draws)
+        i = plan.lo
+        deferred = []  # runs of common frames whose status words are read after the loop
+        while i <= plan.hi:
+            through = feed.need(i)  # the frames of time steps <= through are resident
+            ctx.set_frame(i)
+            running = plan.running(i)
+            window = plan.starting(i) | running
+            if plan.common[i] and draws is None and not self.return_particles:
+                # device RNG: the whole run of common frames in one call (glh_track: the launches are
+                # enqueued back to back, no host round trip per frame) -- as far as the frames are resident:
+                # a sequence read from files is tracked while its later frames are still being decoded.  Every
+                # frame keeps its own status words, so the per-frame warnings are read afterwards.
+                j = plan.run_end(i, through)
+                self.set_active(window)
+                ctx.track(list(range(i, j + 1)), self.taus[i - 1:j], self.images[i:j + 1], seed=self.seed)
+                feed.stats["track_calls"] = feed.stats.get("track_calls", 0) + 1
+                deferred.append((i, j))
+                i = j + 1
+                continue
+            if plan.common[i]:
+                self.common_frame(i, draws, window, running)
+            else:
+                self.general_frame(i, draws, window, running)
+            self.frame_outputs(i, window)
+            i += 1
+        feed.close()
+        self.deferred_statuses(deferred)
+        return ctx.point_status(), ctx.point_error_frame()
+
+    def common_frame(self, i, draws, window, running):
+        """ONE fused launch (glh_step) for a frame where every track is running and no template starts."""
+        self.set_active(window)
+        drawn = dict(seed=self.seed) if draws is None else dict(normals=draws["evolve"][i], u=draws["u"][i])
+        self.ctx.step(i, self.taus[i - 1], self.images[i], **drawn)
+        self.note_skips(running, self.ctx.observer_status())
+
+    def general_frame(self, i, draws, window, running):
+        """Any frame, stage by stage: tracks that start, tracks that run, templates that start, weights, resampling, moments."""
+        ctx, starting = self.ctx, self.plan.starting(i)
+        if draws is None:  # (how the stages draw: the device's counter-based stream, or the staged host draws)
+            init, evolve, resample = dict(seed=self.seed), dict(seed=self.seed, step=i), dict(seed=self.seed, step=i)
+        else:
+            init, evolve, resample = dict(normals=draws["init"]), dict(normals=draws["evolve"][i]), dict(u=draws["u"][i])
+        if starting.any():
+            self.set_active(starting)
+            ctx.init_particles(**init)
+        if running.any():
+            self.set_active(running)
+            ctx.evolve(self.taus[i - 1], **evolve)
+        self.set_active(window)
+        for o in np.nonzero((self.template_indices == i) & self.has[i])[0]:
+            ctx.init_templates(int(o), int(self.matching[i][o]))
+        if running.any():
+            self.set_active(running)
+            ctx.update_weights(self.images[i])
+            self.note_skips(running, ctx.observer_status())
+            ctx.resample(**resample, method=self.method)
+        self.set_active(window)
+        ctx.record_moments(i)
+
+    def frame_outputs(self, i, window):
+        if self.return_covariances:
+            self.set_active(window)
+            self.ctx.record_covariances(i)
+        if self.return_particles:
+            self.out_particles[window, i] = self.ctx.get_particles()[window]
+            self.out_weights[window, i] = self.ctx.get_weights()[window]
+
+    def deferred_statuses(self, deferred):
+        for a, b in deferred:
+            statuses = self.ctx.observer_status_frames(a, b - a + 1)
+            # (one test for the whole run; the per-frame bookkeeping only where something was skipped)
+            skipped = (statuses == _lib.OBS_OUT_OF_BOUNDS) | (statuses == _lib.OBS_TILE_TOO_LARGE)
+            for k in np.nonzero(skipped.any(axis=(1, 2)))[0]:
+                self.note_skips(np.ones(self.ntracks, dtype=bool), statuses[k])  # (a common frame: every track is running)
 
 
 class Tracker:
@@ -603,6 +829,15 @@ class Tracker:
         ctx.set_raster(_lib.RASTER_VIEWSHED, self.viewshed)
 
     # ---- the tracking loop (tracker.py:225-417) ------------------------------------------------
+    def _sequence(self, datetimes, maxdt):
+        """The time steps of a run: the datetimes (given and parsed, or the observers' own), `matching` (T, O: the image
+        of each observer at each step, or None), `has` (where there is one), the step at which each observer's template
+        starts and the T - 1 time differences."""
+        datetimes = self.datetimes if datetimes is None else self.parse_datetimes(datetimes=datetimes, maxdt=maxdt)
+        matching = self.match_datetimes(datetimes=datetimes, maxdt=maxdt)
+        has = np.not_equal(matching, None)
+        return datetimes, matching, has, has.argmax(axis=0), np.diff(datetimes)
+
     def track(self, motion_models, datetimes=None, maxdt=datetime.timedelta(0), tile_size=(15, 15),
               observer_mask=None, return_covariances=False, return_particles=False, reduce_particles=None,
               parallel=False, rng="numpy", seed=0, point_offset=0, _catch_errors=None):
@@ -611,6 +846,8 @@ class Tracker:
         params = dict(motion_models=motion_models, datetimes=datetimes, maxdt=maxdt, tile_size=tile_size,
                       observer_mask=observer_mask, return_covariances=return_covariances,
                       return_particles=return_particles, reduce_particles=reduce_particles, parallel=parallel)
+        opts = dict(params, rng=rng, seed=seed, point_offset=point_offset)  # (what the paths dispatched to take)
+        del opts["motion_models"], opts["parallel"]
         block = isinstance(motion_models, ModelBlock)  # (a worker's tracks as one parameter table: checked where it was made)
         time_unit = motion_models.time_unit if block else motion_models[0].time_unit
         if not block and len(set(map(_GET_TIME_UNIT, motion_models))) > 1:  # (equal timedeltas hash alike: one pass at C speed)
@@ -626,10 +863,7 @@ class Tracker:
         raise_errors = ntracks < 2 if _catch_errors is None else not _catch_errors
         workers = self._parse_parallel(parallel, ntracks)
         if workers > 1:
-            return self._track_parallel(workers, motion_models, params, datetimes=datetimes, maxdt=maxdt,
-                                        tile_size=tile_size, observer_mask=observer_mask,
-                                        return_covariances=return_covariances, return_particles=return_particles,
-                                        reduce_particles=reduce_particles, rng=rng, seed=seed, point_offset=point_offset)
+            return self._track_parallel(workers, motion_models, params, opts)
         n = motion_models[0].n
         if rng not in ("numpy", "philox"):
             raise ValueError("rng must be 'numpy' or 'philox'")
@@ -643,31 +877,15 @@ class Tracker:
             # its own n, tracker.py:305-314), their own dem / dem_sigma rasters (motion.py:136-141), user-defined
             # models: consecutive compatible models form one batch, the batches run in order -- so the legacy
             # np.random stream is consumed track after track like the reference -- and are merged.
-            return self._track_runs(motion_models, params, datetimes=datetimes, maxdt=maxdt, tile_size=tile_size,
-                                    observer_mask=observer_mask, return_covariances=return_covariances,
-                                    return_particles=return_particles, reduce_particles=reduce_particles, rng=rng,
-                                    seed=seed, point_offset=point_offset, serial=serial)
-        if datetimes is None:
-            datetimes = self.datetimes
-        else:
-            datetimes = self.parse_datetimes(datetimes=datetimes, maxdt=maxdt)
-        nobs = len(self.observers)
-        if observer_mask is None:
-            observer_mask = np.ones((ntracks, nobs), dtype=bool)
-        observer_mask = np.asarray(observer_mask, dtype=bool)
-        matching = self.match_datetimes(datetimes=datetimes, maxdt=maxdt)
-        has = np.not_equal(matching, None)
-        template_indices = has.argmax(axis=0)
-        ntimes = len(datetimes)
-        dts = np.diff(datetimes)
-        taus = np.array([dt.total_seconds() / time_unit.total_seconds() for dt in dts])
-        # per-track [first, last] window (tracker.py:321-325)
-        observed = (has[None, :, :] & observer_mask[:, None, :]).any(axis=2)  # (P, T)
-        first = observed.argmax(axis=1)
-        last = ntimes - 1 - observed[:, ::-1].argmax(axis=1)
-        empty = ~observed.any(axis=1)
-        first[empty], last[empty] = 0, -1
+            return self._track_runs(motion_models, params, opts, serial=serial)
 
+        # one device batch -- the plan: which frames, which tracks, which workspaces
+        datetimes, matching, has, template_indices, dts = self._sequence(datetimes, maxdt)
+        mask = np.ones((ntracks, len(self.observers)), dtype=bool) if observer_mask is None else \
+            np.asarray(observer_mask, dtype=bool)
+        ntimes = len(datetimes)
+        taus = np.array([dt.total_seconds() / time_unit.total_seconds() for dt in dts])
+        plan = _Plan(has, mask, template_indices, self.resample_method)
         # search-tile workspaces: the caller's size, or a guess from the prior that grows (and re-runs) on demand
         dim = self.max_search_dim
         if dim is None and self._ctx is not None and self._ctx_key[:4] == (ntracks, n, ntimes, max(tile_size)):
@@ -675,206 +893,32 @@ class Tracker:
         elif dim is None:
             dim = max(self._estimate_search_dim(motion_models, matching, taus, tile_size), max(31, max(tile_size)) + 16)
         ctx = self._context(ntracks, n, ntimes, tile_size, dim)
-        outgrown = [False]  # a search tile did not fit the workspaces (this attempt)
-        uniform = bool(observer_mask.all()) and bool((first == first[0]).all()) and bool((last == last[0]).all())
 
-        warn_log = {}  # track -> its warnings (most tracks have none)
-        images_of = lambda i: [m if m is not None else -1 for m in matching[i]]  # noqa: E731
+        # the run
+        run = _BatchRun(self, plan, motion_models, matching, has, template_indices, taus, ctx, dim, mask, opts)
+        status, err_frame = run.execute()
+        ctx, out_particles, out_weights = run.ctx, run.out_particles, run.out_weights
 
-        def set_active(mask):
-            ctx.set_active(None if (uniform and mask.all()) else mask.astype(np.uint8))
-
-        lo, hi = int(first[~empty].min()) if (~empty).any() else 0, int(last.max())
-        method = self.resample_method
-        systematic = method == "systematic"
-
-        def run(draws):
-            """The frame loop (tracker.py:326-357) for all tracks at once."""
-            ctx.begin_sequence(ntracks, n, tile_size)
-            feed = self._frame_feed(ctx, matching)  # (frames from files are decoded while the frames before them are tracked)
-            self._upload_surfaces(ctx, motion_models)
-            ctx.set_motion(params_table(motion_models))
-            ctx.set_observer_mask(None if observer_mask.all() else observer_mask.astype(np.uint8))
-            ctx.set_point_offset(point_offset)
-            # device-RNG runs have no reference stream to be bit-exact with: fast arithmetic (GLH_MATH_FAST)
-            ctx.set_math("fast" if draws is None else "exact")
-            ctx.track_covariances(bool(return_covariances))  # (runs of frames in one call record them on the way)
-            warn_log.clear()
-            out_p = np.full((ntracks, ntimes, n, 6), np.nan) if return_particles else None
-            out_w = np.full((ntracks, ntimes, n), np.nan) if return_particles else None
-            def note_skips(running, status):
-                for o in range(nobs):
-                    for p in np.nonzero(running & (status[o] == _lib.OBS_OUT_OF_BOUNDS))[0]:
-                        warn_log.setdefault(int(p), []).append(UserWarning(_OOB_WARNING))
-                    for p in np.nonzero(running & (status[o] == _lib.OBS_TILE_TOO_LARGE))[0]:
-                        outgrown[0] = True
-                        warn_log.setdefault(int(p), []).append(RuntimeWarning(
-                            f"search tile exceeds max_search_dim={dim}; observer {o} skipped"))
-
-            def common(i):
-                """Every track is running and no template starts at frame i: ONE fused launch does evolve +
-                likelihood + resample + moments (glh_step)."""
-                return (uniform and systematic and bool(((first < i) & (i <= last)).all())
-                        and not (template_indices == i).any())
-
-            i = lo
-            deferred = []  # runs of common frames whose status words are read after the loop
-            while i <= hi:
-                through = feed.need(i)  # the frames of time steps <= through are resident
-                ctx.set_frame(i)
-                starting = (first == i) & ~empty
-                running = (first < i) & (i <= last)
-                window = starting | running
-                if common(i):
-                    set_active(window)
-                    if draws is None and not return_particles:
-                        # device RNG: the whole run of common frames in one call (glh_track: the launches are
-                        # enqueued back to back, no host round trip per frame) -- as far as the frames are resident:
-                        # a sequence read from files is tracked while its later frames are still being decoded.  Every
-                        # frame keeps its own status words, so the per-frame warnings are read afterwards.
-                        j = i
-                        while j + 1 <= min(hi, through) and common(j + 1):
-                            j += 1
-                        ctx.track(list(range(i, j + 1)), taus[i - 1:j], [images_of(k) for k in range(i, j + 1)], seed=seed)
-                        feed.stats["track_calls"] = feed.stats.get("track_calls", 0) + 1
-                        deferred.append((i, j))
-                        i = j + 1
-                        continue
-                    if draws is None:
-                        ctx.step(i, taus[i - 1], images_of(i), seed=seed)
-                    else:
-                        ctx.step(i, taus[i - 1], images_of(i), normals=draws["evolve"][i], u=draws["u"][i])
-                    note_skips(running, ctx.observer_status())
-                else:
-                    if starting.any():
-                        set_active(starting)
-                        if draws is None:
-                            ctx.init_particles(seed=seed)
-                        else:
-                            ctx.init_particles(normals=draws["init"])
-                    if running.any():
-                        set_active(running)
-                        if draws is None:
-                            ctx.evolve(taus[i - 1], seed=seed, step=i)
-                        else:
-                            ctx.evolve(taus[i - 1], normals=draws["evolve"][i])
-                    set_active(window)
-                    for o in np.nonzero(template_indices == i)[0]:
-                        if has[i, o]:
-                            ctx.init_templates(int(o), int(matching[i][o]))
-                    if running.any():
-                        set_active(running)
-                        ctx.update_weights(images_of(i))
-                        note_skips(running, ctx.observer_status())
-                        if draws is None:
-                            ctx.resample(seed=seed, step=i, method=method)
-                        else:
-                            ctx.resample(u=draws["u"][i], method=method)
-                    set_active(window)
-                    ctx.record_moments(i)
-                if return_covariances:
-                    set_active(window)
-                    ctx.record_covariances(i)
-                if return_particles:
-                    P_, W_ = ctx.get_particles(), ctx.get_weights()
-                    out_p[window, i] = P_[window]
-                    out_w[window, i] = W_[window]
-                i += 1
-            feed.close()
-            for a, b in deferred:
-                statuses = ctx.observer_status_frames(a, b - a + 1)
-                # (one test for the whole run; the per-frame bookkeeping only where something was skipped)
-                skipped = (statuses == _lib.OBS_OUT_OF_BOUNDS) | (statuses == _lib.OBS_TILE_TOO_LARGE)
-                for k in np.nonzero(skipped.any(axis=(1, 2)))[0]:
-                    note_skips(np.ones(ntracks, dtype=bool), statuses[k])  # (a common frame: every track is running)
-            return out_p, out_w, ctx.point_status(), ctx.point_error_frame()
-
-        state0 = np.random.get_state() if rng == "numpy" else None
-        while True:
-            outgrown[0] = False
-            out_particles, out_weights, status, err_frame = self._attempt(run, rng, state0, ntracks, n, first, last,
-                                                                          systematic, motion_models)
-            if not outgrown[0] or self.max_search_dim is not None:
-                break
-            # an automatic workspace was too small for some search tile (that observer was skipped on that frame):
-            # nothing of this attempt is kept -- same draws, larger workspaces, within what the kernels take and the
-            # device's memory allows (beyond that the run stands as it is, with its 'observer skipped' warnings).  Only
-            # the context of this shape remembers the size: a diverging track does not enlarge later, unrelated runs.
-            grown = self._fit_dim(2 * dim, self._dim_limit(ntracks))
-            if grown <= dim:
-                break
-            try:
-                # (the context in use stays until the larger one exists: if that cannot be made, its results stand)
-                bigger = self._context(ntracks, n, ntimes, tile_size, grown, keep_old=True)
-            except (_lib.GlhError, MemoryError):
-                break
-            ctx, dim = bigger, grown
-
+        # the results
         means, sigmas = ctx.get_tracks(0, ntimes)  # (P, T, 6) each, laid out on the device
         covariances = None
         if return_covariances:  # tracker.py:307-308, :352: (P, T, 6, 6) instead of sigmas
             covariances = np.ascontiguousarray(np.transpose(ctx.get_covariances(0, ntimes), (1, 0, 2, 3)))
-        errors = [None] * ntracks
-        for p in np.nonzero(status)[0]:
-            if status[p]:
-                for bit, cls, msg in _ERRORS:
-                    if status[p] & bit:
-                        errors[p] = cls(msg)
-                        break
-                e = int(err_frame[p])
-                means[p, e:] = np.nan
-                sigmas[p, e:] = np.nan
-                if covariances is not None:
-                    covariances[p, e:] = np.nan
-                if return_particles:
-                    out_particles[p, e:] = np.nan
-                    out_weights[p, e:] = np.nan
+        errors = _failures(status, err_frame, (means, sigmas, covariances, out_particles, out_weights))
         if raise_errors and errors[0] is not None:
             raise errors[0]
         # single-track state, like the reference leaves it after the last track
         self._particles = self._weights = None
         self._last_state = (ctx, ntracks - 1)  # fetched when `particles` / `weights` are first read
-        warnings = [None] * ntracks
-        for p_, w_ in warn_log.items():
-            warnings[p_] = tuple(w_)
-        kwargs = dict(time_unit=time_unit, datetimes=datetimes, means=means,
-                      sigmas=None if return_covariances else sigmas, covariances=covariances,
-                      particles=None if reduce_particles else out_particles,
-                      weights=None if reduce_particles else out_weights, tracker=self, images=matching,
-                      params=params, errors=errors,
-                      warnings=warnings)
-        tracks = Tracks(**kwargs)
+        warnings = [tuple(run.warn_log[p]) if p in run.warn_log else None for p in range(ntracks)]
+        tracks = Tracks(time_unit=time_unit, datetimes=datetimes, means=means,
+                        sigmas=None if return_covariances else sigmas, covariances=covariances,
+                        particles=None if reduce_particles else out_particles,
+                        weights=None if reduce_particles else out_weights, tracker=self, images=matching,
+                        params=params, errors=errors, warnings=warnings)
         if reduce_particles:
             tracks.reduced = [reduce_particles(out_particles[p], out_weights[p]) for p in range(ntracks)]
         return tracks
-
-    def _attempt(self, run, rng, state0, ntracks, n, first, last, systematic, motion_models):
-        """One pass over the sequence: `run(None)` on the device RNG, or the replay loop on the np.random stream."""
-        if rng == "philox":
-            return run(None)
-        # The reference stops drawing for a track at the frame where it fails, which shifts
-        # the stream of the tracks after it: replay until the assumed consumption is consistent.
-        stops = np.stack((last, last, last), axis=1)
-        for _ in range(ntracks + 1):
-            np.random.set_state(state0)
-            draws = self._draw_numpy(ntracks, n, first, last, stops, per_particle_u=not systematic,
-                                     models=motion_models)
-            out = run(draws)
-            status, err_frame = out[2], out[3]
-            new_stops = np.stack((last, last, last), axis=1)
-            for p in np.nonzero(status)[0]:
-                e = int(err_frame[p])
-                # a dem / dem_sigma raster that does not cover the initial positions raises inside
-                # initialize_particles right after randn(n, 2) (motion.py:158): nothing else is drawn
-                gridded = isinstance(motion_models[p].dem, Raster) or isinstance(motion_models[p].dem_sigma, Raster)
-                if e == first[p] and status[p] & _lib.PT_RASTER_OOB and gridded:
-                    new_stops[p, 2] = -1
-                new_stops[p, 0] = e
-                new_stops[p, 1] = e if (status[p] & _lib.PT_RESAMPLE_CLAMP and not status[p] & 0x77) else e - 1
-            if (new_stops == stops).all():
-                break
-            stops = new_stops
-        return out
 
     # ---- parallel=N: N worker processes, one GPU each (the reference's process pool, tracker.py:381-387) ----------
     @staticmethod
@@ -889,8 +933,7 @@ class Tracker:
             n = int(parallel)
         return max(0, min(n, ntracks))
 
-    def _track_parallel(self, workers, motion_models, params, observer_mask=None, rng="numpy", seed=0, point_offset=0,
-                        **kw):
+    def _track_parallel(self, workers, motion_models, params, opts):
         """Tracks are independent (the reference maps `process` over them, tracker.py:381-387): contiguous blocks of
         tracks go to `workers` PERSISTENT processes (glimpse_amd/parallel.py: started at the first parallel call, one
         context each on GPU (worker mod device count), reused by later calls), each with `point_offset` = its first
@@ -900,33 +943,52 @@ class Tracker:
         communicator, through host memory otherwise -- `Tracks.transport` says which.  With rng="numpy" every worker gets
         its own np.random seed (drawn here from the global stream): like the reference's pool, a parallel run is not
         stream-compatible with a serial one."""
-        import time
-
         from . import parallel, sharding
 
-        t_start = time.perf_counter()
+        times = [time.perf_counter()]  # start, jobs ready, workers replied, arrays imported
         ntracks = len(motion_models)
         ndev = max(1, _lib.device_count())
         # (objects defined in the caller's main script can only be unpickled by workers that run that script again -- which
         # then needs its `if __name__ == "__main__":` guard; everything else starts workers that do not)
         from_main = any(getattr(type(m), "__module__", "") == "__main__" for m in motion_models) or \
-            getattr(kw.get("reduce_particles"), "__module__", "") == "__main__"
+            getattr(opts["reduce_particles"], "__module__", "") == "__main__"
         pool = getattr(self, "_pool", None)
         if pool is None or pool.n != workers or not pool.alive() or (from_main and not pool.import_main):
             if pool is not None:
                 pool.close()
             pool = self._pool = parallel.WorkerPool(workers, [w % ndev for w in range(workers)], import_main=from_main)
         shared = pool.share(self.observers)
-        mask = None if observer_mask is None else np.asarray(observer_mask, dtype=bool)
-        seeds = np.random.randint(0, 2 ** 31 - 1, size=workers) if rng == "numpy" else [None] * workers
         bounds = [sharding.shard_range(ntracks, workers, w) for w in range(workers)]  # (workers <= ntracks: none empty)
-        sizes = [b - a for a, b in bounds]
         # one device batch per block (the usual case): the block's history lies in ONE context and can be gathered there;
         # blocks that run as several batches (ragged particle counts, user-defined models, the serial residual stream)
         # hand their host results over instead
-        serial = self.resample_method == "residual" and rng == "numpy"
+        serial = self.resample_method == "residual" and opts["rng"] == "numpy"
         gather = not serial and all(_batches(motion_models[a:b]) == [0] and _on_device(motion_models[a])
                                     for a, b in bounds)
+        jobs, result = self._parallel_jobs(pool, motion_models, bounds, gather, ndev, opts)
+        times.append(time.perf_counter())
+        # (the arrays of the Rasters the models and the viewshed bring travel through shared memory, once: while the jobs
+        # are pickled the Rasters hold references instead)
+        with pool.rasters.lent(parallel.rasters_of(motion_models, self.viewshed)):
+            replies = pool.call("track", jobs)
+        times.append(time.perf_counter())
+        parts = [{k: [parallel._import(x) for x in v] if isinstance(v, list) else parallel._import(v)
+                  for k, v in part.items()} for part in replies]
+        times.append(time.perf_counter())
+        transport = parts[0]["transport"] if gather else "host"
+        means, sigmas = self._parallel_history(pool, parts, bounds, result, transport, not opts["return_covariances"])
+        if gather and transport != "rccl":
+            why = next((part["why_host"] for part in parts if part.get("why_host")), "")
+            parallel.log.warning("Tracker.track(parallel=%d): no RCCL communicator (%s); the posterior history was "
+                                 "collected through host memory", workers, why or "unavailable")
+        return self._parallel_tracks(pool, parts, means, sigmas, params, transport, shared, times)
+
+    def _parallel_jobs(self, pool, motion_models, bounds, gather, ndev, opts):
+        """One job per worker (its block of tracks and `track`'s options for it), and the shared-memory block the
+        workers write the history into (None when there is none)."""
+        workers, ntracks = len(bounds), len(motion_models)
+        mask = None if opts["observer_mask"] is None else np.asarray(opts["observer_mask"], dtype=bool)
+        seeds = np.random.randint(0, 2 ** 31 - 1, size=workers) if opts["rng"] == "numpy" else [None] * workers
         settings = dict(viewshed=self.viewshed, resample_method=self.resample_method, highpass=self.highpass,
                         interpolation=self.interpolation, max_search_dim=self.max_search_dim)
         # where the history goes: one shared-memory block (tracks, times, 12) the workers write their rows into -- when the
@@ -934,9 +996,7 @@ class Tracker:
         result = None
         if gather:
             try:
-                dts = self.datetimes if kw.get("datetimes") is None else \
-                    self.parse_datetimes(datetimes=kw["datetimes"], maxdt=kw.get("maxdt", datetime.timedelta(0)))
-                result = pool.result_block((ntracks, len(dts), 12))
+                result = pool.result_block((ntracks, len(self._sequence(opts["datetimes"], opts["maxdt"])[0]), 12))
             except Exception:  # noqa: BLE001  (the workers raise it properly)
                 result = None
         # what a worker gets of its tracks: ONE parameter table when the block is one device batch (`gather`: every block
@@ -947,33 +1007,17 @@ class Tracker:
         for w, (a, b) in enumerate(bounds):
             models = ModelBlock.from_models(motion_models[a:b]) if gather else motion_models[a:b]
             jobs.append(dict(tracker=settings, models=models, np_seed=seeds[w], catch=ntracks >= 2,
-                             gather=gather, sizes=sizes, call=pool.calls, want_last=w == workers - 1, result=result,
-                             host_only=host_only,
-                             rows=(a, b),
-                             kw=dict(kw, observer_mask=None if mask is None else mask[a:b], rng=rng, seed=seed,
-                                     point_offset=point_offset + a)))
-        t_ready = time.perf_counter()
-        # (the arrays of the Rasters the models and the viewshed bring travel through shared memory, once: while the jobs
-        # are pickled the Rasters hold references instead)
-        with pool.rasters.lent(parallel.rasters_of(motion_models, self.viewshed)):
-            replies = pool.call("track", jobs)
-        t_replied = time.perf_counter()
-        parts = [{k: [parallel._import(x) for x in v] if isinstance(v, list) else parallel._import(v)
-                  for k, v in part.items()} for part in replies]
-        t_imported = time.perf_counter()
+                             gather=gather, sizes=[hi - lo for lo, hi in bounds], call=pool.calls,
+                             want_last=w == workers - 1, result=result, host_only=host_only, rows=(a, b),
+                             kw=dict(opts, observer_mask=None if mask is None else mask[a:b],
+                                     point_offset=opts["point_offset"] + a)))
+        return jobs, result
 
-        def cat(name):
-            values = [part[name] for part in parts]
-            if values[0] is None:
-                return None
-            if all(isinstance(v, np.ndarray) for v in values) and len({v.shape[1:] for v in values}) == 1:
-                return np.concatenate(values, axis=0)
-            return [row for v in values for row in v]
-
-        errors = cat("errors")
-        transport = parts[0]["transport"] if gather else "host"
+    @staticmethod
+    def _parallel_history(pool, parts, bounds, result, transport, want_sigmas):
+        """`means` and `sigmas` of all tracks from the workers' replies: out of the shared block, out of worker 0's
+        gathered history, or merged from the arrays the workers sent."""
         in_block = [part.get("in_block") for part in parts]
-        want_sigmas = not kw.get("return_covariances")
         # (a view of the shared block: means / sigmas below are the copies that leave this function)
         full = pool.result_view(result[1]) if result is not None and any(in_block) else None  # (tracks, times, 12)
         if transport == "rccl":
@@ -984,48 +1028,31 @@ class Tracker:
                 full = np.ascontiguousarray(np.transpose(parts[0]["gathered"], (1, 0, 2)))
             means = np.ascontiguousarray(full[:, :, 0:6])
             sigmas = np.ascontiguousarray(full[:, :, 6:12]) if want_sigmas else None
-            lo = 0
-            for part, n in zip(parts, sizes):
+            for part, (lo, _) in zip(parts, bounds):
                 for p, e in part.get("nan_from", ()):
-                    means[lo + p, e:] = np.nan
-                    if sigmas is not None:
-                        sigmas[lo + p, e:] = np.nan
-                lo += n
-        elif full is not None and all(tag == "rows" for tag in in_block):
+                    _blank((means, sigmas), lo + p, e)
+            return means, sigmas
+        if full is not None and all(tag == "rows" for tag in in_block):
             # every worker wrote its rows into the block: one copy out of it per array
-            means = np.ascontiguousarray(full[:, :, 0:6])
-            sigmas = np.ascontiguousarray(full[:, :, 6:12]) if want_sigmas else None
-        else:
-            mparts, sparts = [], []
-            for part, (a, b) in zip(parts, bounds):
-                if part.get("in_block") == "rows":
-                    mparts.append(np.ascontiguousarray(full[a:b, :, 0:6]))
-                    sparts.append(np.ascontiguousarray(full[a:b, :, 6:12]) if want_sigmas else None)
-                else:
-                    mparts.append(part["means"])
-                    sparts.append(part["sigmas"])
+            return np.ascontiguousarray(full[:, :, 0:6]), np.ascontiguousarray(full[:, :, 6:12]) if want_sigmas else None
+        mparts, sparts = [], []
+        for part, tag, (a, b) in zip(parts, in_block, bounds):  # (its rows in the block, or the arrays it sent)
+            mparts.append(np.ascontiguousarray(full[a:b, :, 0:6]) if tag == "rows" else part["means"])
+            sparts.append(part["sigmas"] if tag != "rows" else np.ascontiguousarray(full[a:b, :, 6:12]) if want_sigmas else None)
+        return merge_parts(mparts), merge_parts(sparts)
 
-            def join(values):
-                if values[0] is None:
-                    return None
-                if all(isinstance(v, np.ndarray) for v in values) and len({v.shape[1:] for v in values}) == 1:
-                    return np.concatenate(values, axis=0)
-                return [row for v in values for row in v]
-
-            means, sigmas = join(mparts), join(sparts)
-        if gather and transport != "rccl":
-            why = next((part["why_host"] for part in parts if part.get("why_host")), "")
-            parallel.log.warning("Tracker.track(parallel=%d): no RCCL communicator (%s); the posterior history was "
-                                 "collected through host memory", workers, why or "unavailable")
-        if ntracks < 2 and errors[0] is not None:
-            raise errors[0]
+    def _parallel_tracks(self, pool, parts, means, sigmas, params, transport, shared, times):
+        """The `Tracks` of a parallel run, with what the run cost (`parallel_info`)."""
+        merged = {k: merge_parts([part[k] for part in parts])
+                  for k in ("errors", "covariances", "particles", "weights", "warnings")}
+        if len(params["motion_models"]) < 2 and merged["errors"][0] is not None:
+            raise merged["errors"][0]
         self.particles, self.weights = parts[-1]["last_particles"], parts[-1]["last_weights"]
-        tracks = Tracks(datetimes=parts[0]["datetimes"], time_unit=parts[0]["time_unit"], means=means,
-                        sigmas=sigmas, covariances=cat("covariances"), particles=cat("particles"),
-                        weights=cat("weights"), tracker=self, images=parts[0]["images"], params=params, errors=errors,
-                        warnings=cat("warnings"))
+        tracks = Tracks(datetimes=parts[0]["datetimes"], time_unit=parts[0]["time_unit"], means=means, sigmas=sigmas,
+                        tracker=self, images=parts[0]["images"], params=params, **merged)
         tracks.transport = transport
-        tracks.parallel_info = dict(workers=workers, transport=transport, frames_shared_now=shared,
+        t_start, t_ready, t_replied, t_imported = times
+        tracks.parallel_info = dict(workers=len(parts), transport=transport, frames_shared_now=shared,
                                     shared_frame_bytes=pool.frames.nbytes() if pool.frames else 0,
                                     contexts_made=[bool(part["context_made"]) for part in parts],
                                     worker_seconds=[part["seconds"] for part in parts],
@@ -1034,7 +1061,7 @@ class Tracker:
                                     parent_seconds=dict(prepare=t_ready - t_start, workers=t_replied - t_ready,
                                                         import_arrays=t_imported - t_replied,
                                                         assemble=time.perf_counter() - t_imported))
-        if kw.get("reduce_particles"):
+        if params["reduce_particles"]:
             tracks.reduced = [r for part in parts for r in part["reduced"]]
         return tracks
 
@@ -1075,36 +1102,29 @@ class Tracker:
         except Exception:  # noqa: BLE001
             pass
 
-    def _track_runs(self, motion_models, params, observer_mask=None, reduce_particles=None, point_offset=0,
-                    serial=False, **kw):
+    def _track_runs(self, motion_models, params, opts, serial=False):
         """Tracks that cannot share one batch (`_batches`): consecutive compatible device models form a batch, every
         user-defined model is a run of its own (`_track_custom`); the runs go in track order, so np.random is consumed
         like the reference consumes it (one track after another), and are merged.  `serial`: every track is a run of
         its own through the per-track loop (residual resampling on the np.random stream)."""
         ntracks = len(motion_models)
-        if observer_mask is not None:
-            observer_mask = np.asarray(observer_mask, dtype=bool)
+        observer_mask = None if opts["observer_mask"] is None else np.asarray(opts["observer_mask"], dtype=bool)
+        custom = {k: v for k, v in opts.items() if k not in ("observer_mask", "point_offset")}
         bounds = list(range(ntracks + 1)) if serial else _batches(motion_models) + [ntracks]
         parts = []
         for a, b in zip(bounds[:-1], bounds[1:]):
             mask = None if observer_mask is None else observer_mask[a:b]
             if serial or not _on_device(motion_models[a]):
                 parts.append(self._track_custom(motion_models[a], None if mask is None else mask[0],
-                                                reduce_particles=reduce_particles, catch_errors=ntracks >= 2, **kw))
+                                                catch_errors=ntracks >= 2, **custom))
             else:
-                parts.append(self.track(motion_models[a:b], observer_mask=mask, reduce_particles=reduce_particles,
-                                        point_offset=point_offset + a, _catch_errors=ntracks >= 2, **kw))
-
-        def cat(name):
-            values = [getattr(part, name) for part in parts]
-            return None if values[0] is None else [row for v in values for row in v]
-
-        first = parts[0]
-        tracks = Tracks(datetimes=first.datetimes, time_unit=first.time_unit, means=cat("means"), sigmas=cat("sigmas"),
-                        covariances=cat("covariances"), particles=cat("particles"), weights=cat("weights"),
-                        tracker=self, images=first.images, params=params, errors=cat("errors"),
-                        warnings=cat("warnings"))
-        if reduce_particles:
+                parts.append(self.track(motion_models[a:b], _catch_errors=ntracks >= 2,
+                                        **dict(opts, observer_mask=mask, point_offset=opts["point_offset"] + a)))
+        merged = {k: merge_parts([getattr(part, k) for part in parts], rows=True)
+                  for k in ("means", "sigmas", "covariances", "particles", "weights", "errors", "warnings")}
+        tracks = Tracks(datetimes=parts[0].datetimes, time_unit=parts[0].time_unit, tracker=self, images=parts[0].images,
+                        params=params, **merged)
+        if opts["reduce_particles"]:
             tracks.reduced = [r for part in parts for r in part.reduced]
         return tracks
 
@@ -1117,14 +1137,9 @@ class Tracker:
         moments: device kernels) in between.  np.random is consumed exactly as the reference consumes it."""
         if reduce_particles:
             return_particles = True
-        datetimes = self.datetimes if datetimes is None else self.parse_datetimes(datetimes=datetimes, maxdt=maxdt)
-        nobs = len(self.observers)
-        mask = np.ones(nobs, dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
-        matching = self.match_datetimes(datetimes=datetimes, maxdt=maxdt)
-        has = np.not_equal(matching, None)
-        template_indices = has.argmax(axis=0)
+        datetimes, matching, has, template_indices, dts = self._sequence(datetimes, maxdt)
+        mask = np.ones(len(self.observers), dtype=bool) if mask is None else np.asarray(mask, dtype=bool)
         ntimes = len(datetimes)
-        dts = np.diff(datetimes)
         n = int(model.n)
         means = np.full((ntimes, 6), np.nan)
         sigmas = np.full((ntimes, 6, 6) if return_covariances else (ntimes, 6), np.nan)
@@ -1162,8 +1177,7 @@ class Tracker:
                 raise
             error = e
             first_bad = int(np.argmax(np.isnan(means[:, 0]))) if np.isnan(means[:, 0]).any() else ntimes
-            means[first_bad:] = np.nan
-            sigmas[first_bad:] = np.nan
+            _blank((means[None], sigmas[None]), 0, first_bad)
         tracks = Tracks(datetimes=datetimes, time_unit=model.time_unit, means=[means],
                         sigmas=None if return_covariances else [sigmas], covariances=[sigmas] if return_covariances else None,
                         particles=None if (reduce_particles or not return_particles) else [particles],

@@ -39,6 +39,16 @@ def fuse_normals(means, sigmas, axis, comonotone=False, ignore_nan=False):
     return mean, sigma
 
 
+def merge_parts(values, rows=False):
+    """The parts of a result (one per batch or worker) as one: None when the first part has none, one array when every
+    part is an array of one trailing shape (and `rows` does not ask for a list), a list of rows otherwise."""
+    if values[0] is None:
+        return None
+    if not rows and all(isinstance(v, np.ndarray) for v in values) and len({v.shape[1:] for v in values}) == 1:
+        return np.concatenate(values, axis=0)
+    return [row for v in values for row in v]
+
+
 class Tracks:
     def __init__(self, datetimes, time_unit, means, sigmas=None, covariances=None, particles=None, weights=None,
                  tracker=None, images=None, params=None, errors=None, warnings=None):
