@@ -5,6 +5,7 @@ Drop-in names for that path only (see DESIGN.md for scope):
     from glimpse_amd import Camera, Image, Observer, CartesianMotion, Tracker, Tracks
     (+ CylindricalMotion, TangentCartesianMotion, TangentCylindricalMotion)
     from glimpse_amd.optimize import ObserverCameras, RotationMatchesXYZ   # orienting an image sequence
+    from glimpse_amd.optimize import Cameras, Points, Lines, Matches       # calibrating cameras
 
 The compute runs in hand-written HIP kernels behind a C ABI (include/glimpse_hip.h,
 glimpse_amd/lib/libglimpse_hip.so, bound with ctypes in glimpse_amd._lib).  There is no CPU
@@ -17,7 +18,8 @@ from .motion import (CartesianMotion, CylindricalMotion, Motion, TangentCartesia
                      TangentCylindricalMotion)
 from . import optimize
 from .observer import Observer
-from .optimize import Matches, ObserverCameras, RotationMatches, RotationMatchesXY, RotationMatchesXYZ
+from .optimize import (Cameras, Lines, Matches, ObserverCameras, Points, Polynomial, RotationMatches, RotationMatchesXY,
+                       RotationMatchesXYZ, ransac)
 from .raster import Raster, RasterInterpolant
 from .tracker import Tracker
 from .tracks import Tracks
@@ -25,5 +27,5 @@ from .tracks import Tracks
 __all__ = ["Camera", "Image", "Observer", "Motion", "CartesianMotion", "CylindricalMotion",
            "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "RasterInterpolant", "Tracker", "Tracks", "maximum_filter",
            "gaussian_filter", "optimize", "Matches", "RotationMatches", "RotationMatchesXY", "RotationMatchesXYZ",
-           "ObserverCameras"]
+           "ObserverCameras", "Cameras", "Points", "Lines", "Polynomial", "ransac"]
 __version__ = "0.1.0"

@@ -168,6 +168,9 @@ SIGNATURES = {
     "glh_orient_create": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "glh_orient_eval": (_I, [_P, _P, _P, _P, _P, _P]),
     "glh_orient_destroy": (_I, [_P]),
+    "glh_calib_create": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "glh_calib_eval": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
+    "glh_calib_destroy": (_I, [_P]),
 }
 
 _lib = None
@@ -1257,6 +1260,88 @@ class Orient:
         if self._h:
             handle, self._h = self._h, C.c_void_p()
             check(load().glh_orient_destroy(handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+CALIB_TIMES = ("upload", "points", "line_points", "nearest", "download")
+CALIB_KINDS = {"points": 0, "lines": 1, "matches": 2, "rotation": 3, "rotation_xy": 4}
+
+
+class Calib:
+    """The controls of a camera calibration on the device (glh_calib_create): uploaded once, evaluated under many sets
+    of camera vectors (optimize.Cameras).  Control c is of `kind[c]` (CALIB_KINDS), belongs to camera `cam_a[c]` (the match
+    kinds: to `cam_a[c]` and `cam_b[c]`) of `n_cams` and owns rows row_offset[c] .. row_offset[c + 1] of `obs` (N, 2) and
+    `src` (N, 3) (include/glimpse_hip.h says what each kind keeps there)."""
+
+    def __init__(self, n_cams, kind, cam_a, cam_b, directions, row_offset, obs, src, device_id=0):
+        self.n_cams = int(n_cams)
+        self._h = C.c_void_p()
+        kind, cam_a, cam_b = _arr(kind, np.int32), _arr(cam_a, np.int32), _arr(cam_b, np.int32)
+        directions = _arr(directions, np.int32)
+        self.rows = np.diff(_arr(row_offset, np.int64, (len(kind) + 1,)))
+        self.kind = kind
+        row_offset = _arr(row_offset, np.int64)
+        obs, src = _arr(obs, np.float64).reshape(-1, 2), _arr(src, np.float64).reshape(-1, 3)
+        if kind.ndim != 1 or not (cam_a.shape == cam_b.shape == directions.shape == kind.shape) or len(obs) != len(src) \
+                or len(obs) < row_offset.max():
+            raise ValueError("kind / cam_a / cam_b / directions (n_controls,) and obs (N, 2), src (N, 3) with N >= row_offset.max()")
+        check(load().glh_calib_create(int(device_id), self.n_cams, len(kind), _ptr(kind), _ptr(cam_a), _ptr(cam_b),
+                                      _ptr(directions), _ptr(row_offset), _ptr(obs), _ptr(src), C.byref(self._h)))
+
+    def eval(self, cams, rot, job_control, job_set, job_side=None, tables=None, return_times=False):
+        """`predicted` (rows, 2) of the jobs, concatenated in job order: job q is control `job_control[q]` under the
+        camera vectors `cams[job_set[q]]` (n_sets, n_cams, 24), with `rot` (n_sets, n_cams, 3, 3) the rotation matrices the
+        host methods use.  `job_side`: which camera of a match control predicts (default 0).  `tables`: for every job
+        None, or the segment table of a Lines job: (seg_vertex (S + 1,), seg_count (S,), seg_par (S, 5), vertex (V, 3))."""
+        if not self._h:
+            raise GlhError(-4, "the handle is closed")
+        cams = _arr(cams, np.float64)
+        if cams.ndim != 3 or cams.shape[1:] != (self.n_cams, CAM_LEN):
+            raise ValueError(f"expected camera vectors (n_sets, {self.n_cams}, {CAM_LEN}), got {cams.shape}")
+        rot = _arr(rot, np.float64, (len(cams), self.n_cams, 3, 3))
+        job_control = _arr(job_control, np.int32)
+        job_set = _arr(job_set, np.int32, job_control.shape)
+        job_side = np.zeros(len(job_control), np.int32) if job_side is None else _arr(job_side, np.int32, job_control.shape)
+        if tables is None:
+            tables = [None] * len(job_control)
+        job_seg, seg_vertex, seg_count, seg_par, vertex, nv = [0], [np.zeros(1, np.int64)], [], [], [], 0
+        for table in tables:
+            if table is not None:
+                sv, sc, sp, vx = table
+                seg_vertex.append(np.asarray(sv[1:], dtype=np.int64) + nv)
+                seg_count.append(np.asarray(sc, dtype=np.int64))
+                seg_par.append(np.asarray(sp, dtype=np.float64).reshape(-1, 5))
+                vertex.append(np.asarray(vx, dtype=np.float64).reshape(-1, 3))
+                nv += len(vertex[-1])
+            job_seg.append(sum(len(c) for c in seg_count))
+        job_seg = _arr(job_seg, np.int64)
+        seg_vertex = _arr(np.concatenate(seg_vertex), np.int64)
+        seg_count = _arr(np.concatenate(seg_count) if seg_count else np.zeros(0), np.int64)
+        seg_par = _arr(np.concatenate(seg_par) if seg_par else np.zeros((0, 5)), np.float64)
+        vertex = _arr(np.concatenate(vertex) if vertex else np.zeros((0, 3)), np.float64)
+        in_range = (job_control >= 0) & (job_control < len(self.rows))
+        predicted = np.empty((int(self.rows[job_control[in_range]].sum()), 2))
+        times = np.zeros(len(CALIB_TIMES))
+        check(load().glh_calib_eval(self._h, len(cams), _ptr(cams), _ptr(rot), len(job_control), _ptr(job_control),
+                                    _ptr(job_set), _ptr(job_side), _ptr(job_seg), _ptr(seg_vertex), _ptr(seg_count),
+                                    _ptr(seg_par), len(vertex), _ptr(vertex), _ptr(predicted), _ptr(times)))
+        return _timed(predicted, CALIB_TIMES, times, return_times)
+
+    def close(self):
+        if self._h:
+            handle, self._h = self._h, C.c_void_p()
+            check(load().glh_calib_destroy(handle))
 
     def __enter__(self):
         return self

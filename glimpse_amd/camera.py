@@ -9,8 +9,7 @@ the per-frame path.  Of the rendering methods, `project_dem` (camera.py:967-1129
 camera records of a DEM) and `rasterize` (:858-883: points to a mean image) are served, on the GPU
 (`glh_stage_project_dem`, `glh_stage_rasterize`); `project_dem` without the per-tile rescaling (`scale_limits` other than
 (1, 1), which fails in the reference itself).  `Rprime` and the camera-coordinate halves of the projection (`_uv_to_xy`
-on the GPU, `_xy_to_uv`, `_xy_to_xyz`, `_xyz_to_xy` on the host) serve `glimpse_amd.optimize`; the other calibration
-methods are out of scope.
+on the GPU, `_xy_to_uv`, `_xy_to_xyz`, `_xyz_to_xy` on the host) and `edges` serve `glimpse_amd.optimize`.
 """
 import numpy as np
 
@@ -255,6 +254,20 @@ class Camera:
         uv = np.asarray(uv)
         with np.errstate(invalid="ignore"):
             return np.all((uv >= 0) & (uv <= self.imgsz), axis=1)
+
+    def edges(self, step=1):
+        """camera.py:763-800: image coordinates along the image edges, clockwise from (0, 0), `step` apart (one number
+        or one per axis)."""
+        if isinstance(step, (int, float)):
+            step = (step, step)
+        u = np.linspace(0, self.imgsz[0], int(self.imgsz[0] / step[0] + 1))
+        v = np.linspace(0, self.imgsz[1], int(self.imgsz[1] / step[1] + 1))
+        return np.vstack((
+            np.column_stack((u, np.repeat(0, len(u)))),
+            np.column_stack((np.repeat(u[-1], len(v) - 2), v[1:-1])),
+            np.column_stack((u[::-1], np.repeat(v[-1], len(u)))),
+            np.column_stack((np.repeat(0, len(v) - 2), v[::-1][1:-1])),
+        ))
 
     def uv_to_xyz(self, uv, directions=True, depth=1):
         """camera.py:630-663 on the device (`glh_stage_unproject`): closed form for k1 alone, else the Oulu

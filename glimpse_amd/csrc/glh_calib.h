@@ -1,0 +1,46 @@
+// glh_calib.h -- what glimpse_hip.hip (the C ABI: glh_calib_create / _eval / _destroy) hands to glh_calib.hip (the
+// predictions of the controls of optimize.Cameras -- Points, Lines and the match classes -- under many sets of camera
+// vectors at once).  Host-only declarations.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace glh {
+
+constexpr int CAL_TIMES = 5;   // entries of times_ms (include/glimpse_hip.h)
+constexpr int CAL_TB = 256;    // threads of a workgroup, all three kernels
+constexpr int CAL_TILE = 256;  // projected points of a Lines job held in LDS at a time (tests/calib_restated.py: TILE)
+
+struct CalibHandle;  // the uploaded controls (glh_calib.hip)
+struct CamDev;
+
+struct CalibControls {
+  int n_cams, n_controls;
+  const int32_t *kind, *cam_a, *cam_b, *directions;  // [n_controls]
+  const int64_t* row_offset;            // [n_controls + 1]
+  const double* obs;                    // [N][2]
+  const double* src;                    // [N][3]
+};
+
+struct CalibEval {
+  int n_sets;
+  const CamDev* cams;  // [n_sets][n_cams], expanded by the caller
+  const double* rot;   // [n_sets][n_cams][9]
+  int n_jobs;
+  const int32_t *job_control, *job_set, *job_side;  // [n_jobs]
+  const int64_t* job_seg;                           // [n_jobs + 1]
+  const int64_t* seg_vertex;                        // [n_segments + 1]
+  const int64_t* seg_count;                         // [n_segments]
+  const double* seg_par;                            // [n_segments][5]
+  const double* vertex;                             // [n_vertices][3]
+  double* predicted;
+  double* times_ms;
+};
+
+// The arguments have been checked (glimpse_hip.hip).  A GLH_* status, with the message left for glh_last_error() on
+// failure (glh_stage.h: fail).
+int calib_create(int device, const CalibControls& c, CalibHandle** out);
+int calib_eval(CalibHandle* h, const CalibEval& e);
+void calib_destroy(CalibHandle* h);
+
+}  // namespace glh

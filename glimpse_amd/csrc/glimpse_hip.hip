@@ -19,6 +19,7 @@
 #include "glh_point_variants.h"
 #include "glh_project_dem.h"
 #include "glh_horizon.h"
+#include "glh_calib.h"
 #include "glh_orient.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
@@ -2907,6 +2908,116 @@ extern "C" int glh_stage_uv_to_xy(int dev, const double* cam, const double* uv, 
   CamDev cd;
   expand_camera(cam, &cd);
   return uv_to_xy_run(dev, cd, uv, n, xy);
+}
+
+// optimize.Cameras' predictions (optimize.py:1721-1764): the arguments are checked here, before a device is touched; the
+// kernels and the launches are glh_calib.hip's.
+struct glh_calib {
+  CalibHandle* h;
+  int n_cams;
+  std::vector<int32_t> kind;
+  std::vector<int64_t> rows;  // of every control
+};
+
+extern "C" int glh_calib_create(int dev, int n_cams, int n_controls, const int32_t* kind, const int32_t* cam_a,
+                                const int32_t* cam_b, const int32_t* directions, const int64_t* row_offset, const double* obs,
+                                const double* src, glh_calib** handle) {
+  if (!handle) return fail(GLH_E_INVALID, "calib: null handle pointer");
+  *handle = nullptr;
+  if (n_cams < 1 || n_controls < 0) return fail(GLH_E_INVALID, "calib: %d cameras, %d controls", n_cams, n_controls);
+  if (n_cams >= (1 << 20) || n_controls >= (1 << 24))
+    return fail(GLH_E_INVALID, "calib: %d cameras, %d controls: fewer than 2^20 cameras and 2^24 controls are served", n_cams,
+                n_controls);
+  if (!row_offset || (n_controls && (!kind || !cam_a || !cam_b || !directions)))
+    return fail(GLH_E_INVALID, "calib: null control arrays");
+  if (row_offset[0] != 0) return fail(GLH_E_INVALID, "calib: row_offset[0] is %lld, not 0", (long long)row_offset[0]);
+  for (int c = 0; c < n_controls; ++c) {
+    if (row_offset[c + 1] < row_offset[c])
+      return fail(GLH_E_INVALID, "calib: row_offset decreases at control %d (%lld after %lld)", c, (long long)row_offset[c + 1],
+                  (long long)row_offset[c]);
+    if (kind[c] < GLH_CALIB_POINTS || kind[c] > GLH_CALIB_ROTATION_XY)
+      return fail(GLH_E_INVALID, "calib: control %d is of unknown kind %d", c, kind[c]);
+    const bool pair = kind[c] >= GLH_CALIB_MATCHES;
+    if (cam_a[c] < 0 || cam_a[c] >= n_cams || (pair && (cam_b[c] < 0 || cam_b[c] >= n_cams)))
+      return fail(GLH_E_INVALID, "calib: control %d names cameras %d and %d of %d", c, cam_a[c], cam_b[c], n_cams);
+  }
+  if (row_offset[n_controls] >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "calib: %lld rows: fewer than 2^31 are served", (long long)row_offset[n_controls]);
+  if (row_offset[n_controls] > 0 && (!obs || !src)) return fail(GLH_E_INVALID, "calib: null coordinates");
+  glh_calib* g = new (std::nothrow) glh_calib{nullptr, n_cams, {}, {}};
+  if (!g) return fail(GLH_E_NOMEM, "calib: no memory for a handle");
+  g->kind.assign(kind, kind + n_controls);
+  for (int c = 0; c < n_controls; ++c) g->rows.push_back(row_offset[c + 1] - row_offset[c]);
+  std::vector<int32_t> b(cam_b, cam_b + n_controls);
+  for (int c = 0; c < n_controls; ++c)
+    if (kind[c] < GLH_CALIB_MATCHES) b[c] = cam_a[c];  // (one camera: both names are it)
+  const CalibControls cc{n_cams, n_controls, kind, cam_a, b.data(), directions, row_offset, obs, src};
+  const int rc = calib_create(dev, cc, &g->h);
+  if (rc != GLH_OK) {
+    delete g;
+    return rc;
+  }
+  *handle = g;
+  return GLH_OK;
+}
+
+extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams, const double* rot, int n_jobs,
+                              const int32_t* job_control, const int32_t* job_set, const int32_t* job_side,
+                              const int64_t* job_seg, const int64_t* seg_vertex, const int64_t* seg_count,
+                              const double* seg_par, int64_t n_vertices, const double* vertex, double* predicted,
+                              double* times_ms) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "calib: null handle");
+  if (n_sets < 1 || n_jobs < 0 || n_vertices < 0) return fail(GLH_E_INVALID, "calib: %d sets, %d jobs", n_sets, n_jobs);
+  if ((int64_t)n_sets * handle->n_cams >= ((int64_t)1 << 24))
+    return fail(GLH_E_INVALID, "calib: %d sets of %d cameras: fewer than 2^24 cameras in all are served", n_sets, handle->n_cams);
+  if (!cams || !rot || !job_seg || !seg_vertex || (n_jobs && (!job_control || !job_set || !job_side)))
+    return fail(GLH_E_INVALID, "calib: null argument");
+  if (job_seg[0] != 0 || seg_vertex[0] != 0) return fail(GLH_E_INVALID, "calib: the segment table does not start at 0");
+  const int n_controls = (int)handle->kind.size();
+  int64_t rows = 0, points = 0;
+  for (int q = 0; q < n_jobs; ++q) {
+    if (job_control[q] < 0 || job_control[q] >= n_controls || job_set[q] < 0 || job_set[q] >= n_sets || job_side[q] < 0 ||
+        job_side[q] > 1)
+      return fail(GLH_E_INVALID, "calib: job %d is control %d of %d, set %d of %d, side %d", q, job_control[q], n_controls,
+                  job_set[q], n_sets, job_side[q]);
+    const int64_t n_segs = job_seg[q + 1] - job_seg[q];
+    const bool lines = handle->kind[job_control[q]] == GLH_CALIB_LINES;
+    if (n_segs < 0 || n_segs >= ((int64_t)1 << 31) || (lines ? n_segs < 1 : n_segs != 0))
+      return fail(GLH_E_INVALID, "calib: job %d (%s) has %lld segments", q, lines ? "lines" : "not lines", (long long)n_segs);
+    if (lines && job_side[q] != 0) return fail(GLH_E_INVALID, "calib: job %d (lines) has side %d", q, job_side[q]);
+    if (n_segs && (!seg_count || !seg_par || !vertex)) return fail(GLH_E_INVALID, "calib: null segment table");
+    int64_t job_points = 0;
+    for (int64_t k = job_seg[q]; k < job_seg[q + 1]; ++k) {
+      if (seg_vertex[k + 1] <= seg_vertex[k] || seg_vertex[k + 1] > n_vertices || seg_count[k] < 1 ||
+          seg_count[k] >= ((int64_t)1 << 31))
+        return fail(GLH_E_INVALID, "calib: segment %lld has vertices %lld .. %lld of %lld and %lld points", (long long)k,
+                    (long long)seg_vertex[k], (long long)seg_vertex[k + 1], (long long)n_vertices, (long long)seg_count[k]);
+      job_points += seg_count[k];
+    }
+    if (job_points >= ((int64_t)1 << 31)) return fail(GLH_E_INVALID, "calib: job %d has %lld points", q, (long long)job_points);
+    rows += handle->rows[job_control[q]];
+    points += job_points;
+  }
+  if (rows >= ((int64_t)1 << 31) || points >= ((int64_t)1 << 31) || n_vertices >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "calib: %lld rows, %lld points, %lld vertices: fewer than 2^31 of each are served", (long long)rows,
+                (long long)points, (long long)n_vertices);
+  if (rows > 0 && !predicted) return fail(GLH_E_INVALID, "calib: null output");
+  const size_t n_cam_sets = (size_t)n_sets * handle->n_cams;
+  std::vector<CamDev> cd(n_cam_sets);
+  for (size_t i = 0; i < n_cam_sets; ++i) {
+    if (cams[i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "calib: camera %zu is a raster grid", i);
+    expand_camera(cams + i * GLH_CAM_LEN, &cd[i]);
+  }
+  const CalibEval e{n_sets, cd.data(), rot, n_jobs, job_control, job_set, job_side, job_seg, seg_vertex, seg_count, seg_par,
+                    vertex, predicted, times_ms};
+  return calib_eval(handle->h, e);
+}
+
+extern "C" int glh_calib_destroy(glh_calib* handle) {
+  if (!handle) return GLH_OK;
+  calib_destroy(handle->h);
+  delete handle;
+  return GLH_OK;
 }
 
 // Raster.sample(grid=True) / resample, Raster.resize and RasterInterpolant (raster.py:1042-1083, :1178-1187, :1673-1700):

@@ -1,5 +1,6 @@
-"""The few functions of the reference's src/glimpse/helpers.py that the host-side raster logic needs, restated, and
-`polygons_to_mask`, which runs on the GPU."""
+"""The few functions of the reference's src/glimpse/helpers.py that the host-side raster logic and the camera calibration
+(`optimize.Lines`: splitting, clipping and resampling polylines) need, restated, and `polygons_to_mask`, which runs on the
+GPU."""
 import numpy as np
 
 
@@ -90,3 +91,156 @@ def polygons_to_mask(polygons, size, holes=None, return_times=False):
         raise ValueError(f"{ring_off[-1]} vertices: fewer than 2^31 are served")
     return _lib.stage_polygon_mask(np.vstack(rings + hole_rings), ring_off, len(rings), len(hole_rings), nx, ny,
                                    return_times=return_times)
+
+
+# ---- polylines (optimize.Lines) ------------------------------------------------------------------------------------------
+def boolean_split(a, mask, axis=0, circular=False, include="all"):
+    """helpers.py:762-812: `a` cut where `mask` changes, as a list of runs; `include`: "all" runs, or only the "true" or
+    the "false" ones.  `circular`: the last run joins the first when both ends of `mask` hold the same value."""
+    mask = np.asarray(mask)
+    cuts = np.nonzero(mask[1:] != mask[:-1])[0] + 1
+    splits = np.split(a, cuts, axis=axis)
+    if circular and len(splits) > 1 and mask[0] == mask[-1]:
+        splits[0] = np.concatenate((splits[-1], splits[0]), axis=axis)
+        splits.pop(-1)
+    if include == "all":
+        return splits
+    if include == "true":
+        return splits[slice(0, None, 2) if mask[0] else slice(1, None, 2)]
+    if include == "false":
+        return splits[slice(1, None, 2) if mask[0] else slice(0, None, 2)]
+    return []
+
+
+def unravel_box(box):
+    """helpers.py:1414-1436: (xmin, ..., xmax, ...) as [(xmin, ...), (xmax, ...)]."""
+    box = np.asarray(box)
+    if box.size % 2 != 0:
+        raise ValueError("Box length is not divisible by 2")
+    return box.reshape(-1, box.size // 2)
+
+
+def in_box(points, box):
+    """helpers.py:815-832: which points (n, ndim) lie in or on the box."""
+    box = unravel_box(box)
+    return np.all((points >= box[0, :]) & (points <= box[1, :]), axis=1)
+
+
+def intersect_rays_box(origin, directions, box, t=False):
+    """helpers.py:919-1001: entrances and exits of rays from one `origin` through an axis-aligned box (2-d or 3-d), NaN
+    for a miss, an origin inside the box (entrance) or an intersection behind the ray; `t`: as multiples of `directions`
+    (n, 1) instead of coordinates."""
+    directions = np.asarray(directions, dtype=float)
+    box = np.asarray(box, dtype=float).ravel()
+    ndims = directions.shape[1]
+    with np.errstate(divide="ignore"):
+        invdir = 1 / directions
+    sign = invdir < 0
+    with np.errstate(invalid="ignore"):
+        def slab(axis):  # the near and the far bound of an axis, along the ray
+            near = np.where(sign[:, axis], box[axis + ndims], box[axis])
+            far = np.where(sign[:, axis], box[axis], box[axis + ndims])
+            return (near - origin[axis]) * invdir[:, axis], (far - origin[axis]) * invdir[:, axis]
+
+        tmin, tmax = slab(0)
+        for axis in range(1, min(ndims, 3)):
+            amin, amax = slab(axis)
+            misses = (tmin > amax) | (amin > tmax)
+            tmin[misses] = np.nan
+            tmax[misses] = np.nan
+            later = amin > tmin
+            tmin[later] = amin[later]
+            sooner = amax < tmax
+            tmax[sooner] = amax[sooner]
+        tmin[tmin < 0] = np.nan
+        tmax[tmax < 0] = np.nan
+    if t:
+        return tmin[:, None], tmax[:, None]
+    return origin + tmin[:, None] * directions, origin + tmax[:, None] * directions
+
+
+def intersect_edge_box(origin, distance, box):
+    """helpers.py:890-916: the multiple of `distance` in (0, 1) at which the edge from `origin` meets the box, or None."""
+    import warnings
+
+    distance = np.asarray(distance).reshape(1, -1)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)  # (all-NaN: a miss)
+        t = np.nanmin(intersect_rays_box(origin, distance, box, t=True))
+    if t > 0 and t < 1:
+        return t
+    return None
+
+
+def clip_polyline_box(line, box, t=False):
+    """helpers.py:835-887: the runs of `line` (n, ndim [+ 1 distance measure if `t`]) inside the box, each with a vertex
+    inserted where it crosses the boundary.  A crossing between two consecutive outside vertices is not looked for."""
+    cols = slice(None, -1) if t else slice(None)
+    mask = in_box(line[:, cols], box)
+    segments = boolean_split(line, mask)
+    trues = slice(int(~mask[0]), None, 2)
+    nsegments = len(segments)
+    for i in range(*trues.indices(nsegments)):
+        if i > 0:
+            origin = segments[i - 1][-1, :]
+            distance = segments[i][0, :] - origin
+            ti = intersect_edge_box(origin[cols], distance[cols], box)
+            if ti is not None:
+                segments[i] = np.vstack((origin + ti * distance, segments[i]))
+        if i < nsegments - 1:
+            origin = segments[i][-1, :]
+            distance = segments[i + 1][0, :] - origin
+            ti = intersect_edge_box(origin[cols], distance[cols], box)
+            if ti is not None:
+                segments[i] = np.vstack((segments[i], origin + ti * distance))
+    return segments[trues]
+
+
+def line_distances(vertices):
+    """The cumulative Euclidean distance at each vertex, from 0 (helpers.py:1373-1377)."""
+    return np.insert(np.cumsum(np.sqrt(np.sum(np.diff(vertices, axis=0) ** 2, axis=1))), 0, 0)
+
+
+def line_count(x, dx):
+    """How many evenly spaced points `interpolate_line(dx=dx)` places over the distances `x` (helpers.py:1380-1383)."""
+    n = abs((x[-1] - x[0]) / dx)
+    if n == int(n):
+        n += 1
+    return int(round(n))
+
+
+def interpolate_line(vertices, x=None, xi=None, n=None, dx=None, error=True, fill="endpoints"):
+    """helpers.py:1322-1411: points at the distances `xi` along a polyline -- or `n` evenly spaced ones, or ones nominally
+    `dx` apart -- by linear interpolation between the vertices, whose distance measures are `x` (default: cumulative
+    Euclidean distance)."""
+    vertices = np.asarray(vertices)
+    if all((xi is None, n is None, dx is None)):
+        raise ValueError("One of xi, n, or dx is required")
+    if x is None:
+        x = line_distances(vertices)
+    if xi is None:
+        if n is None:
+            n = line_count(x, dx)
+        xi = np.linspace(start=x[0], stop=x[-1], num=n, endpoint=True)
+        error = False
+        fill = "endpoints"
+    if len(x) > 1 and x[1] < x[0]:
+        sort_index = np.argsort(x)
+        x = x[sort_index]
+        vertices = vertices[sort_index, :]
+    result = np.column_stack([np.interp(xi, x, vertices[:, i]) for i in range(vertices.shape[1])])
+    if isinstance(fill, str) and fill == "endpoints":
+        if error is False:
+            return result
+        fill = (vertices[0], vertices[-1])
+    if not np.iterable(fill):
+        fill = (fill, fill)
+    left = np.less(xi, x[0])
+    right = np.greater(xi, x[-1])
+    if x[0] > x[-1]:
+        right, left = left, right
+    if error and (left.any() or right.any()):
+        raise ValueError("Requested distance outside range")
+    result[left, :] = fill[0]
+    result[right, :] = fill[1]
+    return result

@@ -1,5 +1,13 @@
-"""`optimize`: orienting the images of an `Observer` from point matches between image pairs
-(the reference's optimize.py: `Matches` :462-740, `RotationMatches*` :743-975, `ObserverCameras` :1974-2083).
+"""`optimize`: fitting camera models to observations (the reference's optimize.py: `Points` :46-236, `Lines` :239-459,
+`Matches` :462-740, `RotationMatches*` :743-975, `Polynomial` :985-1130, `Cameras` :1133-1971, `ObserverCameras`
+:1974-2083, `ransac` :2091-2188).
+
+`Cameras.fit` finds camera parameters (position, view direction, focal length, distortion ...; per camera or shared by a
+group) that minimise the reprojection residuals of its controls -- surveyed points, traced lines, point matches between
+cameras -- with scipy.optimize.least_squares.  The residual function, which the optimiser needs once per step and once per
+Jacobian column, is evaluated on the GPU (`glh_calib_eval`): the controls are uploaded once per fit and one call
+evaluates every (control, perturbed parameter) block of a Jacobian.  What stays on the host is the vertex-level work of
+`Lines` (projecting, splitting and clipping the world polylines: the segment table) and the optimiser itself.
 
 `ObserverCameras.fit` finds one view direction per image, with one or more anchor images held in place, by minimising the
 L1 distance between the matched unit ray directions with BFGS.  Its objective and gradient -- a map over every match of
@@ -8,18 +16,175 @@ the callback sends 36 doubles per image (R and Rprime, made on the host by `came
 NumPy's) and receives 3 per image and the objective.  The summation order is fixed, so a fit is reproducible
 to the bit.  The match classes predict through the projection kernels.
 
-Not served: detecting and matching keypoints (`KeypointMatcher`: SIFT and FLANN of `cv2`) -- matches are passed in --
-and `Cameras.fit`, `Points`, `Lines`, `ransac`, `Polynomial` and plotting.
+Not served: detecting and matching keypoints (`KeypointMatcher`: SIFT and FLANN of `cv2`) -- matches are passed in --,
+the lmfit methods other than "least_squares" (lmfit is not a dependency) and plotting.
 """
+import math
 import sys
 
 import numpy as np
 
-from . import _lib
-from .camera import rotations
+from . import _lib, helpers
+from .camera import Camera, rotations
 
 _NO_MATCHER = ("keypoint detection and matching (SIFT and FLANN of cv2) are not served: pass the matches to "
                "ObserverCameras(observer, matches=...)")
+
+
+_NO_PLOT = "plotting is out of scope"
+
+
+class Points:
+    """optimize.py:46-236: image-world point correspondences of one camera: world coordinates `xyz` (n, 3) (ray directions
+    if `directions`; the camera must not move then) whose projections should be the image coordinates `uv` (n, 2)."""
+
+    def __init__(self, cam, uv, xyz, directions=False):
+        if len(uv) != len(xyz):
+            raise ValueError("Image and world coordinates have different length")
+        self.cam = cam
+        self.uv = np.asarray(uv, dtype=float)
+        self.xyz = np.asarray(xyz, dtype=float)
+        self.directions = directions
+        self._position = cam.xyz.copy()
+        self._imgsz = cam.imgsz.copy()
+
+    @property
+    def size(self):
+        return len(self.uv)
+
+    def observed(self, index=slice(None)):
+        return self.uv[index]
+
+    def _test_position(self):
+        if self.directions and any(self.cam.xyz != self._position):
+            raise ValueError("Camera position has changed and world coordinates are ray directions")
+
+    def predicted(self, index=slice(None)):
+        """Image coordinates of the world coordinates (the projection kernel)."""
+        self._test_position()
+        return self.cam.xyz_to_uv(self.xyz[index], directions=self.directions)
+
+    def plot(self, *args, **kwargs):
+        raise NotImplementedError(_NO_PLOT)
+
+    def _scale(self, scale):
+        if np.any(scale != 1):
+            self.uv = self.uv * scale
+
+    def resize(self, size=None, force=False):
+        """optimize.py:202-236: resize the camera (unless `size` is None) and scale the image coordinates to it."""
+        if size is not None:
+            self.cam.resize(size=size, force=force)
+        self._scale(self.cam.imgsz / self._imgsz)
+        self._imgsz = self.cam.imgsz.copy()
+
+
+def _clip_box(cam):
+    """The box of camera coordinates that holds the image: Lines._xyzs_to_uvs (optimize.py:328-330)."""
+    xy_edges = cam._uv_to_xy(cam.edges(step=cam.imgsz / 2))
+    return np.hstack((np.min(xy_edges, axis=0), np.max(xy_edges, axis=0)))
+
+
+def segment_table(cam, xyzs, directions=False, density=1, xy_box=None):
+    """What `glh_calib_eval` takes of a Lines job: the world polylines `xyzs` projected into camera coordinates, split at
+    vertices behind the camera, clipped to `xy_box` (default: the camera's own, `_clip_box`) and measured -- the vertex
+    half of Lines._xyzs_to_uvs (optimize.py:320-353); the pixel half (a point every 1 / density pixels along each clipped
+    segment, distorted) is the device's.  Returns (seg_vertex (S + 1,), seg_count (S,), seg_par (S, 5), vertex (V, 3)):
+    segment s has vertices seg_vertex[s] .. seg_vertex[s + 1] of `vertex` (x, y, cumulative distance) and seg_count[s]
+    points (helpers.interpolate_line's count; a segment whose count rounds to 0 is left out) at the distances
+    np.linspace(start, stop, count), of which seg_par[s] = (start, stop, step, stop - start, count - 1).  With no line in
+    frame, every vertex in front of the camera is a segment of one point (the reference's fallback)."""
+    xy_step = (1 / density) / cam.f.max()
+    if xy_box is None:
+        xy_box = _clip_box(cam)
+    segments, inlines, clipped = [], [], False
+    for xyz in xyzs:
+        xy = cam._xyz_to_xy(xyz, directions=directions)
+        for line in helpers.boolean_split(xy, np.isnan(xy[:, 0]), include="false"):
+            inlines.append(line)
+            for cline in helpers.clip_polyline_box(line, xy_box):
+                clipped = True
+                cline = np.array(cline)
+                x = helpers.line_distances(cline)
+                n = helpers.line_count(x, xy_step)
+                if n > 0:
+                    segments.append((cline, x, n))
+    if not clipped:
+        segments = [(line[k:k + 1], np.zeros(1), 1) for line in inlines for k in range(len(line))]
+    if not segments:
+        raise ValueError("No world line vertices project into the image or in front of the camera")
+    seg_vertex = np.concatenate(([0], np.cumsum([len(v) for v, _, _ in segments]))).astype(np.int64)
+    seg_count = np.array([n for _, _, n in segments], dtype=np.int64)
+    seg_par = np.empty((len(segments), 5))
+    for s, (_, x, n) in enumerate(segments):
+        delta = x[-1] - x[0]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            seg_par[s] = (x[0], x[-1], delta / (n - 1) if n > 1 else np.nan, delta, n - 1)
+    vertex = np.vstack([np.column_stack((v, x)) for v, x, _ in segments])
+    return seg_vertex, seg_count, seg_par, vertex
+
+
+class Lines(Points):
+    """optimize.py:239-459: image-world line correspondences of one camera.  The image polylines `uvs` are merged into
+    the points `uv`; the world polylines `xyzs` are projected onto the image at `density` points per pixel, and each image
+    point is matched to the nearest projected point.  `predicted` runs on the GPU (`glh_calib_eval` with one job) from the
+    segment table the host makes (`segment_table`).  A camera with an elevation correction is not served (the host half
+    of the projection, `Camera._xyz_to_xy`, has none) unless `directions`."""
+
+    def __init__(self, cam, uvs, xyzs, directions=False, density=1):
+        self.cam = cam
+        self.uvs = [np.asarray(uv, dtype=float) for uv in uvs]
+        self.uv = np.vstack(self.uvs)
+        self.xyzs = xyzs
+        self.directions = directions
+        self.density = density
+        self._position = cam.xyz.copy()
+        self._imgsz = cam.imgsz.copy()
+        self._boxes = {}  # the camera's internal parameters -> its clip box (a device call)
+
+    def _xy_box(self):
+        key = self.cam._vector[6:].tobytes()
+        if key not in self._boxes:
+            if len(self._boxes) >= 64:
+                self._boxes.clear()
+            self._boxes[key] = _clip_box(self.cam)
+        return self._boxes[key]
+
+    def _segment_table(self):
+        return segment_table(self.cam, self.xyzs, directions=self.directions, density=self.density, xy_box=self._xy_box())
+
+    def _xyzs_to_uvs(self):
+        """optimize.py:320-353 on the host: the projected world lines as image coordinates [(ni, 2), ...], one array per
+        clipped segment (per line in front of the camera when none is in frame)."""
+        xy_step = (1 / self.density) / self.cam.f.max()
+        xy_box = self._xy_box()
+        puvs, inlines = [], []
+        for xyz in self.xyzs:
+            xy = self.cam._xyz_to_xy(xyz, directions=self.directions)
+            for line in helpers.boolean_split(xy, np.isnan(xy[:, 0]), include="false"):
+                inlines.append(line)
+                for cline in helpers.clip_polyline_box(line, xy_box):
+                    puvs.append(self.cam._xy_to_uv(helpers.interpolate_line(np.array(cline), dx=xy_step)))
+        if puvs:
+            return puvs
+        return [self.cam._xy_to_uv(line) for line in inlines]
+
+    def predicted(self, index=slice(None)):
+        """For each observed point (of `index`), the nearest point of the projected world lines."""
+        self._test_position()
+        observed = np.ascontiguousarray(self.observed(index=index))
+        if not len(observed):
+            return np.empty((0, 2))
+        table = self._segment_table()
+        with _lib.Calib(1, [_lib.CALIB_KINDS["lines"]], [0], [0], [int(bool(self.directions))], [0, len(observed)], observed,
+                        np.zeros((len(observed), 3))) as handle:
+            return handle.eval(self.cam.vector24[None, None], self.cam.R[None, None], [0], [0], tables=[table])
+
+    def _scale(self, scale):
+        if np.any(scale != 1):
+            for i, uv in enumerate(self.uvs):
+                self.uvs[i] = uv * scale
+            self.uv *= scale
 
 
 class Matches:
@@ -69,7 +234,7 @@ class Matches:
         return self.cams[ci].xyz_to_uv(dxyz, directions=True)
 
     def plot(self, *args, **kwargs):
-        raise NotImplementedError("plotting is out of scope")
+        raise NotImplementedError(_NO_PLOT)
 
     def to_type(self, mtype):
         if mtype is type(self):
@@ -219,6 +384,687 @@ class KeypointMatcher:
 
     def __init__(self, *args, **kwargs):
         raise NotImplementedError(_NO_MATCHER)
+
+
+class Polynomial:
+    """optimize.py:985-1130: a least-squares polynomial of degree `deg` through the points `xy` (n, 2), as a model for
+    `ransac`."""
+
+    def __init__(self, xy, deg=1):
+        self.xy = np.asarray(xy)
+        self.deg = deg
+
+    @property
+    def size(self):
+        return len(self.xy)
+
+    def predict(self, params, index=slice(None)):
+        return np.polyval(params, self.xy[index, 0])
+
+    def errors(self, params, index=slice(None)):
+        prediction = self.predict(params, index)
+        return np.abs(prediction - self.xy[index, 1])
+
+    def fit(self, index=slice(None)):
+        return np.polyfit(self.xy[index, 0], self.xy[index, 1], deg=self.deg)
+
+    def plot(self, *args, **kwargs):
+        raise NotImplementedError(_NO_PLOT)
+
+
+_ATTRIBUTES = ("xyz", "viewdir", "imgsz", "f", "c", "k", "p")
+_LENGTHS = (3, 3, 2, 2, 2, 6, 2)
+_NO_LMFIT = ("lmfit is not installed: only method='least_squares' is served, through scipy.optimize.least_squares "
+             "(got method={!r})")
+
+
+def _kind_of(control):
+    if isinstance(control, Lines):
+        return _lib.CALIB_KINDS["lines"]
+    if isinstance(control, Points):
+        return _lib.CALIB_KINDS["points"]
+    if isinstance(control, RotationMatchesXYZ):
+        raise NotImplementedError("RotationMatchesXYZ has no observed(): it is ObserverCameras' control, not Cameras'")
+    if isinstance(control, RotationMatchesXY):
+        return _lib.CALIB_KINDS["rotation_xy"]
+    if isinstance(control, RotationMatches):
+        return _lib.CALIB_KINDS["rotation"]
+    if isinstance(control, Matches):
+        return _lib.CALIB_KINDS["matches"]
+    raise TypeError(f"not a control: {type(control).__name__}")
+
+
+class Cameras:
+    """optimize.py:1133-1971: the parameters of the cameras `cams` that minimise the reprojection errors of the `controls`
+    (`Points`, `Lines`, `Matches` and its rotation subclasses).  `cam_params`: per camera, the parameters to fit
+    (`parse_params`); `group_params`: per group of cameras (`group_indices`, default one group of all), parameters that
+    take one value for the whole group.  `weights`: one per control point.  `scales`: compute a scale factor per
+    parameter (`camera_scales`); `sparsity`: compute the sparsity structure of the Jacobian.
+
+    `params` is an ordered mapping label -> (value, min, max), groups first, where the reference keeps lmfit.Parameters."""
+
+    def __init__(self, cams, controls, cam_params=None, group_indices=None, group_params=None, weights=None, scales=True,
+                 sparsity=True):
+        cams, controls, cam_params, group_indices, group_params = self._as_lists(cams, controls, cam_params, group_indices,
+                                                                                 group_params)
+        self.cams = cams
+        self.controls = self.prune_controls(controls, cams=self.cams)
+        ncams = len(self.cams)
+        if cam_params is None:
+            cam_params = [{}] * ncams
+        self.cam_params = cam_params
+        if group_indices is None:
+            group_indices = [range(ncams)]
+        self.group_indices = group_indices
+        if group_params is None:
+            group_params = [{}] * len(self.group_indices)
+        self.group_params = group_params
+        self.weights = weights
+        self.device_id = 0
+        self._handle = None
+        self.update_params()
+        self._test()
+        self.vectors = [cam.to_array() for cam in self.cams]
+        self.scales = None
+        if scales:
+            self._build_scales()
+        self.sparsity = None
+        if sparsity:
+            self._build_sparsity()
+
+    @property
+    def weights(self):
+        return self._weights
+
+    @weights.setter
+    def weights(self, value):
+        if value is None:
+            self._weights = value
+        else:
+            value = np.atleast_2d(value).reshape(-1, 1)
+            self._weights = value * len(value) / sum(value)
+
+    @staticmethod
+    def _as_lists(cams, controls, cam_params, group_indices, group_params):
+        if isinstance(cams, Camera):
+            cams = [cams]
+        if isinstance(controls, (Points, Lines, Matches)):
+            controls = [controls]
+        if isinstance(cam_params, dict):
+            cam_params = [cam_params]
+        if isinstance(group_indices, int):
+            group_indices = [group_indices]
+        if group_indices is not None and isinstance(group_indices[0], int):
+            group_indices = [group_indices]
+        if isinstance(group_params, dict):
+            group_params = [group_params]
+        return cams, controls, cam_params, group_indices, group_params
+
+    @staticmethod
+    def _lmfit_labels(mask, cam=None, group=None):
+        """The labels of the selected parameters: "f0", "viewdir2" ... behind "cam<i>_" or "group<i>_"."""
+        base_labels = np.array([attribute + str(i) for attribute, length in zip(_ATTRIBUTES, _LENGTHS) for i in range(length)])
+        labels = base_labels[mask]
+        if cam is not None:
+            labels = ["cam" + str(cam) + "_" + label for label in labels]
+        if group is not None:
+            labels = ["group" + str(group) + "_" + label for label in labels]
+        return labels
+
+    @staticmethod
+    def _get_control_cams(control):
+        if isinstance(control, (Points, Lines)):
+            return [control.cam]
+        return control.cams
+
+    @classmethod
+    def prune_controls(cls, controls, cams):
+        """The controls that reference one or more of `cams`."""
+        return [control for control in controls if len(set(cams) & set(cls._get_control_cams(control))) > 0]
+
+    @staticmethod
+    def camera_scales(cam, controls=None):
+        """optimize.py:1327-1407: per camera parameter (20), the estimated change that moves an image point by a pixel;
+        `controls`: world controls of the camera, for the effect of moving it."""
+        dpixels = np.ones(20, dtype=float)
+        mean_r_uv = (cam.imgsz.mean() / 6) * (np.sqrt(2) + np.log(1 + np.sqrt(2)))
+        mean_r_xy = mean_r_uv / cam.f.mean()
+        if controls:
+            xyz = []
+            for control in controls:
+                if isinstance(control, (Points, Lines)) and cam is control.cam and not control.directions:
+                    if hasattr(control, "xyz"):
+                        xyz.append(control.xyz)
+                    elif hasattr(control, "xyzs"):
+                        xyz.extend(control.xyzs)
+            if xyz:
+                dpixels[0:3] = cam.f.mean() / np.linalg.norm(np.vstack(xyz) - cam.xyz).mean()
+        imgsz_degrees = (2 * np.arctan(cam.imgsz / (2 * cam.f))) * (180 / np.pi)
+        dpixels[3:5] = cam.imgsz / imgsz_degrees
+        theta = np.pi / 180
+        dpixels[5] = 2 * mean_r_uv * np.sin(theta / 2)
+        dpixels[6:8] = 0.5
+        dpixels[8:10] = mean_r_xy
+        dpixels[10:12] = 1
+        dpixels[12:18] = [
+            mean_r_xy ** 3 * cam.f.mean() * 2 ** (1 / 2),
+            mean_r_xy ** 5 * cam.f.mean() * 2 ** (3 / 2),
+            mean_r_xy ** 7 * cam.f.mean() * 2 ** (5 / 2),
+            mean_r_xy ** 3 / (1 + cam.k[3] * mean_r_xy ** 2) * cam.f.mean() * 2 ** (1 / 2),
+            mean_r_xy ** 5 / (1 + cam.k[4] * mean_r_xy ** 4) * cam.f.mean() * 2 ** (3 / 2),
+            mean_r_xy ** 7 / (1 + cam.k[5] * mean_r_xy ** 6) * cam.f.mean() * 2 ** (5 / 2),
+        ]
+        dpixels[18:20] = np.sqrt(5) * mean_r_xy ** 2 * cam.f.mean()
+        return 1 / dpixels
+
+    @staticmethod
+    def camera_bounds(cam):
+        """optimize.py:1410-1456: default bounds (20, 2) of the camera parameters."""
+        k = cam.f.mean() / 4000
+        p = cam.f.mean() / 40000
+        return np.array([
+            [-np.inf, np.inf], [-np.inf, np.inf], [-np.inf, np.inf],
+            [-np.inf, np.inf], [-np.inf, np.inf], [-np.inf, np.inf],
+            [0, np.inf], [0, np.inf],
+            [0, np.inf], [0, np.inf],
+            [-0.5, 0.5] * cam.imgsz[0:1], [-0.5, 0.5] * cam.imgsz[1:2],
+            [-k, k], [-k / 2, k / 2], [-k / 2, k / 2], [-k, k], [-k, k], [-k, k],
+            [-p, p], [-p, p],
+        ], dtype=float)
+
+    @staticmethod
+    def parse_params(params=None, default_bounds=None):
+        """optimize.py:1459-1522: (mask (20,), bounds (20, 2)) of `params`: {"viewdir": True}, {"viewdir": 0},
+        {"viewdir": [0, 1]}, or with bounds (indices, min, max), min and max one number or one per index; None or NaN take
+        `default_bounds`, else -inf / inf."""
+        if params is None:
+            params = {}
+        indices = (0, 3, 6, 8, 10, 12, 18, 20)
+        mask = np.zeros(20, dtype=bool)
+        bounds = np.full((20, 2), np.nan)
+        for key, value in params.items():
+            if key in _ATTRIBUTES:
+                selection = value[0] if isinstance(value, tuple) else value
+                if selection or selection == 0:
+                    i = _ATTRIBUTES.index(key)
+                    if selection is True:
+                        positions = range(indices[i], indices[i + 1])
+                    else:
+                        positions = indices[i] + np.atleast_1d(selection)
+                    mask[positions] = True
+                if isinstance(value, tuple):
+                    min_bounds = np.atleast_1d(np.asarray(value[1], dtype=float))
+                    if len(min_bounds) == 1:
+                        min_bounds = np.repeat(min_bounds, len(positions))
+                    max_bounds = np.atleast_1d(np.asarray(value[2], dtype=float))
+                    if len(max_bounds) == 1:
+                        max_bounds = np.repeat(max_bounds, len(positions))
+                    bounds[positions] = np.column_stack((min_bounds, max_bounds))
+        if default_bounds is not None:
+            missing_min, missing_max = np.isnan(bounds[:, 0]), np.isnan(bounds[:, 1])
+            bounds[missing_min, 0] = default_bounds[missing_min, 0]
+            bounds[missing_max, 1] = default_bounds[missing_max, 1]
+        bounds[np.isnan(bounds[:, 0]), 0] = -np.inf
+        bounds[np.isnan(bounds[:, 1]), 1] = np.inf
+        return mask, bounds
+
+    def _test(self):
+        if not len(self.controls):
+            raise ValueError("No controls reference the cameras")
+        for i, idx in enumerate(self.group_indices):
+            fc = "f" in self.group_params[i] or "c" in self.group_params[i]
+            sizes = np.unique(np.vstack([self.cams[j].imgsz for j in idx]), axis=0)
+            if fc and len(sizes) > 1:
+                raise ValueError("Group " + str(i) + ": 'f' or 'c' in parameters but image sizes not equal")
+        M = np.vstack(self.group_masks)
+        overlaps = np.nonzero(np.count_nonzero(M, axis=0) > 1)[0]
+        for i in overlaps:
+            groups = np.nonzero(M[:, i])[0]
+            idx = np.concatenate([self.group_indices[group] for group in groups])
+            if len(np.unique(idx)) < len(idx):
+                raise ValueError("Some cameras are in multiple groups with overlapping masks")
+        control_cams = [cam for control in self.controls for cam in self._get_control_cams(control)]
+        cams_with_params = [cam for i, cam in enumerate(self.cams)
+                            if self.cam_params[i]
+                            or any([self.group_params[j] for j, idx in enumerate(self.group_indices) if i in idx])]
+        if set(cams_with_params) - set(control_cams):
+            raise ValueError("Not all cameras with params appear in controls")
+
+    def _build_scales(self):
+        scales = [self.camera_scales(cam, self.controls) for cam in self.cams]
+        cam_scales = [scale[mask] for scale, mask in zip(scales, self.cam_masks)]
+        group_scales = [np.nanmean(np.vstack([scales[i][mask] for i in idx]), axis=0)
+                        for mask, idx in zip(self.group_masks, self.group_indices)]
+        self.scales = np.hstack((np.hstack(group_scales), np.hstack(cam_scales)))
+
+    def _build_sparsity(self):
+        """optimize.py:1580-1613: which residuals (two per control point) depend on which parameter."""
+        import scipy.sparse
+
+        m_control = [2 * control.size for control in self.controls]
+        n = self.cam_breaks[-1]
+        groups = np.zeros((len(self.cams), len(self.group_indices)), dtype=bool)
+        for i, idx in enumerate(self.group_indices):
+            groups[list(idx), i] = True
+        S = scipy.sparse.lil_matrix((sum(m_control), n), dtype=int)
+        control_breaks = np.cumsum([0] + m_control)
+        for i, control in enumerate(self.controls):
+            ctrl_slice = slice(control_breaks[i], control_breaks[i + 1])
+            for cam in self._get_control_cams(control):
+                try:
+                    j = self.cams.index(cam)
+                except ValueError:
+                    continue
+                S[ctrl_slice, slice(self.cam_breaks[j], self.cam_breaks[j + 1])] = 1
+                for group in np.nonzero(groups[j])[0]:
+                    S[ctrl_slice, slice(self.group_breaks[group], self.group_breaks[group + 1])] = 1
+        self.sparsity = S
+
+    def update_params(self):
+        """optimize.py:1615-1670: `params` (label -> (value, min, max)) and the masks and breaks `set_cameras` uses, from
+        the cameras' current state.  A group parameter starts at the mean over its cameras."""
+        self.params = {}
+        cam_bounds = [self.camera_bounds(cam) for cam in self.cams]
+        self.cam_masks, cam_bounds = zip(*[self.parse_params(params, default_bounds=bounds)
+                                           for params, bounds in zip(self.cam_params, cam_bounds)])
+        cam_labels = [self._lmfit_labels(mask, cam=i, group=None) for i, mask in enumerate(self.cam_masks)]
+        cam_values = [self.cams[i]._vector[mask] for i, mask in enumerate(self.cam_masks)]
+        self.group_masks = []
+        for group, idx in enumerate(self.group_indices):
+            bounds = np.column_stack((np.column_stack([cam_bounds[i][:, 0] for i in idx]).max(axis=1),
+                                      np.column_stack([cam_bounds[i][:, 1] for i in idx]).min(axis=1)))
+            mask, bounds = self.parse_params(self.group_params[group], default_bounds=bounds)
+            labels = self._lmfit_labels(mask, cam=None, group=group)
+            values = np.nanmean(np.vstack([self.cams[i]._vector[mask] for i in idx]), axis=0)
+            for label, value, bound in zip(labels, values, bounds[mask]):
+                self.params[label] = (float(value), float(bound[0]), float(bound[1]))
+            self.group_masks.append(mask)
+        for i in range(len(self.cams)):
+            for label, value, bound in zip(cam_labels[i], cam_values[i], cam_bounds[i][self.cam_masks[i]]):
+                self.params[label] = (float(value), float(bound[0]), float(bound[1]))
+        self.group_breaks = np.cumsum([0] + [np.count_nonzero(mask) for mask in self.group_masks])
+        self.cam_breaks = np.cumsum([self.group_breaks[-1]] + [np.count_nonzero(mask) for mask in self.cam_masks])
+
+    def set_cameras(self, params, save=False):
+        """optimize.py:1672-1696: write parameter values ([group0 | group1 | cam0 | cam1 | ...], or a mapping as
+        `params`) into the cameras; `save`: also as the state `reset_cameras` returns to."""
+        if isinstance(params, dict):
+            params = [value[0] if isinstance(value, tuple) else value for value in params.values()]
+        for i, idx in enumerate(self.group_indices):
+            for j in idx:
+                self.cams[j]._vector[self.group_masks[i]] = params[self.group_breaks[i]:self.group_breaks[i + 1]]
+                self.cams[j]._vector[self.cam_masks[j]] = params[self.cam_breaks[j]:self.cam_breaks[j + 1]]
+        if save:
+            self.vectors = [cam.to_array() for cam in self.cams]
+
+    def reset_cameras(self):
+        for cam, vector in zip(self.cams, self.vectors):
+            cam._vector = vector.copy()
+
+    @property
+    def size(self):
+        return np.sum([control.size for control in self.controls])
+
+    def observed(self, index=slice(None)):
+        if len(self.controls) == 1:
+            return self.controls[0].observed(index=index)
+        return np.vstack([control.observed() for control in self.controls])[index]
+
+    # ---- the controls on the device
+    def upload(self):
+        """The controls on the device, as `_lib.Calib`; while it is open, `predicted`, `residuals` and `jacobian` evaluate
+        through it (close it after use, or use it as a context manager)."""
+        dev_cams = list(self.cams)
+        for control in self.controls:
+            for cam in self._get_control_cams(control):
+                if not any(cam is c for c in dev_cams):
+                    dev_cams.append(cam)  # (a camera that is not fitted: it keeps its vector)
+        where = lambda cam: [cam is c for c in dev_cams].index(True)  # noqa: E731
+        kind, cam_a, cam_b, directions, obs, src = [], [], [], [], [], []
+        for control in self.controls:
+            k = _kind_of(control)
+            kind.append(k)
+            cams = self._get_control_cams(control)
+            cam_a.append(where(cams[0]))
+            cam_b.append(where(cams[-1]))
+            directions.append(int(bool(getattr(control, "directions", False))))
+            if k in (_lib.CALIB_KINDS["points"], _lib.CALIB_KINDS["lines"]):
+                first = control.uv
+                second = control.xyz if k == _lib.CALIB_KINDS["points"] else np.zeros((control.size, 3))
+            else:
+                sides = control.uvs if k == _lib.CALIB_KINDS["matches"] else control.xys
+                first, second = sides[0], np.column_stack((sides[1], np.zeros(len(sides[1]))))
+            obs.append(np.asarray(first, dtype=float).reshape(-1, 2))
+            src.append(np.asarray(second, dtype=float).reshape(-1, 3))
+        offsets = np.concatenate(([0], np.cumsum([len(o) for o in obs]))).astype(np.int64)
+        handle = _lib.Calib(len(dev_cams), kind, cam_a, cam_b, directions, offsets, np.concatenate(obs), np.concatenate(src),
+                            device_id=self.device_id)
+        self._handle, self._dev_cams = handle, dev_cams
+        return handle
+
+    def _open(self):
+        return self._handle if self._handle is not None and self._handle._h else None
+
+    def _job_table(self, control):
+        """The checks `control.predicted` makes, at the cameras' current state, and the segment table of a Lines control."""
+        control._test_position()
+        if isinstance(control, RotationMatches):
+            control._test_internals()
+        return control._segment_table() if isinstance(control, Lines) else None
+
+    def _evaluate(self, handle, sets, jobs, return_times=False):
+        """`predicted` of the `jobs` [(control, set)] under the camera vectors `sets` [[vector (20,) per camera]], as one
+        device call: a list of (size, 2) arrays in job order."""
+        import time
+
+        saved = [cam._vector for cam in self.cams]
+        by_set = {}
+        for q, (_, s) in enumerate(jobs):
+            by_set.setdefault(s, []).append(q)
+        tables = [None] * len(jobs)
+        t0 = time.perf_counter()
+        try:
+            for s, members in by_set.items():
+                for cam, vector in zip(self.cams, sets[s]):
+                    cam._vector = vector
+                for q in members:
+                    tables[q] = self._job_table(self.controls[jobs[q][0]])
+        finally:
+            for cam, vector in zip(self.cams, saved):
+                cam._vector = vector
+        t1 = time.perf_counter()
+        cams24 = np.empty((len(sets), len(self._dev_cams), _lib.CAM_LEN))
+        cams24[:] = np.array([cam.vector24 for cam in self._dev_cams])
+        cams24[:, :len(self.cams), :20] = np.asarray(sets, dtype=float)
+        rot = rotations(cams24[:, :, 3:6].reshape(-1, 3))[0].reshape(len(sets), len(self._dev_cams), 3, 3)
+        out = handle.eval(cams24, rot, [i for i, _ in jobs], [s for _, s in jobs], tables=tables, return_times=return_times)
+        flat, times = out if return_times else (out, None)
+        breaks = np.cumsum([self.controls[i].size for i, _ in jobs])[:-1]
+        blocks = np.split(flat, breaks)
+        if return_times:
+            times["segment_tables_host"] = (t1 - t0) * 1e3
+            return blocks, times
+        return blocks
+
+    def predicted(self, params=None, index=slice(None)):
+        """optimize.py:1721-1746: the controls' predicted coordinates, at `params` if given (the cameras are left as they
+        were).  Through the handle of `upload` while it is open -- one device call -- else control by control."""
+        if params is not None:
+            vectors = [cam.to_array() for cam in self.cams]
+            self.set_cameras(params)
+        try:
+            handle = self._open()
+            if handle is not None:
+                blocks = self._evaluate(handle, [[cam._vector for cam in self.cams]], [(i, 0) for i in range(len(self.controls))])
+                result = np.vstack(blocks)[index]
+            elif len(self.controls) == 1:
+                result = self.controls[0].predicted(index=index)
+            else:
+                result = np.vstack([control.predicted() for control in self.controls])[index]
+        finally:
+            if params is not None:
+                for cam, vector in zip(self.cams, vectors):
+                    cam._vector = vector
+        return result
+
+    def residuals(self, params=None, index=slice(None)):
+        """optimize.py:1748-1764: predicted - observed, times the weights."""
+        d = self.predicted(params=params, index=index) - self.observed(index=index)
+        if self.weights is None:
+            return d
+        return d * self.weights[index]
+
+    def errors(self, params=None, index=slice(None)):
+        return np.linalg.norm(self.residuals(params=params, index=index), axis=1)
+
+    def _values_bounds(self, params=None):
+        table = np.array(list(self.params.values()), dtype=float).reshape(-1, 3)
+        if params is None:
+            x = table[:, 0].copy()
+        elif isinstance(params, dict):
+            x = np.array([value[0] if isinstance(value, tuple) else value for value in params.values()], dtype=float)
+        else:
+            x = np.array(params, dtype=float)
+        return x, table[:, 1], table[:, 2]
+
+    @staticmethod
+    def _steps(x0, lb, ub):
+        """scipy.optimize's forward-difference steps (approx_derivative, "2-point", default relative step):
+        sqrt(eps) * (+1 if x >= 0 else -1) * max(1, |x|), turned round where x + h leaves the bounds and -h fits, and
+        shortened to the wider side where neither fits."""
+        h = np.finfo(np.float64).eps ** 0.5 * ((x0 >= 0).astype(float) * 2 - 1) * np.maximum(1.0, np.abs(x0))
+        lower_dist, upper_dist = x0 - lb, ub - x0
+        x = x0 + h
+        violated = (x < lb) | (x > ub)
+        fitting = np.abs(h) <= np.maximum(lower_dist, upper_dist)
+        h[violated & fitting] *= -1
+        forward = (upper_dist >= lower_dist) & ~fitting
+        h[forward] = upper_dist[forward]
+        backward = (upper_dist < lower_dist) & ~fitting
+        h[backward] = -lower_dist[backward]
+        return h
+
+    def _jacobian_plan(self, params=None):
+        """(sets, dx, jobs) of one Jacobian at `params`: the camera vectors of the base set and of every set with one
+        parameter stepped, the steps as the difference quotient divides by them ((x_j + h) - x_j), and the jobs
+        [(control, set)]: every control at the base set, then per parameter the controls `self.sparsity` marks."""
+        import scipy.sparse
+
+        x0, lb, ub = self._values_bounds(params)
+        if np.any((x0 < lb) | (x0 > ub)):
+            raise ValueError("`x0` violates bound constraints.")
+        h = self._steps(x0, lb, ub)
+        n, n_controls = len(x0), len(self.controls)
+        breaks = 2 * np.concatenate(([0], np.cumsum([control.size for control in self.controls])))
+        if self.sparsity is None:
+            marked = [range(n_controls)] * n
+        else:
+            S = scipy.sparse.csc_matrix(self.sparsity)
+            marked = [np.unique(np.searchsorted(breaks, S.indices[S.indptr[j]:S.indptr[j + 1]], side="right") - 1) for j in range(n)]
+        saved = [cam._vector for cam in self.cams]
+        sets, dx = [], np.empty(n)
+        try:
+            for j in range(-1, n):
+                x = x0.copy()
+                if j >= 0:
+                    x[j] = x0[j] + h[j]
+                    dx[j] = x[j] - x0[j]
+                for cam, vector in zip(self.cams, saved):
+                    cam._vector = vector.copy()
+                self.set_cameras(x)
+                sets.append([cam._vector for cam in self.cams])
+        finally:
+            for cam, vector in zip(self.cams, saved):
+                cam._vector = vector
+        jobs = [(i, 0) for i in range(n_controls)] + [(int(i), j + 1) for j in range(n) for i in marked[j]]
+        return sets, dx, jobs
+
+    def jacobian(self, params=None, index=slice(None), return_times=False):
+        """The Jacobian of `residuals(params, index).ravel()` by scipy.optimize's 2-point forward differences, entry
+        (f(x + h e_j) - f(x)) / ((x_j + h) - x_j) with the steps of `_steps` inside `params`' bounds -- bit for bit what
+        scipy.optimize.least_squares(jac="2-point", jac_sparsity=self.sparsity) computes from the same residuals -- with
+        every (control, parameter) block that `self.sparsity` marks (every block without one) evaluated in ONE device call.
+        A sparse matrix of that structure (dense without).  Needs the handle of `upload` open."""
+        import scipy.sparse
+
+        handle = self._open()
+        if handle is None:
+            raise RuntimeError("Cameras.jacobian evaluates through the handle of Cameras.upload(): open one first")
+        sets, dx, jobs = self._jacobian_plan(params)
+        n, n_controls = len(dx), len(self.controls)
+        sizes = [control.size for control in self.controls]
+        breaks = 2 * np.concatenate(([0], np.cumsum(sizes)))
+        out = self._evaluate(handle, sets, jobs, return_times=return_times)
+        blocks, times = out if return_times else (out, None)
+        weights = None if self.weights is None else np.split(self.weights, np.cumsum(sizes)[:-1])
+
+        def residual(q):
+            i = jobs[q][0]
+            d = blocks[q] - self.controls[i].observed()
+            return (d if weights is None else d * weights[i]).ravel()
+
+        f0 = [residual(i) for i in range(n_controls)]
+        rows, cols, values = [], [], []
+        for q in range(n_controls, len(jobs)):
+            i, j = jobs[q][0], jobs[q][1] - 1
+            rows.append(np.arange(breaks[i], breaks[i + 1]))
+            cols.append(np.full(2 * sizes[i], j))
+            values.append((residual(q) - f0[i]) / dx[j])
+        m = int(breaks[-1])
+        if self.sparsity is None:  # (every block is there; written in place: a sum into zeros would lose the sign of -0.0)
+            J = np.zeros((m, n))
+            for r, c, v in zip(rows, cols, values):
+                J[r, c] = v
+        else:
+            J = scipy.sparse.csr_matrix(scipy.sparse.coo_matrix(
+                (np.concatenate(values) if values else np.zeros(0), (np.concatenate(rows) if rows else np.zeros(0, int),
+                                                                     np.concatenate(cols) if cols else np.zeros(0, int))), shape=(m, n)))
+        if not (isinstance(index, slice) and index == slice(None)):
+            picked = np.arange(m // 2)[index] if isinstance(index, slice) else np.asarray(index)
+            J = J[np.dstack((2 * picked, 2 * picked + 1)).ravel()]
+        return (J, times) if return_times else J
+
+    def fit(self, index=slice(None), cam_params=None, group_params=None, full=False, method="least_squares", **kwargs):
+        """optimize.py:1781-1878: the parameter values that minimise the residuals (`index`: of which control points), by
+        scipy.optimize.least_squares inside the parameters' bounds, with `x_scale=self.scales` and
+        `jac_sparsity=self.sparsity` (its rows of `index`) unless `kwargs` say otherwise.  Only this, the reference's
+        default method, is served: it is what lmfit.minimize(method="least_squares") runs.  `cam_params`, `group_params`:
+        lists of parameter sets to fit one after the other first, each from the previous result (each such fit with its
+        own scales and sparsity; the caller's `kwargs` are passed on).  `nan_policy` ("omit", the default: rows with NaN
+        are dropped from each evaluation; "raise"; "propagate") is lmfit's -- with a sparsity structure, dropped rows end
+        in scipy's shape error, as in the reference.
+
+        Unless `kwargs` has `jac`, the controls are uploaded and the Jacobian is `self.jacobian`: all its columns in one
+        device call.  Returns the values as an array, or None (and prints the message) if the fit failed; `full`: scipy's
+        OptimizeResult with `params` (label -> (value, min, max)) added."""
+        import scipy.optimize
+
+        if method != "least_squares":
+            raise NotImplementedError(_NO_LMFIT.format(method))
+        user_kwargs = dict(kwargs)
+        kwargs = {"nan_policy": "omit", **kwargs}
+        nan_policy = kwargs.pop("nan_policy")
+        if self.scales is not None and "x_scale" not in kwargs:
+            kwargs["x_scale"] = self.scales
+        if self.sparsity is not None and "jac_sparsity" not in kwargs:
+            if isinstance(index, slice) and index == slice(None):
+                kwargs["jac_sparsity"] = self.sparsity
+            else:
+                jac_index = np.arange(self.size)[index] if isinstance(index, slice) else np.asarray(index)
+                jac_index = np.dstack((2 * jac_index, 2 * jac_index + 1)).ravel()
+                kwargs["jac_sparsity"] = self.sparsity.tocsr()[jac_index]
+        iterations = max(len(cam_params) if cam_params else 0, len(group_params) if group_params else 0)
+        if iterations:
+            for n in range(iterations):
+                model = Cameras(cams=self.cams, controls=self.controls,
+                                cam_params=cam_params[n] if cam_params else self.cam_params,
+                                group_params=group_params[n] if group_params else self.group_params)
+                values = model.fit(index=index, method=method, **user_kwargs)
+                if values is not None:
+                    model.set_cameras(params=values)
+            self.update_params()
+
+        def keep(r):
+            if nan_policy == "omit":
+                return ~np.isnan(r)
+            if nan_policy == "raise" and np.isnan(r).any():
+                raise ValueError("NaN values detected in your input data or the output of your objective/model function - "
+                                 "fitting algorithms cannot handle this!")
+            return np.ones(len(r), dtype=bool)
+
+        def fun(x):
+            resid = self.residuals(x, index=index)
+            with np.errstate(invalid="ignore"):
+                err = np.linalg.norm(resid.reshape(-1, 2), ord=2, axis=1).mean()
+            sys.stdout.write("\r" + str(err))
+            sys.stdout.flush()
+            r = np.asarray(resid).ravel()
+            return r[keep(r)]
+
+        def jac(x):
+            J = self.jacobian(x, index=index)
+            if self.sparsity is None:
+                r = np.asarray(self.residuals(x, index=index)).ravel()
+                J = J[keep(r)]
+            return J
+
+        x0, lb, ub = self._values_bounds()
+        own = "jac" not in kwargs
+        try:
+            if own:
+                self.upload()
+                kwargs["jac"] = jac
+            result = scipy.optimize.least_squares(fun, x0, bounds=(lb, ub), **kwargs)
+        finally:
+            if own and self._handle is not None:
+                self._handle.close()
+                self._handle = None
+        sys.stdout.write("\n")
+        if iterations:
+            self.reset_cameras()
+            self.update_params()
+        if not result.success:
+            print(result.message)
+        if full:
+            result.params = {label: (float(value), bounds[1], bounds[2])
+                             for (label, bounds), value in zip(self.params.items(), result.x)}
+            return result
+        if result.success:
+            return np.array(result.x)
+        return None
+
+    def plot(self, *args, **kwargs):
+        raise NotImplementedError(_NO_PLOT)
+
+    def plot_weights(self, *args, **kwargs):
+        raise NotImplementedError(_NO_PLOT)
+
+
+def ransac(model, n, max_error, min_inliers, iterations=100, **kwargs):
+    """optimize.py:2091-2150: (parameters, inlier indices) of `model` -- an object with `size`, `fit(index)` and
+    `errors(params, index)` -- by Random Sample Consensus: fit to samples of `n`, keep the fit whose members within
+    `max_error` number more than `min_inliers` besides the sample and have the smallest mean error."""
+    params = None
+    err = np.inf
+    full = np.arange(model.size)
+    for maybe_idx in _ransac_samples(n=n, size=model.size, iterations=iterations):
+        maybe_params = model.fit(maybe_idx, **kwargs)
+        if maybe_params is None:
+            continue
+        test_idx = np.delete(full, maybe_idx)
+        test_errs = model.errors(maybe_params, test_idx)
+        also_idx = test_idx[test_errs < max_error]
+        if len(also_idx) > min_inliers:
+            better_idx = np.concatenate((maybe_idx, also_idx))
+            better_params = model.fit(better_idx, **kwargs)
+            if better_params is None:
+                continue
+            this_err = np.mean(model.errors(better_params, better_idx))
+            if this_err < err:
+                params = better_params
+                err = this_err
+    if params is None:
+        raise ValueError("Best fit does not meet acceptance criteria")
+    inliers = np.where(model.errors(params) <= max_error)[0]
+    return params, inliers
+
+
+def _ransac_samples(n, size, iterations=100):
+    """optimize.py:2153-2188: up to `iterations` different samples of `n` of `size` indices, drawn by np.random.shuffle
+    (at most as many as there are combinations)."""
+    if n >= size:
+        raise ValueError("Sample size is larger or equal to total size")
+    log = math.lgamma(size + 1) - math.lgamma(n + 1) - math.lgamma(size - n + 1)
+    if log:
+        iterations = min(iterations, np.floor(np.exp(log)))
+    samples = set()
+    indices = np.arange(size)
+    while len(samples) < iterations:
+        np.random.shuffle(indices)
+        sample = frozenset(indices[:n])
+        if sample not in samples:
+            yield list(sample)
+            samples.add(sample)
 
 
 def match_pairs(matches):

@@ -695,6 +695,55 @@ int glh_orient_eval(glh_orient* handle, const double* R, const double* Rprime, d
 /* Frees the handle and its device memory (NULL: nothing).                                                              */
 int glh_orient_destroy(glh_orient* handle);
 
+/* ---- optimize.Cameras: the predictions of the controls under many sets of camera vectors (optimize.py:1721-1764) ------
+ * A handle holds the controls of a calibration on the device; they are uploaded once and evaluated many times.  Control c
+ * is of kind[c] (GLH_CALIB_*), belongs to camera cam_a[c] of the n_cams cameras (the match kinds: to cam_a[c] and
+ * cam_b[c], the first and the second camera of the matches) and owns rows row_offset[c] .. row_offset[c + 1] (int64
+ * [n_controls + 1], from 0, not decreasing) of obs [N][2] and src [N][3]:
+ *   POINTS       obs = the observed image coordinates, src = the world coordinates (ray directions if directions[c])
+ *   LINES        obs = the observed image coordinates, src unused
+ *   MATCHES      obs = the first camera's image coordinates, src[.][0:2] = the second camera's
+ *   ROTATION, ROTATION_XY   likewise, with normalised camera coordinates instead of image coordinates
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, n_cams < 1, n_controls < 0, an unknown kind, a camera
+ * index outside 0 .. n_cams - 1, offsets that do not start at 0 or decrease, 2^31 rows or more).                        */
+#define GLH_CALIB_POINTS 0
+#define GLH_CALIB_LINES 1
+#define GLH_CALIB_MATCHES 2
+#define GLH_CALIB_ROTATION 3
+#define GLH_CALIB_ROTATION_XY 4
+typedef struct glh_calib glh_calib;
+int glh_calib_create(int device_id, int n_cams, int n_controls, const int32_t* kind, const int32_t* cam_a,
+                     const int32_t* cam_b, const int32_t* directions, const int64_t* row_offset, const double* obs,
+                     const double* src, glh_calib** handle);
+/* One evaluation of n_jobs jobs.  Job q is control job_control[q] under the camera vectors of set job_set[q] of cams
+ * [n_sets][n_cams][GLH_CAM_LEN]; rot [n_sets][n_cams][9] are the cameras' rotation matrices as the caller's own host code
+ * makes them (Camera.R, row-major: what Camera._xy_to_xyz and _xyz_to_xy of the ROTATION kinds multiply by).  For the
+ * match kinds job_side[q] says which camera predicts: 0 the first (from the second's points), 1 the second; 0 otherwise.
+ * predicted: the jobs' rows [sum of rows][2] in job order --
+ *   POINTS       Camera.xyz_to_uv of the world coordinates
+ *   MATCHES      Camera.uv_to_xyz of the other camera, then Camera.xyz_to_uv(directions=True)
+ *   ROTATION     Camera._xy_to_xyz of the other camera ((R[0][k] x + R[1][k] y) + R[2][k], with rot), then xyz_to_uv
+ *   ROTATION_XY  the same rays, then Camera._xyz_to_xy with rot: camera coordinates
+ *   LINES        for every observed point the nearest (dx dx + dy dy; the first of equal ones; index 0 if none is below
+ *                +inf) of the job's projected points.  Those are made from the job's segment table, segments job_seg[q] ..
+ *                job_seg[q + 1] (int64 [n_jobs + 1]; other kinds have none, a LINES job at least one): segment s has the
+ *                vertices seg_vertex[s] .. seg_vertex[s + 1] (int64 [n_segments + 1]) of vertex [n_vertices][3] -- camera
+ *                coordinates x, y and the distance along the segment, not decreasing -- and seg_count[s] >= 1 points at
+ *                the distances of np.linspace, from seg_par[s] = (start, stop, step, delta, div): i step + start (i / div
+ *                times delta where step is 0; i delta for a single point), the last one stop.  A point's camera
+ *                coordinates are np.interp's; Camera._distort and _xy_to_uv of the job's camera make its image
+ *                coordinates.
+ * float64, no contraction, no atomics: two evaluations give the same bytes.  times_ms (or NULL) [5]: HIP-event
+ * milliseconds -- [0] upload, [1] the point and match rows, [2] the line points, [3] the nearest search, [4] download.
+ * GLH_E_INVALID: null pointers, an index out of range, a table that does not add up, 2^31 rows, points or vertices or
+ * more; GLH_E_UNSUPPORTED: a raster grid among the cameras.                                                             */
+int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams, const double* rot, int n_jobs,
+                   const int32_t* job_control, const int32_t* job_set, const int32_t* job_side, const int64_t* job_seg,
+                   const int64_t* seg_vertex, const int64_t* seg_count, const double* seg_par, int64_t n_vertices,
+                   const double* vertex, double* predicted, double* times_ms);
+/* Frees the handle and its device memory (NULL: nothing).                                                              */
+int glh_calib_destroy(glh_calib* handle);
+
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
 
