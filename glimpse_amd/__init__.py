@@ -6,6 +6,7 @@ Drop-in names for that path only (see DESIGN.md for scope):
     (+ CylindricalMotion, TangentCartesianMotion, TangentCylindricalMotion)
     from glimpse_amd.optimize import ObserverCameras, RotationMatchesXYZ   # orienting an image sequence
     from glimpse_amd.optimize import Cameras, Points, Lines, Matches       # calibrating cameras
+    from glimpse_amd.optimize import KeypointMatcher, match_keypoints      # matching keypoints between images
 
 The compute runs in hand-written HIP kernels behind a C ABI (include/glimpse_hip.h,
 glimpse_amd/lib/libglimpse_hip.so, bound with ctypes in glimpse_amd._lib).  There is no CPU
@@ -18,8 +19,8 @@ from .motion import (CartesianMotion, CylindricalMotion, Motion, TangentCartesia
                      TangentCylindricalMotion)
 from . import optimize
 from .observer import Observer
-from .optimize import (Cameras, Lines, Matches, ObserverCameras, Points, Polynomial, RotationMatches, RotationMatchesXY,
-                       RotationMatchesXYZ, ransac)
+from .optimize import (Cameras, KeypointMatcher, Lines, Matches, ObserverCameras, Points, Polynomial, RotationMatches,
+                       RotationMatchesXY, RotationMatchesXYZ, match_keypoints, ransac)
 from .raster import Raster, RasterInterpolant
 from .tracker import Tracker
 from .tracks import Tracks
@@ -27,5 +28,5 @@ from .tracks import Tracks
 __all__ = ["Camera", "Image", "Observer", "Motion", "CartesianMotion", "CylindricalMotion",
            "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "RasterInterpolant", "Tracker", "Tracks", "maximum_filter",
            "gaussian_filter", "optimize", "Matches", "RotationMatches", "RotationMatchesXY", "RotationMatchesXYZ",
-           "ObserverCameras", "Cameras", "Points", "Lines", "Polynomial", "ransac"]
+           "ObserverCameras", "Cameras", "Points", "Lines", "Polynomial", "ransac", "KeypointMatcher", "match_keypoints"]
 __version__ = "0.1.0"

@@ -171,6 +171,11 @@ SIGNATURES = {
     "glh_calib_create": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "glh_calib_eval": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "glh_calib_destroy": (_I, [_P]),
+    "glh_match_create": (_I, [_I, _P]),
+    "glh_match_put": (_I, [_P, _I, _I, _I, _I, _P]),
+    "glh_match_drop": (_I, [_P, _I]),
+    "glh_match_knn2": (_I, [_P, _I, _I, _P, _P, _P]),
+    "glh_match_destroy": (_I, [_P]),
 }
 
 _lib = None
@@ -1342,6 +1347,87 @@ class Calib:
         if self._h:
             handle, self._h = self._h, C.c_void_p()
             check(load().glh_calib_destroy(handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MATCH_TIMES = ("upload", "prepare", "search", "merge", "download")
+MATCH_U8, MATCH_F32 = 0, 1
+MATCH_U8_MAX_DIM = 256  # csrc/glh_match.h
+
+
+class Matcher:
+    """Descriptor sets on the device (glh_match_create): each is uploaded once under a slot number and searched many
+    times (optimize.match_keypoints, optimize.KeypointMatcher.build_matches).  `knn2(q, t)` is, for every row of slot q's
+    set, the two rows of slot t's with the smallest keys (squared distance, row index): equal distances go to the lower
+    index."""
+
+    def __init__(self, device_id=0):
+        self._h = C.c_void_p()
+        self._sets = {}  # slot -> (kind, n, dim)
+        check(load().glh_match_create(int(device_id), C.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise GlhError(-4, "the handle is closed")
+        return self._h
+
+    def put(self, slot, descriptors, path=None):
+        """Uploads `descriptors` (n, dim) under `slot`, in the place of what it held; returns the path taken.  uint8
+        rows, and float rows whose values are all integers in 0 .. 255, take the integer path when dim <= 256 (exact
+        int32 distances on the matrix cores); everything else the float path (float32, summed in element order).
+        `path="float"` forces the float path."""
+        handle = self._handle()
+        if path not in (None, "float"):
+            raise ValueError(f'path is None or "float", not {path!r}')
+        d = np.asarray(descriptors)
+        if d.ndim != 2:
+            raise ValueError(f"expected descriptors (n, dim), got shape {d.shape}")
+        integer = path is None and d.shape[1] <= MATCH_U8_MAX_DIM and d.dtype != np.bool_ and (
+            d.dtype == np.uint8 or bool(np.all((d >= 0) & (d <= 255) & (d == np.floor(d)))))
+        kind = MATCH_U8 if integer else MATCH_F32
+        d = _arr(d, np.uint8 if integer else np.float32)
+        check(load().glh_match_put(handle, int(slot), kind, d.shape[0], d.shape[1], _ptr(d)))
+        self._sets[int(slot)] = (kind, d.shape[0], d.shape[1])
+        return "integer" if integer else "float"
+
+    def drop(self, slot):
+        check(load().glh_match_drop(self._handle(), int(slot)))
+        self._sets.pop(int(slot), None)
+
+    def slots(self):
+        return sorted(self._sets)
+
+    def path(self, slot):
+        """"integer" or "float": the path the set of `slot` was prepared for; None when the slot is empty."""
+        held = self._sets.get(int(slot))
+        return None if held is None else ("integer" if held[0] == MATCH_U8 else "float")
+
+    def knn2(self, slot_q, slot_t, return_times=False):
+        """(idx int32 (n_q, 2), d2 float32 (n_q, 2)): the nearest and second nearest row of slot_t's set for every row
+        of slot_q's.  A set of one row has no second: (-1, inf)."""
+        handle = self._handle()
+        n_q = self._sets.get(int(slot_q), (0, 0, 0))[1]  # (an unknown slot is the library's to report)
+        idx, d2 = np.empty((n_q, 2), np.int32), np.empty((n_q, 2), np.float32)
+        times = np.zeros(len(MATCH_TIMES))
+        check(load().glh_match_knn2(handle, int(slot_q), int(slot_t), _ptr(idx), _ptr(d2), _ptr(times)))
+        return _timed((idx, d2), MATCH_TIMES, times, return_times, extend=True)
+
+    def close(self):
+        if self._h:
+            handle, self._h = self._h, C.c_void_p()
+            self._sets = {}
+            check(load().glh_match_destroy(handle))
 
     def __enter__(self):
         return self

@@ -20,6 +20,7 @@
 #include "glh_project_dem.h"
 #include "glh_horizon.h"
 #include "glh_calib.h"
+#include "glh_match.h"
 #include "glh_orient.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
@@ -2908,6 +2909,70 @@ extern "C" int glh_stage_uv_to_xy(int dev, const double* cam, const double* uv, 
   CamDev cd;
   expand_camera(cam, &cd);
   return uv_to_xy_run(dev, cd, uv, n, xy);
+}
+
+// optimize.match_keypoints' nearest-neighbour search (optimize.py:2234-2309): the arguments are checked here, before a
+// device is touched; the kernels and the launches are glh_match.hip's.
+struct glh_match {
+  MatchHandle* h;
+};
+
+extern "C" int glh_match_create(int dev, glh_match** handle) {
+  if (!handle) return fail(GLH_E_INVALID, "match: null handle pointer");
+  *handle = nullptr;
+  if (dev < 0) return fail(GLH_E_INVALID, "match: device %d", dev);
+  glh_match* g = new (std::nothrow) glh_match{nullptr};
+  if (!g) return fail(GLH_E_NOMEM, "match: no memory for a handle");
+  const int rc = match_create(dev, &g->h);
+  if (rc != GLH_OK) {
+    delete g;
+    return rc;
+  }
+  *handle = g;
+  return GLH_OK;
+}
+
+extern "C" int glh_match_put(glh_match* handle, int slot, int kind, int n, int dim, const void* data) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "match: null handle");
+  if (slot < 0) return fail(GLH_E_INVALID, "match: slot %d", slot);
+  if (kind != GLH_MATCH_U8 && kind != GLH_MATCH_F32) return fail(GLH_E_INVALID, "match: unknown kind %d", kind);
+  if (n == 0) return fail(GLH_E_INVALID, "match: a set of 0 rows (n == 0) cannot be searched");
+  if (n < 0 || n > MT_MAX_ROWS) return fail(GLH_E_INVALID, "match: %d rows: 1 .. 2^30 are served", n);
+  const int max_dim = kind == GLH_MATCH_U8 ? MT_U8_MAX_DIM : MT_MAX_DIM;
+  if (dim < 1 || dim > max_dim)
+    return fail(GLH_E_INVALID, "match: dim %d: 1 .. %d are served for %s", dim, max_dim, kind == GLH_MATCH_U8 ? "uint8" : "float32");
+  if ((int64_t)n * ((dim + 31) / 32 * 32) > MT_MAX_ELEMS)
+    return fail(GLH_E_INVALID, "match: %d rows of %d elements: at most 2^35 padded elements a set are served", n, dim);
+  if (!data) return fail(GLH_E_INVALID, "match: null data");
+  return match_put(handle->h, slot, kind, n, dim, data);
+}
+
+extern "C" int glh_match_drop(glh_match* handle, int slot) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "match: null handle");
+  MatchSetInfo s;
+  if (!match_info(handle->h, slot, &s)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot);
+  match_drop(handle->h, slot);
+  return GLH_OK;
+}
+
+extern "C" int glh_match_knn2(glh_match* handle, int slot_q, int slot_t, int32_t* idx, float* d2, double* times_ms) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "match: null handle");
+  if (!idx || !d2) return fail(GLH_E_INVALID, "match: null argument");
+  MatchSetInfo q, t;
+  if (!match_info(handle->h, slot_q, &q)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot_q);
+  if (!match_info(handle->h, slot_t, &t)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot_t);
+  if (q.kind != t.kind)
+    return fail(GLH_E_INVALID, "match: mixed kinds: slot %d is %s, slot %d is %s", slot_q, q.kind == GLH_MATCH_U8 ? "uint8" : "float32",
+                slot_t, t.kind == GLH_MATCH_U8 ? "uint8" : "float32");
+  if (q.dim != t.dim) return fail(GLH_E_INVALID, "match: dim mismatch: slot %d has %d, slot %d has %d", slot_q, q.dim, slot_t, t.dim);
+  return match_knn2(handle->h, slot_q, slot_t, idx, d2, times_ms);
+}
+
+extern "C" int glh_match_destroy(glh_match* handle) {
+  if (!handle) return GLH_OK;
+  match_destroy(handle->h);
+  delete handle;
+  return GLH_OK;
 }
 
 // optimize.Cameras' predictions (optimize.py:1721-1764): the arguments are checked here, before a device is touched; the

@@ -1,6 +1,10 @@
 """The few functions of the reference's src/glimpse/helpers.py that the host-side raster logic and the camera calibration
 (`optimize.Lines`: splitting, clipping and resampling polylines) need, restated, and `polygons_to_mask`, which runs on the
 GPU."""
+import gzip
+import pickle
+from pathlib import Path
+
 import numpy as np
 
 
@@ -244,3 +248,30 @@ def interpolate_line(vertices, x=None, xi=None, n=None, dx=None, error=True, fil
     result[left, :] = fill[0]
     result[right, :] = fill[1]
     return result
+
+
+def strip_path(path, extensions=True):
+    """helpers.py:137-160: the final component of `path` without its file extensions (`extensions`: how many at the
+    most, True for all)."""
+    basename = Path(path).name
+    if extensions:
+        if extensions is True:
+            extensions = -1
+        return basename[::-1].split(".", maxsplit=extensions)[-1][::-1]
+    return basename
+
+
+def write_pickle(obj, path, gz=False, binary=True, **kwargs):
+    """helpers.py:210-235: `obj` as a pickle at `path` (its directory is made)."""
+    path = Path(path)
+    path.parent.mkdir(parents=True, exist_ok=True)
+    mode = "wb" if binary else "w"
+    with (gzip.open(path, mode=mode) if gz else open(path, mode=mode)) as fp:
+        pickle.dump(obj, file=fp, **kwargs)
+
+
+def read_pickle(path, gz=False, binary=True, **kwargs):
+    """helpers.py:238-257: the object of the pickle at `path`."""
+    mode = "rb" if binary else "r"
+    with (gzip.open(path, mode=mode) if gz else open(path, mode=mode)) as fp:
+        return pickle.load(fp, **kwargs)

@@ -1,6 +1,6 @@
 """`optimize`: fitting camera models to observations (the reference's optimize.py: `Points` :46-236, `Lines` :239-459,
 `Matches` :462-740, `RotationMatches*` :743-975, `Polynomial` :985-1130, `Cameras` :1133-1971, `ObserverCameras`
-:1974-2083, `ransac` :2091-2188).
+:1974-2083, `ransac` :2091-2188, `match_keypoints` :2234-2309, `KeypointMatcher` :2312-2773).
 
 `Cameras.fit` finds camera parameters (position, view direction, focal length, distortion ...; per camera or shared by a
 group) that minimise the reprojection residuals of its controls -- surveyed points, traced lines, point matches between
@@ -16,11 +16,23 @@ the callback sends 36 doubles per image (R and Rprime, made on the host by `came
 NumPy's) and receives 3 per image and the objective.  The summation order is fixed, so a fit is reproducible
 to the bit.  The match classes predict through the projection kernels.
 
-Not served: detecting and matching keypoints (`KeypointMatcher`: SIFT and FLANN of `cv2`) -- matches are passed in --,
-the lmfit methods other than "least_squares" (lmfit is not a dependency) and plotting.
+`match_keypoints` and `KeypointMatcher.build_matches` match the keypoint descriptors of image pairs on the GPU
+(`glh_match_knn2`): for every descriptor the two nearest of the other image by exact brute force, equal distances going to
+the lower index.  uint8 descriptors (SIFT) are compared in exact integers on the int8 matrix cores, anything else in
+float32 summed in element order; both are restated bit for bit in NumPy (tests/matcher_restated.py).  This is the exact
+answer that the reference's default matcher, the approximate and unseeded `cv2.FlannBasedMatcher`, approximates: it is
+pinned to the stated rule, not to FLANN's output.  The descriptors of an image are uploaded once per `build_matches` call
+and stay on the device until the last pair that needs them.
+
+Not served: detecting keypoints (`detect_keypoints`, the detecting branch of `build_keypoints`: SIFT of `cv2`; keypoints
+are read from files or passed in), CLAHE, a `mask` for the GPU matcher, the lmfit methods other than "least_squares"
+(lmfit is not a dependency) and plotting.
 """
+import collections
+import datetime
 import math
 import sys
+from pathlib import Path
 
 import numpy as np
 
@@ -32,6 +44,11 @@ _NO_MATCHER = ("keypoint detection and matching (SIFT and FLANN of cv2) are not 
 
 
 _NO_PLOT = "plotting is out of scope"
+_NO_DETECT = ("keypoint detection (SIFT of cv2) is not served: give KeypointMatcher.keypoints, or a directory of "
+              "keypoint files, as (points, descriptors) per image")
+_NO_CLAHE = "CLAHE (cv2.createCLAHE) is not served: pass clahe=False"
+_NO_MASK = ("a knnMatch mask is not served by the GPU matcher (the reference's own code cannot index the short lists "
+            "cv2 returns for one): pass mask=None, or a matcher object of your own")
 
 
 class Points:
@@ -379,11 +396,387 @@ class RotationMatchesXYZ(RotationMatchesXY):
         raise NotImplementedError()
 
 
-class KeypointMatcher:
-    """optimize.py (`KeypointMatcher`): not served."""
+def detect_keypoints(array, mask=None, method=None, root=False, **kwargs):
+    """optimize.py:2194-2231: not served (SIFT of cv2)."""
+    raise NotImplementedError(_NO_DETECT)
 
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError(_NO_MATCHER)
+
+DMatch = collections.namedtuple("DMatch", "queryIdx trainIdx distance")  # what the logic below reads of a cv2.DMatch
+
+
+def _point(keypoint):
+    """(u, v) of a keypoint: a row of an (n, 2) array, or an object with `.pt` (cv2.KeyPoint)."""
+    return keypoint.pt if hasattr(keypoint, "pt") else keypoint
+
+
+def _device_knn(handle, slots, descriptors, k):
+    """[[DMatch] * k] for every row of `descriptors[0]` among `descriptors[1]`, which `handle` (a `_lib.Matcher`) holds or
+    will hold under `slots`: the distance is np.sqrt of the float32 squared distance, as a Python float (cv2's is one).
+    Sets that took different paths are searched on the float path."""
+    for slot, d in zip(slots, descriptors):
+        if handle.path(slot) is None:
+            handle.put(slot, d)
+    paths = [handle.path(slot) for slot in slots]
+    if paths[0] != paths[1]:
+        for slot, d, path in zip(slots, descriptors, paths):
+            if path == "integer":
+                handle.put(slot, d, path="float")
+    idx, d2 = handle.knn2(slots[0], slots[1])
+    distance = np.sqrt(d2).tolist()
+    idx = idx.tolist()
+    return [[DMatch(q, idx[q][r], distance[q][r]) for r in range(k)] for q in range(len(idx))]
+
+
+def _match_keypoints(ka, kb, knn, cross_check, max_ratio, max_distance, return_ratios):
+    """optimize.py:2270-2309 after the matcher: `knn(False)` is knnMatch(ka, kb), `knn(True)` knnMatch(kb, ka)."""
+    def _build_empty(return_ratios):
+        empty = np.array([], dtype=float).reshape(0, 2)
+        uva, uvb = empty, empty.copy()
+        ratios = np.array([], dtype=float)
+        if return_ratios:
+            return uva, uvb, ratios
+        return uva, uvb
+
+    compute_ratios = max_ratio or return_ratios
+    n = 2 if compute_ratios else 1
+    if len(ka[0]) >= n and len(kb[0]) >= n:
+        matches = knn(False)
+        if cross_check:
+            matches_ba = knn(True)
+            ba = {(m[0].trainIdx, m[0].queryIdx) for m in matches_ba}  # (a list in the reference: the same members)
+            matches = [m for m in matches if (m[0].queryIdx, m[0].trainIdx) in ba]
+        if max_ratio:
+            matches = [m for m in matches if m[0].distance / m[1].distance < max_ratio]
+        if not matches:
+            return _build_empty(return_ratios)
+        uva = np.asarray([_point(ka[0][m[0].queryIdx]) for m in matches])
+        uvb = np.asarray([_point(kb[0][m[0].trainIdx]) for m in matches])
+        if return_ratios:
+            ratios = np.array([m.distance / n.distance for m, n in matches])
+        if max_distance:
+            valid = np.linalg.norm(uva - uvb, axis=1) < max_distance
+            uva, uvb = uva[valid], uvb[valid]
+            if return_ratios:
+                ratios = ratios[valid]
+    else:
+        return _build_empty(return_ratios)
+    if return_ratios:
+        return uva, uvb, ratios
+    return uva, uvb
+
+
+def match_keypoints(ka, kb, mask=None, cross_check=False, max_ratio=None, max_distance=None, return_ratios=False,
+                    matcher=None, device_id=0, resident=None):
+    """optimize.py:2234-2309: the image coordinates (n, 2), (n, 2) of the matched keypoints of two images, and with
+    `return_ratios` the ratio (n,) of the best to the second best descriptor distance of each.  A keypoint set is
+    (points, descriptors): `points` an (n, 2) array or a sequence of objects with `.pt`, `descriptors` (n, dim).
+
+    With `matcher=None` the nearest neighbours are searched on the GPU (`_lib.Matcher`): the exact two nearest by
+    brute force, equal distances going to the lower index -- the exact answer that the reference's default, the
+    approximate and unseeded cv2.FlannBasedMatcher, approximates; pinned to that rule, not to FLANN's output.  The
+    distance is np.sqrt of the float32 squared distance.  `cross_check` runs the same search the other way round.  The
+    reference's logic follows unchanged: cross-check, then the ratio test (<), then `max_distance` (<); the ratios are
+    quotients of Python floats, so a second best distance of 0 raises ZeroDivisionError as it does there.  `mask` with
+    the GPU matcher raises NotImplementedError.
+
+    Any other `matcher` with knnMatch(query, train, k=, mask=) is used on the host exactly as the reference uses it.
+
+    Two parameters beyond the reference's, for the GPU matcher only: `device_id`, the device a search of its own runs
+    on; `resident` = (a `_lib.Matcher`, (slot of ka, slot of kb)), a handle of the caller's that holds, or will hold,
+    the two descriptor sets under those slots and stays open (what `KeypointMatcher.build_matches` passes)."""
+    if mask is not None:
+        mask = np.asarray(mask, dtype=np.uint8)
+    n = 2 if (max_ratio or return_ratios) else 1
+    if matcher is not None:
+        def knn(swap):
+            q, t = (kb[1], ka[1]) if swap else (ka[1], kb[1])
+            return matcher.knnMatch(q, t, k=n, mask=mask)
+        return _match_keypoints(ka, kb, knn, cross_check, max_ratio, max_distance, return_ratios)
+    if mask is not None:
+        raise NotImplementedError(_NO_MASK)
+    handle, slots = resident if resident is not None else (None, (0, 1))
+    own = handle is None
+    if own and len(ka[0]) >= n and len(kb[0]) >= n:
+        handle = _lib.Matcher(device_id=device_id)
+    try:
+        def knn(swap):
+            order = (1, 0) if swap else (0, 1)
+            return _device_knn(handle, [slots[o] for o in order], [(ka[1], kb[1])[o] for o in order], n)
+        return _match_keypoints(ka, kb, knn, cross_check, max_ratio, max_distance, return_ratios)
+    finally:
+        if own and handle is not None:
+            handle.close()
+
+
+class PairMatches:
+    """The matches of image pairs as `KeypointMatcher.matches` keeps them: `data` (an object array of `Matches`), `row`
+    and `col` (the images of each) and `shape` (n, n) -- the attributes of the scipy.sparse.coo_matrix the reference
+    builds, which the installed SciPy cannot build of objects (INPUTS.md).  `match_pairs` reads it."""
+
+    def __init__(self, data, row, col, shape):
+        self.data = np.empty(len(data), dtype=object)
+        for k, m in enumerate(data):
+            self.data[k] = m
+        self.row, self.col = np.asarray(row, dtype=int), np.asarray(col, dtype=int)
+        self.shape = tuple(shape)
+
+    def eliminate_zeros(self):
+        """scipy's: drops the entries whose data is False / 0."""
+        keep = np.array([not (isinstance(m, (bool, int, float)) and m == 0) for m in self.data], dtype=bool)
+        self.data, self.row, self.col = self.data[keep], self.row[keep], self.col[keep]
+
+
+class KeypointMatcher:
+    """optimize.py:2312-2773: matches the keypoints of `images` (in ascending temporal order) pair by pair, on the GPU
+    (`build_matches`).  `keypoints`: per image (points, descriptors) as `match_keypoints` takes them; they are passed in
+    or read from files (`build_keypoints`), detection is not served, nor is `clahe`."""
+
+    def __init__(self, images=None, clahe=False):
+        if images is None:
+            raise NotImplementedError(_NO_MATCHER)
+        dts = np.diff([img.datetime for img in images])
+        if np.any(dts < datetime.timedelta(0)):
+            raise ValueError("Images are not in ascending temporal order")
+        self.images = np.empty(len(images), dtype=object)
+        for i, img in enumerate(images):
+            self.images[i] = img
+        if clahe is not False:
+            raise NotImplementedError(_NO_CLAHE)
+        self.clahe = None
+        self.device_id = 0
+        self.keypoints = None
+        self.matches = None
+
+    def _prepare_image_basenames(self):
+        basenames = [helpers.strip_path(img.path) for img in self.images]
+        if len(basenames) != len(set(basenames)):
+            raise ValueError("Image basenames are not unique")
+        return basenames
+
+    def build_keypoints(self, masks=None, path=None, overwrite=False, clear_images=True, clear_keypoints=False,
+                        parallel=False, **kwargs):
+        """optimize.py:2367-2445: the reading, writing and cached branches (`basename.pkl` under `path`); an image whose
+        keypoints would have to be detected raises NotImplementedError.  `parallel` is accepted and ignored."""
+        if path:
+            path = Path(path)
+        if clear_keypoints and not path:
+            raise ValueError("path is required when clear_keypoints is True")
+        if path and path.is_file():
+            raise ValueError("path must be a directory")
+        basenames = self._prepare_image_basenames()
+        if not self.keypoints:
+            self.keypoints = [None] * len(self.images)
+        result = []
+        for i, img in enumerate(self.images):
+            print(img.path)
+            if path:
+                outpath = path / f"{basenames[i]}.pkl"
+                written = outpath.exists()
+            else:
+                written = False
+            keypoints = self.keypoints[i]
+            read = keypoints is not None
+            if not read and written and not clear_keypoints:
+                keypoints = helpers.read_pickle(outpath)
+            elif read and not written and path:
+                helpers.write_pickle(keypoints, path=outpath)
+            elif (not read and not written) or overwrite:
+                raise NotImplementedError(_NO_DETECT)
+            if clear_keypoints:
+                keypoints = None
+            result.append(keypoints)
+        self.keypoints = result
+
+    def _matching_images(self, maxdt=None, seq=None, imgs=None):
+        """optimize.py:2513-2537: for every image the later images it is matched with."""
+        n = len(self.images)
+        if maxdt is None and seq is None:
+            matching_images = [np.arange(i + 1, n) for i in range(n)]
+        elif maxdt is not None:
+            datetimes = np.array([img.datetime for img in self.images])
+            ends = np.searchsorted(datetimes, datetimes + maxdt, side="right")
+            matching_images = [np.arange(i + 1, end) for i, end in enumerate(ends)]
+        elif seq is not None:
+            matching_images = [np.array([], dtype=int) for i in range(n)]
+        if seq is not None:
+            seq = np.asarray(seq)
+            seq = np.unique(seq[seq > 0])
+            for i, m in enumerate(matching_images):
+                iseq = seq + i
+                iseq = iseq[: np.searchsorted(iseq, n)]
+                matching_images[i] = np.unique(np.concatenate((m, iseq)))
+        if imgs is not None:
+            for i, m in enumerate(matching_images):
+                if i in imgs:
+                    matching_images[i] = m
+                else:
+                    matching_images[i] = m[np.isin(m, imgs)]
+        return matching_images
+
+    def build_matches(self, maxdt=None, seq=None, imgs=None, keypoints_path=None, path=None, overwrite=False,
+                      clear_keypoints=True, clear_matches=False, parallel=False, weights=False, mtype=None, filter=None,
+                      **kwargs):
+        """optimize.py:2447-2622, every argument as there: the pairs (i, j > i) named by `maxdt`, `seq` and `imgs` are
+        matched with `match_keypoints(**kwargs)`, read from and written to `basenames[i]-basenames[j].pkl` under `path`,
+        and kept in `self.matches` (a `PairMatches`) unless `clear_matches`.  `parallel` is accepted and ignored: the
+        GPU is the parallelism.  One `_lib.Matcher` serves the whole call: the descriptors of an image are uploaded when
+        the first pair needs them and dropped after the last row that does."""
+        if path:
+            path = Path(path)
+        if keypoints_path:
+            keypoints_path = Path(keypoints_path)
+        if clear_matches and not path:
+            raise ValueError("path is required when clear_matches is True")
+        if path and path.is_file():
+            raise ValueError("path must be a directory")
+        kwargs = {**kwargs, **{"return_ratios": weights}}
+        basenames = self._prepare_image_basenames()
+        if self.keypoints is None:
+            self.keypoints = [None] * len(self.images)
+        if any(k is None for k in self.keypoints) and not keypoints_path:
+            raise ValueError("Missing keypoints so keypoints_path is required")
+        matching_images = self._matching_images(maxdt=maxdt, seq=seq, imgs=imgs)
+        last_row = {}  # image -> the last row that searches its descriptors
+        for i, js in enumerate(matching_images):
+            for j in js:
+                last_row[int(j)] = i
+            if len(js):
+                last_row[i] = max(last_row.get(i, i), i)
+        on_device = kwargs.get("matcher") is None and kwargs.get("mask") is None
+        handle = None  # (opened when the first pair has to be searched: cached pairs need no device)
+        matches = []
+        try:
+            for i, js in enumerate(matching_images):
+                if len(js) > 0:
+                    print("Matching", i, "->", ", ".join(js.astype(str)))
+                row = []
+                imgA = self.images[i]
+                if self.keypoints[i] is None:
+                    self.keypoints[i] = helpers.read_pickle(keypoints_path / f"{basenames[i]}.pkl")
+                for j in js:
+                    imgB = self.images[j]
+                    if self.keypoints[j] is None:
+                        self.keypoints[j] = helpers.read_pickle(keypoints_path / f"{basenames[j]}.pkl")
+                    if path:
+                        outfile = path / f"{basenames[i]}-{basenames[j]}.pkl"
+                    if path and not overwrite and outfile.exists():
+                        if not clear_matches:
+                            match = helpers.read_pickle(outfile)
+                            match.cams = (imgA.cam, imgB.cam)  # (the cameras of this sequence, not the file's copies)
+                            if mtype is not None:
+                                match = match.to_type(mtype)
+                            row.append(match)
+                    else:
+                        if on_device and handle is None:
+                            handle = _lib.Matcher(device_id=self.device_id)
+                        resident = (handle, (i, int(j))) if on_device else None
+                        result = match_keypoints(self.keypoints[i], self.keypoints[j], resident=resident, **kwargs)
+                        match = Matches(cams=(imgA.cam, imgB.cam), uvs=result[0:2],
+                                        weights=(1 / result[2]) if weights else None)
+                        if path is not None:
+                            helpers.write_pickle(match, outfile)
+                        if not clear_matches:
+                            if mtype is not None:
+                                match = match.to_type(mtype)
+                            row.append(match)
+                if clear_keypoints:
+                    self.keypoints[i] = None
+                if handle is not None:
+                    for slot in handle.slots():
+                        if last_row.get(slot, -1) <= i:
+                            handle.drop(slot)
+                if filter and not clear_matches:
+                    for match in row:
+                        if match:
+                            match.filter(**filter)
+                matches.append(row)
+        finally:
+            if handle is not None:
+                handle.close()
+        if clear_matches:
+            self.matches = None
+            return
+        rows = np.concatenate([np.asarray([i] * len(row), dtype=int) for i, row in enumerate(matching_images)])
+        cols = np.concatenate(matching_images)
+        # (the shape scipy.sparse.coo_matrix infers from the indices, as the reference's does; (0, 0) without a pair, where
+        # the reference's constructor fails)
+        shape = (int(rows.max()) + 1, int(cols.max()) + 1) if len(rows) else (0, 0)
+        self.matches = PairMatches([m for row in matches for m in row], rows, cols, shape)
+
+    def _test_matches(self):
+        if self.matches is None:
+            raise ValueError("Matches have not been initialized. Run build_matches()")
+
+    def _assign_cameras(self):
+        for m, i, j in zip(self.matches.data, self.matches.row, self.matches.col):
+            m.cams = self.images[i].cam, self.images[j].cam
+
+    def convert_matches(self, mtype, clear_uvs=False, parallel=False):
+        """optimize.py:2634-2671 (`parallel` is accepted and ignored)."""
+        self._test_matches()
+        for i, m in enumerate(self.matches.data):
+            m = m.to_type(mtype)
+            if clear_uvs and mtype in (RotationMatchesXY, RotationMatchesXYZ):
+                m.uvs = None
+            self.matches.data[i] = m
+
+    def filter_matches(self, clear_weights=False, parallel=False, **kwargs):
+        """optimize.py:2673-2707 (`parallel` is accepted and ignored)."""
+        self._test_matches()
+        for i, m in enumerate(self.matches.data):
+            if kwargs:
+                m.filter(**kwargs)
+            if clear_weights:
+                m.weights = None
+            self.matches.data[i] = m
+
+    def _images_mask(self, imgs):
+        if np.iterable(imgs):
+            return np.isin(self.matches.row, imgs) | np.isin(self.matches.col, imgs)
+        return (self.matches.row == imgs) | (self.matches.col == imgs)
+
+    def _images_matches(self, imgs):
+        return self.matches.data[self._images_mask(imgs)]
+
+    def matches_per_image(self):
+        """optimize.py:2720-2727: the matched points of every image."""
+        self._test_matches()
+        image_matches = [self._images_matches(i) for i in range(len(self.images))]
+        return np.array([np.sum([mi.size for mi in m]) for m in image_matches])
+
+    def images_per_image(self):
+        """optimize.py:2729-2733: the images every image has matches with."""
+        self._test_matches()
+        image_matches = [self._images_matches(i) for i in range(len(self.images))]
+        return np.array([np.sum([mi.size > 0 for mi in m]) for m in image_matches])
+
+    def drop_images(self, imgs):
+        """optimize.py:2735-2758: drops the matches of `imgs`, then every image left without a match."""
+        self._test_matches()
+        mask = self._images_mask(imgs)
+        self.matches.data[mask] = False
+        self.matches.eliminate_zeros()
+        all = np.arange(len(self.images))
+        keep = np.union1d(self.matches.row, self.matches.col)
+        drop = np.setdiff1d(all, keep)
+        _, new_row = np.unique(np.concatenate((self.matches.row, keep)), return_inverse=True)
+        self.matches.row = new_row[: -len(keep)]
+        _, new_col = np.unique(np.concatenate((self.matches.col, keep)), return_inverse=True)
+        self.matches.col = new_col[: -len(keep)]
+        n = len(self.images) - len(drop)
+        self.matches.shape = (n, n)
+        self.images = np.delete(self.images, drop)
+
+    def match_breaks(self, min_matches=0):
+        """optimize.py:2760-2773: the images after which the chain of pairwise matches breaks."""
+        self._test_matches()
+        all_starts = np.arange(len(self.images) - 1)
+        starts, counts = np.unique(self.matches.row, return_counts=True)
+        breaks = np.setdiff1d(all_starts, starts)
+        if min_matches:
+            min_matches = np.minimum(min_matches, len(self.images) - np.arange(len(self.images)))
+            breaks = np.sort(np.concatenate((breaks, np.where(counts < min_matches)[0])))
+        return breaks
 
 
 class Polynomial:
@@ -1094,7 +1487,7 @@ class ObserverCameras:
             anchors = [0]
         self.anchors = anchors
         self.matches = matches
-        self.matcher = None  # (a KeypointMatcher in the reference)
+        self.matcher = None  # (set it to a KeypointMatcher(observer.images) for build_keypoints / build_matches)
         self.device_id = 0
         self.viewdirs = np.vstack([img.cam.viewdir.copy() for img in self.observer.images])
 
@@ -1106,10 +1499,17 @@ class ObserverCameras:
         self.set_cameras(viewdirs=self.viewdirs.copy())
 
     def build_keypoints(self, **kwargs):
-        raise NotImplementedError(_NO_MATCHER)
+        if self.matcher is None:
+            raise NotImplementedError(_NO_MATCHER)
+        self.matcher.build_keypoints(**kwargs)
 
     def build_matches(self, **kwargs):
-        raise NotImplementedError(_NO_MATCHER)
+        """optimize.py:2018-2022, with `self.matcher` a `KeypointMatcher` of the observer's images."""
+        if self.matcher is None:
+            raise NotImplementedError(_NO_MATCHER)
+        self.matcher.build_matches(**kwargs)
+        self.matcher.convert_matches(RotationMatchesXYZ)
+        self.matches = self.matcher.matches
 
     def upload(self):
         """The matches on the device, as `_lib.Orient` (what `fit` evaluates; close it after use)."""

@@ -744,6 +744,34 @@ int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams, const doub
 /* Frees the handle and its device memory (NULL: nothing).                                                              */
 int glh_calib_destroy(glh_calib* handle);
 
+/* ---- optimize.match_keypoints: the exact two nearest neighbours among descriptor sets (optimize.py:2234-2309) ----------
+ * A handle keeps descriptor sets on the device, each under a slot number >= 0 of the caller's choosing; a set is uploaded
+ * once and searched many times.  For every row q of set Q, glh_match_knn2 gives the two rows of set T with the smallest
+ * keys (d2, row index) in lexicographic order: equal distances go to the lower index.  The order is total, so the result
+ * is a function of the two sets alone.
+ *   GLH_MATCH_U8   data uint8 [n][dim], dim <= 256.  d2 = |q|^2 + |t|^2 - 2 q.t on x - 128 in int32 (the int8 matrix
+ *                  instructions), exact; returned as the float32 of that integer (below 2^24).
+ *   GLH_MATCH_F32  data float32 [n][dim].  d2 accumulated in float32 in element order k = 0 .. dim - 1 as
+ *                  s = s + (q_k - t_k) * (q_k - t_k), every operation rounded, no FMA.  A NaN distance is never taken.  */
+#define GLH_MATCH_U8 0
+#define GLH_MATCH_F32 1
+typedef struct glh_match glh_match;
+int glh_match_create(int device_id, glh_match** handle);
+/* Uploads and prepares n >= 1 rows of dim >= 1 elements under `slot`, in the place of what the slot held.
+ * GLH_E_INVALID: a null pointer, slot < 0, an unknown kind, n == 0 or n > 2^30, dim < 1, dim > 256 (U8) or 2^16 (F32),
+ * more than 2^35 elements (n times dim rounded up to a multiple of 32).                                                 */
+int glh_match_put(glh_match* handle, int slot, int kind, int n, int dim, const void* data);
+/* Frees the set of `slot`.  GLH_E_INVALID: nothing is in that slot.                                                     */
+int glh_match_drop(glh_match* handle, int slot);
+/* idx int32 [n_q][2], d2 float32 [n_q][2]: the nearest and the second nearest row of slot_t's set for every row of
+ * slot_q's (the same slot may be both).  A set of one row has no second: (-1, +inf).  times_ms (or NULL) [5]: HIP-event
+ * milliseconds -- [0] upload and [1] preparation of the two sets, as measured when they were put, [2] the search kernel,
+ * [3] the merge of T's ranges (0 when T is one range), [4] download.
+ * GLH_E_INVALID: a null pointer, an unknown slot, sets of different dim or of different kinds.                          */
+int glh_match_knn2(glh_match* handle, int slot_q, int slot_t, int32_t* idx, float* d2, double* times_ms);
+/* Frees the handle, its sets and its device memory (NULL: nothing).                                                    */
+int glh_match_destroy(glh_match* handle);
+
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
 
