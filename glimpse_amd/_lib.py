@@ -4,6 +4,7 @@ There is no CPU fallback: if the HIP library is missing or cannot be loaded, eve
 entry point raises.  Build it with `python -m glimpse_amd.build` (hipcc, gfx950).
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -176,6 +177,12 @@ SIGNATURES = {
     "glh_match_drop": (_I, [_P, _I]),
     "glh_match_knn2": (_I, [_P, _I, _I, _P, _P, _P]),
     "glh_match_destroy": (_I, [_P]),
+    "glh_sift_create": (_I, [_I, _P]),
+    "glh_sift_detect": (_I, [_P, _P, _I, _I, _P, _P, _P]),
+    "glh_sift_read": (_I, [_P, _P, _P]),
+    "glh_sift_counts": (_I, [_P, _P]),
+    "glh_sift_layer": (_I, [_P, _I, _I, _I, _P]),
+    "glh_sift_destroy": (_I, [_P]),
 }
 
 _lib = None
@@ -1428,6 +1435,109 @@ class Matcher:
             handle, self._h = self._h, C.c_void_p()
             self._sets = {}
             check(load().glh_match_destroy(handle))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+SIFT_TIMES = ("upload", "base", "pyramid", "extrema", "refine", "describe", "download")
+SIFT_GAUSS, SIFT_DOG, SIFT_CANDIDATES, SIFT_REFINED, SIFT_CELLS = range(5)
+SIFT_MAX_LAYERS = 8  # csrc/glh_sift.h
+
+
+def sift_tables(n_layers, sigma):
+    """[(radius, weights float64)] of the S + 3 blurs of the SIFT pyramid (INPUTS.md, "SIFT: the rule"): [0] the doubled
+    image's, sqrt(max(sigma^2 - 1, 0.01)); [i] from Gaussian layer i - 1 to layer i.  Radius (round(8 sig + 1) | 1) // 2,
+    exp(-x^2 / 2 sig^2) normalised, in float64."""
+    k = 2.0 ** (1.0 / n_layers)
+    sigs = [math.sqrt(max(sigma * sigma - 1.0, 0.01))]
+    for i in range(1, n_layers + 3):
+        prev = math.pow(k, i - 1) * sigma
+        total = prev * k
+        sigs.append(math.sqrt(total * total - prev * prev))
+    tables = []
+    for sig in sigs:
+        r = (int(np.rint(8.0 * sig + 1.0)) | 1) // 2
+        x = np.arange(-r, r + 1, dtype=np.float64)
+        w = np.exp(-(x * x) / (2.0 * sig * sig))
+        tables.append((r, w / w.sum()))
+    return tables
+
+
+class Sift:
+    """SIFT detection and description on the device (glh_sift_create): the pyramid's buffers stay allocated between
+    images of one size.  `detect` gives the keypoints in the rule's order, before the host-side steps of optimize.SIFT."""
+
+    def __init__(self, device_id=0):
+        self._h = C.c_void_p()
+        check(load().glh_sift_create(int(device_id), C.byref(self._h)))
+
+    def _handle(self):
+        if not self._h:
+            raise GlhError(-4, "the handle is closed")
+        return self._h
+
+    def detect(self, image, n_layers=3, contrast=0.04, edge=10.0, sigma=1.6, return_times=False):
+        """(keypoints float64 (n, 6): pt x, pt y, size, angle, response, octave; descriptors uint8 (n, 128)) of `image`
+        uint8 (h, w)."""
+        handle = self._handle()
+        image = np.asarray(image)
+        if image.ndim != 2 or image.dtype != np.uint8:
+            raise TypeError(f"a two-dimensional uint8 image (got {image.dtype}, {image.ndim} dimensions)")
+        image = np.ascontiguousarray(image)
+        n_layers = int(n_layers)
+        if not 1 <= n_layers <= SIFT_MAX_LAYERS:
+            raise ValueError(f"nOctaveLayers {n_layers}: 1 .. {SIFT_MAX_LAYERS} are served")
+        tables = sift_tables(n_layers, float(sigma))
+        params = np.concatenate([[n_layers, contrast, edge, sigma], [r for r, _ in tables], *[w for _, w in tables]])
+        params = np.ascontiguousarray(params, np.float64)
+        n = C.c_int(0)
+        times = np.zeros(len(SIFT_TIMES))
+        check(load().glh_sift_detect(handle, _ptr(image), image.shape[1], image.shape[0], _ptr(params), C.byref(n),
+                                     _ptr(times)))
+        keypoints, descriptors = np.zeros((n.value, 6)), np.zeros((n.value, 128), np.uint8)
+        check(load().glh_sift_read(handle, _ptr(keypoints), _ptr(descriptors)))
+        return _timed((keypoints, descriptors), SIFT_TIMES, times, return_times, extend=True)
+
+    def counts(self):
+        """{octaves, candidates, keypoints, layers, width, height} of the last detection (width, height: doubled)."""
+        out = np.zeros(6, np.int32)
+        check(load().glh_sift_counts(self._handle(), _ptr(out)))
+        return dict(zip(("octaves", "candidates", "keypoints", "layers", "width", "height"), out.tolist()))
+
+    def layer(self, kind, octave=0, index=0):
+        """One stage of the last detection (include/glimpse_hip.h: glh_sift_layer)."""
+        c = self.counts()
+        if kind in (SIFT_GAUSS, SIFT_DOG):
+            if not 0 <= octave < c["octaves"]:
+                raise ValueError(f"octave {octave}: the pyramid has {c['octaves']}")
+            scale = (1 << octave) - 1
+            out = np.zeros(((c["height"] + scale) >> octave, (c["width"] + scale) >> octave), np.float32)
+        elif kind == SIFT_CANDIDATES:
+            out = np.zeros((c["candidates"], 4), np.int32)
+        elif kind == SIFT_REFINED:
+            out = np.zeros((c["candidates"], 12), np.float64)
+        elif kind == SIFT_CELLS:
+            out = np.zeros((c["keypoints"], 5), np.int32)
+        else:
+            raise ValueError(f"unknown kind {kind}")
+        if out.size:
+            check(load().glh_sift_layer(self._handle(), int(kind), int(octave), int(index), _ptr(out)))
+        return out
+
+    def close(self):
+        if self._h:
+            handle, self._h = self._h, C.c_void_p()
+            check(load().glh_sift_destroy(handle))
 
     def __enter__(self):
         return self

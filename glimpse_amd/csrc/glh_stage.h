@@ -1,5 +1,5 @@
 // glh_stage.h -- the host scaffold of a device stage: what glimpse_hip.hip (the C ABI) and the stage files
-// (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_filters.hip, glh_terrain.hip, glh_orient.hip, glh_calib.hip, glh_match.hip) share to
+// (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_filters.hip, glh_terrain.hip, glh_orient.hip, glh_calib.hip, glh_match.hip, glh_sift.hip) share to
 // report an error, to own device memory and to time their phases.  Host-only.
 #pragma once
 #include <hip/hip_runtime.h>

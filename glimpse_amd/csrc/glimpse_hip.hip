@@ -21,6 +21,7 @@
 #include "glh_horizon.h"
 #include "glh_calib.h"
 #include "glh_match.h"
+#include "glh_sift.h"
 #include "glh_orient.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
@@ -2971,6 +2972,83 @@ extern "C" int glh_match_knn2(glh_match* handle, int slot_q, int slot_t, int32_t
 extern "C" int glh_match_destroy(glh_match* handle) {
   if (!handle) return GLH_OK;
   match_destroy(handle->h);
+  delete handle;
+  return GLH_OK;
+}
+
+// optimize.SIFT (INPUTS.md, "SIFT: the rule"): the arguments are checked here, before a device is touched; the kernels and
+// the launches are glh_sift.hip's.
+struct glh_sift {
+  SiftHandle* h;
+};
+
+extern "C" int glh_sift_create(int dev, glh_sift** handle) {
+  if (!handle) return fail(GLH_E_INVALID, "sift: null handle pointer");
+  *handle = nullptr;
+  if (dev < 0) return fail(GLH_E_INVALID, "sift: device %d", dev);
+  glh_sift* g = new (std::nothrow) glh_sift{nullptr};
+  if (!g) return fail(GLH_E_NOMEM, "sift: no memory for a handle");
+  const int rc = sift_create(dev, &g->h);
+  if (rc != GLH_OK) {
+    delete g;
+    return rc;
+  }
+  *handle = g;
+  return GLH_OK;
+}
+
+extern "C" int glh_sift_detect(glh_sift* handle, const uint8_t* image, int w, int h, const double* params, int* n,
+                               double* times_ms) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!image || !params || !n) return fail(GLH_E_INVALID, "sift: null argument");
+  if (w < 1 || h < 1 || w > SF_MAX_SIDE || h > SF_MAX_SIDE)
+    return fail(GLH_E_INVALID, "sift: an image of %d x %d: sides of 1 .. 2^23 are served", w, h);
+  if ((int64_t)(2 * (int64_t)w) * (2 * (int64_t)h) >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "sift: an image of %d x %d doubles to 2^31 cells or more", w, h);
+  SiftParams p;
+  if (!(params[0] >= 1.0 && params[0] <= (double)SF_MAX_LAYERS) || params[0] != floor(params[0]))
+    return fail(GLH_E_INVALID, "sift: nOctaveLayers %g: 1 .. %d are served", params[0], SF_MAX_LAYERS);
+  p.S = (int)params[0];
+  p.contrast = params[1];
+  p.edge = params[2];
+  p.sigma = params[3];
+  if (!(p.contrast >= 0.0 && p.contrast <= 1e6)) return fail(GLH_E_INVALID, "sift: contrastThreshold %g", p.contrast);
+  if (!(p.edge > 0.0 && p.edge <= 1e6)) return fail(GLH_E_INVALID, "sift: edgeThreshold %g", p.edge);
+  if (!(p.sigma > 0.0 && p.sigma <= SF_MAX_SIGMA)) return fail(GLH_E_INVALID, "sift: sigma %g: 0 < sigma <= %g is served", p.sigma, SF_MAX_SIGMA);
+  const double* table = params + 4 + p.S + 3;
+  for (int i = 0; i < p.S + 3; ++i) {
+    const double r = params[4 + i];
+    if (!(r >= 0.0 && r <= (double)SF_MAX_RADIUS) || r != floor(r))
+      return fail(GLH_E_INVALID, "sift: the radius of table %d is %g: 0 .. %d are served", i, r, SF_MAX_RADIUS);
+    p.radius[i] = (int)r;
+    p.table[i] = table;
+    table += 2 * p.radius[i] + 1;
+  }
+  return sift_detect(handle->h, image, w, h, p, n, times_ms);
+}
+
+extern "C" int glh_sift_read(glh_sift* handle, double* keypoints, uint8_t* descriptors) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!keypoints || !descriptors) return fail(GLH_E_INVALID, "sift: null argument");
+  return sift_read(handle->h, keypoints, descriptors);
+}
+
+extern "C" int glh_sift_counts(glh_sift* handle, int32_t* counts) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!counts) return fail(GLH_E_INVALID, "sift: null argument");
+  sift_counts(handle->h, counts);
+  return GLH_OK;
+}
+
+extern "C" int glh_sift_layer(glh_sift* handle, int kind, int octave, int index, void* out) {
+  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!out) return fail(GLH_E_INVALID, "sift: null argument");
+  return sift_layer(handle->h, kind, octave, index, out);
+}
+
+extern "C" int glh_sift_destroy(glh_sift* handle) {
+  if (!handle) return GLH_OK;
+  sift_destroy(handle->h);
   delete handle;
   return GLH_OK;
 }

@@ -24,9 +24,14 @@ answer that the reference's default matcher, the approximate and unseeded `cv2.F
 pinned to the stated rule, not to FLANN's output.  The descriptors of an image are uploaded once per `build_matches` call
 and stay on the device until the last pair that needs them.
 
-Not served: detecting keypoints (`detect_keypoints`, the detecting branch of `build_keypoints`: SIFT of `cv2`; keypoints
-are read from files or passed in), CLAHE, a `mask` for the GPU matcher, the lmfit methods other than "least_squares"
-(lmfit is not a dependency) and plotting.
+`detect_keypoints(array, method=optimize.SIFT)` and `KeypointMatcher.build_keypoints(method=optimize.SIFT)` detect and
+describe SIFT keypoints on the GPU (`glh_sift_detect`): Lowe 2004 with the structure and constants of OpenCV's
+implementation, pinned to the rule written out in INPUTS.md ("SIFT: the rule") and to its NumPy restatement
+(tests/sift_restated.py) in every bit, not to OpenCV's bytes.  The descriptors are uint8, so they take the matcher's integer
+path.  The reference's default `method` (`cv2.SIFT`) is still refused: `cv2` is not a dependency.
+
+Not served: `cv2.SIFT` itself (the default `method` of `detect_keypoints` and `build_keypoints`), CLAHE, a `mask` for the GPU
+matcher, the lmfit methods other than "least_squares" (lmfit is not a dependency) and plotting.
 """
 import collections
 import datetime
@@ -45,7 +50,7 @@ _NO_MATCHER = ("keypoint detection and matching (SIFT and FLANN of cv2) are not 
 
 _NO_PLOT = "plotting is out of scope"
 _NO_DETECT = ("keypoint detection (SIFT of cv2) is not served: give KeypointMatcher.keypoints, or a directory of "
-              "keypoint files, as (points, descriptors) per image")
+              "keypoint files, as (points, descriptors) per image, or pass method=optimize.SIFT (SIFT on the GPU)")
 _NO_CLAHE = "CLAHE (cv2.createCLAHE) is not served: pass clahe=False"
 _NO_MASK = ("a knnMatch mask is not served by the GPU matcher (the reference's own code cannot index the short lists "
             "cv2 returns for one): pass mask=None, or a matcher object of your own")
@@ -396,9 +401,99 @@ class RotationMatchesXYZ(RotationMatchesXY):
         raise NotImplementedError()
 
 
+KeyPoint = collections.namedtuple("KeyPoint", "pt size angle response octave class_id")  # the fields of a cv2.KeyPoint
+
+
+class SIFT:
+    """SIFT on the GPU, shaped like a cv2.Feature2D: `SIFT.create(...).detectAndCompute(array, mask=None)`.  The rule is
+    INPUTS.md's "SIFT: the rule".  Keypoints are `KeyPoint`s with float64 fields, descriptors uint8 (n, 128) (cv2 stores the
+    same integers as float32); an image too small for an octave gives ([], None)."""
+
+    def __init__(self, nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6, device_id=0):
+        self.nfeatures = int(nfeatures)
+        self.nOctaveLayers = int(nOctaveLayers)
+        self.contrastThreshold = float(contrastThreshold)
+        self.edgeThreshold = float(edgeThreshold)
+        self.sigma = float(sigma)
+        self.device_id = int(device_id)
+        self._handle = None
+
+    @classmethod
+    def create(cls, nfeatures=0, nOctaveLayers=3, contrastThreshold=0.04, edgeThreshold=10, sigma=1.6):
+        return cls(nfeatures, nOctaveLayers, contrastThreshold, edgeThreshold, sigma)
+
+    def detect_arrays(self, array, mask=None):
+        """(keypoints float64 (n, 6): pt x, pt y, size, angle, response, octave; descriptors uint8 (n, 128)) after the
+        host-side steps, or (None, None) when the image holds no octave."""
+        array = np.asarray(array)
+        if array.ndim != 2:
+            raise NotImplementedError("SIFT takes a two-dimensional array: cv2 would weigh the channels of a colour image "
+                                      "as BGR; KeypointMatcher.build_keypoints takes their mean first")
+        array = np.asarray(array, dtype=np.uint8)
+        if min(array.shape) < 6:  # the doubled image has no octave of 12 cells a side
+            return None, None
+        if self._handle is None:
+            self._handle = _lib.Sift(self.device_id)
+        kps, desc = self._handle.detect(array, self.nOctaveLayers, self.contrastThreshold, self.edgeThreshold, self.sigma)
+        keep = np.ones(len(kps), bool)
+        if len(kps) > 1:  # a keypoint equal to its predecessor in pt, size and angle is dropped
+            keep[1:] = np.any(kps[1:, :4] != kps[:-1, :4], axis=1)
+        if mask is not None:
+            mask = np.asarray(mask, dtype=np.uint8)
+            v, u = (kps[:, 1] + 0.5).astype(np.int64), (kps[:, 0] + 0.5).astype(np.int64)
+            inside = (v >= 0) & (v < mask.shape[0]) & (u >= 0) & (u < mask.shape[1])
+            keep &= inside
+            keep[inside] &= mask[v[inside], u[inside]] != 0
+        kps, desc = kps[keep], desc[keep]
+        if self.nfeatures > 0 and len(kps) > self.nfeatures:  # the largest responses, ties to the earlier, order kept
+            order = np.sort(np.argsort(-kps[:, 4], kind="stable")[:self.nfeatures])
+            kps, desc = kps[order], desc[order]
+        return kps, desc
+
+    def close(self):
+        """Frees the device handle and its pyramid (a later call makes a new one)."""
+        if self._handle is not None:
+            handle, self._handle = self._handle, None
+            handle.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def detectAndCompute(self, array, mask=None):
+        kps, desc = self.detect_arrays(array, mask)
+        if kps is None:
+            return [], None
+        keypoints = [KeyPoint((row[0], row[1]), row[2], row[3], row[4], int(row[5]), -1) for row in kps.tolist()]
+        return keypoints, desc
+
+
 def detect_keypoints(array, mask=None, method=None, root=False, **kwargs):
-    """optimize.py:2194-2231: not served (SIFT of cv2)."""
-    raise NotImplementedError(_NO_DETECT)
+    """optimize.py:2194-2231 with `method=optimize.SIFT` (SIFT on the GPU; `kwargs` go to `SIFT.create`).  The reference's
+    default method, cv2.SIFT (`method=None` here), is not served, nor is any other."""
+    with _create_detector(method, kwargs) as detector:
+        return _detect(detector, array, mask, root)
+
+
+def _create_detector(method, kwargs):
+    if method is None:
+        raise NotImplementedError(_NO_DETECT)
+    if method is not SIFT:
+        raise NotImplementedError(f"method {method!r} is not served: optimize.SIFT is")
+    return method.create(**kwargs)
+
+
+def _detect(detector, array, mask, root):
+    """What `detect_keypoints` returns, from a detector that is already made (`build_keypoints` keeps one for all its
+    images, so that frames of one size share the pyramid's device memory)."""
+    keypoints, descriptors = detector.detectAndCompute(array, mask=mask)
+    # Empty result: ([], None)
+    if root and descriptors is not None:
+        descriptors = descriptors.astype(np.float32)  # (what cv2 returns)
+        descriptors = np.sqrt(descriptors / (descriptors.sum(axis=1, keepdims=True) + 1e-7))
+    return keypoints, descriptors
 
 
 DMatch = collections.namedtuple("DMatch", "queryIdx trainIdx distance")  # what the logic below reads of a cv2.DMatch
@@ -529,7 +624,7 @@ class PairMatches:
 class KeypointMatcher:
     """optimize.py:2312-2773: matches the keypoints of `images` (in ascending temporal order) pair by pair, on the GPU
     (`build_matches`).  `keypoints`: per image (points, descriptors) as `match_keypoints` takes them; they are passed in
-    or read from files (`build_keypoints`), detection is not served, nor is `clahe`."""
+    or read from files, or detected with `build_keypoints(method=optimize.SIFT)`; `clahe` is not served."""
 
     def __init__(self, images=None, clahe=False):
         if images is None:
@@ -553,10 +648,18 @@ class KeypointMatcher:
             raise ValueError("Image basenames are not unique")
         return basenames
 
+    def _prepare_image(self, array):
+        """optimize.py:2358-2365: the channel mean, then uint8 (CLAHE is refused by the constructor)."""
+        if array.ndim > 2:
+            array = array.mean(axis=2)
+        return array.astype(np.uint8, copy=False)
+
     def build_keypoints(self, masks=None, path=None, overwrite=False, clear_images=True, clear_keypoints=False,
                         parallel=False, **kwargs):
-        """optimize.py:2367-2445: the reading, writing and cached branches (`basename.pkl` under `path`); an image whose
-        keypoints would have to be detected raises NotImplementedError.  `parallel` is accepted and ignored."""
+        """optimize.py:2367-2445: the reading, writing and cached branches (`basename.pkl` under `path`), and with
+        `method=optimize.SIFT` in `kwargs` the detecting branch (`detect_keypoints` on the channel mean as uint8, `masks`
+        one array for all images or one per image).  Without it an image whose keypoints would have to be detected raises
+        NotImplementedError.  `parallel` is accepted and ignored."""
         if path:
             path = Path(path)
         if clear_keypoints and not path:
@@ -564,27 +667,44 @@ class KeypointMatcher:
         if path and path.is_file():
             raise ValueError("path must be a directory")
         basenames = self._prepare_image_basenames()
+        if masks is None or isinstance(masks, np.ndarray):
+            masks = [masks] * len(self.images)
         if not self.keypoints:
             self.keypoints = [None] * len(self.images)
         result = []
-        for i, img in enumerate(self.images):
-            print(img.path)
-            if path:
-                outpath = path / f"{basenames[i]}.pkl"
-                written = outpath.exists()
-            else:
-                written = False
-            keypoints = self.keypoints[i]
-            read = keypoints is not None
-            if not read and written and not clear_keypoints:
-                keypoints = helpers.read_pickle(outpath)
-            elif read and not written and path:
-                helpers.write_pickle(keypoints, path=outpath)
-            elif (not read and not written) or overwrite:
-                raise NotImplementedError(_NO_DETECT)
-            if clear_keypoints:
-                keypoints = None
-            result.append(keypoints)
+        detector = None  # made for the first image that has to be detected, kept until the last
+        try:
+            for i, img in enumerate(self.images):
+                print(img.path)
+                if path:
+                    outpath = path / f"{basenames[i]}.pkl"
+                    written = outpath.exists()
+                else:
+                    written = False
+                keypoints = self.keypoints[i]
+                read = keypoints is not None
+                if not read and written and not clear_keypoints:
+                    keypoints = helpers.read_pickle(outpath)
+                elif read and not written and path:
+                    helpers.write_pickle(keypoints, path=outpath)
+                elif (not read and not written) or overwrite:
+                    if kwargs.get("method") is None:
+                        raise NotImplementedError(_NO_DETECT)
+                    if detector is None:
+                        create = {k: v for k, v in kwargs.items() if k not in ("method", "root")}
+                        detector = _create_detector(kwargs["method"], create)
+                    array = self._prepare_image(img.read())
+                    keypoints = _detect(detector, array, masks[i], kwargs.get("root", False))
+                    if path:
+                        helpers.write_pickle(keypoints, path=outpath)
+                    if clear_images:
+                        img.array = None
+                if clear_keypoints:
+                    keypoints = None
+                result.append(keypoints)
+        finally:
+            if detector is not None:
+                detector.close()
         self.keypoints = result
 
     def _matching_images(self, maxdt=None, seq=None, imgs=None):

@@ -249,6 +249,7 @@ int glh_init_templates(glh_ctx* ctx, int obs, int image);
  * images[o] >= 0, compute_observer_log_likelihoods (tracker.py:563-625); plus
  * CartesianMotion.compute_log_likelihoods (motion.py:181-204); w = exp(-sum) + 1e-300.     */
 int glh_update_weights(glh_ctx* ctx, const int32_t* images /* [O], -1 = None */);
+
 /* Tracker.resample_particles("systematic") (track/tracker.py:168-176, :222-223).
  * GLH_RNG_HOST: u [P] = the np.random.random() draw of each point.                         */
 int glh_resample(glh_ctx* ctx, int rng_mode, const double* u, uint64_t seed, uint64_t step);
@@ -771,6 +772,45 @@ int glh_match_drop(glh_match* handle, int slot);
 int glh_match_knn2(glh_match* handle, int slot_q, int slot_t, int32_t* idx, float* d2, double* times_ms);
 /* Frees the handle, its sets and its device memory (NULL: nothing).                                                    */
 int glh_match_destroy(glh_match* handle);
+
+/* ---- optimize.SIFT: keypoint detection and description (Lowe 2004 with OpenCV's structure and constants) ---------------
+ * The rule is INPUTS.md's "SIFT: the rule"; tests/sift_restated.py restates it in NumPy and the results equal it in every
+ * bit.  A handle keeps the pyramid's buffers between images: a sequence of frames of one size allocates once.
+ * params (float64): [0] nOctaveLayers S (1 .. 8), [1] contrastThreshold (0 .. 10^6), [2] edgeThreshold (> 0, <= 10^6),
+ * [3] sigma (0 < sigma <= 16), [4 .. 4 + S + 3) the radii r_i (0 .. 4096) of the S + 3 weight tables -- [0] the blur of the
+ * doubled image, [i] the step from Gaussian layer i - 1 to layer i -- and after them the tables themselves, 2 r_i + 1
+ * weights each (symmetric; made by the caller: NumPy's exp).
+ * glh_sift_detect: image uint8 [h][w].  *n: the keypoints found, in the rule's order, before the caller's steps (equal
+ * neighbours, mask, nfeatures).  times_ms (or NULL) [7]: HIP-event milliseconds -- [0] upload, [1] base, [2] pyramid,
+ * [3] extrema, [4] refinement and orientation, [5] descriptors, [6] download.  An image too small for an octave gives
+ * *n = 0.  GLH_E_INVALID: a null pointer, w or h < 1 or above 2^23, a doubled image of 2^31 cells or more, parameters
+ * outside the ranges above; GLH_E_NOMEM: an allocation failed (the message has the bytes asked for).                     */
+typedef struct glh_sift glh_sift;
+int glh_sift_create(int device_id, glh_sift** handle);
+int glh_sift_detect(glh_sift* handle, const uint8_t* image, int w, int h, const double* params, int* n, double* times_ms);
+/* keypoints float64 [n][6] (pt x, pt y, size, angle, response, octave as OpenCV packs it), descriptors uint8 [n][128] of
+ * the last detection.  GLH_E_INVALID: a null pointer, nothing detected yet.                                              */
+int glh_sift_read(glh_sift* handle, double* keypoints, uint8_t* descriptors);
+/* counts int32 [6] of the last detection: octaves, candidates, keypoints, S, doubled width, doubled height (octave o has
+ * (side + 2^o - 1) >> o cells a side).                                                                                   */
+int glh_sift_counts(glh_sift* handle, int32_t* counts);
+/* One stage of the last detection, for tests that tell where a difference starts:
+ *   GLH_SIFT_GAUSS       float32 [H][W]: Gaussian layer `index` (0 .. S + 2) of `octave`
+ *   GLH_SIFT_DOG         float32 [H][W]: difference `index` (0 .. S + 1) of `octave`
+ *   GLH_SIFT_CANDIDATES  int32 [candidates][4]: octave, layer, row, column, ascending
+ *   GLH_SIFT_REFINED     float64 [candidates][12]: status (0 kept, 1 zero pivot, 2 left the border or the layers, 3 not
+ *                        settled, 4 contrast, 5 edge, 6 a step above 10^6), then of a kept one: octave, layer, row, column
+ *                        of the settled cell, xc, xr, xi, contrast, size, pt x, pt y (zeros otherwise)
+ *   GLH_SIFT_CELLS       int32 [keypoints][5]: octave, layer, row, column, orientation bin of every keypoint
+ * GLH_E_INVALID: a null pointer, nothing detected yet, an unknown kind, a layer the pyramid does not have.               */
+#define GLH_SIFT_GAUSS 0
+#define GLH_SIFT_DOG 1
+#define GLH_SIFT_CANDIDATES 2
+#define GLH_SIFT_REFINED 3
+#define GLH_SIFT_CELLS 4
+int glh_sift_layer(glh_sift* handle, int kind, int octave, int index, void* out);
+/* Frees the handle and its device memory (NULL: nothing).                                                              */
+int glh_sift_destroy(glh_sift* handle);
 
 /* Tracker.resample_particles("systematic") on one population: idx int64 [n].                 */
 int glh_stage_resample(int device_id, const double* weights, int n, double u, int64_t* idx);
