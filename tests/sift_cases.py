@@ -7,8 +7,10 @@ from scipy.ndimage import gaussian_filter
 
 from tests import sift_restated as sr
 
-SIZES = {"61x47": (47, 61), "47x61": (61, 47), "256x192": (192, 256), "strip": (40, 12), "5x5": (5, 5)}  # (rows, columns)
+SIZES = {"61x47": (47, 61), "47x61": (61, 47), "256x192": (192, 256), "strip": (40, 12), "5x5": (5, 5),
+         "300x400": (300, 400)}  # (rows, columns)
 FULL = ("61x47", "47x61", "256x192")  # the images on which every branch of the rule must be seen to fire
+LIST_SLOTS = 4096  # the candidate list of a fresh handle (glh_sift.hip); "300x400" yields more, the others fewer
 SEED = 1
 
 

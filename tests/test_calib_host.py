@@ -282,3 +282,58 @@ def test_weights_sizes_and_resize(golden):
     cam.xyz = (1, 0, 0)
     with pytest.raises(ValueError, match="Camera position has changed and world coordinates are ray directions"):
         moved._test_position()
+
+
+def test_the_wide_model_meets_the_conditions_of_the_gpu_test():
+    """tests/calib_cases.py, asserted without a device: the rows of every control and of every job of one Jacobian, the
+    interleaving of the kinds, the distortion, and -- by the formulas of oracle/camera.py -- that the NaN rows of Points
+    behind the camera and of match rays behind the other camera lie in a job's second and later workgroups."""
+    from glimpse_amd import optimize
+    from tests import calib_cases as cc
+
+    model, cams = cc.model()
+    kinds = {optimize.Points: "points", optimize.Lines: "lines", optimize.Matches: "matches",
+             optimize.RotationMatches: "rotation", optimize.RotationMatchesXY: "rotation_xy"}
+    assert [(kinds[type(c)], c.size) for c in model.controls] == [(k, n) for k, _, n in cc.CONTROLS]
+    rows = {k: sorted(n for kind, _, n in cc.CONTROLS if kind == k) for k in kinds.values()}
+    assert rows == {"points": [1, 255, 256, 257, 600], "lines": [300], "matches": [257, 1000], "rotation": [257, 1000],
+                    "rotation_xy": [257, 1000]}
+    assert all(cam.k.all() and cam.p.all() for cam in cams) and len(cams) == 3
+    first = np.concatenate(([0], np.cumsum([n for _, _, n in cc.CONTROLS])))[:-1]
+    assert all(first[i] > 0 for i, (_, _, n) in enumerate(cc.CONTROLS) if n > cc.TB)  # no wide job at row 0 of the output
+    order = [k for k, _, _ in cc.CONTROLS]
+    assert order.index("points") < order.index("matches") < order.index("lines") < len(order) - 1 - order[::-1].index("points")
+    sets, dx, jobs = model._jacobian_plan()
+    assert len(sets) == 10 and len(dx) == 9 and jobs[:12] == [(i, 0) for i in range(12)] and len(jobs) > 12
+    assert {s for _, s in jobs} == set(range(10)) and max(model.controls[i].size for i, _ in jobs) == 1000
+    assert sum(model.controls[i].size > cc.TB for i, _ in jobs) >= 30  # jobs of two to four workgroups
+    vectors = cc.oracle_vectors()
+    for cam, vector in zip(cams, vectors):
+        assert np.array_equal(cam.vector24[:20], vector[:20])
+    for n, ((kind, members, size), arrays) in enumerate(zip(cc.CONTROLS, cc.data())):
+        if kind == "lines":
+            continue
+        for side in ((0,) if kind == "points" else (0, 1)):
+            nan = np.flatnonzero(np.isnan(cc.oracle_predicted(kind, vectors, members, arrays, side)).any(axis=1))
+            print(n, kind, size, "rows, side", side, ":", len(nan), "NaN rows", nan[:8])
+            if kind == "points":
+                assert nan.tolist() == list(cc.BEHIND.get(n, ()))
+            elif kind == "matches":
+                assert 0 < len(nan) < size // 4 and (size == 257 or (nan >= 2 * cc.TB).any()) and (nan >= cc.TB).any()
+            else:
+                assert nan.tolist() == list(cc.FAR[n])
+    assert all(max(rows) >= cc.TB for rows in list(cc.BEHIND.values())[1:] + list(cc.FAR.values()))
+    # the Lines control between them: more projected points than one LDS tile of the nearest kernel, and no near tie
+    lines, v = model.controls[3], vectors[0]
+    xy_edges = oc_undistorted_edges(cams[0], v)
+    info = {}
+    rs.lines_predicted(v, cams[0].R, lines.uv, lines.xyzs, np.hstack((xy_edges.min(axis=0), xy_edges.max(axis=0))), info=info)
+    print("lines:", info["n_projected"], "projected points, gap", info["gap"])
+    assert info["n_projected"] > rs.TILE and info["gap"] > MIN_GAP
+
+
+def oc_undistorted_edges(cam, vector):
+    """The camera coordinates of the image's edge points (the clip box's corners and mid-points) by oracle/camera.py."""
+    from oracle import camera as oc
+
+    return oc.undistort(vector, (cam.edges(step=cam.imgsz / 2) - (vector[6:8] / 2 + vector[10:12])) * (1 / vector[8:10]))

@@ -309,3 +309,93 @@ def test_errors_and_hygiene(golden):
         _lib.Calib(1, [9], [0], [0], [0], [0, 2], np.zeros((2, 2)), np.zeros((2, 3)))
     with pytest.raises(_lib.GlhError):
         _lib.Calib(1, [0], [1], [0], [0], [0, 2], np.zeros((2, 2)), np.zeros((2, 3)))
+
+
+# ---- row jobs wider than a workgroup (tests/calib_cases.py; tests/test_calib_host.py asserts what the model holds) ----
+def _count(got, want):
+    """(blocks that differ in shape, values that differ in any bit) between two lists of blocks."""
+    shapes = sum(a.shape != b.shape for a, b in zip(got, want)) + abs(len(got) - len(want))
+    return shapes, sum(int(np.count_nonzero(_bits(a) != _bits(b))) for a, b in zip(got, want) if a.shape == b.shape)
+
+
+@pytest.fixture(scope="module")
+def wide():
+    """The wide model with its handle open, the plan of one Jacobian and every job of it one control at a time."""
+    from tests import calib_cases as cc
+
+    model, cams = cc.model()
+    sets, _, jobs = model._jacobian_plan()
+    want = sequential(model, sets, jobs)
+    with model.upload() as handle:
+        yield dict(model=model, cams=cams, sets=sets, jobs=jobs, want=want, handle=handle)
+
+
+def test_wide_jobs_equal_one_control_at_a_time(wide):
+    """Jobs of up to four workgroups of k_calib_rows (CalBlock.first 0, 256, 512, 768) between and behind other jobs, the
+    Lines job's blocks among them, NaN rows in the later workgroups: the full job list of one Jacobian, the list
+    reversed, and the largest job alone, bit for bit; and the same bytes from a second call."""
+    model, sets, jobs, want, handle = (wide[k] for k in ("model", "sets", "jobs", "want", "handle"))
+    sizes = [model.controls[i].size for i, _ in jobs]
+    largest = int(np.argmax(sizes))
+    assert sizes[largest] == 1000 and sum(sizes) > 30000
+    for name, picked in (("full", list(range(len(jobs)))), ("reversed", list(range(len(jobs)))[::-1]), ("largest", [largest])):
+        got = model._evaluate(handle, sets, [jobs[q] for q in picked])
+        again = model._evaluate(handle, sets, [jobs[q] for q in picked])
+        expected = [want[q] for q in picked]
+        print(name, len(picked), "jobs,", sum(sizes[q] for q in picked), "rows: blocks of another shape, differing values:",
+              _count(got, expected), "; second call:", _count(again, got), "; NaN rows",
+              int(sum(np.isnan(b).any(axis=1).sum() for b in got)))
+        assert _count(got, expected) == (0, 0) and _count(again, got) == (0, 0), name
+    assert sum(np.isnan(b).any(axis=1).sum() for b in want[:12]) >= 100  # (NaN equals NaN bit for bit above)
+
+
+def test_wide_match_jobs_predict_in_the_second_camera(wide):
+    """job_side 1 on the three match kinds at 1000 rows."""
+    from glimpse_amd.camera import rotations
+    from tests import calib_cases as cc
+
+    model, handle = wide["model"], wide["handle"]
+    cams24 = np.array([[cam.vector24 for cam in model._dev_cams]])
+    rot = rotations(cams24[0, :, 3:6])[0][None]
+    picked = [i for i, (kind, _, rows) in enumerate(cc.CONTROLS) if rows == 1000]
+    assert [cc.CONTROLS[i][0] for i in picked] == ["rotation", "matches", "rotation_xy"]
+    for i in picked:
+        got = handle.eval(cams24, rot, [i], [0], job_side=[1])
+        again = handle.eval(cams24, rot, [i], [0], job_side=[1])
+        expected = model.controls[i].predicted(cam=1)
+        print(cc.CONTROLS[i], "side 1: differing values", _count([got], [expected]), "second call", _count([again], [got]))
+        assert same(got, expected) and same(again, got), i
+        assert not same(got, wide["want"][i])  # (the other side's prediction is another one)
+
+
+def test_wide_jobs_against_the_oracle(wide):
+    """The base set's twelve jobs against formulas that are not the package's: oracle/camera.py for Points and the
+    match kinds (both sides), the restatement for Lines.  Tolerances: TOL for image coordinates, rtol 1e-11 / atol 1e-12
+    for camera coordinates, as the existing camera tests."""
+    from glimpse_amd.camera import rotations
+    from tests import calib_cases as cc
+
+    model, handle = wide["model"], wide["handle"]
+    got = model._evaluate(handle, wide["sets"], wide["jobs"][:12])
+    vectors = cc.oracle_vectors()
+    cams24 = np.array([[cam.vector24 for cam in model._dev_cams]])
+    rot = rotations(cams24[0, :, 3:6])[0][None]
+    for i, ((kind, members, rows), arrays) in enumerate(zip(cc.CONTROLS, cc.data())):
+        if kind == "lines":
+            info = {}
+            expected = restated(model.controls[i], info=info)
+            assert info["gap"] > MIN_GAP and info["n_projected"] > T
+            print(i, kind, rows, "rows,", info["n_projected"], "projected points: differing values", _count([got[i]], [expected]))
+            assert same(got[i], expected)
+            continue
+        tol = dict(rtol=1e-11, atol=1e-12) if kind == "rotation_xy" else TOL
+        for side in ((0,) if kind == "points" else (0, 1)):
+            found = got[i] if side == 0 else handle.eval(cams24, rot, [i], [0], job_side=[1])
+            expected = cc.oracle_predicted(kind, vectors, members, arrays, side)
+            nan = np.isnan(expected).any(axis=1)
+            with np.errstate(invalid="ignore"):
+                excess = np.abs(found - expected) - (tol["atol"] + tol["rtol"] * np.abs(expected))
+            print(i, kind, rows, "rows, side", side, ":", int(nan.sum()), "NaN rows; largest |difference| - tolerance",
+                  float(np.nanmax(excess)) if not nan.all() else None)
+            assert np.array_equal(np.isnan(found), np.isnan(expected))
+            np.testing.assert_allclose(found, expected, **tol)

@@ -4,7 +4,8 @@ refined list, the angles and the descriptors, then the public surface with every
 KeypointMatcher from images to matches on the integer path.
 
 The images (tests/sift_cases.py): 61 x 47 and 47 x 61 (odd sides: odd decimation, partial blocks), 256 x 192 (many blocks
-of every kernel), a 12 x 40 strip (its second octave is 12 cells wide: two interior columns) and 5 x 5 (no octave)."""
+of every kernel), a 12 x 40 strip (its second octave is 12 cells wide: two interior columns), 5 x 5 (no octave) and
+400 x 300 (more candidates than a fresh handle's list holds: the extrema run twice)."""
 import datetime
 
 import numpy as np
@@ -30,6 +31,37 @@ def same_bits(found, expected, what):
     assert np.array_equal(found.view(np.uint8), expected.view(np.uint8)), what
 
 
+def every_stage(lib, sift, name, **params):
+    """One detection of image `name` on the handle `sift`: every stage against the restatement's, bit for bit (the number
+    of differing bytes of each stage is printed first).  Returns what `detect` gave."""
+    st = sc.stages(name, **params)
+    layers = params.get("nOctaveLayers", 3)
+    kps, desc = sift.detect(sc.image(name), n_layers=layers, sigma=params.get("sigma", 1.6))
+    counts = sift.counts()
+    assert counts["octaves"] == len(st["gauss"]) and counts["layers"] == layers
+    assert all(len(gauss) == layers + 3 and len(dog) == layers + 2 for gauss, dog in zip(st["gauss"], st["dog"]))
+    compared = []
+    for o, (gauss, dog) in enumerate(zip(st["gauss"], st["dog"])):
+        compared += [(sift.layer(lib.SIFT_GAUSS, o, i), layer, f"Gaussian layer {i} of octave {o}") for i, layer in enumerate(gauss)]
+        compared += [(sift.layer(lib.SIFT_DOG, o, i), layer, f"DoG layer {i} of octave {o}") for i, layer in enumerate(dog)]
+    refined = sift.layer(lib.SIFT_REFINED)
+    compared += [(sift.layer(lib.SIFT_CANDIDATES), st["candidates"], "candidates"),
+                 (refined[:, 0], st["refined"][:, 0], "which rule rejected which candidate"),
+                 (refined[:, 1:5], st["refined"][:, 1:5], "settled cells"),
+                 (refined, st["refined"], "refined list: offsets, contrast, size, position"),
+                 (sift.layer(lib.SIFT_CELLS), st["cells"], "keypoint cells and orientation bins"),
+                 (kps[:, [0, 1, 2, 4, 5]], st["keypoints"][:, [0, 1, 2, 4, 5]], "position, size, response, octave"),
+                 (kps[:, 3], st["keypoints"][:, 3], "angles"), (desc, st["descriptors"], "descriptors")]
+    differing = {what: (int(np.count_nonzero(np.ascontiguousarray(f).view(np.uint8) != np.ascontiguousarray(e).view(np.uint8)))
+                        if f.shape == e.shape and f.dtype == e.dtype else f"shape {f.shape}, not {e.shape}")
+                 for f, e, what in compared}
+    print(name, params, counts, "differing bytes:", {w: n for w, n in differing.items() if n} or "none in",
+          len(compared), "arrays")
+    for found, expected, what in compared:
+        same_bits(found, expected, what)
+    return kps, desc
+
+
 @pytest.mark.parametrize("name", ["61x47", "47x61", "256x192", "strip"])
 def test_every_stage_equals_the_restatement(lib, name):
     st = sc.stages(name)
@@ -39,23 +71,50 @@ def test_every_stage_equals_the_restatement(lib, name):
         for what in ("moved", "contrast", "edge", "border", "two_orientations", "clipped"):
             assert trace[what] >= 1, what
     with lib.Sift() as sift:
-        kps, desc = sift.detect(sc.image(name))
-        counts = sift.counts()
-        assert counts["octaves"] == len(st["gauss"]) and counts["layers"] == 3
-        for o, (gauss, dog) in enumerate(zip(st["gauss"], st["dog"])):
-            for i, layer in enumerate(gauss):
-                same_bits(sift.layer(lib.SIFT_GAUSS, o, i), layer, f"Gaussian layer {i} of octave {o}")
-            for i, layer in enumerate(dog):
-                same_bits(sift.layer(lib.SIFT_DOG, o, i), layer, f"DoG layer {i} of octave {o}")
-        same_bits(sift.layer(lib.SIFT_CANDIDATES), st["candidates"], "candidates")
-        refined = sift.layer(lib.SIFT_REFINED)
-        same_bits(refined[:, 0], st["refined"][:, 0], "which rule rejected which candidate")
-        same_bits(refined[:, 1:5], st["refined"][:, 1:5], "settled cells")
-        same_bits(refined, st["refined"], "refined list: offsets, contrast, size, position")
-        same_bits(sift.layer(lib.SIFT_CELLS), st["cells"], "keypoint cells and orientation bins")
-        same_bits(kps[:, [0, 1, 2, 4, 5]], st["keypoints"][:, [0, 1, 2, 4, 5]], "position, size, response, octave")
-        same_bits(kps[:, 3], st["keypoints"][:, 3], "angles")
-        same_bits(desc, st["descriptors"], "descriptors")
+        every_stage(lib, sift, name)
+
+
+@pytest.mark.parametrize("name, layers", [("47x61", 8), ("strip", 8), ("strip", 1)])
+def test_every_stage_at_the_ends_of_the_layer_range(lib, name, layers):
+    """Eleven Gaussian and ten DoG layers per octave with nOctaveLayers = 8, and with 1 the blurs of radius 11, 22 and 45,
+    which on the strip's octaves (24 and 12 cells wide) fold the reflection up to four times."""
+    with lib.Sift() as sift:
+        every_stage(lib, sift, name, nOctaveLayers=layers)
+
+
+@pytest.fixture(scope="module")
+def fresh_300x400(lib):
+    """A fresh handle's first detection on "300x400" (4446 candidates for a list of 4096: two attempts), every stage
+    compared; the handle and what it gave."""
+    assert len(sc.stages("300x400")["candidates"]) > sc.LIST_SLOTS
+    with lib.Sift() as sift:
+        yield sift, every_stage(lib, sift, "300x400")
+
+
+def test_candidate_list_overflows_and_the_octaves_run_again(lib, fresh_300x400):
+    """The second attempt of the candidate list (glh_sift.hip: "the counter goes on counting past `cap`"): every stage of
+    the first detection on a fresh handle (the fixture), then the same handle again, whose list is now long enough for
+    one attempt: the same bytes, every stage again."""
+    sift, (kps, desc) = fresh_300x400
+    assert sift.counts()["candidates"] == len(sc.stages("300x400")["candidates"]) > sc.LIST_SLOTS
+    again = every_stage(lib, sift, "300x400")
+    same_bits(again[0], kps, "one attempt after two: keypoints")
+    same_bits(again[1], desc, "one attempt after two: descriptors")
+
+
+def test_candidate_list_grows_on_a_used_handle_and_serves_a_small_image_after(lib, fresh_300x400):
+    """A handle that has detected on "61x47" (94 candidates), then "300x400": equal to the fresh handle's; then "61x47"
+    on the grown handle: equal to a fresh handle's, every stage."""
+    _, (kps, desc) = fresh_300x400
+    with lib.Sift() as used, lib.Sift() as fresh_small:
+        small = every_stage(lib, fresh_small, "61x47")
+        used.detect(sc.image("61x47"))
+        grown = every_stage(lib, used, "300x400")
+        same_bits(grown[0], kps, "grown handle: keypoints")
+        same_bits(grown[1], desc, "grown handle: descriptors")
+        after = every_stage(lib, used, "61x47")
+        same_bits(after[0], small[0], "small image on the grown handle: keypoints")
+        same_bits(after[1], small[1], "small image on the grown handle: descriptors")
 
 
 def _arrays(keypoints, descriptors):
@@ -68,6 +127,20 @@ def _arrays(keypoints, descriptors):
     {"nfeatures": 10}, {"root": True}], ids=lambda k: "-".join(k) or "defaults")
 @pytest.mark.parametrize("name", ["61x47", "47x61"])
 def test_detect_keypoints_equals_the_restatement(lib, name, kwargs):
+    detect_keypoints_case(name, kwargs)
+
+
+@pytest.mark.parametrize("kwargs", [{"nOctaveLayers": 1}, {"nOctaveLayers": 8}, {"nOctaveLayers": 8, "sigma": 2.4}],
+                         ids=["1", "8", "8-sigma2.4"])
+@pytest.mark.parametrize("name", ["61x47", "47x61"])
+def test_detect_keypoints_at_the_ends_of_the_layer_range(lib, name, kwargs):
+    """nOctaveLayers 1 and 8, the ends of what is served: the [SF_MAX_LAYERS + 3] tables full, the layer field of the
+    sort key and the octave packing up to 8 (tests/test_sift_restated.py asserts that keypoints of layer 8 are there),
+    and with one layer a last blur of radius 45 in octaves of 12 to 16 rows."""
+    detect_keypoints_case(name, kwargs)
+
+
+def detect_keypoints_case(name, kwargs):
     from glimpse_amd import optimize
 
     kwargs = dict(kwargs)
@@ -83,6 +156,8 @@ def test_detect_keypoints_equals_the_restatement(lib, name, kwargs):
                                                        nfeatures=nfeatures, **kwargs)
     assert all(type(k) is optimize.KeyPoint and k.class_id == -1 and type(k.octave) is int for k in keypoints)
     found_k, found_d = _arrays(keypoints, descriptors)
+    print(name, kwargs, len(found_k), "keypoints, expected", len(expected_k), "; differing keypoint values:",
+          int(np.count_nonzero(found_k.view(np.uint64) != expected_k.view(np.uint64))) if found_k.shape == expected_k.shape else "-")
     same_bits(found_k, expected_k, "keypoints")
     if root:
         expected_d = sr.root_descriptors(expected_d)

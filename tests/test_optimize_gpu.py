@@ -55,6 +55,77 @@ def test_eval_equals_the_restatement_bit_for_bit(golden, lib, fixture):
         assert not got[1][5].any()  # the image in no pair
 
 
+def _differing(a, b):
+    return int(np.count_nonzero(_bits(a) != _bits(b)))
+
+
+@pytest.mark.parametrize("n_images", oc.SYNTHETIC)
+def test_sequences_past_one_workgroup_equal_the_restatement_and_the_longdouble_sums(lib, n_images):
+    """`orient_cases.synthetic` (256, 257, 300 and 600 images: 1, 2, 2 and 3 image workgroups of k_orient_reduce, 803 to
+    1487 pairs: 4 to 6 turns of the objective's lanes, pairs of one to three chunks in a lane's first and second turn, a
+    hub image with 300 pairs in its incidence list, images in no pair either side of image 256;
+    tests/test_optimize_host.py asserts all of it) through `_lib.Orient`: the restatement bit for bit, the same bytes
+    twice, and inside the derived bound of plain longdouble sums, which share nothing of the kernel's structure.
+
+    Ratio of the error to u sum |addend| on an MI355X, as on the CPU (the restatement is equal bit for bit): objective
+    0.26, 0.13, 1.2, 0.39 and gradient 2.2, 2.8, 14, 4.1 for 256, 257, 300 and 600 images (the largest is the hub image's,
+    which 22 684 addends feed); the bound's factor n_adds is 58 064 or more for the objective, and no entry uses more than
+    0.15 % of its bound."""
+    case = oc.synthetic_case(n_images)
+    want, details = case["want"], case["details"]
+    assert details["min_abs_dxyz"] > 1e-9
+    with lib.Orient(n_images, *oc.flat(case["pairs"])) as handle:
+        got = handle.eval(case["R"], case["Rprime"])
+        again = handle.eval(case["R"], case["Rprime"])
+    bound_o, bound_g = oc.longdouble_bounds(details, case["exact"][2])
+    (err_o, ratio_o), (err_g, ratio_g) = oc.longdouble_ratios(got, case["exact"], details)
+    print(n_images, "images,", len(case["pairs"]), "pairs: differing from the restatement: objective", _differing(got[0], want[0]),
+          "gradient entries", _differing(got[1], want[1]), "of", got[1].size, "; second call:", _differing(got[0], again[0]),
+          _differing(got[1], again[1]), "; against longdouble, ratio to u sum |addend|: objective", ratio_o, "of",
+          bound_o / (oc.U * details["abs_objective"]), "gradient", ratio_g, "; largest share of its bound",
+          float((err_g[bound_g > 0] / bound_g[bound_g > 0]).max()))
+    assert _bits(got[0]) == _bits(want[0]) and np.array_equal(_bits(got[1]), _bits(want[1]))
+    assert _bits(again[0]) == _bits(got[0]) and np.array_equal(_bits(again[1]), _bits(got[1]))
+    isolated = oc.synthetic_isolated(n_images)
+    assert not _bits(got[1][isolated]).any()  # the images in no pair: exactly +0
+    assert err_o <= bound_o and (err_g <= bound_g).all()
+
+
+def test_a_handle_made_after_a_larger_one_was_destroyed(lib):
+    """600 images evaluated and destroyed, then 257: what the allocator hands back holds the larger sequence's lists,
+    partial sums and gradient.  Image 256 of the 257, the only one of the second workgroup, is in no pair: a kernel that
+    never wrote its row would pass on fresh memory that happens to be zero, and fails here."""
+    big, small = oc.synthetic_case(600), oc.synthetic_case(257)
+    with lib.Orient(600, *oc.flat(big["pairs"])) as handle:
+        handle.eval(big["R"], big["Rprime"])
+    with lib.Orient(257, *oc.flat(small["pairs"])) as handle:
+        got = handle.eval(small["R"], small["Rprime"])
+    print("differing from the restatement: objective", _differing(got[0], small["want"][0]), "gradient entries",
+          _differing(got[1], small["want"][1]), "of", got[1].size)
+    assert _bits(got[0]) == _bits(small["want"][0]) and np.array_equal(_bits(got[1]), _bits(small["want"][1]))
+
+
+def test_observer_cameras_of_257_images_through_the_public_surface(lib):
+    """ObserverCameras built from a dict of 803 matches between 257 images: `evaluate` with anchor_weight 0 and 1e6 at the
+    start and half a degree off it, against the restatement's callback bit for bit."""
+    from glimpse_amd.camera import rotations
+
+    model, pairs = oc.synthetic_observer(257)
+    start = oc.synthetic_case(257)["viewdirs"]
+    assert np.array_equal(model.viewdirs, start) and len(model.matches) == len(pairs) == 803
+    with model.upload() as handle:
+        for point in (start, oc.synthetic_probe(start)):
+            for weight in (0.0, 1e6):
+                d = {}
+                want = rs.callback(point, start, model.anchors, weight, pairs, rotations, d)
+                assert d["min_abs_dxyz"] > 1e-9
+                objective, gradient = model.evaluate(handle, point, anchor_weight=weight)
+                print("anchor_weight", weight, "anchors' objective", d["anchor_objective"], ": differing objective",
+                      _differing(objective, want[0]), "gradient entries", _differing(gradient, want[1]), "of", gradient.size)
+                assert _bits(objective) == _bits(want[0]) and np.array_equal(_bits(gradient), _bits(want[1]))
+                assert gradient.shape == (257, 3) and (weight == 0.0 or point is start or d["anchor_objective"] > 0)
+
+
 def test_match_classes_against_the_reference(golden):
     """`predicted` of the four classes on pair (1, 2) of the fixture, both cameras, and the camera coordinates the classes
     make, against the reference's.  Tolerances are those of the existing camera tests: rtol 1e-11, atol 1e-12 for what
@@ -195,6 +266,7 @@ def test_handles_come_and_go(golden, lib):
     with lib.Orient(3, [], [], [0], np.empty((0, 2)), np.empty((0, 2))) as empty:
         objective, gradient = empty.eval(np.zeros((3, 3, 3)), np.zeros((3, 3, 3, 3)))
         assert objective == 0.0 and gradient.shape == (3, 3) and not gradient.any()
+        assert not _bits(objective).any() and not _bits(gradient).any()  # exactly +0, not -0
     assert len(pairs) == 6
 
 

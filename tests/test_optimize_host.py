@@ -66,6 +66,52 @@ def test_an_image_in_no_pair_has_no_gradient_and_an_empty_pair_adds_nothing(gold
     assert abs(objective - objective_2) <= 8 * U * objective
 
 
+@pytest.mark.parametrize("n_images", oc.SYNTHETIC)
+def test_the_synthetic_sequences_meet_the_conditions_of_the_gpu_test(n_images):
+    """What tests/test_optimize_gpu.py relies on to reach the paths past one workgroup, asserted without a device: the
+    image and pair counts, the pair sizes in a lane's first and second turn, the images in no pair, the image that is only
+    ever j, the hub, and the noise condition; and the restatement itself inside the longdouble bound."""
+    case = oc.synthetic_case(n_images)
+    pairs, details = case["pairs"], case["details"]
+    workgroups = {256: 1, 257: 2, 300: 2, 600: 3}[n_images]
+    assert len(case["R"]) == n_images and -(-n_images // rs.TB) == workgroups
+    assert -(-len(pairs) // rs.TB) >= max(2, workgroups)  # the objective's lanes take that many turns
+    order = [(i, j) for i, j, _, _ in pairs]
+    assert order == sorted(order) and len(set(order)) == len(order) and all(i != j for i, j in order)
+    assert all((i, i + d) in order for i in (0, 1, 50, n_images - 8) for d in (1, 2))  # the chain
+    sizes = [len(p[2]) for p in pairs]
+    assert all(len(p[3]) == m for p, m in zip(pairs, sizes))
+    assert sizes[3:12] == list(oc.PAIR_SIZES) == sizes[260:269] and oc.PAIR_SIZES == (0, 1, 255, 256, 257, 4095, 4096, 4097, 8193)
+    xy = np.concatenate([p[2] for p in pairs])
+    assert np.abs(xy).max() <= 0.4 and np.abs(xy).max() > 0.39
+    members = [set(i for i, _ in order), set(j for _, j in order)]
+    isolated = oc.synthetic_isolated(n_images)
+    assert isolated[0] < 256 and not (members[0] | members[1]) & set(isolated)
+    assert len(isolated) == (2 if n_images > 256 else 1) and all(m >= 256 for m in isolated[1:])  # (256 images: none past 255)
+    assert not case["want"][1][isolated].any() and not np.signbit(case["want"][1][isolated]).any()  # exactly +0
+    only_j = members[1] - members[0]
+    assert only_j and all(np.any(case["want"][1][m] != 0) for m in only_j)
+    assert 0 in members[0] - members[1]
+    hub_i, hub_j = [j for i, j in order if i == oc.HUB], [i for i, j in order if j == oc.HUB]
+    others = n_images - 3 - len(isolated)  # not the hub, not the two end images, not the isolated ones
+    assert len(hub_i) >= 150 and len(hub_j) >= 150 and len(hub_i) + len(hub_j) >= 300
+    assert len(set(hub_i) | set(hub_j)) >= min(300, others)  # other images as far as there are any
+    assert details["min_abs_dxyz"] > 1e-9
+    assert details["matches"] == sum(sizes) >= 2 * sum(oc.PAIR_SIZES)
+    bound_o, bound_g = oc.longdouble_bounds(details, case["exact"][2])
+    (err_o, ratio_o), (err_g, ratio_g) = oc.longdouble_ratios(case["want"], case["exact"], details)
+    print(n_images, "images,", len(pairs), "pairs,", details["matches"], "matches, min |dxyz|", details["min_abs_dxyz"],
+          "ratio to u sum |addend|: objective", ratio_o, "gradient", ratio_g)
+    assert err_o <= bound_o and (err_g <= bound_g).all()
+    if n_images == 257:  # the case that goes through ObserverCameras: the same conditions half a degree off the start
+        model, same_pairs = oc.synthetic_observer(257)
+        assert same_pairs is pairs and list(model.matches) == order and model.anchors == [0, 130]
+        assert [(i, j) for _, i, j in optimize.match_pairs(model.matches)] == order
+        d = {}
+        rs.callback(oc.synthetic_probe(case["viewdirs"]), case["viewdirs"], model.anchors, 1e6, pairs, rotations, d)
+        assert d["min_abs_dxyz"] > 1e-9 and d["anchor_objective"] > 0
+
+
 def test_rotations_equal_the_properties_and_the_reference_bit_for_bit(golden):
     for fixture in oc.FIXTURES:
         g = golden(fixture)

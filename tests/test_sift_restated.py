@@ -142,6 +142,43 @@ def test_the_images_of_the_gpu_test_meet_its_conditions():
             assert trace[what] >= 1, (name, what)
 
 
+def test_the_large_image_overflows_a_fresh_candidate_list_and_the_others_do_not():
+    """ "300x400" is there for the second attempt of the device's candidate list (sc.LIST_SLOTS slots on a fresh handle);
+    "61x47", which the reuse test runs before and after it, must fit the first."""
+    st = sc.stages("300x400")
+    print("300x400:", len(st["candidates"]), "candidates,", len(st["keypoints"]), "keypoints")
+    assert sc.LIST_SLOTS == 4096 and len(st["candidates"]) > 4096
+    assert (len(st["candidates"]), len(st["keypoints"])) == (4446, 1608)  # (the figures of INPUTS.md)
+    assert len(st["keypoints"]) <= 2 * len(st["candidates"]) + 64  # (the keypoint list's own second attempt is not reached)
+    for name in ("61x47", "47x61", "256x192", "strip"):
+        assert len(sc.stages(name)["candidates"]) < sc.LIST_SLOTS, name
+
+
+def test_the_ends_of_the_layer_range_meet_the_conditions_of_the_gpu_test():
+    """nOctaveLayers 1 and 8 on the images tests/test_gpu_sift.py runs them on: enough keypoints for the sweep's floor,
+    keypoints of the last layer (8) and of more than one octave, all S + 3 tables, and the radii that fold the strip's
+    reflection more than once."""
+    for name in ("61x47", "47x61"):
+        for params in ({"nOctaveLayers": 1}, {"nOctaveLayers": 8}, {"nOctaveLayers": 8, "sigma": 2.4}):
+            st = sc.stages(name, **params)
+            kept = sr.finish(st["keypoints"], st["descriptors"])[0]
+            print(name, params, len(st["candidates"]), "candidates,", len(kept), "keypoints")
+            assert len(kept) >= 5
+            layers = set(st["cells"][:, 1].tolist())
+            assert layers == {1} if params["nOctaveLayers"] == 1 else (8 in layers and len(layers) >= 7)
+            assert np.array_equal((st["keypoints"][:, 5].astype(np.int64) >> 8) & 255, st["cells"][:, 1])
+    assert len(sr.finish(*[sc.stages("47x61", nOctaveLayers=8)[k] for k in ("keypoints", "descriptors")])[0]) == 64
+    assert len(sr.finish(*[sc.stages("47x61", nOctaveLayers=1)[k] for k in ("keypoints", "descriptors")])[0]) == 16
+    for name, layers in (("47x61", 8), ("strip", 8), ("strip", 1)):
+        st = sc.stages(name, nOctaveLayers=layers)
+        assert all(len(g) == layers + 3 and len(d) == layers + 2 for g, d in zip(st["gauss"], st["dog"]))
+        assert len(st["gauss"]) >= 2 and len(st["candidates"]) >= 1
+        assert layers == 1 or (len(st["candidates"]) >= 5 and len(st["keypoints"]) >= 1)  # (one layer: for the pyramid)
+    assert len(sr.tables(8, 1.6)) == 11 and [r for r, _ in sr.tables(1, 1.6)] == [5, 11, 22, 45]
+    assert sc.stages("strip", nOctaveLayers=1)["gauss"][1][0].shape == (40, 12)  # radius 45 over 12 cells: four folds
+    assert max(r for r, _ in sr.tables(8, 1.6)) == 6  # (with eight layers the blurs are narrow: no fold past the first)
+
+
 def test_elementary_functions_are_close_to_the_library():
     """They are the rule's own (determinism is what counts), but they must still be the functions they are named for."""
     x = np.linspace(-60.0, 3.0, 2001)
