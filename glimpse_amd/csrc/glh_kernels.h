@@ -93,6 +93,10 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 
 __device__ __forceinline__ void flag_point(uint32_t* pt_status, int32_t* pt_err_frame, int pt,
                                            uint32_t bit, int frame) {
+  // A track ends at the frame of its first error (the reference raises there).  The state it is left in keeps raising bits
+  // in the frames after it -- NaN heights of a point that was out of bounds when drawn, for one -- and those are not its
+  // error: only the bits of the failing frame itself accumulate, so the word names what the reference would have raised.
+  if (__hip_atomic_load(&pt_err_frame[pt], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < frame) return;
   atomicOr(&pt_status[pt], bit);
   atomicMin(&pt_err_frame[pt], frame);
 }

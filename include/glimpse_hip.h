@@ -75,7 +75,9 @@ extern "C" {
                                * (glh_set_extra_log_likelihoods); the device does the observer likelihoods,
                                * resampling and moments                                                          */
 
-/* ---- per-point status bits (sticky; the Python Tracker turns them into Tracks.errors) */
+/* ---- per-point status bits (sticky; the Python Tracker turns them into Tracks.errors).  A word holds the bits of the frame
+ * at which its point first failed (glh_get_point_error_frame); what later frames would raise on the state the failure left
+ * behind is not recorded: the reference has ended the track there. */
 #define GLH_PT_NAN 1u            /* ValueError "missing (NaN) values"      tracker.py:118  */
 #define GLH_PT_TEMPLATE_OOB 2u   /* IndexError "Box extends beyond grid"   raster.py:417   */
 #define GLH_PT_SAMPLE_OUTSIDE 4u /* ValueError "sampling points outside"   observer.py:201 */
