@@ -20,6 +20,7 @@ RNG_HOST, RNG_PHILOX = 0, 1
 MATH_EXACT, MATH_FAST = 0, 1
 RESAMPLE = {"systematic": 0, "stratified": 1, "choice": 2, "residual": 3}
 OK = 0
+E_STATE = -4  # GLH_E_STATE (include/glimpse_hip.h); here: a call on a closed handle
 PT_NAN, PT_TEMPLATE_OOB, PT_SAMPLE_OUTSIDE, PT_RESAMPLE_CLAMP, PT_CONST_TILE = 1, 2, 4, 8, 16
 PT_RASTER_OOB, PT_NOT_VISIBLE = 32, 64
 RASTER_DEM, RASTER_DEM_SIGMA, RASTER_VIEWSHED = 0, 1, 2
@@ -1236,42 +1237,24 @@ def stage_polygon_mask(xy, ring_off, n_polygons, n_holes, nx, ny, device_id=0, r
     return _timed(out.view(bool), POLYGON_MASK_TIMES, times, return_times)
 
 
-ORIENT_TIMES = ("upload", "map", "reduce", "download")
+class _Handle:
+    """A device object of the library (glh_X_create): `_h` is its handle, null once closed.  A subclass names the
+    export that frees it (`_destroy`) and passes `self._handle()` to every other."""
+    _destroy = None
+    _h = None  # (closed until __init__ has run)
 
-
-class Orient:
-    """The matches of an image sequence on the device (glh_orient_create): uploaded once, evaluated at many view
-    directions (optimize.ObserverCameras.fit).  `pair_i`, `pair_j` (n_pairs,): the images of every pair; `pair_offset`
-    (n_pairs + 1,): pair p's matches are rows pair_offset[p] .. pair_offset[p + 1] of `xy_i`, `xy_j` (N, 2), the
-    normalised camera coordinates of a match in image i and in image j."""
-
-    def __init__(self, n_images, pair_i, pair_j, pair_offset, xy_i, xy_j, device_id=0):
-        self.n_images = int(n_images)
+    def __init__(self):
         self._h = C.c_void_p()
-        pair_i, pair_j = _arr(pair_i, np.int32), _arr(pair_j, np.int32)
-        pair_offset = _arr(pair_offset, np.int64, (len(pair_i) + 1,))
-        xy_i, xy_j = _arr(xy_i, np.float64).reshape(-1, 2), _arr(xy_j, np.float64).reshape(-1, 2)
-        # (the library is not told N: the rows the offsets name must exist; what else is wrong with them it reports)
-        if pair_i.ndim != 1 or pair_j.shape != pair_i.shape or len(xy_i) != len(xy_j) or len(xy_i) < pair_offset.max():
-            raise ValueError("pair_i / pair_j (n_pairs,) and xy_i / xy_j (N, 2) with N >= pair_offset.max()")
-        check(load().glh_orient_create(int(device_id), self.n_images, len(pair_i), _ptr(pair_i), _ptr(pair_j),
-                                       _ptr(pair_offset), _ptr(xy_i), _ptr(xy_j), C.byref(self._h)))
 
-    def eval(self, R, Rprime, return_times=False):
-        """(objective, gradient (n_images, 3)) of the matches at the rotation matrices `R` (n_images, 3, 3) and their
-        derivatives `Rprime` (n_images, 3, 3, 3) ([r][w][k], Camera.Rprime)."""
+    def _handle(self):
         if not self._h:
-            raise GlhError(-4, "the handle is closed")
-        R = _arr(R, np.float64, (self.n_images, 3, 3))
-        Rprime = _arr(Rprime, np.float64, (self.n_images, 3, 3, 3))
-        objective, gradient, times = C.c_double(0.0), np.empty((self.n_images, 3)), np.zeros(len(ORIENT_TIMES))
-        check(load().glh_orient_eval(self._h, _ptr(R), _ptr(Rprime), C.byref(objective), _ptr(gradient), _ptr(times)))
-        return _timed((objective.value, gradient), ORIENT_TIMES, times, return_times, extend=True)
+            raise GlhError(E_STATE, "the handle is closed")
+        return self._h
 
     def close(self):
         if self._h:
-            handle, self._h = self._h, C.c_void_p()
-            check(load().glh_orient_destroy(handle))
+            handle, self._h = self._h, C.c_void_p()  # (first: a second close, or __del__ after a failed one, has nothing to free)
+            check(getattr(load(), self._destroy)(handle))
 
     def __enter__(self):
         return self
@@ -1286,19 +1269,55 @@ class Orient:
             pass
 
 
+ORIENT_TIMES = ("upload", "map", "reduce", "download")
+
+
+class Orient(_Handle):
+    """The matches of an image sequence on the device (glh_orient_create): uploaded once, evaluated at many view
+    directions (optimize.ObserverCameras.fit).  `pair_i`, `pair_j` (n_pairs,): the images of every pair; `pair_offset`
+    (n_pairs + 1,): pair p's matches are rows pair_offset[p] .. pair_offset[p + 1] of `xy_i`, `xy_j` (N, 2), the
+    normalised camera coordinates of a match in image i and in image j."""
+
+    _destroy = "glh_orient_destroy"
+
+    def __init__(self, n_images, pair_i, pair_j, pair_offset, xy_i, xy_j, device_id=0):
+        super().__init__()
+        self.n_images = int(n_images)
+        pair_i, pair_j = _arr(pair_i, np.int32), _arr(pair_j, np.int32)
+        pair_offset = _arr(pair_offset, np.int64, (len(pair_i) + 1,))
+        xy_i, xy_j = _arr(xy_i, np.float64).reshape(-1, 2), _arr(xy_j, np.float64).reshape(-1, 2)
+        # (the library is not told N: the rows the offsets name must exist; what else is wrong with them it reports)
+        if pair_i.ndim != 1 or pair_j.shape != pair_i.shape or len(xy_i) != len(xy_j) or len(xy_i) < pair_offset.max():
+            raise ValueError("pair_i / pair_j (n_pairs,) and xy_i / xy_j (N, 2) with N >= pair_offset.max()")
+        check(load().glh_orient_create(int(device_id), self.n_images, len(pair_i), _ptr(pair_i), _ptr(pair_j),
+                                       _ptr(pair_offset), _ptr(xy_i), _ptr(xy_j), C.byref(self._h)))
+
+    def eval(self, R, Rprime, return_times=False):
+        """(objective, gradient (n_images, 3)) of the matches at the rotation matrices `R` (n_images, 3, 3) and their
+        derivatives `Rprime` (n_images, 3, 3, 3) ([r][w][k], Camera.Rprime)."""
+        handle = self._handle()
+        R = _arr(R, np.float64, (self.n_images, 3, 3))
+        Rprime = _arr(Rprime, np.float64, (self.n_images, 3, 3, 3))
+        objective, gradient, times = C.c_double(0.0), np.empty((self.n_images, 3)), np.zeros(len(ORIENT_TIMES))
+        check(load().glh_orient_eval(handle, _ptr(R), _ptr(Rprime), C.byref(objective), _ptr(gradient), _ptr(times)))
+        return _timed((objective.value, gradient), ORIENT_TIMES, times, return_times, extend=True)
+
+
 CALIB_TIMES = ("upload", "points", "line_points", "nearest", "download")
 CALIB_KINDS = {"points": 0, "lines": 1, "matches": 2, "rotation": 3, "rotation_xy": 4}
 
 
-class Calib:
+class Calib(_Handle):
     """The controls of a camera calibration on the device (glh_calib_create): uploaded once, evaluated under many sets
     of camera vectors (optimize.Cameras).  Control c is of `kind[c]` (CALIB_KINDS), belongs to camera `cam_a[c]` (the match
     kinds: to `cam_a[c]` and `cam_b[c]`) of `n_cams` and owns rows row_offset[c] .. row_offset[c + 1] of `obs` (N, 2) and
     `src` (N, 3) (include/glimpse_hip.h says what each kind keeps there)."""
 
+    _destroy = "glh_calib_destroy"
+
     def __init__(self, n_cams, kind, cam_a, cam_b, directions, row_offset, obs, src, device_id=0):
+        super().__init__()
         self.n_cams = int(n_cams)
-        self._h = C.c_void_p()
         kind, cam_a, cam_b = _arr(kind, np.int32), _arr(cam_a, np.int32), _arr(cam_b, np.int32)
         directions = _arr(directions, np.int32)
         self.rows = np.diff(_arr(row_offset, np.int64, (len(kind) + 1,)))
@@ -1316,8 +1335,7 @@ class Calib:
         camera vectors `cams[job_set[q]]` (n_sets, n_cams, 24), with `rot` (n_sets, n_cams, 3, 3) the rotation matrices the
         host methods use.  `job_side`: which camera of a match control predicts (default 0).  `tables`: for every job
         None, or the segment table of a Lines job: (seg_vertex (S + 1,), seg_count (S,), seg_par (S, 5), vertex (V, 3))."""
-        if not self._h:
-            raise GlhError(-4, "the handle is closed")
+        handle = self._handle()
         cams = _arr(cams, np.float64)
         if cams.ndim != 3 or cams.shape[1:] != (self.n_cams, CAM_LEN):
             raise ValueError(f"expected camera vectors (n_sets, {self.n_cams}, {CAM_LEN}), got {cams.shape}")
@@ -1345,27 +1363,10 @@ class Calib:
         in_range = (job_control >= 0) & (job_control < len(self.rows))
         predicted = np.empty((int(self.rows[job_control[in_range]].sum()), 2))
         times = np.zeros(len(CALIB_TIMES))
-        check(load().glh_calib_eval(self._h, len(cams), _ptr(cams), _ptr(rot), len(job_control), _ptr(job_control),
+        check(load().glh_calib_eval(handle, len(cams), _ptr(cams), _ptr(rot), len(job_control), _ptr(job_control),
                                     _ptr(job_set), _ptr(job_side), _ptr(job_seg), _ptr(seg_vertex), _ptr(seg_count),
                                     _ptr(seg_par), len(vertex), _ptr(vertex), _ptr(predicted), _ptr(times)))
         return _timed(predicted, CALIB_TIMES, times, return_times)
-
-    def close(self):
-        if self._h:
-            handle, self._h = self._h, C.c_void_p()
-            check(load().glh_calib_destroy(handle))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 MATCH_TIMES = ("upload", "prepare", "search", "merge", "download")
@@ -1373,21 +1374,18 @@ MATCH_U8, MATCH_F32 = 0, 1
 MATCH_U8_MAX_DIM = 256  # csrc/glh_match.h
 
 
-class Matcher:
+class Matcher(_Handle):
     """Descriptor sets on the device (glh_match_create): each is uploaded once under a slot number and searched many
     times (optimize.match_keypoints, optimize.KeypointMatcher.build_matches).  `knn2(q, t)` is, for every row of slot q's
     set, the two rows of slot t's with the smallest keys (squared distance, row index): equal distances go to the lower
     index."""
 
+    _destroy = "glh_match_destroy"
+
     def __init__(self, device_id=0):
-        self._h = C.c_void_p()
+        super().__init__()
         self._sets = {}  # slot -> (kind, n, dim)
         check(load().glh_match_create(int(device_id), C.byref(self._h)))
-
-    def _handle(self):
-        if not self._h:
-            raise GlhError(-4, "the handle is closed")
-        return self._h
 
     def put(self, slot, descriptors, path=None):
         """Uploads `descriptors` (n, dim) under `slot`, in the place of what it held; returns the path taken.  uint8
@@ -1432,21 +1430,8 @@ class Matcher:
 
     def close(self):
         if self._h:
-            handle, self._h = self._h, C.c_void_p()
             self._sets = {}
-            check(load().glh_match_destroy(handle))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        super().close()
 
 
 SIFT_TIMES = ("upload", "base", "pyramid", "extrema", "refine", "describe", "download")
@@ -1473,18 +1458,15 @@ def sift_tables(n_layers, sigma):
     return tables
 
 
-class Sift:
+class Sift(_Handle):
     """SIFT detection and description on the device (glh_sift_create): the pyramid's buffers stay allocated between
     images of one size.  `detect` gives the keypoints in the rule's order, before the host-side steps of optimize.SIFT."""
 
-    def __init__(self, device_id=0):
-        self._h = C.c_void_p()
-        check(load().glh_sift_create(int(device_id), C.byref(self._h)))
+    _destroy = "glh_sift_destroy"
 
-    def _handle(self):
-        if not self._h:
-            raise GlhError(-4, "the handle is closed")
-        return self._h
+    def __init__(self, device_id=0):
+        super().__init__()
+        check(load().glh_sift_create(int(device_id), C.byref(self._h)))
 
     def detect(self, image, n_layers=3, contrast=0.04, edge=10.0, sigma=1.6, return_times=False):
         """(keypoints float64 (n, 6): pt x, pt y, size, angle, response, octave; descriptors uint8 (n, 128)) of `image`
@@ -1533,20 +1515,3 @@ class Sift:
         if out.size:
             check(load().glh_sift_layer(self._handle(), int(kind), int(octave), int(index), _ptr(out)))
         return out
-
-    def close(self):
-        if self._h:
-            handle, self._h = self._h, C.c_void_p()
-            check(load().glh_sift_destroy(handle))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -5,13 +5,14 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct glh_calib;  // the C ABI's handle: the uploaded controls (glh_calib.hip)
+
 namespace glh {
 
 constexpr int CAL_TIMES = 5;   // entries of times_ms (include/glimpse_hip.h)
 constexpr int CAL_TB = 256;    // threads of a workgroup, all three kernels
 constexpr int CAL_TILE = 256;  // projected points of a Lines job held in LDS at a time (tests/calib_restated.py: TILE)
 
-struct CalibHandle;  // the uploaded controls (glh_calib.hip)
 struct CamDev;
 
 struct CalibControls {
@@ -20,6 +21,12 @@ struct CalibControls {
   const int64_t* row_offset;            // [n_controls + 1]
   const double* obs;                    // [N][2]
   const double* src;                    // [N][3]
+};
+
+struct CalibTable {  // what a handle keeps of its controls: an evaluation's jobs are checked against it
+  int n_cams, n_controls;
+  const int32_t* kind;        // [n_controls]
+  const int64_t* row_offset;  // [n_controls + 1]
 };
 
 struct CalibEval {
@@ -39,8 +46,9 @@ struct CalibEval {
 
 // The arguments have been checked (glimpse_hip.hip).  A GLH_* status, with the message left for glh_last_error() on
 // failure (glh_stage.h: fail).
-int calib_create(int device, const CalibControls& c, CalibHandle** out);
-int calib_eval(CalibHandle* h, const CalibEval& e);
-void calib_destroy(CalibHandle* h);
+int calib_create(int device, const CalibControls& c, glh_calib** out);
+CalibTable calib_table(const glh_calib* h);
+int calib_eval(glh_calib* h, const CalibEval& e);
+void calib_destroy(glh_calib* h);
 
 }  // namespace glh

@@ -31,7 +31,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/glimpse_hip.h"
@@ -184,46 +183,31 @@ __global__ void __launch_bounds__(CAL_TB) k_calib_nearest(const CalBlock* __rest
   if (live) out[(size_t)j.out0 + r] = pj[index];
 }
 
-// a device buffer that only grows (the evaluations of a fit are all of one size)
-struct GrowBuf {
-  DevBuf b;
-  size_t cap = 0;
-  int reserve(size_t bytes) {
-    if (bytes <= cap && b.p) return GLH_OK;
-    if (b.p) {
-      (void)hipFree(b.p);
-      b.p = nullptr;
-      cap = 0;
-    }
-    CHK(b.alloc(bytes));
-    cap = bytes;
-    return GLH_OK;
-  }
-};
-
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 }  // namespace
+}  // namespace glh
 
-struct CalibHandle {
-  int device = 0, n_cams = 0, n_controls = 0;
+struct glh_calib : glh::DeviceObject {
+  int n_cams = 0, n_controls = 0;
   std::vector<int32_t> kind, cam_a, cam_b, directions;
   std::vector<int64_t> row_offset;
-  DevBuf obs, src;
-  GrowBuf in, puv, out;
-  StageEvents<CAL_TIMES + 1> ev;
+  glh::DevBuf obs, src;
+  glh::GrowBuf in, puv, out;  // (they only grow: the evaluations of a fit are all of one size)
+  glh::StageEvents<glh::CAL_TIMES + 1> ev;
   std::vector<char> stage;
 };
 
-static int calib_fill(CalibHandle* h, int device, const CalibControls& c) {
-  h->device = device, h->n_cams = c.n_cams, h->n_controls = c.n_controls;
+namespace glh {
+
+static int calib_fill(glh_calib* h, const CalibControls& c) {
+  h->n_cams = c.n_cams, h->n_controls = c.n_controls;
   h->kind.assign(c.kind, c.kind + c.n_controls);
   h->cam_a.assign(c.cam_a, c.cam_a + c.n_controls);
   h->cam_b.assign(c.cam_b, c.cam_b + c.n_controls);
   h->directions.assign(c.directions, c.directions + c.n_controls);
   h->row_offset.assign(c.row_offset, c.row_offset + c.n_controls + 1);
   const size_t N = (size_t)c.row_offset[c.n_controls];
-  HIPCHK(hipSetDevice(device));
   CHK(h->ev.create());
   const double none[3] = {0.0, 0.0, 0.0};
   CHK(h->obs.up(N ? c.obs : none, (N ? N : 1) * 16));
@@ -231,21 +215,15 @@ static int calib_fill(CalibHandle* h, int device, const CalibControls& c) {
   return GLH_OK;
 }
 
-int calib_create(int device, const CalibControls& c, CalibHandle** out) {
-  CalibHandle* h = new (std::nothrow) CalibHandle;
-  if (!h) return fail(GLH_E_NOMEM, "calib: no memory for a handle");
-  const int rc = calib_fill(h, device, c);
-  if (rc != GLH_OK) {
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return GLH_OK;
+int calib_create(int device, const CalibControls& c, glh_calib** out) {
+  return create_object("calib", device, out, [&](glh_calib* h) { return calib_fill(h, c); });
 }
 
-int calib_eval(CalibHandle* h, const CalibEval& e) {
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernels)
+CalibTable calib_table(const glh_calib* h) { return CalibTable{h->n_cams, h->n_controls, h->kind.data(), h->row_offset.data()}; }
+
+int calib_eval(glh_calib* h, const CalibEval& e) {
+  CHK(h->use());
+  hipStream_t s = h->stream;
   const size_t n_cam_sets = (size_t)e.n_sets * h->n_cams;
   const size_t S = (size_t)e.job_seg[e.n_jobs], V = (size_t)e.seg_vertex[S];
   // the jobs, the workgroups of the three kernels and the segment table, in one staging buffer
@@ -325,16 +303,16 @@ int calib_eval(CalibHandle* h, const CalibEval& e) {
   CHK(h->puv.reserve((size_t)(puv_total ? puv_total : 1) * 16));
   CHK(h->out.reserve((size_t)(out_rows ? out_rows : 1) * 16));
   CHK(h->ev.record(0, s));
-  HIPCHK(hipMemcpy(h->in.b.p, st, h->stage.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->in.p, st, h->stage.size(), hipMemcpyHostToDevice));
   CHK(h->ev.record(1, s));
-  const char* d = h->in.b.as<char>();
+  const char* d = h->in.as<char>();
   const CalJob* d_jobs = reinterpret_cast<const CalJob*>(d + o_jobs);
   const CamDev* d_cams = reinterpret_cast<const CamDev*>(d + o_cams);
   if (!rows_b.empty()) {
     hipLaunchKernelGGL(k_calib_rows, dim3((unsigned)rows_b.size()), dim3(CAL_TB), 0, s,
                        reinterpret_cast<const CalBlock*>(d + o_rows), d_jobs, d_cams,
                        reinterpret_cast<const double*>(d + o_rot), h->obs.as<double2>(), h->src.as<double>(),
-                       h->out.b.as<double2>());
+                       h->out.as<double2>());
     HIPCHK(hipGetLastError());
   }
   CHK(h->ev.record(2, s));
@@ -343,28 +321,24 @@ int calib_eval(CalibHandle* h, const CalibEval& e) {
                        reinterpret_cast<const CalBlock*>(d + o_points), d_jobs, d_cams,
                        reinterpret_cast<const CalSeg*>(d + o_segs), reinterpret_cast<const double*>(d + o_vx),
                        reinterpret_cast<const double*>(d + o_vy), reinterpret_cast<const double*>(d + o_vd),
-                       h->puv.b.as<double2>());
+                       h->puv.as<double2>());
     HIPCHK(hipGetLastError());
   }
   CHK(h->ev.record(3, s));
   if (!nearest_b.empty()) {
     hipLaunchKernelGGL(k_calib_nearest, dim3((unsigned)nearest_b.size()), dim3(CAL_TB), 0, s,
                        reinterpret_cast<const CalBlock*>(d + o_nearest), d_jobs, h->obs.as<double2>(),
-                       h->puv.b.as<double2>(), h->out.b.as<double2>());
+                       h->puv.as<double2>(), h->out.as<double2>());
     HIPCHK(hipGetLastError());
   }
   CHK(h->ev.record(4, s));
-  if (out_rows) CHK(h->out.b.down(e.predicted, (size_t)out_rows * 16));
+  if (out_rows) CHK(h->out.down(e.predicted, (size_t)out_rows * 16));
   CHK(h->ev.record(5, s));
   HIPCHK(hipEventSynchronize(h->ev.e[5]));
   h->ev.report(e.times_ms, CAL_TIMES, CAL_TIMES);
   return GLH_OK;
 }
 
-void calib_destroy(CalibHandle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  delete h;
-}
+void calib_destroy(glh_calib* h) { destroy_object(h); }
 
 }  // namespace glh

@@ -275,58 +275,32 @@ struct MatchSet {
   double upload_ms = 0.0, prepare_ms = 0.0;
 };
 
-// A device buffer that only grows.
-struct GrowBuf {
-  DevBuf buf;
-  size_t bytes = 0;
-  int need(size_t want) {
-    if (want <= bytes) return GLH_OK;
-    if (buf.p) (void)hipFree(buf.p);
-    buf.p = nullptr, bytes = 0;
-    CHK(buf.alloc(want));
-    bytes = want;
-    return GLH_OK;
-  }
-};
-
 }  // namespace
+}  // namespace glh
 
-struct MatchHandle {
-  int device = 0;
-  std::map<int, std::unique_ptr<MatchSet>> sets;
-  GrowBuf partial, idx, d2;
-  StageEvents<4> ev;
+struct glh_match : glh::DeviceObject {
+  std::map<int, std::unique_ptr<glh::MatchSet>> sets;
+  glh::GrowBuf partial, idx, d2;
+  glh::StageEvents<4> ev;
 };
 
-int match_create(int device, MatchHandle** out) {
-  MatchHandle* h = new (std::nothrow) MatchHandle;
-  if (!h) return fail(GLH_E_NOMEM, "match: no memory for a handle");
-  h->device = device;
-  int rc = GLH_OK;
-  if (hipSetDevice(device) != hipSuccess) {
-    (void)hipGetLastError();
-    rc = fail(GLH_E_HIP, "match: hipSetDevice(%d) failed", device);
-  }
-  if (rc == GLH_OK) rc = h->ev.create();
-  if (rc != GLH_OK) {
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return GLH_OK;
+namespace glh {
+
+int match_create(int device, glh_match** out) {
+  return create_object("match", device, out, [](glh_match* h) { return h->ev.create(); });
 }
 
-bool match_info(const MatchHandle* h, int slot, MatchSetInfo* info) {
+bool match_info(const glh_match* h, int slot, MatchSetInfo* info) {
   const auto it = h->sets.find(slot);
   if (it == h->sets.end()) return false;
   *info = MatchSetInfo{it->second->kind, it->second->n, it->second->dim};
   return true;
 }
 
-static int match_fill(MatchHandle* h, MatchSet* s, const void* data) {
+static int match_fill(glh_match* h, MatchSet* s, const void* data) {
   const size_t n = (size_t)s->n;
   DevBuf raw;
-  hipStream_t st = nullptr;  // (the null stream: the copy is ordered with the kernel)
+  hipStream_t st = h->stream;
   CHK(h->ev.record(0, st));
   CHK(raw.up(data, n * s->dim * (s->kind == GLH_MATCH_U8 ? 1 : 4)));
   CHK(h->ev.record(1, st));
@@ -351,8 +325,8 @@ static int match_fill(MatchHandle* h, MatchSet* s, const void* data) {
   return GLH_OK;
 }
 
-int match_put(MatchHandle* h, int slot, int kind, int n, int dim, const void* data) {
-  HIPCHK(hipSetDevice(h->device));
+int match_put(glh_match* h, int slot, int kind, int n, int dim, const void* data) {
+  CHK(h->use());
   std::unique_ptr<MatchSet> s(new (std::nothrow) MatchSet);
   if (!s) return fail(GLH_E_NOMEM, "match: no memory for a set");
   s->kind = kind, s->n = n, s->dim = dim;
@@ -361,15 +335,15 @@ int match_put(MatchHandle* h, int slot, int kind, int n, int dim, const void* da
   return GLH_OK;
 }
 
-void match_drop(MatchHandle* h, int slot) {
+void match_drop(glh_match* h, int slot) {
   (void)hipSetDevice(h->device);
   h->sets.erase(slot);
 }
 
-int match_knn2(MatchHandle* h, int slot_q, int slot_t, int32_t* idx, float* d2, double* times_ms) {
+int match_knn2(glh_match* h, int slot_q, int slot_t, int32_t* idx, float* d2, double* times_ms) {
   const MatchSet& Q = *h->sets.at(slot_q);
   const MatchSet& T = *h->sets.at(slot_t);
-  HIPCHK(hipSetDevice(h->device));
+  CHK(h->use());
   const bool u8 = Q.kind == GLH_MATCH_U8;
   const int tile_rows = u8 ? MT_TI : MT_TF;
   const int n_tiles = (T.n + tile_rows - 1) / tile_rows, q_blocks = (Q.n + MT_QB - 1) / MT_QB;
@@ -377,14 +351,14 @@ int match_knn2(MatchHandle* h, int slot_q, int slot_t, int32_t* idx, float* d2, 
   want = want < 1 ? 1 : (want > n_tiles ? n_tiles : want);
   const int tiles_per_range = (n_tiles + want - 1) / want;
   const int ranges = (n_tiles + tiles_per_range - 1) / tiles_per_range;
-  CHK(h->idx.need((size_t)Q.n * 8));
-  CHK(h->d2.need((size_t)Q.n * 8));
-  if (ranges > 1) CHK(h->partial.need((size_t)ranges * Q.n * sizeof(Best2)));
-  Best2* partial = ranges > 1 ? h->partial.buf.as<Best2>() : nullptr;
-  int32_t* d_idx = h->idx.buf.as<int32_t>();
-  float* d_d2 = h->d2.buf.as<float>();
+  CHK(h->idx.reserve((size_t)Q.n * 8));
+  CHK(h->d2.reserve((size_t)Q.n * 8));
+  if (ranges > 1) CHK(h->partial.reserve((size_t)ranges * Q.n * sizeof(Best2)));
+  Best2* partial = ranges > 1 ? h->partial.as<Best2>() : nullptr;
+  int32_t* d_idx = h->idx.as<int32_t>();
+  float* d_d2 = h->d2.as<float>();
   const dim3 grid((unsigned)q_blocks, (unsigned)ranges);
-  hipStream_t st = nullptr;
+  hipStream_t st = h->stream;
   CHK(h->ev.record(0, st));
   if (u8) {
 #define MT_LAUNCH(KS)                                                                                                \
@@ -408,8 +382,8 @@ int match_knn2(MatchHandle* h, int slot_q, int slot_t, int32_t* idx, float* d2, 
     HIPCHK(hipGetLastError());
   }
   CHK(h->ev.record(2, st));
-  CHK(h->idx.buf.down(idx, (size_t)Q.n * 8));
-  CHK(h->d2.buf.down(d2, (size_t)Q.n * 8));
+  CHK(h->idx.down(idx, (size_t)Q.n * 8));
+  CHK(h->d2.down(d2, (size_t)Q.n * 8));
   CHK(h->ev.record(3, st));
   HIPCHK(hipEventSynchronize(h->ev.e[3]));
   if (times_ms) {
@@ -421,10 +395,6 @@ int match_knn2(MatchHandle* h, int slot_q, int slot_t, int32_t* idx, float* d2, 
   return GLH_OK;
 }
 
-void match_destroy(MatchHandle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  delete h;
-}
+void match_destroy(glh_match* h) { destroy_object(h); }
 
 }  // namespace glh

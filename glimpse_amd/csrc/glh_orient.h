@@ -5,20 +5,20 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct glh_orient;  // the C ABI's handle: the uploaded matches of one sequence (glh_orient.hip)
+
 namespace glh {
 
 constexpr int OR_TIMES = 4;     // entries of times_ms (include/glimpse_hip.h)
 constexpr int OR_CHUNK = 4096;  // matches per workgroup of the map kernel: part of the summation order
 
-struct OrientHandle;  // the uploaded matches of one sequence (glh_orient.hip)
-
 // The arguments have been checked (glimpse_hip.hip).  A GLH_* status, with the message left for glh_last_error() on
 // failure (glh_stage.h: fail).
 int orient_create(int device, int n_images, int n_pairs, const int32_t* pair_i, const int32_t* pair_j,
-                  const int64_t* pair_offset, const double* xy_i, const double* xy_j, OrientHandle** out);
-int orient_eval(OrientHandle* h, const double* R, const double* Rprime, double* objective, double* gradient,
+                  const int64_t* pair_offset, const double* xy_i, const double* xy_j, glh_orient** out);
+int orient_eval(glh_orient* h, const double* R, const double* Rprime, double* objective, double* gradient,
                 double* times_ms);
-void orient_destroy(OrientHandle* h);
+void orient_destroy(glh_orient* h);
 
 struct CamDev;
 int uv_to_xy_run(int device, const CamDev& cam, const double* uv, int n, double* xy);

@@ -30,7 +30,6 @@
 
 #include <cmath>
 #include <cstdint>
-#include <new>
 #include <vector>
 
 #include "../../include/glimpse_hip.h"
@@ -158,17 +157,20 @@ __global__ void __launch_bounds__(OR_TB) k_uv_to_xy(const CamDev* __restrict__ c
 }
 
 }  // namespace
+}  // namespace glh
 
-struct OrientHandle {
-  int device = 0, n_images = 0, n_pairs = 0, n_chunks = 0;
-  DevBuf chunks, pair_i, pair_j, xy_i, xy_j, chunk_off, inc_off, inc, rot, partial, out;
-  StageEvents<OR_TIMES + 1> ev;
+struct glh_orient : glh::DeviceObject {
+  int n_images = 0, n_pairs = 0, n_chunks = 0;
+  glh::DevBuf chunks, pair_i, pair_j, xy_i, xy_j, chunk_off, inc_off, inc, rot, partial, out;
+  glh::StageEvents<glh::OR_TIMES + 1> ev;
   std::vector<double> stage;  // host side of `rot` ([n][9] R, then [n][27] Rprime) and of `out`
 };
 
-static int orient_fill(OrientHandle* h, int device, int n_images, int n_pairs, const int32_t* pair_i, const int32_t* pair_j,
+namespace glh {
+
+static int orient_fill(glh_orient* h, int n_images, int n_pairs, const int32_t* pair_i, const int32_t* pair_j,
                        const int64_t* pair_offset, const double* xy_i, const double* xy_j) {
-  h->device = device, h->n_images = n_images, h->n_pairs = n_pairs;
+  h->n_images = n_images, h->n_pairs = n_pairs;
   std::vector<OrChunk> chunks;
   std::vector<int32_t> chunk_off(n_pairs + 1, 0), inc_off(n_images + 1, 0);
   for (int p = 0; p < n_pairs; ++p) {
@@ -188,7 +190,6 @@ static int orient_fill(OrientHandle* h, int device, int n_images, int n_pairs, c
   }
   h->n_chunks = (int)chunks.size();
   const size_t N = (size_t)pair_offset[n_pairs];
-  HIPCHK(hipSetDevice(device));
   CHK(h->ev.create());
   if (chunks.empty()) chunks.push_back(OrChunk{0, 0, 0});  // (nothing is copied from a null pointer; n_chunks stays 0)
   const double none[2] = {0.0, 0.0};
@@ -210,23 +211,17 @@ static int orient_fill(OrientHandle* h, int device, int n_images, int n_pairs, c
 }
 
 int orient_create(int device, int n_images, int n_pairs, const int32_t* pair_i, const int32_t* pair_j,
-                  const int64_t* pair_offset, const double* xy_i, const double* xy_j, OrientHandle** out) {
-  OrientHandle* h = new (std::nothrow) OrientHandle;
-  if (!h) return fail(GLH_E_NOMEM, "orient: no memory for a handle");
-  const int rc = orient_fill(h, device, n_images, n_pairs, pair_i, pair_j, pair_offset, xy_i, xy_j);
-  if (rc != GLH_OK) {
-    delete h;
-    return rc;
-  }
-  *out = h;
-  return GLH_OK;
+                  const int64_t* pair_offset, const double* xy_i, const double* xy_j, glh_orient** out) {
+  return create_object("orient", device, out, [&](glh_orient* h) {
+    return orient_fill(h, n_images, n_pairs, pair_i, pair_j, pair_offset, xy_i, xy_j);
+  });
 }
 
-int orient_eval(OrientHandle* h, const double* R, const double* Rprime, double* objective, double* gradient,
+int orient_eval(glh_orient* h, const double* R, const double* Rprime, double* objective, double* gradient,
                 double* times_ms) {
   const size_t n = (size_t)h->n_images;
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernels)
+  CHK(h->use());
+  hipStream_t s = h->stream;
   for (size_t k = 0; k < 9 * n; ++k) h->stage[k] = R[k];
   for (size_t k = 0; k < 27 * n; ++k) h->stage[9 * n + k] = Rprime[k];
   CHK(h->ev.record(0, s));
@@ -253,11 +248,7 @@ int orient_eval(OrientHandle* h, const double* R, const double* Rprime, double* 
   return GLH_OK;
 }
 
-void orient_destroy(OrientHandle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  delete h;
-}
+void orient_destroy(glh_orient* h) { destroy_object(h); }
 
 int uv_to_xy_run(int device, const CamDev& cam, const double* uv, int n, double* xy) {
   HIPCHK(hipSetDevice(device));

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+struct glh_sift;  // the C ABI's handle: the pyramid and the lists of one device (glh_sift.hip)
+
 namespace glh {
 
 constexpr int SF_TIMES = 7;         // entries of times_ms (include/glimpse_hip.h)
@@ -24,15 +26,13 @@ struct SiftParams {
   const double* table[SF_MAX_LAYERS + 3];  // [2 r + 1] each, host
 };
 
-struct SiftHandle;  // the pyramid and the lists of one device (glh_sift.hip)
-
 // The arguments have been checked (glimpse_hip.hip).  A GLH_* status, with the message left for glh_last_error() on
 // failure (glh_stage.h: fail).
-int sift_create(int device, SiftHandle** out);
-int sift_detect(SiftHandle* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n, double* times_ms);
-void sift_counts(const SiftHandle* h, int32_t* out);  // octaves, candidates, keypoints, S, doubled width, doubled height
-int sift_read(const SiftHandle* h, double* keypoints, uint8_t* descriptors);
-int sift_layer(SiftHandle* h, int kind, int octave, int index, void* out);
-void sift_destroy(SiftHandle* h);
+int sift_create(int device, glh_sift** out);
+int sift_detect(glh_sift* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n, double* times_ms);
+void sift_counts(const glh_sift* h, int32_t* out);  // octaves, candidates, keypoints, S, doubled width, doubled height
+int sift_read(const glh_sift* h, double* keypoints, uint8_t* descriptors);
+int sift_layer(glh_sift* h, int kind, int octave, int index, void* out);
+void sift_destroy(glh_sift* h);
 
 }  // namespace glh

@@ -523,44 +523,18 @@ __global__ void __launch_bounds__(SF_TB) k_sf_iota(uint32_t* out, unsigned n) {
   if (i < n) out[i] = i;
 }
 
-// a device buffer that keeps its memory between calls and grows when asked for more
-struct Grow {
-  void* p = nullptr;
-  size_t cap = 0;
-  ~Grow() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  int reserve(size_t bytes) {
-    if (bytes <= cap) return GLH_OK;
-    release();
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) {
-      (void)hipGetLastError();
-      p = nullptr;
-      return fail(GLH_E_NOMEM, "sift: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-    }
-    cap = bytes;
-    return GLH_OK;
-  }
-  template <typename T>
-  T* as() const {
-    return static_cast<T*>(p);
-  }
-};
-
 unsigned blocks_for(size_t n) { return (unsigned)((n + SF_TB - 1) / SF_TB); }
 
 }  // namespace
+}  // namespace glh
 
-struct SiftHandle {
-  int device = 0;
-  Grow image, pyramid, temp, tables, keys_a, keys_b, refined, kps, kp_keys, kp_keys_b, order_a, order_b, sorted, desc, counters,
-      sort_temp;
-  SfPyr pyr{};
-  size_t g_off[SF_MAX_OCTAVES] = {}, d_off[SF_MAX_OCTAVES] = {};
+struct glh_sift : glh::DeviceObject {
+  // (they keep their memory between the images of one size)
+  glh::GrowBuf image, pyramid, temp, tables, keys_a, keys_b, refined, kps, kp_keys, kp_keys_b, order_a, order_b, sorted, desc,
+      counters, sort_temp;
+  glh::StageEvents<glh::SF_TIMES + 1> ev;
+  glh::SfPyr pyr{};
+  size_t g_off[glh::SF_MAX_OCTAVES] = {}, d_off[glh::SF_MAX_OCTAVES] = {};
   int w = 0, h = 0;  // of the last image
   int n_cand = 0, n_kp = 0;
   bool have = false;  // a detection has been made
@@ -569,26 +543,15 @@ struct SiftHandle {
   std::vector<int32_t> host_cells;
 };
 
-int sift_create(int device, SiftHandle** out) {
-  SiftHandle* h = new (std::nothrow) SiftHandle;
-  if (!h) return fail(GLH_E_NOMEM, "sift: no memory for a handle");
-  h->device = device;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) {
-    delete h;
-    return fail(GLH_E_HIP, "hipSetDevice(%d) failed: %s (%s:%d)", device, hipGetErrorString(e), __FILE__, __LINE__);
-  }
-  *out = h;
-  return GLH_OK;
+namespace glh {
+
+int sift_create(int device, glh_sift** out) {
+  return create_object("sift", device, out, [](glh_sift* h) { return h->ev.create(); });
 }
 
-void sift_destroy(SiftHandle* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  delete h;
-}
+void sift_destroy(glh_sift* h) { destroy_object(h); }
 
-void sift_counts(const SiftHandle* h, int32_t* out) {
+void sift_counts(const glh_sift* h, int32_t* out) {
   out[0] = h->have ? h->pyr.n_oct : 0;
   out[1] = h->have ? h->n_cand : 0;
   out[2] = h->have ? h->n_kp : 0;
@@ -598,7 +561,7 @@ void sift_counts(const SiftHandle* h, int32_t* out) {
 }
 
 // one blur of `in` into `out` through the handle's temporary layer
-static int sift_blur(SiftHandle* h, const float* in, float* out, const double* table, int r, int W, int H, hipStream_t s) {
+static int sift_blur(glh_sift* h, const float* in, float* out, const double* table, int r, int W, int H, hipStream_t s) {
   const size_t n = (size_t)W * H, lds = (size_t)(r + 1) * 8;
   hipLaunchKernelGGL(k_sf_blur, dim3(blocks_for(n)), dim3(SF_TB), lds, s, in, h->temp.as<float>(), table, r, W, H, 0);
   hipLaunchKernelGGL(k_sf_blur, dim3(blocks_for(n)), dim3(SF_TB), lds, s, (const float*)h->temp.as<float>(), out, table, r, W,
@@ -607,12 +570,12 @@ static int sift_blur(SiftHandle* h, const float* in, float* out, const double* t
   return GLH_OK;
 }
 
-static int sift_detect_run(SiftHandle* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n_out,
+static int sift_detect_run(glh_sift* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n_out,
                            double* times_ms);
-static int sift_layer_run(SiftHandle* h, int kind, int octave, int index, void* out);
+static int sift_layer_run(glh_sift* h, int kind, int octave, int index, void* out);
 
 // (the host lists are std::vectors: an allocation that fails there is reported like one that fails on the device)
-int sift_detect(SiftHandle* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n_out, double* times_ms) {
+int sift_detect(glh_sift* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n_out, double* times_ms) {
   try {
     return sift_detect_run(h, image, w, h_px, p, n_out, times_ms);
   } catch (const std::bad_alloc&) {
@@ -621,7 +584,7 @@ int sift_detect(SiftHandle* h, const uint8_t* image, int w, int h_px, const Sift
   }
 }
 
-int sift_layer(SiftHandle* h, int kind, int octave, int index, void* out) {
+int sift_layer(glh_sift* h, int kind, int octave, int index, void* out) {
   try {
     return sift_layer_run(h, kind, octave, index, out);
   } catch (const std::bad_alloc&) {
@@ -629,12 +592,11 @@ int sift_layer(SiftHandle* h, int kind, int octave, int index, void* out) {
   }
 }
 
-static int sift_detect_run(SiftHandle* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n_out,
+static int sift_detect_run(glh_sift* h, const uint8_t* image, int w, int h_px, const SiftParams& p, int* n_out,
                            double* times_ms) {
-  HIPCHK(hipSetDevice(h->device));
-  hipStream_t s = nullptr;
-  StageEvents<SF_TIMES + 1> ev;
-  CHK(ev.create());
+  CHK(h->use());
+  hipStream_t s = h->stream;
+  StageEvents<SF_TIMES + 1>& ev = h->ev;
   h->have = false;
   const int S = p.S;
   // the octaves: while the smaller side holds 12 cells
@@ -817,7 +779,7 @@ static int sift_detect_run(SiftHandle* h, const uint8_t* image, int w, int h_px,
   return GLH_OK;
 }
 
-int sift_read(const SiftHandle* h, double* keypoints, uint8_t* descriptors) {
+int sift_read(const glh_sift* h, double* keypoints, uint8_t* descriptors) {
   if (!h->have) return fail(GLH_E_INVALID, "sift: nothing has been detected on this handle");
   if (h->n_kp) {
     memcpy(keypoints, h->host_kp.data(), h->host_kp.size() * 8);
@@ -826,9 +788,9 @@ int sift_read(const SiftHandle* h, double* keypoints, uint8_t* descriptors) {
   return GLH_OK;
 }
 
-static int sift_layer_run(SiftHandle* h, int kind, int octave, int index, void* out) {
+static int sift_layer_run(glh_sift* h, int kind, int octave, int index, void* out) {
   if (!h->have) return fail(GLH_E_INVALID, "sift: nothing has been detected on this handle");
-  HIPCHK(hipSetDevice(h->device));
+  CHK(h->use());
   const SfPyr& pyr = h->pyr;
   if (kind == GLH_SIFT_GAUSS || kind == GLH_SIFT_DOG) {
     const int layers = kind == GLH_SIFT_GAUSS ? pyr.S + 3 : pyr.S + 2;

@@ -1,10 +1,14 @@
 // glh_stage.h -- the host scaffold of a device stage: what glimpse_hip.hip (the C ABI) and the stage files
 // (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_filters.hip, glh_terrain.hip, glh_orient.hip, glh_calib.hip, glh_match.hip, glh_sift.hip) share to
-// report an error, to own device memory and to time their phases.  Host-only.
+// report an error, to own device memory and to time their phases.  The four handle-based objects (glh_orient, glh_calib,
+// glh_match, glh_sift) also share what a handle is made of: a buffer that grows (GrowBuf), the device and the stream
+// (DeviceObject) and how a handle comes and goes (create_object, destroy_object).  Host-only.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <stddef.h>
+
+#include <new>
 
 #include "../../include/glimpse_hip.h"
 
@@ -16,13 +20,15 @@ int fail(int code, const char* fmt, ...);
 
 }  // namespace glh
 
-#define HIPCHK(expr)                                                                         \
-  do {                                                                                       \
-    hipError_t e_ = (expr);                                                                  \
-    if (e_ != hipSuccess)                                                                    \
-      return fail(GLH_E_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
-                  __LINE__);                                                                 \
+// (HIPCHK_AT: the same report made on behalf of a caller, whose file and line it names)
+#define HIPCHK_AT(call, expr, file, line)                                                            \
+  do {                                                                                               \
+    hipError_t e_ = (expr);                                                                          \
+    if (e_ != hipSuccess)                                                                            \
+      return fail(GLH_E_HIP, "%s failed: %s (%s:%d)", call, hipGetErrorString(e_), file, line);      \
   } while (0)
+
+#define HIPCHK(expr) HIPCHK_AT(#expr, expr, __FILE__, __LINE__)
 
 #define CHK(expr)          \
   do {                     \
@@ -61,6 +67,61 @@ struct DevBuf {
     return GLH_OK;
   }
 };
+
+// A device buffer that keeps its memory between calls and is replaced by a larger one when more is asked for.  After a
+// reserve that succeeded p is never null (0 bytes get DevBuf::alloc's 8), so it can be handed to a library for which a
+// null pointer means something else (rocprim's scratch argument).
+struct GrowBuf : DevBuf {
+  size_t cap = 0;  // the bytes last asked for
+  int reserve(size_t bytes) {
+    if (bytes <= cap && p) return GLH_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr, cap = 0;
+    CHK(alloc(bytes));
+    cap = bytes;
+    return GLH_OK;
+  }
+};
+
+// What the handle of every device object starts with.
+struct DeviceObject {
+  int device = 0;
+  // The null stream: every copy an object makes is ordered with its kernels.
+  static constexpr hipStream_t stream = nullptr;
+  // Makes the device current for the calling thread; a failure names the caller's line (a method of the object's file).
+  int use(const char* file = __builtin_FILE(), int line = __builtin_LINE()) const {
+    const hipError_t e = hipSetDevice(device);
+    if (e != hipSuccess) (void)hipGetLastError();  // (the error is sticky: the next launch check would report it again)
+    HIPCHK_AT("hipSetDevice(device)", e, file, line);
+    return GLH_OK;
+  }
+};
+
+// X_create: a handle H (a DeviceObject) of `who` on `device`, made current and then filled by fill(h); *out gets it only
+// when all of that succeeded.
+template <typename H, typename Fill>
+int create_object(const char* who, int device, H** out, Fill fill, const char* file = __builtin_FILE(),
+                  int line = __builtin_LINE()) {
+  H* h = new (std::nothrow) H;
+  if (!h) return fail(GLH_E_NOMEM, "%s: no memory for a handle", who);
+  h->device = device;
+  int rc = h->use(file, line);
+  if (rc == GLH_OK) rc = fill(h);
+  if (rc != GLH_OK) {
+    delete h;  // (with what a fill that failed half way had allocated)
+    return rc;
+  }
+  *out = h;
+  return GLH_OK;
+}
+
+// X_destroy: frees the handle's device memory on its device; nothing on null.
+template <typename H>
+void destroy_object(H* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  delete h;
+}
 
 // The N events a stage records between its phases; times_ms of the C ABI is made of the spans between them.
 template <int N>

@@ -2852,11 +2852,8 @@ extern "C" int glh_stage_horizon(int dev, const void* z, int z_dtype, int nx, in
 }
 
 // optimize.ObserverCameras.fit's objective and gradient (optimize.py:2047-2072) and Camera._uv_to_xy (camera.py:1510-1519):
-// the arguments are checked here, before a device is touched; the kernels and the launches are glh_orient.hip's.
-struct glh_orient {
-  OrientHandle* h;
-};
-
+// the arguments are checked here, before a device is touched; the kernels and the launches are glh_orient.hip's, and so is
+// the handle: glh_orient, like glh_match, glh_sift and glh_calib below, is defined by its stage file.
 extern "C" int glh_orient_create(int dev, int n_images, int n_pairs, const int32_t* pair_i, const int32_t* pair_j,
                                  const int64_t* pair_offset, const double* xy_i, const double* xy_j, glh_orient** handle) {
   if (!handle) return fail(GLH_E_INVALID, "orient: null handle pointer");
@@ -2879,28 +2876,18 @@ extern "C" int glh_orient_create(int dev, int n_images, int n_pairs, const int32
     return fail(GLH_E_INVALID, "orient: %lld matches: fewer than 2^31 chunks of %d are served", (long long)pair_offset[n_pairs],
                 OR_CHUNK);
   if (pair_offset[n_pairs] > 0 && (!xy_i || !xy_j)) return fail(GLH_E_INVALID, "orient: null match coordinates");
-  glh_orient* g = new (std::nothrow) glh_orient{nullptr};
-  if (!g) return fail(GLH_E_NOMEM, "orient: no memory for a handle");
-  const int rc = orient_create(dev, n_images, n_pairs, pair_i, pair_j, pair_offset, xy_i, xy_j, &g->h);
-  if (rc != GLH_OK) {
-    delete g;
-    return rc;
-  }
-  *handle = g;
-  return GLH_OK;
+  return orient_create(dev, n_images, n_pairs, pair_i, pair_j, pair_offset, xy_i, xy_j, handle);
 }
 
 extern "C" int glh_orient_eval(glh_orient* handle, const double* R, const double* Rprime, double* objective, double* gradient,
                                double* times_ms) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "orient: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "orient: null handle");
   if (!R || !Rprime || !objective || !gradient) return fail(GLH_E_INVALID, "orient: null argument");
-  return orient_eval(handle->h, R, Rprime, objective, gradient, times_ms);
+  return orient_eval(handle, R, Rprime, objective, gradient, times_ms);
 }
 
 extern "C" int glh_orient_destroy(glh_orient* handle) {
-  if (!handle) return GLH_OK;
-  orient_destroy(handle->h);
-  delete handle;
+  orient_destroy(handle);  // (nothing on null)
   return GLH_OK;
 }
 
@@ -2914,27 +2901,15 @@ extern "C" int glh_stage_uv_to_xy(int dev, const double* cam, const double* uv, 
 
 // optimize.match_keypoints' nearest-neighbour search (optimize.py:2234-2309): the arguments are checked here, before a
 // device is touched; the kernels and the launches are glh_match.hip's.
-struct glh_match {
-  MatchHandle* h;
-};
-
 extern "C" int glh_match_create(int dev, glh_match** handle) {
   if (!handle) return fail(GLH_E_INVALID, "match: null handle pointer");
   *handle = nullptr;
   if (dev < 0) return fail(GLH_E_INVALID, "match: device %d", dev);
-  glh_match* g = new (std::nothrow) glh_match{nullptr};
-  if (!g) return fail(GLH_E_NOMEM, "match: no memory for a handle");
-  const int rc = match_create(dev, &g->h);
-  if (rc != GLH_OK) {
-    delete g;
-    return rc;
-  }
-  *handle = g;
-  return GLH_OK;
+  return match_create(dev, handle);
 }
 
 extern "C" int glh_match_put(glh_match* handle, int slot, int kind, int n, int dim, const void* data) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "match: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "match: null handle");
   if (slot < 0) return fail(GLH_E_INVALID, "match: slot %d", slot);
   if (kind != GLH_MATCH_U8 && kind != GLH_MATCH_F32) return fail(GLH_E_INVALID, "match: unknown kind %d", kind);
   if (n == 0) return fail(GLH_E_INVALID, "match: a set of 0 rows (n == 0) cannot be searched");
@@ -2945,61 +2920,47 @@ extern "C" int glh_match_put(glh_match* handle, int slot, int kind, int n, int d
   if ((int64_t)n * ((dim + 31) / 32 * 32) > MT_MAX_ELEMS)
     return fail(GLH_E_INVALID, "match: %d rows of %d elements: at most 2^35 padded elements a set are served", n, dim);
   if (!data) return fail(GLH_E_INVALID, "match: null data");
-  return match_put(handle->h, slot, kind, n, dim, data);
+  return match_put(handle, slot, kind, n, dim, data);
 }
 
 extern "C" int glh_match_drop(glh_match* handle, int slot) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "match: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "match: null handle");
   MatchSetInfo s;
-  if (!match_info(handle->h, slot, &s)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot);
-  match_drop(handle->h, slot);
+  if (!match_info(handle, slot, &s)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot);
+  match_drop(handle, slot);
   return GLH_OK;
 }
 
 extern "C" int glh_match_knn2(glh_match* handle, int slot_q, int slot_t, int32_t* idx, float* d2, double* times_ms) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "match: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "match: null handle");
   if (!idx || !d2) return fail(GLH_E_INVALID, "match: null argument");
   MatchSetInfo q, t;
-  if (!match_info(handle->h, slot_q, &q)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot_q);
-  if (!match_info(handle->h, slot_t, &t)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot_t);
+  if (!match_info(handle, slot_q, &q)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot_q);
+  if (!match_info(handle, slot_t, &t)) return fail(GLH_E_INVALID, "match: unknown slot %d", slot_t);
   if (q.kind != t.kind)
     return fail(GLH_E_INVALID, "match: mixed kinds: slot %d is %s, slot %d is %s", slot_q, q.kind == GLH_MATCH_U8 ? "uint8" : "float32",
                 slot_t, t.kind == GLH_MATCH_U8 ? "uint8" : "float32");
   if (q.dim != t.dim) return fail(GLH_E_INVALID, "match: dim mismatch: slot %d has %d, slot %d has %d", slot_q, q.dim, slot_t, t.dim);
-  return match_knn2(handle->h, slot_q, slot_t, idx, d2, times_ms);
+  return match_knn2(handle, slot_q, slot_t, idx, d2, times_ms);
 }
 
 extern "C" int glh_match_destroy(glh_match* handle) {
-  if (!handle) return GLH_OK;
-  match_destroy(handle->h);
-  delete handle;
+  match_destroy(handle);  // (nothing on null)
   return GLH_OK;
 }
 
 // optimize.SIFT (INPUTS.md, "SIFT: the rule"): the arguments are checked here, before a device is touched; the kernels and
 // the launches are glh_sift.hip's.
-struct glh_sift {
-  SiftHandle* h;
-};
-
 extern "C" int glh_sift_create(int dev, glh_sift** handle) {
   if (!handle) return fail(GLH_E_INVALID, "sift: null handle pointer");
   *handle = nullptr;
   if (dev < 0) return fail(GLH_E_INVALID, "sift: device %d", dev);
-  glh_sift* g = new (std::nothrow) glh_sift{nullptr};
-  if (!g) return fail(GLH_E_NOMEM, "sift: no memory for a handle");
-  const int rc = sift_create(dev, &g->h);
-  if (rc != GLH_OK) {
-    delete g;
-    return rc;
-  }
-  *handle = g;
-  return GLH_OK;
+  return sift_create(dev, handle);
 }
 
 extern "C" int glh_sift_detect(glh_sift* handle, const uint8_t* image, int w, int h, const double* params, int* n,
                                double* times_ms) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "sift: null handle");
   if (!image || !params || !n) return fail(GLH_E_INVALID, "sift: null argument");
   if (w < 1 || h < 1 || w > SF_MAX_SIDE || h > SF_MAX_SIDE)
     return fail(GLH_E_INVALID, "sift: an image of %d x %d: sides of 1 .. 2^23 are served", w, h);
@@ -3024,44 +2985,35 @@ extern "C" int glh_sift_detect(glh_sift* handle, const uint8_t* image, int w, in
     p.table[i] = table;
     table += 2 * p.radius[i] + 1;
   }
-  return sift_detect(handle->h, image, w, h, p, n, times_ms);
+  return sift_detect(handle, image, w, h, p, n, times_ms);
 }
 
 extern "C" int glh_sift_read(glh_sift* handle, double* keypoints, uint8_t* descriptors) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "sift: null handle");
   if (!keypoints || !descriptors) return fail(GLH_E_INVALID, "sift: null argument");
-  return sift_read(handle->h, keypoints, descriptors);
+  return sift_read(handle, keypoints, descriptors);
 }
 
 extern "C" int glh_sift_counts(glh_sift* handle, int32_t* counts) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "sift: null handle");
   if (!counts) return fail(GLH_E_INVALID, "sift: null argument");
-  sift_counts(handle->h, counts);
+  sift_counts(handle, counts);
   return GLH_OK;
 }
 
 extern "C" int glh_sift_layer(glh_sift* handle, int kind, int octave, int index, void* out) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "sift: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "sift: null handle");
   if (!out) return fail(GLH_E_INVALID, "sift: null argument");
-  return sift_layer(handle->h, kind, octave, index, out);
+  return sift_layer(handle, kind, octave, index, out);
 }
 
 extern "C" int glh_sift_destroy(glh_sift* handle) {
-  if (!handle) return GLH_OK;
-  sift_destroy(handle->h);
-  delete handle;
+  sift_destroy(handle);  // (nothing on null)
   return GLH_OK;
 }
 
 // optimize.Cameras' predictions (optimize.py:1721-1764): the arguments are checked here, before a device is touched; the
 // kernels and the launches are glh_calib.hip's.
-struct glh_calib {
-  CalibHandle* h;
-  int n_cams;
-  std::vector<int32_t> kind;
-  std::vector<int64_t> rows;  // of every control
-};
-
 extern "C" int glh_calib_create(int dev, int n_cams, int n_controls, const int32_t* kind, const int32_t* cam_a,
                                 const int32_t* cam_b, const int32_t* directions, const int64_t* row_offset, const double* obs,
                                 const double* src, glh_calib** handle) {
@@ -3087,21 +3039,11 @@ extern "C" int glh_calib_create(int dev, int n_cams, int n_controls, const int32
   if (row_offset[n_controls] >= ((int64_t)1 << 31))
     return fail(GLH_E_INVALID, "calib: %lld rows: fewer than 2^31 are served", (long long)row_offset[n_controls]);
   if (row_offset[n_controls] > 0 && (!obs || !src)) return fail(GLH_E_INVALID, "calib: null coordinates");
-  glh_calib* g = new (std::nothrow) glh_calib{nullptr, n_cams, {}, {}};
-  if (!g) return fail(GLH_E_NOMEM, "calib: no memory for a handle");
-  g->kind.assign(kind, kind + n_controls);
-  for (int c = 0; c < n_controls; ++c) g->rows.push_back(row_offset[c + 1] - row_offset[c]);
   std::vector<int32_t> b(cam_b, cam_b + n_controls);
   for (int c = 0; c < n_controls; ++c)
     if (kind[c] < GLH_CALIB_MATCHES) b[c] = cam_a[c];  // (one camera: both names are it)
   const CalibControls cc{n_cams, n_controls, kind, cam_a, b.data(), directions, row_offset, obs, src};
-  const int rc = calib_create(dev, cc, &g->h);
-  if (rc != GLH_OK) {
-    delete g;
-    return rc;
-  }
-  *handle = g;
-  return GLH_OK;
+  return calib_create(dev, cc, handle);
 }
 
 extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams, const double* rot, int n_jobs,
@@ -3109,14 +3051,15 @@ extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams,
                               const int64_t* job_seg, const int64_t* seg_vertex, const int64_t* seg_count,
                               const double* seg_par, int64_t n_vertices, const double* vertex, double* predicted,
                               double* times_ms) {
-  if (!handle || !handle->h) return fail(GLH_E_INVALID, "calib: null handle");
+  if (!handle) return fail(GLH_E_INVALID, "calib: null handle");
+  const CalibTable table = calib_table(handle);  // (the controls it was made with)
   if (n_sets < 1 || n_jobs < 0 || n_vertices < 0) return fail(GLH_E_INVALID, "calib: %d sets, %d jobs", n_sets, n_jobs);
-  if ((int64_t)n_sets * handle->n_cams >= ((int64_t)1 << 24))
-    return fail(GLH_E_INVALID, "calib: %d sets of %d cameras: fewer than 2^24 cameras in all are served", n_sets, handle->n_cams);
+  if ((int64_t)n_sets * table.n_cams >= ((int64_t)1 << 24))
+    return fail(GLH_E_INVALID, "calib: %d sets of %d cameras: fewer than 2^24 cameras in all are served", n_sets, table.n_cams);
   if (!cams || !rot || !job_seg || !seg_vertex || (n_jobs && (!job_control || !job_set || !job_side)))
     return fail(GLH_E_INVALID, "calib: null argument");
   if (job_seg[0] != 0 || seg_vertex[0] != 0) return fail(GLH_E_INVALID, "calib: the segment table does not start at 0");
-  const int n_controls = (int)handle->kind.size();
+  const int n_controls = table.n_controls;
   int64_t rows = 0, points = 0;
   for (int q = 0; q < n_jobs; ++q) {
     if (job_control[q] < 0 || job_control[q] >= n_controls || job_set[q] < 0 || job_set[q] >= n_sets || job_side[q] < 0 ||
@@ -3124,7 +3067,7 @@ extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams,
       return fail(GLH_E_INVALID, "calib: job %d is control %d of %d, set %d of %d, side %d", q, job_control[q], n_controls,
                   job_set[q], n_sets, job_side[q]);
     const int64_t n_segs = job_seg[q + 1] - job_seg[q];
-    const bool lines = handle->kind[job_control[q]] == GLH_CALIB_LINES;
+    const bool lines = table.kind[job_control[q]] == GLH_CALIB_LINES;
     if (n_segs < 0 || n_segs >= ((int64_t)1 << 31) || (lines ? n_segs < 1 : n_segs != 0))
       return fail(GLH_E_INVALID, "calib: job %d (%s) has %lld segments", q, lines ? "lines" : "not lines", (long long)n_segs);
     if (lines && job_side[q] != 0) return fail(GLH_E_INVALID, "calib: job %d (lines) has side %d", q, job_side[q]);
@@ -3138,14 +3081,14 @@ extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams,
       job_points += seg_count[k];
     }
     if (job_points >= ((int64_t)1 << 31)) return fail(GLH_E_INVALID, "calib: job %d has %lld points", q, (long long)job_points);
-    rows += handle->rows[job_control[q]];
+    rows += table.row_offset[job_control[q] + 1] - table.row_offset[job_control[q]];
     points += job_points;
   }
   if (rows >= ((int64_t)1 << 31) || points >= ((int64_t)1 << 31) || n_vertices >= ((int64_t)1 << 31))
     return fail(GLH_E_INVALID, "calib: %lld rows, %lld points, %lld vertices: fewer than 2^31 of each are served", (long long)rows,
                 (long long)points, (long long)n_vertices);
   if (rows > 0 && !predicted) return fail(GLH_E_INVALID, "calib: null output");
-  const size_t n_cam_sets = (size_t)n_sets * handle->n_cams;
+  const size_t n_cam_sets = (size_t)n_sets * table.n_cams;
   std::vector<CamDev> cd(n_cam_sets);
   for (size_t i = 0; i < n_cam_sets; ++i) {
     if (cams[i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "calib: camera %zu is a raster grid", i);
@@ -3153,13 +3096,11 @@ extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams,
   }
   const CalibEval e{n_sets, cd.data(), rot, n_jobs, job_control, job_set, job_side, job_seg, seg_vertex, seg_count, seg_par,
                     vertex, predicted, times_ms};
-  return calib_eval(handle->h, e);
+  return calib_eval(handle, e);
 }
 
 extern "C" int glh_calib_destroy(glh_calib* handle) {
-  if (!handle) return GLH_OK;
-  calib_destroy(handle->h);
-  delete handle;
+  calib_destroy(handle);  // (nothing on null)
   return GLH_OK;
 }
 
