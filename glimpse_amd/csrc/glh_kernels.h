@@ -242,14 +242,6 @@ __device__ __forceinline__ double pt_wave_sum63(double v) {
   PT_DPP_LADDER(pt_add, true)
   return v;
 }
-__device__ __forceinline__ double pt_wave_min63(double v) {
-  PT_DPP_LADDER(fmin, false)
-  return v;
-}
-__device__ __forceinline__ double pt_wave_max63(double v) {
-  PT_DPP_LADDER(fmax, false)
-  return v;
-}
 
 // inclusive scans of 32-bit values (lanes without a source read 0: the identity of + and of an unsigned max)
 template <int CTRL, int ROW_MASK, int BANK_MASK>
@@ -290,6 +282,30 @@ __device__ __forceinline__ double group_sum_dpp(double v, int G) {
   if (G > 8) v += pt_dpp_mov<0x140, 0xf, 0xf, false>(v);  // row_mirror
   return v;
 }
+
+// The lane operations of wave_max4_joint (glh_math.h) on a wave's registers: v_permlane32_swap / v_permlane16_swap
+// (gfx950) exchange half-waves / rows of two registers in place -- one instruction per 32-bit half, no select -- and the
+// in-row exchanges are the DPP moves of group_sum_dpp (every lane has a source: nothing is filled, and with the fill
+// declared the move needs no copy of the old value first).
+struct PtWaveLanes {
+  static __device__ __forceinline__ void swap32(double& a, double& b) {
+    const auto lo = __builtin_amdgcn_permlane32_swap((uint32_t)__double2loint(a), (uint32_t)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane32_swap((uint32_t)__double2hiint(a), (uint32_t)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+  }
+  static __device__ __forceinline__ void swap16(double& a, double& b) {
+    const auto lo = __builtin_amdgcn_permlane16_swap((uint32_t)__double2loint(a), (uint32_t)__double2loint(b), false, false);
+    const auto hi = __builtin_amdgcn_permlane16_swap((uint32_t)__double2hiint(a), (uint32_t)__double2hiint(b), false, false);
+    a = __hiloint2double((int)hi[0], (int)lo[0]);
+    b = __hiloint2double((int)hi[1], (int)lo[1]);
+  }
+  static __device__ __forceinline__ double xor1(double v) { return pt_dpp_mov<0xb1, 0xf, 0xf, true>(v); }
+  static __device__ __forceinline__ double xor2(double v) { return pt_dpp_mov<0x4e, 0xf, 0xf, true>(v); }
+  static __device__ __forceinline__ double half_mirror(double v) { return pt_dpp_mov<0x141, 0xf, 0xf, true>(v); }
+  static __device__ __forceinline__ double mirror(double v) { return pt_dpp_mov<0x140, 0xf, 0xf, true>(v); }
+  static __device__ __forceinline__ double max(double a, double b) { return max_nn(a, b); }
+};
 
 // Motion.evolve_particles for one particle p[6], tau2 = tau * tau, n = the step's three normals
 // (randn(n,3); the tangent models draw randn(n,2) then randn(n)):

@@ -195,6 +195,27 @@ GLH_HD double max_nn(double a, double b) {
 #endif
 }
 
+// The maxima of FOUR per-lane values over a 64-lane wave in ONE halving butterfly: the first two exchanges combine lanes
+// and cut the four live values to one (half-wave swap: lanes 32..63 of one value against lanes 0..31 of another, then
+// the same by rows of 16 lanes), four in-row exchanges finish it.  Every lane of row k (lanes 16 k .. 16 k + 15) ends with
+// the maximum of value k over the wave.  Minima go through it negated: min(x) == -max(-x) exactly for non-NaN doubles.
+// V: the 64 lanes of one value (a double on the device; tests/hostcheck runs the same schedule on arrays); X supplies the
+// lane operations: swap32 / swap16 (a, b) exchange lanes 32..63 / rows 1 and 3 of a with lanes 0..31 / rows 0 and 2 of b,
+// xor1 / xor2 / half_mirror / mirror (v) give every lane the value of lane i ^ 1, i ^ 2, 7 - i and 15 - i of its row.
+template <typename V, typename X>
+GLH_HD V wave_max4_joint(V a, V b, V c, V d, const X& x) {
+  x.swap32(a, c);
+  x.swap32(b, d);
+  V p = x.max(a, c), q = x.max(b, d);  // lanes 0..31: a | b over {i, i + 32}; lanes 32..63: c | d
+  x.swap16(p, q);
+  V r = x.max(p, q);  // row 0: a, row 1: b, row 2: c, row 3: d -- sixteen partial maxima each
+  r = x.max(r, x.xor1(r));
+  r = x.max(r, x.xor2(r));
+  r = x.max(r, x.half_mirror(r));  // (the other half of the row holds that half's maximum in all its lanes)
+  r = x.max(r, x.mirror(r));
+  return r;
+}
+
 // project_f in fast arithmetic (perspective cameras and raster grids alike).
 GLH_HD void project_fast(const CamDev& c, uint32_t f, double x, double y, double z, double& u, double& v) {
   if (f & CAM_F_GRID) {

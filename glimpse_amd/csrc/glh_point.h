@@ -1164,13 +1164,13 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
 #pragma unroll
     for (int o = 0; o < NOBS; ++o) {
       if (!live[o]) continue;
-      const double r0 = pt_wave_min63(mn[o][0]), r1 = pt_wave_min63(mn[o][1]);
-      const double r2m = pt_wave_max63(mx[o][0]), r3 = pt_wave_max63(mx[o][1]);
+      // the four extrema in one butterfly (glh_math.h: wave_max4_joint), the minima negated: row k of the wave ends with
+      // value k, and the first lane of each row stores it
+      const double e = wave_max4_joint(-mn[o][0], -mn[o][1], mx[o][0], mx[o][1], PtWaveLanes{});
       const double r4 = __any(nanf[o]) ? 1.0 : 0.0;
-      if (lane == WAVE - 1) {
-        double* b = bred[o][wave];
-        b[0] = r0; b[1] = r1; b[2] = r2m; b[3] = r3; b[4] = r4;
-      }
+      double* b = bred[o][wave];
+      if ((lane & 15) == 0) b[lane >> 4] = lane < 32 ? -e : e;
+      if (lane == WAVE - 1) b[4] = r4;
     }
     __syncthreads();
     PT_STAMP(18);
