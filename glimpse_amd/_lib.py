@@ -142,6 +142,8 @@ SIGNATURES = {
     "glh_stage_project": (_I, [_I, _P, _P, _I, _P]),
     "glh_stage_project_directions": (_I, [_I, _P, _P, _I, _P]),
     "glh_stage_project_depth": (_I, [_I, _P, _P, _I, _I, _P, _P]),
+    "glh_stage_project_fast": (_I, [_I, _P, _P, _I, _I, _I, _P]),
+    "glh_stage_fast_math": (_I, [_I, _I, _P, _I, _P]),
     "glh_stage_unproject": (_I, [_I, _P, _P, _I, _P, _I, _I, _P]),
     "glh_stage_reproject": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P]),
     "glh_stage_template": (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
@@ -737,6 +739,39 @@ def stage_project_depth(cam, xyz, directions=False, device_id=0):
     check(load().glh_stage_project_depth(device_id, _ptr(cam), _ptr(xyz), len(xyz), int(bool(directions)), _ptr(uv),
                                          _ptr(depth)))
     return uv, depth
+
+
+def stage_project_fast(cam, xyz, directions=False, simple=False, device_id=0):
+    """The projection of GLH_MATH_FAST on explicit points: project_fast, or project_simple_fast with simple=True."""
+    cam = _arr(cam, np.float64, (CAM_LEN,))
+    xyz = _arr(xyz, np.float64)
+    uv = np.empty((len(xyz), 2))
+    check(load().glh_stage_project_fast(device_id, _ptr(cam), _ptr(xyz), len(xyz), int(bool(directions)), int(bool(simple)),
+                                        _ptr(uv)))
+    return uv
+
+
+# glh_stage_fast_math: the ops (GLH_FM_* of include/glimpse_hip.h) and how many columns each reads
+FM_ARGS = 8
+FM_OPS = {"RCP": (0, 1), "SQRT": (1, 1), "EXP": (2, 1), "WEIGHT": (3, 1), "MIN_NN": (4, 2), "MAX_NN": (5, 2),
+          "COUNT_FRACTION": (6, 2), "COUNT_LE": (7, 4), "BILINEAR": (8, 6)}
+
+
+def stage_fast_math(op, *columns, device_id=0):
+    """One primitive of GLH_MATH_FAST on the device, one thread per row: `columns` are the op's arguments as equally
+    long 1-D arrays (FM_OPS says how many), the result is a float64 array of that length."""
+    code, n_cols = FM_OPS[op]
+    if len(columns) != n_cols:
+        raise ValueError(f"{op} takes {n_cols} argument columns, got {len(columns)}")
+    cols = [_arr(c, np.float64) for c in columns]
+    if any(c.ndim != 1 or c.shape != cols[0].shape for c in cols):
+        raise ValueError("argument columns must be 1-D and equally long")
+    args = np.zeros((len(cols[0]), FM_ARGS))
+    for j, c in enumerate(cols):
+        args[:, j] = c
+    out = np.empty(len(args))
+    check(load().glh_stage_fast_math(device_id, code, _ptr(args), len(args), _ptr(out)))
+    return out
 
 
 def stage_unproject(cam, uv, depth=None, directions=True, device_id=0):

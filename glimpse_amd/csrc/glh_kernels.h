@@ -2775,6 +2775,48 @@ __global__ __launch_bounds__(BLK) void k_project_points(const CamDev* cam, const
 }
 #endif
 
+// Test hook: the projection in fast arithmetic (glh_stage_project_fast): project_fast with the camera's flags, or -- for
+// a camera whose flags allow it (the host has tested them against CAM_F_NOT_SIMPLE) -- project_simple_fast
+#ifndef GLH_POINT_TU  // (the fused kernel's own translation units carry none of the staged kernels)
+__global__ __launch_bounds__(BLK) void k_project_points_fast(const CamDev* cam, const double* xyz, int n, double* uv,
+                                                             int directions, int simple) {
+  const int i = blockIdx.x * BLK + threadIdx.x;
+  if (i >= n) return;
+  double u, v;
+  if (simple)
+    project_simple_fast(*cam, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], u, v);
+  else
+    project_fast(*cam, cam_flags(*cam) | (directions ? CAM_F_DIRECTIONS : 0u), xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2],
+                 u, v);
+  uv[2 * i] = u;
+  uv[2 * i + 1] = v;
+}
+
+// Test hook: one primitive of the fast arithmetic per row of explicit arguments (glh_stage_fast_math).  The functions
+// called are the ones the kernels call; the table of exp_fast is made and awaited as k_weights makes it.
+__global__ __launch_bounds__(BLK) void k_fast_math(int op, const double* args, int n, double* out) {
+  __shared__ double tab32[GLH_EXP_TAB];
+  exp_table_fill(tab32);
+  __syncthreads();
+  const int i = blockIdx.x * BLK + threadIdx.x;
+  if (i >= n) return;
+  const double* a = args + (size_t)i * GLH_FM_ARGS;
+  double r = NAN;
+  switch (op) {  // (uniform)
+    case GLH_FM_RCP: r = rcp_nr(a[0]); break;
+    case GLH_FM_SQRT: r = sqrt_nr(a[0]); break;
+    case GLH_FM_EXP: r = exp_fast(a[0], tab32); break;
+    case GLH_FM_WEIGHT: r = weight_of<true>(a[0], tab32); break;
+    case GLH_FM_MIN_NN: r = min_nn(a[0], a[1]); break;
+    case GLH_FM_MAX_NN: r = max_nn(a[0], a[1]); break;
+    case GLH_FM_COUNT_FRACTION: r = count_fraction((int)a[0], a[1], 1.0 / a[1]); break;
+    case GLH_FM_COUNT_LE: r = (double)count_le_fast(a[0], a[1], a[2], (int)a[3]); break;
+    case GLH_FM_BILINEAR: r = raster_bilinear_fast(a[0], a[1], a[2], a[3], a[4], a[5]); break;
+  }
+  out[i] = r;
+}
+#endif
+
 // Camera.uv_to_xyz on explicit points; depth null = 1, else [n] (or [1], broadcast)
 #ifndef GLH_POINT_TU  // (the fused kernel's own translation units carry none of the staged kernels)
 __global__ __launch_bounds__(BLK) void k_unproject_points(const CamDev* cam, const double* uv, int n,

@@ -144,6 +144,12 @@ struct glh_ctx {
   int pt_base = 0;  // global index of this context's point 0
   bool all_cartesian = true;  // every point is CartesianMotion (the common fused instantiation; else the general one)
   bool fast_math = false;     // GLH_MATH_FAST (glh_set_math)
+  // A dem_sigma that the fast arithmetic's reciprocal cannot take (sigma_outside_fast_domain), noticed where it was set and
+  // refused where fast arithmetic would use it (check_fast_domain): the constant of a point whose dem is a raster
+  // (glh_set_motion; fast_bad_point -1: none), a node of the dem_sigma raster (glh_set_raster; 0: none) that a point uses
+  int fast_bad_point = -1;
+  double fast_bad_const = 0.0, fast_bad_node = 0.0;
+  bool sigma_raster_used = false;
   int hp_rx = 2, hp_ry = 2;   // half sizes of the median high-pass window (glh_set_highpass; 5 x 5 by default)
   int tile_cap = 0, search_cap = 0, sse_cap = 0, ssd_blocks = 2;
   Observer obs[MAX_OBS];
@@ -867,6 +873,27 @@ static int check_raster_uniform(int nx, int ny, const double* gx, const double* 
   return GLH_OK;
 }
 
+// Fast arithmetic scales the DEM term of a gridded point by rcp_nr(2 zs^2) (glh_kernels.h: dem_log_likelihood<true>), a
+// reciprocal only where its argument is a normal double: for 2 zs^2 below 2^-1022 (|zs| < 1.06e-154, zs^2 may even
+// round to 0) or infinite (|zs| > 9.4e153) it returns NaN -- every weight of the point NaN -- where the IEEE division of
+// the exact arithmetic gives inf or 0 and the particle the floor weight (measured on the device: INPUTS.md, "Fast
+// arithmetic: the primitives").  Such a sigma is refused on the host instead of tested for in the particle loops.
+// (0 is "no term" and NaN is NaN in either arithmetic: neither is refused.)
+static bool sigma_outside_fast_domain(double zs) {
+  if (zs == 0.0 || zs != zs) return false;
+  const double s = 2.0 * (zs * zs);
+  return s < 0x1p-1022 || s > 0x1.fffffffffffffp1023;
+}
+static int check_fast_domain(const glh_ctx* c) {
+  if (!c->fast_math) return GLH_OK;
+  const char* why = "is outside the domain of fast arithmetic (GLH_MATH_FAST needs 1.06e-154 <= |dem_sigma| <= 9.4e153, or 0)";
+  if (c->fast_bad_point >= 0)
+    return fail(GLH_E_UNSUPPORTED, "point %d: dem_sigma = %g %s", c->fast_bad_point, c->fast_bad_const, why);
+  if (c->sigma_raster_used && c->fast_bad_node != 0.0)
+    return fail(GLH_E_UNSUPPORTED, "the dem_sigma raster holds %g, which %s", c->fast_bad_node, why);
+  return GLH_OK;
+}
+
 extern "C" int glh_set_raster(glh_ctx* c, int which, const double* z, int nx, int ny, const double* gx,
                               const double* gy, int sx, int sy, double xmin, double xmax, double ymin,
                               double ymax) {
@@ -881,9 +908,13 @@ extern "C" int glh_set_raster(glh_ctx* c, int which, const double* z, int nx, in
   r.hgx.clear();
   r.hgy.clear();
   c->same_grid = false;
+  if (which == GLH_RASTER_DEM_SIGMA) c->fast_bad_node = 0.0;
   if (!z) return GLH_OK;
   CHK(check_raster_args(nx, ny, gx, gy, sx, sy));
   CHK(check_raster_uniform(nx, ny, gx, gy, xmin, xmax, ymin, ymax));
+  if (which == GLH_RASTER_DEM_SIGMA)
+    for (size_t i = 0; i < (size_t)nx * ny && c->fast_bad_node == 0.0; ++i)
+      if (sigma_outside_fast_domain(z[i])) c->fast_bad_node = z[i];
   CHK(dalloc(&r.z, (size_t)nx * ny));
   CHK(dalloc(&r.gx, (size_t)nx));
   CHK(dalloc(&r.gy, (size_t)ny));
@@ -905,6 +936,8 @@ extern "C" int glh_set_motion(glh_ctx* c, const double* params) {
   if (!params) return fail(GLH_E_INVALID, "params is null");
   c->has_dem = false;
   c->all_cartesian = true;
+  c->fast_bad_point = -1;
+  c->sigma_raster_used = false;
   for (int p = 0; p < c->P; ++p) {
     const double* m = params + (size_t)p * GLH_MOTION_FULL_LEN;
     const int kind = (int)m[18];
@@ -916,6 +949,13 @@ extern "C" int glh_set_motion(glh_ctx* c, const double* params) {
     if (m[21] != 0.0 && !c->rasters[GLH_RASTER_DEM_SIGMA].z)
       return fail(GLH_E_STATE, "point %d uses a dem_sigma raster but glh_set_raster(GLH_RASTER_DEM_SIGMA) was not called", p);
     if (kind <= GLH_MOTION_CYLINDRICAL && (m[17] != 0.0 || m[21] != 0.0)) c->has_dem = true;
+    // (a constant dem_sigma beside a constant dem is scaled by an IEEE division in either arithmetic: k_weights, the fused step)
+    if (kind <= GLH_MOTION_CYLINDRICAL && m[21] != 0.0) c->sigma_raster_used = true;
+    if (kind <= GLH_MOTION_CYLINDRICAL && m[20] != 0.0 && m[21] == 0.0 && c->fast_bad_point < 0 &&
+        sigma_outside_fast_domain(m[17])) {
+      c->fast_bad_point = p;
+      c->fast_bad_const = m[17];
+    }
   }
   UPLOAD(c->motion, params, (size_t)c->P * GLH_MOTION_FULL_LEN, double);
   return GLH_OK;
@@ -1407,6 +1447,7 @@ static int update_weights_impl(glh_ctx* c, const int32_t* images, bool projected
 
 extern "C" int glh_update_weights(glh_ctx* c, const int32_t* images) {
   CHK(need_seq(c));
+  CHK(check_fast_domain(c));
   CHK(check_images(c, images));
   HIPCHK(hipSetDevice(c->cfg.device_id));
   return update_weights_impl(c, images, false);
@@ -1730,6 +1771,7 @@ extern "C" int glh_get_covariances(glh_ctx* c, int frame0, int n_frames, double*
 extern "C" int glh_step(glh_ctx* c, int frame, double tau, const int32_t* images, int rng_mode,
                         const double* normals, const double* u, uint64_t seed) {
   CHK(need_seq(c));
+  CHK(check_fast_domain(c));
   CHK(glh_set_frame(c, frame));
   CHK(check_images(c, images));
   HIPCHK(hipSetDevice(c->cfg.device_id));
@@ -1754,6 +1796,7 @@ extern "C" int glh_step(glh_ctx* c, int frame, double tau, const int32_t* images
 extern "C" int glh_track(glh_ctx* c, int n_frames, const int32_t* frames, const double* taus, const int32_t* images,
                          uint64_t seed) {
   CHK(need_seq(c));
+  CHK(check_fast_domain(c));
   if (n_frames <= 0 || !frames || !taus || !images)
     return fail(GLH_E_INVALID, "n_frames must be > 0 and the arrays non-null");
   const int O = c->cfg.n_observers;
@@ -2339,6 +2382,37 @@ extern "C" int glh_stage_project(int dev, const double* cam, const double* xyz, 
 extern "C" int glh_stage_project_directions(int dev, const double* cam, const double* xyz, int n, double* uv) {
   if (cam && cam[23] != 0.0) return fail(GLH_E_INVALID, "ray directions are a camera notion (not a raster grid)");
   return stage_project_impl(dev, cam, xyz, n, uv, 1);
+}
+
+extern "C" int glh_stage_project_fast(int dev, const double* cam, const double* xyz, int n, int directions, int simple,
+                                      double* uv) {
+  if (!cam || !xyz || !uv || n <= 0) return fail(GLH_E_INVALID, "bad argument");
+  if (directions && cam[23] != 0.0) return fail(GLH_E_INVALID, "ray directions are a camera notion (not a raster grid)");
+  CamDev cd;
+  expand_camera(cam, &cd);
+  if (simple && ((cam_flags(cd) | (directions ? CAM_F_DIRECTIONS : 0u)) & CAM_F_NOT_SIMPLE))
+    return fail(GLH_E_INVALID, "project_simple_fast does not cover this camera (CAM_F_NOT_SIMPLE)");
+  HIPCHK(hipSetDevice(dev));
+  DevBuf dc, dx, du;
+  CHK(dc.up(&cd, sizeof cd));
+  CHK(dx.up(xyz, (size_t)n * 3 * sizeof(double)));
+  CHK(du.alloc((size_t)n * 2 * sizeof(double)));
+  hipLaunchKernelGGL(k_project_points_fast, dim3((n + BLK - 1) / BLK), dim3(BLK), 0, 0, dc.as<CamDev>(), dx.as<double>(),
+                     n, du.as<double>(), directions ? 1 : 0, simple ? 1 : 0);
+  CHK(finish());
+  return du.down(uv, (size_t)n * 2 * sizeof(double));
+}
+
+extern "C" int glh_stage_fast_math(int dev, int op, const double* args, int n, double* out) {
+  if (!args || !out || n <= 0) return fail(GLH_E_INVALID, "bad argument");
+  if (op < GLH_FM_RCP || op > GLH_FM_BILINEAR) return fail(GLH_E_INVALID, "op is not one of GLH_FM_*");
+  HIPCHK(hipSetDevice(dev));
+  DevBuf da, dout;
+  CHK(da.up(args, (size_t)n * GLH_FM_ARGS * sizeof(double)));
+  CHK(dout.alloc((size_t)n * sizeof(double)));
+  hipLaunchKernelGGL(k_fast_math, dim3((n + BLK - 1) / BLK), dim3(BLK), 0, 0, op, da.as<double>(), n, dout.as<double>());
+  CHK(finish());
+  return dout.down(out, (size_t)n * sizeof(double));
 }
 
 extern "C" int glh_stage_unproject(int dev, const double* cam, const double* uv, int n, const double* depth,

@@ -176,7 +176,9 @@ class CartesianMotion(Motion):
                  vxyz_sigma=(0, 0, 0), axyz=(0, 0, 0), axyz_sigma=(0, 0, 0)):
         """motion.py:121-147.  `dem` / `dem_sigma`: numbers (constant surfaces) or `glimpse_amd.Raster`s;
         `dem_sigma=None` crashes in the reference (KeyError 'buf_xsize'), so a value is
-        required here."""
+        required here.  On the device's random streams (fast arithmetic) a non-zero `dem_sigma` of a model with a
+        gridded surface must lie in 1.06e-154 .. 9.4e153 in magnitude: the library refuses others (INPUTS.md, "Fast
+        arithmetic: the primitives")."""
         self.xy = xy
         self.time_unit = time_unit
         self.dem = _surface(dem, "dem", "CartesianMotion")

@@ -110,7 +110,12 @@ extern "C" {
                           * table exp and no normalisation pass in the systematic resampling: ~1e-13 relative on the
                           * posteriors, 10-15 % faster; meant for device-RNG runs, where no reference stream exists to be
                           * bit-exact with.  Small fitted surfaces are sampled in a per-cell power form.  Every motion
-                          * model and surface kind has it (their own evolve steps and lookups have one form only).    */
+                          * model and surface kind has it (their own evolve steps and lookups have one form only).
+                          * One limit: a non-zero dem_sigma of a point with a gridded surface (a constant beside a dem
+                          * raster, or a node of the dem_sigma raster) must have 1.06e-154 <= |dem_sigma| <= 9.4e153 --
+                          * the Newton reciprocal of 2 dem_sigma^2 is NaN outside the normal doubles, where the IEEE
+                          * division gives inf or 0; glh_update_weights, glh_step and glh_track return
+                          * GLH_E_UNSUPPORTED for such a value rather than NaN weights.                                  */
 
 typedef struct glh_ctx glh_ctx;
 
@@ -422,6 +427,32 @@ int glh_stage_project_directions(int device_id, const double* cam, const double*
  * point along the optical axis, depth [n] (also for points behind the camera, whose uv are NaN).   */
 int glh_stage_project_depth(int device_id, const double* cam, const double* xyz, int n, int directions,
                             double* uv, double* depth);
+/* The projection of GLH_MATH_FAST (csrc/glh_math.h: project_fast with the camera's flags) on explicit points, as
+ * glh_stage_project runs the exact one; directions != 0 reads xyz as ray directions (GLH_E_INVALID for a raster grid).
+ * simple != 0 runs project_simple_fast, the form the fused kernel's common instantiation compiles: GLH_E_INVALID for a
+ * camera it does not cover (a raster grid, k4..k6, tangential terms, the elevation correction) and with directions.  */
+int glh_stage_project_fast(int device_id, const double* cam, const double* xyz, int n, int directions, int simple,
+                           double* uv);
+/* One primitive of GLH_MATH_FAST (csrc/glh_math.h, csrc/glh_kernels.h) on n rows of GLH_FM_ARGS doubles, one thread per
+ * row: out [n].  Which columns an op reads:
+ *   RCP, SQRT, EXP     x                      rcp_nr, sqrt_nr; exp_fast on the table the device makes (as the weights kernel)
+ *   WEIGHT             ll                     weight_of: exp(-ll) + 1e-300
+ *   MIN_NN, MAX_NN     a, b
+ *   COUNT_FRACTION     k, n                   count_fraction(k, n, 1.0 / n), k an integer in an int's range
+ *   COUNT_LE           ck, scale, u, n        count_le_fast, the count as a double
+ *   BILINEAR           z00, z10, z01, z11, tx, ty   raster_bilinear_fast
+ * GLH_E_INVALID: a null pointer, n <= 0, another op.                                                                 */
+#define GLH_FM_ARGS 8
+#define GLH_FM_RCP 0
+#define GLH_FM_SQRT 1
+#define GLH_FM_EXP 2
+#define GLH_FM_WEIGHT 3
+#define GLH_FM_MIN_NN 4
+#define GLH_FM_MAX_NN 5
+#define GLH_FM_COUNT_FRACTION 6
+#define GLH_FM_COUNT_LE 7
+#define GLH_FM_BILINEAR 8
+int glh_stage_fast_math(int device_id, int op, const double* args, int n, double* out);
 /* Camera.uv_to_xyz (camera.py:630-663): uv [n][2] -> xyz [n][3]; depth NULL (= 1), [1] or [n];
  * undistortion by the closed form for k1 alone, else 20 Oulu iterations (camera.py:1198-1337).   */
 int glh_stage_unproject(int device_id, const double* cam, const double* uv, int n, const double* depth,
