@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "glh_math.h"
+#include "glh_point_plan.h"
 
 namespace glh {
 
@@ -313,24 +314,6 @@ inline void pairwise_plan(int n, PairwisePlan& pl) {
   while (cur <= maxl) pl.level_off[cur++] = (int)ops.size();
   // level_off[l-1] .. level_off[l] are the ops of level l (l = 1 .. maxl); level_off[0] = 0
   pl.level_off[0] = 0;
-}
-
-constexpr int PT_BLK = 512;    // threads per workgroup (TB) for N <= 5120: two workgroups share a CU
-constexpr int PT_BLK_BIG = 1024;  // TB for larger N: c[N] alone is > half the LDS, one 16-wave workgroup per CU
-
-// The launch shape of the fused step (glh_point.h) for N particles and O observers: threads per workgroup (tb) and PPT;
-// glh_point_variants.h carries every shape this returns.
-// N <= 5120: 512 threads, two workgroups per CU; larger N: 1024 threads, one per CU.  u of observer 0 in registers
-// (PPT per thread) and its v in c[] up to 10240 particles, both parked in LDS / the uv scratch beyond that and with
-// three or four observers.  Two observers keep observer 0 in registers as well (round 4: the first observer's pass is
-// peeled off the observer loop, so the registers are dead during the second observer's tile pipeline).
-inline void pt_shape(int N, int O, int* tb, int* ppt) {
-  const bool big = N > 10 * PT_BLK;
-  *tb = big ? PT_BLK_BIG : PT_BLK;
-  int p = N <= 4 * *tb ? 4 : (N <= 10 * *tb ? 10 : 0);
-  if ((big || O == 2) && p == 4) p = 10;  // (the library carries no PPT 4 of 1024 threads or of two observers)
-  if ((big && p != 10) || O >= 3) p = 0;
-  *ppt = p;
 }
 
 }  // namespace glh

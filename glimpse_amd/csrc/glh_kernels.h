@@ -12,6 +12,7 @@
 #include "../../include/glimpse_hip.h"
 #include "glh_math.h"
 #include "glh_median.h"
+#include "glh_point_plan.h"  // ssd_twp
 
 namespace glh {
 
@@ -1912,7 +1913,6 @@ struct SsdArgs {
   double* sse;                // [O][P][sse_cap]
 };
 
-__host__ __device__ __forceinline__ int ssd_twp(int tw) { return (tw + 7) & ~7; }
 // LDS row stride of the search window: >= TOW + twp + 4 and == 8 (mod 64) floats so that the
 // G row-split lanes of neighbouring strips land on distinct banks
 __host__ __device__ __forceinline__ int ssd_ld(int tw) {

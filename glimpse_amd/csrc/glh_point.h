@@ -24,13 +24,12 @@
 // the reference's public step methods) and are bit-identical on the same inputs.
 #pragma once
 #include "glh_kernels.h"
+#include "glh_point_plan.h"
 #include <type_traits>
 
 namespace glh {
 
-constexpr int PT_MAX_TILE = 63;  // largest template side the fused kernel handles (rows padded to 64 floats)
 constexpr int PT_NSTAMP = GLH_NSTAMP;
-constexpr int PT_MAX_OBS = 4;    // observers per point in the fused kernel (= MAX_OBS of the library)
 
 template <int TB>
 __device__ __forceinline__ double pt_block_sum(double v, double* red) {
@@ -167,32 +166,6 @@ struct PointArgs {
   int32_t stop_at;   // diagnostic (tools/phase_counts.sh): every workgroup returns at this stamp (-1: never)
   int32_t nleaves, nnodes, nlevels, nroots;
 };
-
-__host__ __device__ __forceinline__ int pt_align16(int x) { return (x + 15) & ~15; }
-// LDS row stride (floats) of the search tile: >= ws + 11 readable columns and == 8 (mod 32), so the
-// row-split lanes of a strip (rows g = 0..7) start in distinct 16-byte bank slots
-__host__ __device__ __forceinline__ int pt_search_ld(int ws) { return ((ws + 3 + 31) / 32) * 32 + 8; }
-// histogram | LUT of nb bins (round 4: the cumulative counts are not written out any more -- the thread that owns a bin
-// makes its LUT entry behind the scan, from registers)
-__host__ __device__ __forceinline__ int pt_hcl_bytes(int nb) { return pt_align16(nb * 4) + pt_align16(nb * 8); }
-// bytes of the arrays that always live in LDS: template tile + histogram / cumulative counts / LUT
-__host__ __device__ __forceinline__ int pt_small_bytes(int tw, int th, int nb) {
-  return pt_align16(th * ssd_twp(tw) * 4) + pt_hcl_bytes(nb);
-}
-
-// The raw-key tile of a w x h crop is stored with its 'reflect' border already in place (2 rows above and below,
-// 2 columns left, 3 right), row stride even: every 5x5 window of a PAIR of pixels is then three aligned 32-bit
-// words per row, without index arithmetic.
-__host__ __device__ __forceinline__ int pt_keys_stride(int w) { return (w + 6 + 1) & ~1; }
-__host__ __device__ __forceinline__ int pt_keys_count(int w, int h) { return (h + 4) * pt_keys_stride(w); }
-
-// dynamic LDS the moment sums of phase F are parked in: [13][512] doubles + their 13 totals
-__host__ __device__ __forceinline__ int pt_park_bytes() { return (13 * 512 + 16) * 8; }
-
-// ints of the NumPy pairwise-sum plan staged in LDS: leaf_off | leaf_len | ops | level_off | roots
-__host__ __device__ __forceinline__ int pt_plan_ints(int nleaves, int nnodes, int nlevels, int nroots) {
-  return 2 * nleaves + 3 * (nnodes - nleaves) + (nlevels + 1) + nroots;
-}
 
 // Where one observer's tile arrays live.
 struct TileWs {
@@ -1597,7 +1570,7 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
         PT_STAMP(4);
         if (!to_cells(Zl)) sample_all(Zl, std::false_type{});
       } else {
-        // (the surface stays in its HBM workspace; the scratch of a dense fit -- at most 40 x 40 doubles: fused_plan keeps
+        // (the surface stays in its HBM workspace; the scratch of a dense fit -- at most 40 x 40 doubles: pt_plan keeps
         // that much of region 2 -- at the start of region 2, where everything is dead after the SSD)
         if (dense) ws.Z1 = reinterpret_cast<double*>(r2);
         if (!linear) pt_spline_fit<TB>(ws, wo, ho);

@@ -5,8 +5,8 @@
 // glimpse_amd/build.py reads the two lists below (keep the X(...) entries on these lines).
 #pragma once
 
-// shapes: threads per workgroup, particles of observer 0 kept in registers per thread, observers -- what glh_host.h:
-// pt_shape can pick (tests/test_hostcheck.py checks it)
+// shapes: threads per workgroup, particles of observer 0 kept in registers per thread, observers -- what
+// glh_point_plan.h: pt_shape can pick, as pt_code picks the code (tests/test_hostcheck.py checks both)
 #define GLH_PT_SHAPES(X) X(512, 0, 3) X(512, 0, 4) X(512, 4, 1) X(512, 10, 1) X(512, 10, 2) X(1024, 0, 1) X(1024, 0, 2) X(1024, 0, 3) X(1024, 0, 4) X(1024, 10, 1) X(1024, 10, 2)
 // codes: SURF (0 the plain code; 1 the general code: every motion model, every frame type, constant surfaces; 2 the
 // general code with the context's rasters: gridded dem / dem_sigma, viewshed), FAST (fast arithmetic), CON (compile-time contract)

@@ -77,12 +77,6 @@ int glh::fail(int code, const char* fmt, ...) {
   return code;
 }
 
-// LDS plan of the fused kernel (glh_point.h): c[N] + region 2
-constexpr int PT_LDS_MAX = 152 * 1024;   // dynamic LDS of one workgroup (static <= 5 KB on top, 160 KB per CU)
-constexpr int PT_LDS_HALF = 75 * 1024;   // dynamic LDS that still lets two workgroups share a CU
-constexpr int PT_PATCH_LDS = 3328;       // static LDS of the raster windows (code 2: glh_point.h, PtPatches), taken off both
-static_assert(PT_PATCH_LDS >= 2 * (int)sizeof(RasterPatch), "the raster windows fit their share");
-
 // ------------------------------------------------------------------------------------------
 // stages (for the event timers)
 // ------------------------------------------------------------------------------------------
@@ -1110,6 +1104,17 @@ static int stage_normals(glh_ctx* c, const double* host, size_t count) {
   return GLH_OK;
 }
 
+// GLH_RNG_HOST: the caller's `count` normals (`shape` in the message) go to the device; anything else but the device's
+// Philox draws is refused
+static int stage_rng(glh_ctx* c, int rng_mode, const double* normals, size_t count, const char* shape) {
+  if (rng_mode == GLH_RNG_HOST) {
+    if (!normals) return fail(GLH_E_INVALID, "GLH_RNG_HOST needs normals %s", shape);
+    return stage_normals(c, normals, count);
+  }
+  if (rng_mode != GLH_RNG_PHILOX) return fail(GLH_E_INVALID, "unknown rng_mode %d", rng_mode);
+  return GLH_OK;
+}
+
 // ------------------------------------------------------------------------------------------
 // stages
 // ------------------------------------------------------------------------------------------
@@ -1117,12 +1122,7 @@ extern "C" int glh_init_particles(glh_ctx* c, int rng_mode, const double* normal
   CHK(need_seq(c));
   CHK(ensure_expanded(c));
   HIPCHK(hipSetDevice(c->cfg.device_id));
-  if (rng_mode == GLH_RNG_HOST) {
-    if (!normals) return fail(GLH_E_INVALID, "GLH_RNG_HOST needs normals [P][N][6]");
-    CHK(stage_normals(c, normals, (size_t)c->P * c->N * 6));
-  } else if (rng_mode != GLH_RNG_PHILOX) {
-    return fail(GLH_E_INVALID, "unknown rng_mode %d", rng_mode);
-  }
+  CHK(stage_rng(c, rng_mode, normals, (size_t)c->P * c->N * 6, "[P][N][6]"));
   c->moments_frame = -1;
   InitArgs a{};
   a.particles = c->particles[c->cur];
@@ -1224,12 +1224,7 @@ extern "C" int glh_evolve(glh_ctx* c, double tau, int rng_mode, const double* no
                           uint64_t step) {
   CHK(need_seq(c));
   HIPCHK(hipSetDevice(c->cfg.device_id));
-  if (rng_mode == GLH_RNG_HOST) {
-    if (!normals) return fail(GLH_E_INVALID, "GLH_RNG_HOST needs normals [P][N][3]");
-    CHK(stage_normals(c, normals, (size_t)c->P * c->N * 3));
-  } else if (rng_mode != GLH_RNG_PHILOX) {
-    return fail(GLH_E_INVALID, "unknown rng_mode %d", rng_mode);
-  }
+  CHK(stage_rng(c, rng_mode, normals, (size_t)c->P * c->N * 3, "[P][N][3]"));
   return launch_evolve_project(c, true, tau, rng_mode, seed, step, nullptr);
 }
 
@@ -1396,8 +1391,28 @@ static int launch_tile_stages(glh_ctx* c, const int32_t* images) {
   return GLH_OK;
 }
 
-static int cell_cap(const glh_ctx* c);  // (defined with the fused kernel's LDS plan below)
-static int update_weights_impl(glh_ctx* c, const int32_t* images, bool projected) {
+// (a context with rasters runs the fused step's instantiations with the raster samples)
+static bool has_rasters(const glh_ctx* c) { return c->rasters[0].z || c->rasters[1].z || c->rasters[2].z; }
+
+// What the fused step's host plan (glh_point_plan.h: pt_plan) reads of the context.
+static PtSetup pt_setup(const glh_ctx* c) {
+  PtSetup s{};
+  s.N = c->N, s.O = c->cfg.n_observers, s.tw = c->tw, s.th = c->th;
+  s.max_search_dim = c->cfg.max_search_dim, s.interp_k = c->interp_k;
+  for (int o = 0; o < s.O && o < PT_MAX_OBS; ++o) s.bits[o] = c->obs[o].bits, s.channels[o] = c->obs[o].channels;
+  s.rasters = has_rasters(c);
+  s.nleaves = c->nleaves, s.nnodes = c->nnodes, s.nlevels = c->nlevels, s.nroots = c->nroots;
+  s.small_lds = c->fused == 2;
+  return s;
+}
+
+// Does the fused kernel take the step?  `plan` is filled either way: the staged k_weights takes its cell cap from it.
+static bool fused_takes_step(const glh_ctx* c, PtPlan* plan) {
+  *plan = pt_plan(pt_setup(c));
+  return c->fused && !c->have_active && !c->keep_sse && !c->have_extra && plan->accepted;
+}
+
+static int update_weights_impl(glh_ctx* c, const int32_t* images, bool projected, const PtPlan& plan) {
   CHK(ensure_expanded(c));
   const int O = c->cfg.n_observers;
   // uv + bbox of the (already evolved) particles in the matched images
@@ -1431,7 +1446,7 @@ static int update_weights_impl(glh_ctx* c, const int32_t* images, bool projected
   wa.sse_cap = c->sse_cap;
   wa.frame = c->frame;
   wa.fast = use_fast(c);
-  wa.cell_cap = cell_cap(c);
+  wa.cell_cap = plan.cell_cap;
   wa.linear = c->interp_k == 1;
   wa.general = c->interp_k == 0;
   wa.kx = c->interp_kx;
@@ -1450,7 +1465,7 @@ extern "C" int glh_update_weights(glh_ctx* c, const int32_t* images) {
   CHK(check_fast_domain(c));
   CHK(check_images(c, images));
   HIPCHK(hipSetDevice(c->cfg.device_id));
-  return update_weights_impl(c, images, false);
+  return update_weights_impl(c, images, false, pt_plan(pt_setup(c)));
 }
 
 extern "C" int glh_resample(glh_ctx* c, int rng_mode, const double* u, uint64_t seed, uint64_t step) {
@@ -1538,66 +1553,11 @@ extern "C" int glh_record_moments(glh_ctx* c, int frame) {
   return launch_moments(c, c->moments + (size_t)frame * c->P * 12, 12, 1);
 }
 
-// LDS plan of the fused kernel (glh_point.h): c[N] + region 2.  Two workgroups per CU when the
-// state and a typical tile fit in half the LDS, otherwise one.
-
-static bool fused_plan(const glh_ctx* c, int* r2_bytes, int mode = -1) {
-  if (mode < 0) mode = c->fused;
-  const int O = c->cfg.n_observers;
-  if (O > PT_MAX_OBS || c->tw > PT_MAX_TILE || c->th > PT_MAX_TILE) return false;
-  // (other median windows and bilinear sampling run on the general instantiations: fused_step)
-  if (c->interp_k == 0) return false;  // orders other than (3, 3) / (1, 1): staged kernels
-
-  int nb = 256;
-  for (int o = 0; o < O; ++o) {
-    if (c->obs[o].channels != 1 && c->obs[o].channels != 3) return false;
-    // 16-bit and float frames: ranked in LDS / by linear buckets (glh_point.h: pt_tile_prep_wide, the float branch of
-    // the observer pass) while a tile's pixel count fits a 16-bit key; wider workspaces: staged kernels
-    if (c->obs[o].bits >= 16 && c->cfg.max_search_dim > 255) return false;
-    if (c->obs[o].channels == 3 || c->obs[o].bits >= 16) nb = 766;  // (16-bit / float: the bucket table is no larger)
-  }
-  // c[N] and, behind region 2, the pairwise-sum plan
-  const int cN = pt_align16(c->N * 8) + pt_align16(4 * pt_plan_ints(c->nleaves, c->nnodes, c->nlevels, c->nroots));
-  // phase D/E: tree nodes | clast, then (over them) three rank tables of N uint16
-  const int plan = std::max(pt_align16(c->nnodes * 8) + PT_BLK_BIG * 8, 3 * pt_align16(c->N * 2));
-  // (the big-tile path parks the scratch surface of a dense spline fit behind the template tile)
-  // (... and the scratch of a dense spline fit of the largest surface fitted that way, when that surface itself stays in its
-  // HBM workspace: glh_point.h, the last branch of the observer pass)
-  const int r2_min = std::max(plan, std::max(pt_small_bytes(c->tw, c->th, nb) + GLH_SPL_DENSE_NINV / 2 * 8,
-                                             pt_align16(GLH_SPL_DENSE_MAX * GLH_SPL_DENSE_MAX * 8)));
-  // a 48 x 48 search tile of this template in LDS (what a ~2 px cloud needs)
-  // (the template CDF lies over the search tile while the LUT is made: no bytes of its own)
-  const int typical = pt_small_bytes(c->tw, c->th, nb) + 48 * pt_search_ld(48) * 4 + pt_keys_count(48, 48) * 2;
-  // (a context with rasters runs the instantiations that keep windows of them in static LDS)
-  const int patch = c->rasters[0].z || c->rasters[1].z || c->rasters[2].z ? PT_PATCH_LDS : 0;
-  const int lds_half = PT_LDS_HALF - patch, lds_max = PT_LDS_MAX - patch;
-  int r2;
-  if (cN + std::max(r2_min, typical) <= lds_half)
-    r2 = lds_half - cN;
-  else
-    r2 = std::min(lds_max - cN, 72 * 1024);
-  if (mode == 2) r2 = r2_min;  // test hook: typical tiles no longer fit -> HBM workspaces
-  if (r2 < r2_min || cN + r2 > lds_max) return false;  // (N beyond ~10 900: the staged kernels take the step)
-  *r2_bytes = r2;
-  return true;
-}
-
-// Fast arithmetic samples small fitted surfaces in per-cell power form (glh_math.h: spline_cell_row).  The fused
-// kernel holds the cell table in region 2 and converts at most two rows per thread; the staged kernels apply the
-// same bound, so that a given surface is evaluated by the same formula on either path (bit-identical results).
-static int cell_cap(const glh_ctx* c) {
-  int r2 = 0;
-  if (!fused_plan(c, &r2, c->fused == 2 ? 2 : 1)) return 0;
-  int tb, ppt;
-  pt_shape(c->N, c->cfg.n_observers, &tb, &ppt);
-  return std::min(r2 / (GLH_CELL_LD * 8), 2 * tb / 4);
-}
-
 // The fused frame step (glh_point.h): ONE launch, one workgroup per point.
 // `pt0`, `npts`, `on`: the block of points this launch updates and the stream it is enqueued on (glh_track runs the two
 // halves of a large batch on two streams); `flip`: the last launch of the frame -- the state buffers change roles.
 static int fused_step(glh_ctx* c, int frame, double tau, const int32_t* images, int rng_mode, const double* u,
-                      uint64_t seed, int r2_bytes, int pt0 = 0, int npts = -1, hipStream_t on = nullptr,
+                      uint64_t seed, const PtPlan& plan, int pt0 = 0, int npts = -1, hipStream_t on = nullptr,
                       bool flip = true) {
   const int O = c->cfg.n_observers;
   if (npts < 0) npts = c->P;
@@ -1672,8 +1632,8 @@ static int fused_step(glh_ctx* c, int frame, double tau, const int32_t* images, 
   a.frame = frame;
   a.rng_mode = rng_mode;
   a.has_dem = c->has_dem;
-  a.r2_bytes = r2_bytes;
-  a.cell_cap = cell_cap(c);
+  a.r2_bytes = plan.r2_bytes;
+  a.cell_cap = plan.cell_cap;
   a.hp_rx = c->hp_rx;
   a.hp_ry = c->hp_ry;
   a.interp_k = c->interp_k;
@@ -1686,34 +1646,19 @@ static int fused_step(glh_ctx* c, int frame, double tau, const int32_t* images, 
   a.nroots = c->nroots;
   {
     StageTimer t(c, ST_POINT_STEP, on);
-    // (at least what phase F parks its partial sums in: every plan but fused_plan's small-LDS test hook has more)
-    const size_t lds = std::max((size_t)pt_align16(c->N * 8) + r2_bytes +
-                                    pt_align16(4 * pt_plan_ints(c->nleaves, c->nnodes, c->nlevels, c->nroots)),
-                                (size_t)pt_park_bytes());
-    const dim3 grid(npts);
-    int tb, ppt;
-    pt_shape(c->N, O, &tb, &ppt);
-    const dim3 block(tb);
-    // the general instantiation: gridded surfaces and / or motion models other than CartesianMotion
-    const bool fast = use_fast(c);
-    // ... and, in fast arithmetic, everything the common instantiation is not compiled for (glh_point.h: COMMON): it
-    // takes device Philox draws, compact input records, every observer on and unmasked, and cameras within
-    // perspective + radial numerator (project_simple_fast)
-    bool common = fast && rng_mode == GLH_RNG_PHILOX && c->compact && !c->have_mask;
-    for (int o = 0; o < O; ++o) common &= a.obs[o].on && !(a.cam_flags[o] & CAM_F_NOT_SIMPLE);
-    // (the contract is independent of the surfaces and motion models: the general code has its instantiation too)
-    bool plain = c->hp_rx == 2 && c->hp_ry == 2 && c->interp_k == 3;  // the 5 x 5 median, bicubic sampling ...
-    for (int o = 0; o < O; ++o) plain &= c->obs[o].bits == 8;            // ... of 8-bit frames
-    const bool rast = c->rasters[0].z || c->rasters[1].z || c->rasters[2].z;  // (the instantiations with the raster samples)
-    const bool surf = rast || !c->all_cartesian || (fast && !common) || !plain;
-    c->last_variant[0] = tb; c->last_variant[1] = ppt; c->last_variant[2] = O;
-    c->last_variant[3] = (fast ? 1 : 0) | (surf ? 2 : 0) | (common ? 4 : 0) | (rast ? 8 : 0);
-    // codes the library carries (glh_point_variants.h): exact / exact general / fast common / fast general / fast
-    // general under the contract
-    const void* kern = pt_kernel(tb, ppt, O, rast ? 2 : (surf ? 1 : 0), fast, surf ? common : fast);
-    if (!kern) return fail(GLH_E_STATE, "no instantiation of the fused kernel for <%d, %d, %d>", tb, ppt, O);
+    // the instantiation: the plan's launch shape, the code from what this launch is given (glh_point_plan.h: pt_code)
+    PtLaunch l{};
+    l.fast = use_fast(c), l.philox = rng_mode == GLH_RNG_PHILOX, l.compact = c->compact, l.masked = c->have_mask;
+    l.all_cartesian = c->all_cartesian;
+    l.hp_rx = c->hp_rx, l.hp_ry = c->hp_ry, l.interp_k = c->interp_k;
+    for (int o = 0; o < O; ++o) l.on[o] = a.obs[o].on, l.cam_flags[o] = a.cam_flags[o], l.bits[o] = c->obs[o].bits;
+    const PtCode code = pt_code(l, O, has_rasters(c));
+    c->last_variant[0] = plan.tb; c->last_variant[1] = plan.ppt; c->last_variant[2] = O;
+    c->last_variant[3] = code.flags;
+    const void* kern = pt_kernel(plan.tb, plan.ppt, O, code.surf, code.fast, code.con);
+    if (!kern) return fail(GLH_E_STATE, "no instantiation of the fused kernel for <%d, %d, %d>", plan.tb, plan.ppt, O);
     void* kargs[] = {(void*)&a};
-    HIPCHK(hipLaunchKernel(kern, grid, block, kargs, lds, on));
+    HIPCHK(hipLaunchKernel(kern, dim3(npts), dim3(plan.tb), kargs, plan.lds_bytes, on));
   }
   HIPCHK(hipGetLastError());
   if (flip) {
@@ -1775,18 +1720,12 @@ extern "C" int glh_step(glh_ctx* c, int frame, double tau, const int32_t* images
   CHK(glh_set_frame(c, frame));
   CHK(check_images(c, images));
   HIPCHK(hipSetDevice(c->cfg.device_id));
-  if (rng_mode == GLH_RNG_HOST) {
-    if (!normals) return fail(GLH_E_INVALID, "GLH_RNG_HOST needs normals [P][N][3]");
-    CHK(stage_normals(c, normals, (size_t)c->P * c->N * 3));
-  } else if (rng_mode != GLH_RNG_PHILOX) {
-    return fail(GLH_E_INVALID, "unknown rng_mode %d", rng_mode);
-  }
-  int r2_bytes = 0;
-  if (c->fused && !c->have_active && !c->keep_sse && !c->have_extra && fused_plan(c, &r2_bytes))
-    return fused_step(c, frame, tau, images, rng_mode, u, seed, r2_bytes);
+  CHK(stage_rng(c, rng_mode, normals, (size_t)c->P * c->N * 3, "[P][N][3]"));
+  PtPlan plan;
+  if (fused_takes_step(c, &plan)) return fused_step(c, frame, tau, images, rng_mode, u, seed, plan);
   // one pass over the particle state: evolve, NaN test, project, bbox partials
   CHK(launch_evolve_project(c, true, tau, rng_mode, seed, (uint64_t)frame, images));
-  CHK(update_weights_impl(c, images, true));
+  CHK(update_weights_impl(c, images, true, plan));
   CHK(glh_resample(c, rng_mode, u, seed, (uint64_t)frame));
   return glh_record_moments(c, frame);
 }
@@ -1810,8 +1749,8 @@ extern "C" int glh_track(glh_ctx* c, int n_frames, const int32_t* frames, const 
   // is 12 % of a frame.  The points are independent, so the batch is cut in two halves whose frame loops run on two
   // streams: while one half's launch drains, the other half's launch fills the idle compute units (C3 -6 %, C4 shard
   // -4 %; four ways: worse).  Same kernel, same per-point arithmetic: results are bit for bit those of one stream.
-  int r2_bytes = 0;
-  const bool fused_ok = c->fused && !c->have_active && !c->keep_sse && !c->have_extra && fused_plan(c, &r2_bytes);
+  PtPlan plan;
+  const bool fused_ok = fused_takes_step(c, &plan);
   // Automatic (round 5): two streams as soon as the batch has more points than the chip has compute units.  Round 4 asked
   // for two full rounds of workgroups per half; but a launch ends with its slowest point (their lifetimes spread by 30 %),
   // the halves' launches drift apart and fill each other's tails, and a batch of 1.5 rounds no longer runs a half-empty
@@ -1852,7 +1791,7 @@ extern "C" int glh_track(glh_ctx* c, int n_frames, const int32_t* frames, const 
     rc = glh_set_frame(c, frames[k]);
     for (int q = 0; q < ns && rc == GLH_OK; ++q) {
       const int p0 = (int)((int64_t)c->P * q / ns), p1 = (int)((int64_t)c->P * (q + 1) / ns);
-      rc = fused_step(c, frames[k], taus[k], images + (size_t)k * O, GLH_RNG_PHILOX, nullptr, seed, r2_bytes, p0,
+      rc = fused_step(c, frames[k], taus[k], images + (size_t)k * O, GLH_RNG_PHILOX, nullptr, seed, plan, p0,
                       p1 - p0, on[q], q == ns - 1);
     }
   }

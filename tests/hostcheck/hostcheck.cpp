@@ -1,5 +1,5 @@
 // hostcheck.cpp -- TEST-ONLY harness: compiles the `__host__ __device__` stage math of
-// glimpse_amd/csrc (glh_math.h, glh_median.h, glh_host.h) with g++ so that its logic can be
+// glimpse_amd/csrc (glh_math.h, glh_median.h, glh_host.h, glh_point_plan.h) with g++ so that its logic can be
 // checked against the oracle on a machine without a GPU.  Never loaded by glimpse_amd; the
 // product path has no CPU fallback.
 #include <cstring>
@@ -8,7 +8,9 @@
 #include "../../glimpse_amd/csrc/glh_host.h"
 #include "../../glimpse_amd/csrc/glh_math.h"
 #include "../../glimpse_amd/csrc/glh_median.h"
+#include "../../glimpse_amd/csrc/glh_point_plan.h"
 #include "../../glimpse_amd/csrc/glh_point_variants.h"
+#include "plan_sweep.h"
 
 using namespace glh;
 
@@ -274,11 +276,39 @@ void hc_raster_patch_fast(const double* z, int nx, int ny, const double* gx, con
 }
 int hc_raster_uniform(const double* g, int n, double lo, double hi) { return raster_coordinates_uniform(g, n, lo, hi) ? 1 : 0; }
 
-// the launch shape of the fused step (glh_host.h: pt_shape), and whether the library carries it (glh_point_variants.h)
+// the launch shape of the fused step (glh_point_plan.h: pt_shape), and whether the library carries it with the code
+// (surf, fast, con) (glh_point_variants.h)
 void hc_pt_shape(int n, int o, int* tb_ppt) { pt_shape(n, o, &tb_ppt[0], &tb_ppt[1]); }
-int hc_pt_shape_carried(int tb, int ppt, int nobs) {
-#define HC_PT_SHAPE_IS(TB, PPT, NOBS) || (tb == TB && ppt == PPT && nobs == NOBS)
+int hc_pt_shape_carried(int tb, int ppt, int nobs, int surf, int fast, int con) {
+#define HC_PT_IS(TB, PPT, NOBS, S, F, C) \
+  || (tb == TB && ppt == PPT && nobs == NOBS && surf == S && fast == F && con == C)
+#define HC_PT_SHAPE_IS(TB, PPT, NOBS) GLH_PT_CODES(HC_PT_IS, TB, PPT, NOBS)
   return false GLH_PT_SHAPES(HC_PT_SHAPE_IS) ? 1 : 0;
 #undef HC_PT_SHAPE_IS
+#undef HC_PT_IS
 }
+
+// the host plan of the fused step (glh_point_plan.h: pt_plan) with the pairwise-sum counts of pairwise_plan(N):
+// out = accepted, tb, ppt, r2_bytes, cell_cap, lds_bytes
+void hc_pt_plan(int N, int O, int tw, int th, int max_search_dim, int interp_k, const int* bits, const int* channels,
+                int rasters, int small_lds, int* out) {
+  const PtPlan p = pt_plan(hc_setup(N, O, tw, th, max_search_dim, interp_k, bits, channels, rasters != 0, small_lds != 0));
+  out[0] = p.accepted, out[1] = p.tb, out[2] = p.ppt, out[3] = p.r2_bytes, out[4] = p.cell_cap, out[5] = p.lds_bytes;
+}
+long hc_pt_plan_sweep(int n_max, long* accepted) { return pt_plan_sweep(n_max, accepted); }
+void hc_pt_limits(int* out) { out[0] = PT_LDS_MAX, out[1] = PT_LDS_HALF, out[2] = PT_PATCH_LDS, out[3] = pt_park_bytes(); }
+
+// the code of the instantiation a launch runs (glh_point_plan.h: pt_code): out = surf, fast, con, flags.
+// booleans: bit 0 fast arithmetic, 1 Philox draws, 2 compact input, 3 observer mask, 4 all_cartesian
+void hc_pt_code(int booleans, int hp_rx, int hp_ry, int interp_k, const int* on, const unsigned* cam_flags,
+                const int* bits, int O, int rasters, int* out) {
+  PtLaunch l{};
+  l.fast = booleans & 1, l.philox = booleans & 2, l.compact = booleans & 4, l.masked = booleans & 8;
+  l.all_cartesian = booleans & 16;
+  l.hp_rx = hp_rx, l.hp_ry = hp_ry, l.interp_k = interp_k;
+  for (int o = 0; o < O && o < PT_MAX_OBS; ++o) l.on[o] = on[o] != 0, l.cam_flags[o] = cam_flags[o], l.bits[o] = bits[o];
+  const PtCode k = pt_code(l, O, rasters != 0);
+  out[0] = k.surf, out[1] = k.fast, out[2] = k.con, out[3] = k.flags;
+}
+unsigned hc_cam_f_not_simple() { return CAM_F_NOT_SIMPLE; }
 }

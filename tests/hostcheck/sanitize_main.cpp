@@ -1,5 +1,5 @@
 // sanitize_main.cpp -- TEST-ONLY: the host-side tables and stage math of glimpse_amd/csrc (glh_host.h, glh_math.h,
-// glh_median.h: what the C ABI builds on the host before every launch, and the inline functions shared with the kernels)
+// glh_median.h, glh_point_plan.h: what the C ABI builds on the host before every launch, and the inline functions shared with the kernels)
 // exercised under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (GPU sanitizers are not available on the
 // pool).  Built and run by tests/test_hostcheck.py; never part of the product.
 #include <cmath>
@@ -12,6 +12,8 @@
 #include "../../glimpse_amd/csrc/glh_host.h"
 #include "../../glimpse_amd/csrc/glh_math.h"
 #include "../../glimpse_amd/csrc/glh_median.h"
+#include "../../glimpse_amd/csrc/glh_point_plan.h"
+#include "plan_sweep.h"
 
 using namespace glh;
 
@@ -40,6 +42,12 @@ int main() {
     REQUIRE(pl.ops.size() % 3 == 0);
     for (int v : pl.ops) REQUIRE(v >= 0 && v < pl.nnodes);
     for (int v : pl.roots) REQUIRE(v >= 0 && v < pl.nnodes);
+  }
+  // the fused step's host plan over every particle count (glh_point_plan.h: pt_plan; the sweep of tests/test_hostcheck.py)
+  {
+    long accepted = 0;
+    REQUIRE(pt_plan_sweep(32768, &accepted) == 0);
+    REQUIRE(accepted > 0);
   }
   // spline tables: LU factors and explicit inverses for every size, inverse * matrix = identity
   for (int n = 4; n <= 64; ++n) {

@@ -1,8 +1,9 @@
 """The launch shapes of the fused frame step and the recipe that runs every instantiation of each (a plain helper module).
 
 glh_point_variants.h carries 11 launch shapes (threads, particles of observer 0 in registers, observers) with 8 codes
-(SURF, FAST, CON) each; glh_host.h: pt_shape picks the shape from the particle count N and the observer count O,
-glimpse_hip.hip: fused_step the code from the context's configuration.  This module names
+(SURF, FAST, CON) each; glh_point_plan.h: pt_shape picks the shape from the particle count N and the observer count O,
+pt_code the code from the context's configuration and what the launch is given, pt_plan whether the fused kernel takes
+the count at all (tests/test_hostcheck.py runs the three, compiled for the CPU, against this module).  This module names
 
   * SHAPES: for every shape the particle counts at which its own edges show (tests/test_gpu_launch_shapes.py runs them;
     tests/test_hostcheck.py pins the same N -> shape map on the host);
@@ -27,9 +28,10 @@ import numpy as np
 #   10240          the 1 024-thread kernel exactly full: the last count with observer 0's coordinates in registers
 #   10241          the first count that parks observer 0's coordinates (u in c[], v in the uv scratch)
 #   10500          the count tests/test_hostcheck.py pins; c[N] + region 2 within 4 KB of the LDS limit with rasters
-# Every count is accepted by fused_plan for every configuration below (21 x 21 templates, one channel: c[N], the pairwise-sum
+# Every count is accepted by pt_plan for every configuration below (21 x 21 templates, one channel: c[N], the pairwise-sum
 # plan and the three rank tables of phase D/E take 14 N + ~2 KB of the 152 KB - PT_PATCH_LDS a workgroup may have -- N up to
-# ~10 700 with rasters), so no entry had to settle for a smaller count.
+# ~10 700 with rasters), so no entry had to settle for a smaller count:
+# tests/test_hostcheck.py: test_launch_shape_table_counts_are_accepted_by_the_plan asserts it.
 SHAPES = (
     ((512, 4, 1), (2048,)),
     ((512, 10, 1), (2049, 5120)),
@@ -43,7 +45,7 @@ SHAPES = (
     ((1024, 0, 3), (5121, 10500)),
     ((1024, 0, 4), (5121, 10500)),
 )
-# (shape, code) pairs no particle count reaches, with the line of fused_plan / fused_step that excludes them: none.  The
+# (shape, code) pairs no particle count reaches, with the line of pt_plan / pt_code that excludes them: none.  The
 # coverage assertions count an entry here as accounted for.
 UNREACHABLE = {}
 
@@ -61,8 +63,8 @@ def entries():
 
 def flags_to_code(flags):
     """Context.last_variant()[3] (bit 0 fast arithmetic, bit 1 the general code, bit 2 the contract, bit 3 the raster
-    samples) as the (SURF, FAST, CON) triple of glh_point_variants.h -- fused_step: pt_kernel(tb, ppt, O, rast ? 2 : surf
-    ? 1 : 0, fast, surf ? common : fast)."""
+    samples) as the (SURF, FAST, CON) triple of glh_point_variants.h -- glh_point_plan.h: pt_code returns both, the
+    triple as (rast ? 2 : surf ? 1 : 0, fast, surf ? common : fast)."""
     fast, surf, common, rast = (bool(flags & b) for b in (1, 2, 4, 8))
     return (2 if rast else 1 if surf else 0, int(fast), int(common if surf else fast))
 
@@ -73,7 +75,7 @@ def missing_image(step, n_obs):
 
 
 def expected_code(config, math, step, n_obs):
-    """The code fused_step selects for frame `step` (1 ..) of a run from init_particles(seed=...) on device draws.
+    """The code pt_code selects for frame `step` (1 ..) of a run from init_particles(seed=...) on device draws.
 
     Fast arithmetic runs under the contract (`common`) when the input is the compact state a fused step left and every
     observer has an image: not on frame 1 (the expanded prior) and not on the frame with the missing image."""

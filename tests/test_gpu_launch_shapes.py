@@ -1,6 +1,6 @@
 """Every instantiation of the fused frame step the library carries (glh_point_variants.h: 11 launch shapes x 8 codes), run.
 
-pt_shape (glh_host.h) picks the launch shape from the particle count and the observer count; the other GPU tests stop at
+pt_shape (glh_point_plan.h) picks the launch shape from the particle count and the observer count; the other GPU tests stop at
 counts and observer numbers that reach six of the eleven shapes, and few codes on most of those.  Here, from the recipe
 table of tests/launch_shape_cases.py:
 

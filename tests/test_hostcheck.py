@@ -1,6 +1,8 @@
 """Stage math of the HIP kernels, compiled for the CPU (tests/hostcheck) and checked against
 the oracle / the reference goldens.  Test-only: the product never runs this code on the CPU."""
 import ctypes as C
+import itertools
+import json
 import os
 import subprocess
 
@@ -9,6 +11,7 @@ import pytest
 
 from oracle import resample as oresample
 from oracle import tiles as otiles
+from tests import launch_shape_cases as lc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "hostcheck", "hostcheck.cpp")
@@ -18,8 +21,9 @@ OUT = os.path.join(ROOT, "tests", "hostcheck", "_build", "libhostcheck.so")
 @pytest.fixture(scope="module")
 def hc():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    headers = ("glh_math.h", "glh_median.h", "glh_host.h", "glh_point_variants.h")
-    deps = [SRC] + [os.path.join(ROOT, "glimpse_amd", "csrc", f) for f in headers]
+    headers = ("glh_math.h", "glh_median.h", "glh_host.h", "glh_point_plan.h", "glh_point_variants.h")
+    deps = [SRC, os.path.join(ROOT, "tests", "hostcheck", "plan_sweep.h")]
+    deps += [os.path.join(ROOT, "glimpse_amd", "csrc", f) for f in headers]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", OUT, SRC], check=True)
     lib = C.CDLL(OUT)
@@ -319,7 +323,7 @@ def test_raster_window_serves_the_same_samples(hc):
 
 
 def test_fused_launch_shapes_are_carried_by_the_library(hc):
-    """glh_host.h: pt_shape -- every (threads, PPT, observers) the fused step can launch for 1 .. 32 768 particles and one to
+    """glh_point_plan.h: pt_shape -- every (threads, PPT, observers) the fused step can launch for 1 .. 32 768 particles and one to
     four observers is an instantiation glh_point_variants.h carries, and the shapes the tests and the benchmark rely on
     stay where they are."""
     out = np.zeros(2, dtype=np.int32)
@@ -332,7 +336,7 @@ def test_fused_launch_shapes_are_carried_by_the_library(hc):
     for o in range(1, 5):
         for n in range(1, 32769):
             tb, ppt = shape(n, o)
-            if not hc.hc_pt_shape_carried(tb, ppt, o):
+            if not hc.hc_pt_shape_carried(tb, ppt, o, 0, 0, 0):
                 missing.add((tb, ppt, o))
     assert not missing, sorted(missing)
     pinned = {(2000, 1): (512, 4), (5000, 1): (512, 10), (5000, 2): (512, 10), (5000, 3): (512, 0),
@@ -345,3 +349,119 @@ def test_fused_launch_shapes_are_carried_by_the_library(hc):
                        (10240, o): (1024, 10 if few else 0), (10241, o): (1024, 0)})
     for (n, o), want in pinned.items():
         assert shape(n, o) == want, (n, o)
+
+
+# ---- the host plan of the fused step (glh_point_plan.h: pt_plan, pt_code) -----------------------------------------------
+PLAN_FIELDS = ("accepted", "tb", "ppt", "r2_bytes", "cell_cap", "lds_bytes")
+
+
+def _plan(hc, n, o, tile=(21, 21), frames=(8, 1, 255), rasters=0, hook=0, interp_k=3):
+    """pt_plan for o observers with the same frames entry (bits, channels, max_search_dim), as a tuple of PLAN_FIELDS."""
+    bits = np.full(4, frames[0], dtype=np.int32)
+    channels = np.full(4, frames[1], dtype=np.int32)
+    out = np.zeros(6, dtype=np.int32)
+    hc.hc_pt_plan(n, o, tile[0], tile[1], frames[2], interp_k, p(bits), p(channels), rasters, hook, p(out))
+    return tuple(int(v) for v in out)
+
+
+def _code(hc, n_obs, fast, philox, compact, masked, all_cartesian, rasters, hp=(2, 2), interp_k=3, off=0, not_simple=0,
+          bits=(8, 8, 8, 8)):
+    """pt_code: ((SURF, FAST, CON), flags).  `off` / `not_simple`: bit o set -- observer o has no image / a camera beyond
+    the contract's."""
+    on = (C.c_int * 4)(*[not off >> o & 1 for o in range(4)])
+    flags = (C.c_uint * 4)(*[hc.hc_cam_f_not_simple() if not_simple >> o & 1 else 0 for o in range(4)])
+    out = (C.c_int * 4)()
+    booleans = fast | philox << 1 | compact << 2 | masked << 3 | all_cartesian << 4
+    hc.hc_pt_code(booleans, hp[0], hp[1], interp_k, on, flags, (C.c_int * 4)(*bits), n_obs, rasters, out)
+    return tuple(out[:3]), out[3]
+
+
+def test_fused_plan_equals_the_pinned_decisions_of_its_predecessor(hc):
+    """tests/fused_plan_pins.json: (accepted, tb, ppt, r2_bytes, cell_cap, lds_bytes) of fused_plan / cell_cap / pt_shape and
+    the launch's LDS expression as they stood in glimpse_hip.hip before glh_point_plan.h (the commit is named in the file),
+    over particle counts x observers x tiles x frame types x rasters x the small-LDS hook x sampling orders.  pt_plan gives
+    every row exactly; a row refused there is refused here (all zeros)."""
+    pins = json.load(open(os.path.join(ROOT, "tests", "fused_plan_pins.json")))
+    assert tuple(pins["outcome_fields"]) == PLAN_FIELDS
+    axes = pins["axes"]
+    combos = list(itertools.product(axes["N"], axes["O"], axes["tile"], axes["frames"], axes["rasters"], axes["hook"],
+                                    axes["interp_k"]))
+    assert len(combos) == len(pins["rows"]) == 24480
+    wrong = []
+    n_accepted = 0
+    for (n, o, tile, frames, rasters, hook, k), row in zip(combos, pins["rows"]):
+        want = tuple(pins["outcomes"][row])
+        n_accepted += want[0]
+        got = _plan(hc, n, o, tile, frames, rasters, hook, k)
+        if got != want:
+            wrong.append(((n, o, tile, frames, rasters, hook, k), got, want))
+    assert not wrong, (len(wrong), wrong[:5])
+    assert n_accepted == 7424  # (the table is not all refusals)
+
+
+def test_fused_plan_sweep_stays_within_the_lds(hc):
+    """Every particle count 1 .. 32 768, one to four observers, rasters off and on (tests/hostcheck/plan_sweep.h, the sweep
+    sanitize_main.cpp runs under the sanitizers): an accepted plan's dynamic LDS is at most PT_LDS_MAX less the raster
+    windows and at least pt_park_bytes(), its shape is pt_shape's, cell_cap <= tb / 2; a refused plan is all zeros.  The
+    same conditions once more from Python at the counts around the acceptance limit."""
+    hc.hc_pt_plan_sweep.restype = C.c_long
+    accepted = C.c_long(0)
+    assert hc.hc_pt_plan_sweep(32768, C.byref(accepted)) == 0
+    limits = np.zeros(4, dtype=np.int32)
+    hc.hc_pt_limits(p(limits))
+    lds_max, _, patch, park = (int(v) for v in limits)
+    last = {}
+    for rasters in (0, 1):
+        for o in (1, 2, 3, 4):
+            took = [n for n in range(10000, 12001) if _plan(hc, n, o, rasters=rasters)[0]]
+            assert took == list(range(10000, took[-1] + 1))  # (accepted up to a limit, refused beyond)
+            last[rasters, o] = took[-1]
+            for n in (1, 5120, 5121, took[-1]):
+                ok, tb, ppt, r2, cap, lds = _plan(hc, n, o, rasters=rasters)
+                assert ok and park <= lds <= lds_max - rasters * patch and 0 < r2 <= lds and 0 <= cap <= tb // 2
+            assert _plan(hc, took[-1] + 1, o, rasters=rasters) == (0, 0, 0, 0, 0, 0)
+    assert accepted.value == sum(last.values()), (accepted.value, last)  # (every count below the limit is accepted)
+
+
+def test_launch_shape_table_counts_are_accepted_by_the_plan(hc):
+    """Every (shape, N) of tests/launch_shape_cases.py is accepted with rasters off and on (21 x 21 templates, one-channel
+    8-bit frames), and the plan's (tb, ppt) is the shape the count is listed under: no entry had to settle for a smaller
+    count."""
+    for (tb, ppt, o), n in lc.entries():
+        for rasters in (0, 1):
+            got = _plan(hc, n, o, tile=lc.TILE, rasters=rasters)
+            assert got[0] == 1 and got[1:3] == (tb, ppt), ((tb, ppt, o), n, rasters, got)
+
+
+def test_code_choice_agrees_with_the_recipe_of_launch_shape_cases(hc):
+    """pt_code against tests/launch_shape_cases.py: expected_code for every configuration x arithmetic x frame 1 .. 3 x one
+    to four observers of the recipe (device Philox draws; frame 1 reads the expanded prior, later frames the compact state
+    a fused step left; the last observer has no image on frame 2 when there are several), and flags_to_code of the flag
+    word against the triple."""
+    for config, math, step, n_obs in itertools.product(lc.CONFIGS, lc.MATHS, (1, 2, 3), (1, 2, 3, 4)):
+        off = 1 << (n_obs - 1) if lc.missing_image(step, n_obs) else 0
+        code, flags = _code(hc, n_obs, fast=int(math == "fast"), philox=1, compact=int(step >= 2), masked=0,
+                            all_cartesian=int(config == "plain"), rasters=int(config == "rasters"), off=off)
+        assert code == lc.expected_code(config, math, step, n_obs), (config, math, step, n_obs)
+        assert lc.flags_to_code(flags) == code, (config, math, step, n_obs)
+
+
+def test_every_launch_runs_an_instantiation_the_library_carries(hc):
+    """Over every combination of what varies per launch -- the five booleans, rasters, observers without an image, cameras
+    beyond the contract's, each way of leaving the plain configuration (median window, sampling order, frame depth) -- and
+    every shape of GLH_PT_SHAPES, pt_code's triple is one GLH_PT_CODES carries and flags_to_code reads it off the flags."""
+    from glimpse_amd import build
+
+    shapes = sorted({v[:3] for v in build.variants()})
+    assert len(shapes) == 11
+    ways = [dict(), dict(hp=(1, 2)), dict(hp=(2, 3)), dict(interp_k=1), dict(bits=(8, 8, 8, 16)), dict(bits=(16, 8, 8, 8))]
+    seen = set()
+    for tb, ppt, n_obs in shapes:
+        for b in itertools.product((0, 1), repeat=6):
+            for way, off, not_simple in itertools.product(ways, range(1 << n_obs), range(1 << n_obs)):
+                code, flags = _code(hc, n_obs, *b, off=off, not_simple=not_simple, **way)
+                assert hc.hc_pt_shape_carried(tb, ppt, n_obs, *code), ((tb, ppt, n_obs), b, way, off, not_simple, code)
+                assert lc.flags_to_code(flags) == code
+                seen.add(code)
+    assert len(seen) == 8  # (every code of GLH_PT_CODES is some launch's)
+    assert not hc.hc_pt_shape_carried(512, 4, 1, 0, 1, 0) and not hc.hc_pt_shape_carried(512, 4, 2, 0, 0, 0)

@@ -1,6 +1,7 @@
 """The recipe table of tests/launch_shape_cases.py, checked without a GPU: it maps every instantiation the build carries to
-a case, its flag mapping is fused_step's expression, its particle counts select the shapes it names, and the cases compared
-with the oracle index for index pass the admission rule (both accumulations of the SSD give the same indices)."""
+a case, its flag mapping is pt_code's expression (glh_point_plan.h), its particle counts select the shapes it names, and the
+cases compared with the oracle index for index pass the admission rule (both accumulations of the SSD give the same
+indices).  tests/test_hostcheck.py runs the compiled pt_plan / pt_code against the same table."""
 import itertools
 import os
 import re
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _pt_shape(n, o):
-    """glh_host.h: pt_shape, restated (tests/test_hostcheck.py pins the compiled one at the same counts)."""
+    """glh_point_plan.h: pt_shape, restated (tests/test_hostcheck.py pins the compiled one at the same counts)."""
     big = n > 10 * 512
     tb = 1024 if big else 512
     p = 4 if n <= 4 * tb else (10 if n <= 10 * tb else 0)
@@ -37,7 +38,7 @@ def test_the_table_accounts_for_every_instantiation_the_build_carries():
     missing = carried - covered - unreachable
     assert not missing, f"instantiations without a case: {sorted(missing)}"
     for why in lc.UNREACHABLE.values():
-        assert re.search(r"fused_(plan|step)", why), why
+        assert re.search(r"pt_(plan|code)", why), why
     print(f"{len(carried)} instantiations: {len(covered)} mapped to a case, {len(unreachable)} documented unreachable")
     # every shape runs all eight codes, and the table names every shape once
     shapes = [shape for shape, _ in lc.SHAPES]
@@ -64,15 +65,19 @@ def test_the_counts_select_the_shapes_they_are_listed_under():
 
 
 def test_the_flag_mapping_is_the_expression_of_fused_step():
-    """`rast ? 2 : surf ? 1 : 0`, `fast`, `surf ? common : fast` over every flag word, and the text of that call in the
-    source; the codes the recipe expects are codes the header lists."""
+    """`rast ? 2 : surf ? 1 : 0`, `fast`, `surf ? common : fast` over every flag word, and the text of that expression in
+    the source (glh_point_plan.h: pt_code, which fused_step launches by); the codes the recipe expects are codes the
+    header lists."""
     for fast, surf, common, rast in itertools.product((0, 1), repeat=4):
         flags = fast | surf << 1 | common << 2 | rast << 3
         want = ((2 if rast else (1 if surf else 0)), fast, (common if surf else fast))
         assert lc.flags_to_code(flags) == want, flags
-    src = open(os.path.join(ROOT, "glimpse_amd", "csrc", "glimpse_hip.hip")).read()
-    assert "pt_kernel(tb, ppt, O, rast ? 2 : (surf ? 1 : 0), fast, surf ? common : fast)" in src
+    src = open(os.path.join(ROOT, "glimpse_amd", "csrc", "glh_point_plan.h")).read()
+    assert "PtCode{rast ? 2 : (surf ? 1 : 0), fast, surf ? common : fast," in src
     assert "(fast ? 1 : 0) | (surf ? 2 : 0) | (common ? 4 : 0) | (rast ? 8 : 0)" in src
+    hip = open(os.path.join(ROOT, "glimpse_amd", "csrc", "glimpse_hip.hip")).read()
+    assert "pt_kernel(plan.tb, plan.ppt, O, code.surf, code.fast, code.con)" in hip
+    assert "c->last_variant[3] = code.flags;" in hip
     # the recipe's table (configuration x arithmetic x step), written out: one observer and several
     table = {("plain", "exact"): [(0, 0, 0)] * 3, ("general", "exact"): [(1, 0, 0)] * 3, ("rasters", "exact"): [(2, 0, 0)] * 3,
              ("plain", "fast"): [(1, 1, 0), (0, 1, 1), (0, 1, 1)], ("general", "fast"): [(1, 1, 0), (1, 1, 1), (1, 1, 1)],
