@@ -2389,8 +2389,8 @@ __global__ __launch_bounds__(BLK) void k_sample(SampleArgs a) {
 //       idx_j = #{k : c_k < (j+u)/n} -- binary search (np.searchsorted, side='left')
 //       particles, weights = particles[idx], weights[idx]
 //       mean = sum(w p)/sum(w), sigma = sqrt(sum(w (p-mean)^2)/sum(w)) of the gathered set,
-//       accumulated in one pass around a pivot particle K (shifted moments: no cancellation
-//       at UTM-scale coordinates).
+//       accumulated in one pass around a pivot particle K, the source of output 0 (shifted moments: no
+//       cancellation at UTM-scale coordinates, nor when the set has collapsed far from the point's first particle).
 // ------------------------------------------------------------------------------------------
 // #{j in [0, n): j + u <= ck * scale}, scale = n / total: the number of systematic positions (j + u) / n at or
 // below the cumulative weight ck / total, in fast arithmetic (no verification against the reference's rounding of
@@ -2684,7 +2684,8 @@ __global__ __launch_bounds__(BLK) void k_resample(ResampleArgs a) {
   double* Wout = a.weights_out + (size_t)pt * N;
   double K[6];
 #pragma unroll
-  for (int k = 0; k < 6; ++k) K[k] = Pin[k];  // pivot: the point's first particle
+  for (int k = 0; k < 6; ++k) K[k] = Pin[(size_t)sidx[0] * 6 + k];  // pivot: the source of output 0 (a particle OF the
+                                                                     // resampled set: N copies of it have sigma 0)
   double s0 = 0.0, s1[6] = {0, 0, 0, 0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0};
   constexpr int GU = 4;  // independent gathers in flight per thread
   for (int j0 = tid; j0 < N; j0 += GU * BLK) {

@@ -758,7 +758,7 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
   __shared__ double s_uvbb[NOBS][4];  // min u, min v, max u, max v of the point's projected particles (phase A)
   __shared__ int s_status[NOBS];
   __shared__ double s_u;     // np.random.random() of this point's systematic resampling (tracker.py:173)
-  __shared__ double s_K[6];  // the point's first evolved particle: pivot of the shifted moments (phase A -> F)
+  __shared__ double s_K[6];  // the evolved record of rank 0, the source of output 0: pivot of the shifted moments (phase F)
   __shared__ PtPatches<GRID> s_patches;  // (code 2: windows of the dem / dem_sigma rasters around the point)
   __shared__ CamDev s_cam[NOBS];           // cameras: LDS broadcast reads instead of ~60 live SGPRs each
   __shared__ double s_m[GLH_MOTION_FULL_LEN];  // this point's motion parameters: the loops below store to global
@@ -1071,10 +1071,6 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
           evolve_particle<FAST, GRID>(x, m, n, tau, tau2, a.surf, &raster_oob, s_patches.get(), 0.0, wins);
         else
           evolve_cartesian_m<FAST>(x, m, n, tau, tau2);
-        if (i == 0) {
-#pragma unroll
-          for (int k = 0; k < 6; ++k) s_K[k] = x[k];
-        }
 #pragma unroll
         for (int k = 0; k < 6; ++k) bad |= isnan(x[k]);
         if (GRID && tangent_pt) ZP[i] = x[2];  // (for the gather's re-evolution: evolve_loaded)
@@ -1882,9 +1878,10 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
   double* Pout = a.particles_out + (size_t)pt * N * 6;
   double* Wout = a.weights_out + (size_t)pt * N;
   const int U = max(s_U, 1);
-  double K[6];  // pivot of the shifted moments: the point's first evolved particle (parked by phase A)
-#pragma unroll
-  for (int k = 0; k < 6; ++k) K[k] = s_K[k];
+  // pivot of the shifted moments: the evolved record of rank 0 -- the source of output 0, as in k_resample.  A particle OF
+  // the resampled set: when the set is N copies of one record every d below is 0 and sigma is exactly 0, however far
+  // the point's first particle is.  Thread 0 has it after the first evolve_loaded of the loop below.
+  double K[6] = {0, 0, 0, 0, 0, 0};
   double s0 = 0.0, s1[6] = {0, 0, 0, 0, 0, 0}, s2[6] = {0, 0, 0, 0, 0, 0};
   // records in flight per thread.  The general code keeps ONE: with two, its 128 registers spill two record chunks inside this
   // loop (40 B of scratch); one record in flight, none -- TangentCartesianMotion -3.4 %, uint16 frames -3.3 %, over rasters
@@ -1910,7 +1907,9 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
     }
   };
   fetch_next(tid);
-  for (int h0 = tid; h0 < U; h0 += GU * TB) {
+  // (every thread runs the first iteration, also those without a rank -- they evolve slot 0's record like the idle lanes
+  // of a busy wave do -- because that iteration holds the barrier behind which the pivot is read; `it` is uniform)
+  for (int it = 0, h0 = tid; it == 0 || h0 < U; ++it, h0 += GU * TB) {
     int lo[GU], cnt[GU];
     double2 v[GU][3];
     double zp[GU];  // (tangent models: the evolved height phase A parked)
@@ -1930,6 +1929,15 @@ __global__ __launch_bounds__(TB, MINW) void k_point_step(PointArgs a) {
       if (g) asm volatile("" ::: "memory");
       double x[6] = {v[g][0].x, v[g][0].y, v[g][1].x, v[g][1].y, v[g][2].x, v[g][2].y};
       evolve_loaded(lo[g], x, zp[g]);
+      if (it == 0 && g == 0) {  // uniform
+        if (tid == 0) {
+#pragma unroll
+          for (int k = 0; k < 6; ++k) s_K[k] = x[k];
+        }
+        pt_lds_barrier();
+#pragma unroll
+        for (int k = 0; k < 6; ++k) K[k] = s_K[k];
+      }
       const double w = c[lo[g]];
       const int h = h0 + g * TB;
       if (h < U) {
