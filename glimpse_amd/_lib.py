@@ -165,6 +165,7 @@ SIGNATURES = {
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "glh_stage_gaussian_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_fill_crevasses": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
+    "glh_stage_clahe": (_I, [_I, _P, _I, _I, _I, _D, _I, _I, _P, _P, _P]),
     "glh_stage_gradient": (_I, [_I, _P, _I, _I, _I, _D, _D, _P, _P, _P]),
     "glh_stage_hillshade": (_I, [_I, _P, _I, _I, _I, _D, _D, _D, _P, _D, _P, _P]),
     "glh_stage_polygon_mask": (_I, [_I, _P, _I, _P, _I, _I, _I, _I, _P, _P]),
@@ -1228,6 +1229,29 @@ def stage_fill_crevasses(a, mask, fill, size_y, size_x, max_mode, w0, w1, gauss_
                                           int(size_x), int(max_mode), _ptr(w0), r0, _ptr(w1), r1, int(gauss_mode), _ptr(out),
                                           _ptr(times) if return_times else None))
     return _timed(out, FILTER_TIMES, times, return_times)
+
+
+CLAHE_TIMES = ("upload_ms", "histogram_ms", "lut_ms", "apply_ms", "download_ms")
+
+
+def stage_clahe(array, clip_limit=40.0, tile_grid_size=(8, 8), device_id=0, return_luts=False, return_times=False):
+    """CLAHE by INPUTS.md's "CLAHE: the rule" (optimize.CLAHE) of `array` uint8 (h, w) or (h, w, c) with c in 1 .. 4, whose
+    channels are averaged first ((sum) // c, which is mean(axis=2).astype(uint8)): a new uint8 (h, w).  `tile_grid_size` is
+    (tilesX, tilesY) as cv2 takes it.  `return_luts`: also every tile's table, uint8 (tilesY, tilesX, 256);
+    `return_times`: also a dict of the HIP-event split (CLAHE_TIMES)."""
+    array = np.asarray(array)
+    if array.dtype != np.uint8 or array.ndim not in (2, 3):
+        raise TypeError(f"a uint8 array of two or three dimensions (got {array.dtype}, {array.ndim} dimensions)")
+    array = np.ascontiguousarray(array)
+    h, w = array.shape[:2]
+    channels = array.shape[2] if array.ndim == 3 else 1
+    tiles_x, tiles_y = (int(t) for t in tile_grid_size)
+    out = np.empty((h, w), np.uint8)
+    luts = np.empty((max(tiles_y, 0), max(tiles_x, 0), 256), np.uint8) if return_luts else None
+    times = np.zeros(len(CLAHE_TIMES))
+    check(load().glh_stage_clahe(device_id, _ptr(array), w, h, channels, float(clip_limit), tiles_x, tiles_y, _ptr(out),
+                                 _ptr(luts), _ptr(times) if return_times else None))
+    return _timed((out, luts) if return_luts else out, CLAHE_TIMES, times, return_times, extend=return_luts)
 
 
 TERRAIN_F64, TERRAIN_F32 = F64, F32

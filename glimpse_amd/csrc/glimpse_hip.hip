@@ -26,6 +26,7 @@
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
+#include "glh_clahe.h"
 #include "glh_terrain.h"
 #include "glh_stage.h"
 
@@ -3316,6 +3317,27 @@ extern "C" int glh_stage_fill_crevasses(int dev, const void* a, int dtype, int n
   CHK(check_filter_weights("fill_crevasses", w0, r0, w1, r1, gauss_mode));
   return filters_run(FiltersJob{dev, a, dtype == GLH_FILTER_F32, nx, ny, mask, fill != 0, 1, size_y, size_x, max_mode, 1, w0, r0,
                                 w1, r1, gauss_mode, out, times_ms});
+}
+
+// optimize.CLAHE (INPUTS.md, "CLAHE: the rule"): the arguments are checked here, before a device is touched; the kernels
+// and the launches are glh_clahe.hip's.
+extern "C" int glh_stage_clahe(int dev, const uint8_t* src, int w, int h, int channels, double clip_limit, int tiles_x,
+                               int tiles_y, uint8_t* dst, uint8_t* luts, double* times_ms) {
+  if (!src || !dst) return fail(GLH_E_INVALID, "clahe: null argument");
+  if (w < 1 || h < 1 || (int64_t)w * h >= ((int64_t)1 << 31))
+    return fail(GLH_E_INVALID, "clahe: %d x %d pixels: at least one, fewer than 2^31", w, h);
+  if (channels < 1 || channels > 4) return fail(GLH_E_INVALID, "clahe: %d channels: 1 to 4 are served", channels);
+  if (tiles_x < 1 || tiles_x > w || tiles_y < 1 || tiles_y > h)
+    return fail(GLH_E_INVALID, "clahe: a grid of %d x %d tiles on %d x %d pixels: at least one tile and at most one per pixel "
+                               "along each axis", tiles_x, tiles_y, w, h);
+  if (!std::isfinite(clip_limit)) return fail(GLH_E_INVALID, "clahe: clipLimit %g is not finite", clip_limit);
+  const ClaheGeometry geo = clahe_geometry(w, h, clip_limit, tiles_x, tiles_y);
+  const int64_t lim31 = (int64_t)1 << 31;
+  if (geo.ext_w >= lim31 || geo.ext_h >= lim31 || geo.area >= lim31)
+    return fail(GLH_E_UNSUPPORTED, "clahe: the image extended to the grid is %lld x %lld pixels with %lld to a tile: fewer than "
+                                   "2^31 of each are served (32-bit indices and counts)", (long long)geo.ext_w,
+                (long long)geo.ext_h, (long long)geo.area);
+  return clahe_run(ClaheJob{dev, src, w, h, channels, tiles_x, tiles_y, geo, dst, luts, times_ms});
 }
 
 // Raster.gradient, Raster.hillshade (raster.py:1465-1474, :1249-1264) and helpers.polygons_to_mask (helpers.py:1701-1768):

@@ -30,8 +30,15 @@ implementation, pinned to the rule written out in INPUTS.md ("SIFT: the rule") a
 (tests/sift_restated.py) in every bit, not to OpenCV's bytes.  The descriptors are uint8, so they take the matcher's integer
 path.  The reference's default `method` (`cv2.SIFT`) is still refused: `cv2` is not a dependency.
 
-Not served: `cv2.SIFT` itself (the default `method` of `detect_keypoints` and `build_keypoints`), CLAHE, a `mask` for the GPU
-matcher, the lmfit methods other than "least_squares" (lmfit is not a dependency) and plotting.
+`CLAHE(...).apply(array)` and `KeypointMatcher(images, clahe=optimize.CLAHE(...))` equalise an 8-bit image's contrast
+tile by tile on the GPU (`glh_stage_clahe`) before detection, which is what finds keypoints on snow and ice: OpenCV's CLAHE
+for 8-bit input, pinned to the rule written out in INPUTS.md ("CLAHE: the rule") and to its NumPy restatement
+(tests/clahe_restated.py) in every bit.  The matcher hands the stage the image's channels, and their mean is formed on the
+device.  The reference's own forms (`clahe=True`, a `dict` for `cv2.createCLAHE`) are still refused.
+
+Not served: `cv2.SIFT` itself (the default `method` of `detect_keypoints` and `build_keypoints`), `cv2.createCLAHE` (`clahe=True`
+or a `dict`), a `mask` for the GPU matcher, the lmfit methods other than "least_squares" (lmfit is not a dependency) and
+plotting.
 """
 import collections
 import datetime
@@ -51,7 +58,8 @@ _NO_MATCHER = ("keypoint detection and matching (SIFT and FLANN of cv2) are not 
 _NO_PLOT = "plotting is out of scope"
 _NO_DETECT = ("keypoint detection (SIFT of cv2) is not served: give KeypointMatcher.keypoints, or a directory of "
               "keypoint files, as (points, descriptors) per image, or pass method=optimize.SIFT (SIFT on the GPU)")
-_NO_CLAHE = "CLAHE (cv2.createCLAHE) is not served: pass clahe=False"
+_NO_CLAHE = ("CLAHE by cv2.createCLAHE (clahe=True or a dict of its arguments) is not served: pass clahe=False, or an "
+             "optimize.CLAHE(clipLimit=..., tileGridSize=...) (CLAHE on the GPU)")
 _NO_MASK = ("a knnMatch mask is not served by the GPU matcher (the reference's own code cannot index the short lists "
             "cv2 returns for one): pass mask=None, or a matcher object of your own")
 
@@ -470,6 +478,60 @@ class SIFT:
         return keypoints, desc
 
 
+class CLAHE:
+    """Contrast-limited adaptive histogram equalisation on the GPU, shaped like a cv2.CLAHE: `CLAHE(clipLimit,
+    tileGridSize).apply(array)` of a two-dimensional uint8 array.  The rule is INPUTS.md's "CLAHE: the rule".
+    `tileGridSize` is (tilesX, tilesY); a `clipLimit` of 0 or less does not clip.  It holds no device handle: it pickles and
+    copies as the three numbers it is."""
+
+    def __init__(self, clipLimit=40.0, tileGridSize=(8, 8), device_id=0):
+        self.setClipLimit(clipLimit)
+        self.setTilesGridSize(tileGridSize)
+        self.device_id = int(device_id)
+
+    def getClipLimit(self):
+        return self.clipLimit
+
+    def setClipLimit(self, clipLimit):
+        clipLimit = float(clipLimit)
+        if not math.isfinite(clipLimit):
+            raise ValueError(f"clipLimit {clipLimit} is not finite")
+        self.clipLimit = clipLimit
+
+    def getTilesGridSize(self):
+        return self.tileGridSize
+
+    def setTilesGridSize(self, tileGridSize):
+        grid = tuple(tileGridSize)
+        if len(grid) != 2 or any(int(t) != t or t < 1 for t in grid):
+            raise ValueError(f"tileGridSize {tileGridSize!r}: (tilesX, tilesY), whole numbers of at least 1")
+        self.tileGridSize = (int(grid[0]), int(grid[1]))
+
+    def collectGarbage(self):
+        """cv2's frees its buffers; nothing is kept here between calls."""
+
+    def _stage(self, array):
+        """`array` uint8 (h, w) or (h, w, c <= 4) -> uint8 (h, w): the channel mean and the rule, one stage call."""
+        h, w = array.shape[:2]
+        tiles_x, tiles_y = self.tileGridSize
+        if tiles_x > w or tiles_y > h:
+            raise ValueError(f"a grid of {tiles_x} x {tiles_y} tiles is larger than the image of {w} x {h} pixels")
+        return _lib.stage_clahe(array, self.clipLimit, self.tileGridSize, device_id=self.device_id)
+
+    def apply(self, array):
+        if not isinstance(array, np.ndarray) or array.dtype != np.uint8:
+            what = array.dtype if isinstance(array, np.ndarray) else type(array).__name__
+            raise TypeError(f"CLAHE.apply takes a two-dimensional uint8 array (got {what}): 16-bit CLAHE is not served")
+        if array.ndim != 2 or array.size == 0:
+            raise ValueError(f"CLAHE.apply takes a two-dimensional uint8 array that is not empty (got shape {array.shape})")
+        return self._stage(array)
+
+
+def createCLAHE(clipLimit=40.0, tileGridSize=(8, 8)):
+    """An `optimize.CLAHE`, as cv2.createCLAHE makes a cv2.CLAHE."""
+    return CLAHE(clipLimit, tileGridSize)
+
+
 def detect_keypoints(array, mask=None, method=None, root=False, **kwargs):
     """optimize.py:2194-2231 with `method=optimize.SIFT` (SIFT on the GPU; `kwargs` go to `SIFT.create`).  The reference's
     default method, cv2.SIFT (`method=None` here), is not served, nor is any other."""
@@ -624,7 +686,8 @@ class PairMatches:
 class KeypointMatcher:
     """optimize.py:2312-2773: matches the keypoints of `images` (in ascending temporal order) pair by pair, on the GPU
     (`build_matches`).  `keypoints`: per image (points, descriptors) as `match_keypoints` takes them; they are passed in
-    or read from files, or detected with `build_keypoints(method=optimize.SIFT)`; `clahe` is not served."""
+    or read from files, or detected with `build_keypoints(method=optimize.SIFT)`.  `clahe`: False, or an `optimize.CLAHE`,
+    which `build_keypoints` applies to every image before it detects; True and a dict (cv2.createCLAHE) are not served."""
 
     def __init__(self, images=None, clahe=False):
         if images is None:
@@ -635,9 +698,12 @@ class KeypointMatcher:
         self.images = np.empty(len(images), dtype=object)
         for i, img in enumerate(images):
             self.images[i] = img
-        if clahe is not False:
+        if clahe is False:
+            self.clahe = None
+        elif isinstance(clahe, CLAHE):
+            self.clahe = clahe
+        else:
             raise NotImplementedError(_NO_CLAHE)
-        self.clahe = None
         self.device_id = 0
         self.keypoints = None
         self.matches = None
@@ -649,10 +715,17 @@ class KeypointMatcher:
         return basenames
 
     def _prepare_image(self, array):
-        """optimize.py:2358-2365: the channel mean, then uint8 (CLAHE is refused by the constructor)."""
+        """optimize.py:2358-2365: the channel mean, then uint8, then CLAHE if the matcher has one.  A uint8 image of up to
+        four channels goes to the CLAHE stage as it is: the stage forms the same mean on the device."""
+        if self.clahe is not None and array.dtype == np.uint8 and (
+                array.ndim == 2 or (array.ndim == 3 and 1 <= array.shape[2] <= 4)):
+            return self.clahe._stage(array)
         if array.ndim > 2:
             array = array.mean(axis=2)
-        return array.astype(np.uint8, copy=False)
+        array = array.astype(np.uint8, copy=False)
+        if self.clahe is not None:
+            array = self.clahe.apply(array)
+        return array
 
     def build_keypoints(self, masks=None, path=None, overwrite=False, clear_images=True, clear_keypoints=False,
                         parallel=False, **kwargs):

@@ -648,6 +648,20 @@ int glh_stage_hillshade(int device_id, const void* z, int dtype, int nx, int ny,
  * finite.  GLH_E_UNSUPPORTED: a ring whose rows x edges exceed one launch (2^39 pairs).                                   */
 int glh_stage_polygon_mask(int device_id, const double* xy, int n_vertices, const int32_t* ring_off, int n_polygons,
                            int n_holes, int nx, int ny, uint8_t* out, double* times_ms);
+/* ---- optimize.CLAHE: contrast-limited adaptive histogram equalisation of an 8-bit image -------------------------------
+ * The rule is INPUTS.md's "CLAHE: the rule" (OpenCV's clahe.cpp for 8-bit input, written out); tests/clahe_restated.py
+ * restates it in NumPy and the results equal it in every bit.  src uint8 [h][w][channels], channels 1 .. 4: the image is
+ * gray = (sum of the channels) / channels in integers, which is array.mean(axis=2).astype(uint8).  The grid has
+ * tiles_x x tiles_y tiles of 256 bins; clip_limit <= 0 means no clipping.  dst uint8 [h][w].  luts (or NULL) uint8
+ * [tiles_y][tiles_x][256]: every tile's table, so that a test can tell a wrong table from a wrong blend.  Integer
+ * histograms and one float32 expression per pixel with no contraction: the result is a function of the input alone.
+ * times_ms (or NULL) [5]: HIP-event milliseconds -- [0] upload, [1] histograms (and the gray plane), [2] tables, [3] the
+ * blend, [4] download.
+ * GLH_E_INVALID before a device is touched: src or dst null, w or h < 1, w * h >= 2^31, channels outside 1 .. 4, tiles_x < 1
+ * or > w, tiles_y < 1 or > h (the reflection that extends the image to the grid stays inside it), clip_limit not finite.
+ * GLH_E_UNSUPPORTED: an extended side or a tile of 2^31 cells or more.                                                  */
+int glh_stage_clahe(int device_id, const uint8_t* src, int w, int h, int channels, double clip_limit, int tiles_x,
+                    int tiles_y, uint8_t* dst, uint8_t* luts, double* times_ms);
 /* ---- regridding: Raster.sample(grid=True) / resample, Raster.resize, RasterInterpolant ("regrid", since
  * glh_stage_resample is particle resampling) ------------------------------------------------------------------------------
  * A raster as the source of a spline evaluation.  z [ny][nx] float64 with rows and columns in ASCENDING coordinate order
