@@ -175,6 +175,8 @@ SIGNATURES = {
     "glh_orient_destroy": (_I, [_P]),
     "glh_calib_create": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "glh_calib_eval": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
+    "glh_calib_fit_sets": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I,
+                                C.c_double, _P, _P, _P, _P, _P]),
     "glh_calib_destroy": (_I, [_P]),
     "glh_match_create": (_I, [_I, _P]),
     "glh_match_put": (_I, [_P, _I, _I, _I, _I, _P]),
@@ -1427,7 +1429,48 @@ class Calib(_Handle):
                                     _ptr(seg_par), len(vertex), _ptr(vertex), _ptr(predicted), _ptr(times)))
         return _timed(predicted, CALIB_TIMES, times, return_times)
 
+    def fit_sets(self, cams, fit_cam, slots, x0, lb, ub, x_scale, set_offset, set_rows, weights=None, observed=None,
+                 max_nfev=None, ftol=1e-8, xtol=1e-8, gtol=1e-8, max_error=None, return_times=False):
+        """Fits the entries `slots` of camera `fit_cam`'s vector to each of the row sets in ONE device call
+        (glh_calib_fit_sets; include/glimpse_hip.h says how): set q is set_rows[set_offset[q]:set_offset[q + 1]], global
+        row numbers.  `cams` (n_cams, 24); `x0`, `lb`, `ub`, `x_scale` (p,), lb < ub; `weights` None or (N, 2); `observed`
+        None (the uploaded obs) or (N, 2), which a "rotation" control needs: its obs are camera coordinates; `max_nfev`
+        default 100 p.  Returns (x (S, p), status (S,) int32, mean_error (S,)) -- a status > 0 converged
+        (CALIB_FIT_STATUS) -- and, with `max_error`, inlier (S, N) uint8: 1 where the row's error is < max_error under
+        the set's values, 2 for the set's own rows."""
+        handle = self._handle()
+        cams = _arr(cams, np.float64)
+        if cams.shape != (self.n_cams, CAM_LEN):
+            raise ValueError(f"expected camera vectors ({self.n_cams}, {CAM_LEN}), got {cams.shape}")
+        slots = _arr(slots, np.int32)
+        if slots.ndim != 1:
+            raise ValueError("slots (p,)")
+        x0, lb, ub, x_scale = (_arr(v, np.float64, slots.shape) for v in (x0, lb, ub, x_scale))
+        set_offset, set_rows = _arr(set_offset, np.int64), _arr(set_rows, np.int64)
+        n_rows, n_sets = int(self.rows.sum()), len(set_offset) - 1
+        if set_offset.ndim != 1 or n_sets < 0 or set_rows.ndim != 1 or len(set_rows) < set_offset.max(initial=0):
+            raise ValueError("set_offset (S + 1,) and set_rows (set_offset.max(),)")
+        if weights is not None:
+            weights = _arr(weights, np.float64, (n_rows, 2))
+        if observed is not None:
+            observed = _arr(observed, np.float64, (n_rows, 2))
+        score = max_error is not None
+        x, status, mean_error = np.empty((n_sets, len(slots))), np.empty(n_sets, np.int32), np.empty(n_sets)
+        inlier = np.empty((n_sets, n_rows), np.uint8) if score else None
+        times = np.zeros(len(CALIB_FIT_TIMES))
+        check(load().glh_calib_fit_sets(
+            handle, _ptr(cams), int(fit_cam), len(slots), _ptr(slots), _ptr(x0), _ptr(lb), _ptr(ub), _ptr(x_scale),
+            _ptr(weights), _ptr(observed), n_sets, _ptr(set_offset), _ptr(set_rows),
+            int(100 * len(slots) if max_nfev is None else max_nfev), float(ftol), float(xtol), float(gtol), int(score),
+            float(max_error) if score else 0.0, _ptr(x), _ptr(status), _ptr(mean_error), _ptr(inlier) if score else None,
+            _ptr(times)))
+        out = (x, status, mean_error, inlier) if score else (x, status, mean_error)
+        return _timed(out, CALIB_FIT_TIMES, times, return_times)
 
+
+CALIB_FIT_TIMES = ("upload", "fit", "score", "download")
+CALIB_FIT_STATUS = {1: "gtol", 2: "ftol", 3: "xtol", 0: "the evaluation cap was reached", -1: "fewer residuals than parameters",
+                    -2: "the cost is not finite", -3: "the system is singular"}
 MATCH_TIMES = ("upload", "prepare", "search", "merge", "download")
 MATCH_U8, MATCH_F32 = 0, 1
 MATCH_U8_MAX_DIM = 256  # csrc/glh_match.h

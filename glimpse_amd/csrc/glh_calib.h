@@ -1,4 +1,4 @@
-// glh_calib.h -- what glimpse_hip.hip (the C ABI: glh_calib_create / _eval / _destroy) hands to glh_calib.hip (the
+// glh_calib.h -- what glimpse_hip.hip (the C ABI: glh_calib_create / _eval / _fit_sets / _destroy) hands to glh_calib.hip (the
 // predictions of the controls of optimize.Cameras -- Points, Lines and the match classes -- under many sets of camera
 // vectors at once).  Host-only declarations.
 #pragma once
@@ -12,6 +12,8 @@ namespace glh {
 constexpr int CAL_TIMES = 5;   // entries of times_ms (include/glimpse_hip.h)
 constexpr int CAL_TB = 256;    // threads of a workgroup, all three kernels
 constexpr int CAL_TILE = 256;  // projected points of a Lines job held in LDS at a time (tests/calib_restated.py: TILE)
+constexpr int CAL_FIT_TIMES = 4;  // entries of glh_calib_fit_sets' times_ms
+constexpr int CAL_FIT_TB = 128;   // threads of k_calib_fit's workgroup: the rows of a set it takes at a time
 
 struct CamDev;
 
@@ -44,11 +46,33 @@ struct CalibEval {
   double* times_ms;
 };
 
+struct CalibFit {  // glh_calib_fit_sets' arguments (include/glimpse_hip.h), the cameras expanded by the caller
+  const CamDev* cams;  // [n_cams]
+  const double* base;  // the fitted camera's vector [GLH_CAM_LEN]
+  int fit_cam, p;
+  const int32_t* slots;                  // [p]
+  const double *x0, *lb, *ub, *scale;    // [p]
+  const double* weights;                 // [N][2] or null
+  const double* observed;                // [N][2] or null: the handle's obs
+  int n_sets;
+  const int64_t *set_offset, *set_rows;  // [n_sets + 1], [set_offset[n_sets]]
+  int max_nfev;
+  double ftol, xtol, gtol;
+  int score;
+  double max_error;
+  double* x;           // [n_sets][p]
+  int32_t* status;     // [n_sets]
+  double* mean_error;  // [n_sets]
+  uint8_t* inlier;     // [n_sets][N] when score
+  double* times_ms;
+};
+
 // The arguments have been checked (glimpse_hip.hip).  A GLH_* status, with the message left for glh_last_error() on
 // failure (glh_stage.h: fail).
 int calib_create(int device, const CalibControls& c, glh_calib** out);
 CalibTable calib_table(const glh_calib* h);
 int calib_eval(glh_calib* h, const CalibEval& e);
+int calib_fit_sets(glh_calib* h, const CalibFit& f);
 void calib_destroy(glh_calib* h);
 
 }  // namespace glh

@@ -26,6 +26,19 @@
 //
 // float64, no contraction (-ffp-contract=off), no atomics: two evaluations give the same bytes, and
 // tests/calib_restated.py restates the Lines path in NumPy bit for bit.
+//
+// glh_calib_fit_sets (optimize.ransac(batched=True)) fits one camera's parameters to many sets of rows in one call:
+//
+//   k_calib_fit, one workgroup per set: a damped Gauss-Newton whose residuals and forward-difference columns come from
+//   calib_row, the device function k_calib_rows runs, under cameras rebuilt on the device from the stepped vector; J^T J
+//   and J^T r are summed within each wave, then over the waves and the tiles in a fixed order; the p x p solve, the
+//   damping and the clamp into the bounds are glh_lm.h's, run by thread 0.  Every loop is bounded.
+//
+//   k_calib_score, one thread per (set, row) over all rows of the handle: |weighted residual| < max_error under the set's
+//   fitted values; k_calib_members then marks the set's own rows.
+//
+// These are not NumPy's bits (the rotation matrix is the device's) and need not be: the values optimize.ransac returns
+// come from the host's fit on the set the device picked.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -36,6 +49,7 @@
 #include "../../include/glimpse_hip.h"
 #include "glh_math.h"
 #include "glh_calib.h"
+#include "glh_lm.h"
 #include "glh_stage.h"
 
 namespace glh {
@@ -63,34 +77,26 @@ struct CalBlock {
   int32_t job, first;
 };
 
-__global__ void __launch_bounds__(CAL_TB) k_calib_rows(const CalBlock* __restrict__ blocks, const CalJob* __restrict__ jobs,
-                                                       const CamDev* __restrict__ cams, const double* __restrict__ rot,
-                                                       const double2* __restrict__ obs, const double* __restrict__ src,
-                                                       double2* __restrict__ out) {
-  const CalBlock b = blocks[blockIdx.x];
-  const CalJob j = jobs[b.job];
-  const int r = b.first + (int)threadIdx.x;
-  if (r >= j.n_rows) return;
-  const CamDev& ct = cams[j.cam_t];
+// `predicted` of one row of a Points or match control: what k_calib_rows stores and what k_calib_fit and k_calib_score
+// take their residuals from.  ct, co: the camera that predicts and the other one of a match; Rt, Ro: their rotation
+// matrices as the ROTATION kinds multiply by them.
+__device__ __forceinline__ void calib_row(int kind, int directions, int side, const CamDev& ct, const CamDev& co, const double* Rt,
+                                          const double* Ro, const double2* __restrict__ obs, const double* __restrict__ src,
+                                          size_t row, double& u, double& v) {
   const uint32_t ft = cam_flags(ct);
-  const size_t row = (size_t)j.row0 + r;
-  double u, v;
-  if (j.kind == GLH_CALIB_POINTS) {
-    project_f(ct, ft | (j.directions ? CAM_F_DIRECTIONS : 0u), src[3 * row], src[3 * row + 1], src[3 * row + 2], u, v);
+  if (kind == GLH_CALIB_POINTS) {
+    project_f(ct, ft | (directions ? CAM_F_DIRECTIONS : 0u), src[3 * row], src[3 * row + 1], src[3 * row + 2], u, v);
   } else {
     // the other camera's points: the second side's are kept in src[.][0:2], the first side's are the observed ones
-    const double x = j.side == 0 ? src[3 * row] : obs[row].x, y = j.side == 0 ? src[3 * row + 1] : obs[row].y;
+    const double x = side == 0 ? src[3 * row] : obs[row].x, y = side == 0 ? src[3 * row + 1] : obs[row].y;
     double d[3];
-    if (j.kind == GLH_CALIB_MATCHES) {
-      const CamDev& co = cams[j.cam_o];
+    if (kind == GLH_CALIB_MATCHES) {
       unproject(co, cam_flags(co), x, y, 1.0, 1, d);
     } else {
-      const double* __restrict__ Ro = rot + 9 * (size_t)j.cam_o;  // Camera._xy_to_xyz (camera.py:1486-1492)
-      for (int k = 0; k < 3; ++k) d[k] = (Ro[k] * x + Ro[3 + k] * y) + Ro[6 + k];
+      for (int k = 0; k < 3; ++k) d[k] = (Ro[k] * x + Ro[3 + k] * y) + Ro[6 + k];  // Camera._xy_to_xyz (camera.py:1486-1492)
     }
-    if (j.kind == GLH_CALIB_ROTATION_XY) {
-      const double* __restrict__ Rt = rot + 9 * (size_t)j.cam_t;  // Camera._xyz_to_xy (camera.py:1435-1470), directions
-      double c[3];
+    if (kind == GLH_CALIB_ROTATION_XY) {
+      double c[3];  // Camera._xyz_to_xy (camera.py:1435-1470), directions
       for (int k = 0; k < 3; ++k) c[k] = Rt[3 * k] * d[0] + Rt[3 * k + 1] * d[1] + Rt[3 * k + 2] * d[2];
       u = c[0] / c[2];
       v = c[1] / c[2];
@@ -99,6 +105,19 @@ __global__ void __launch_bounds__(CAL_TB) k_calib_rows(const CalBlock* __restric
       project_f(ct, ft | CAM_F_DIRECTIONS, d[0], d[1], d[2], u, v);
     }
   }
+}
+
+__global__ void __launch_bounds__(CAL_TB) k_calib_rows(const CalBlock* __restrict__ blocks, const CalJob* __restrict__ jobs,
+                                                       const CamDev* __restrict__ cams, const double* __restrict__ rot,
+                                                       const double2* __restrict__ obs, const double* __restrict__ src,
+                                                       double2* __restrict__ out) {
+  const CalBlock b = blocks[blockIdx.x];
+  const CalJob j = jobs[b.job];
+  const int r = b.first + (int)threadIdx.x;
+  if (r >= j.n_rows) return;
+  double u, v;
+  calib_row(j.kind, j.directions, j.side, cams[j.cam_t], cams[j.cam_o], rot + 9 * (size_t)j.cam_t, rot + 9 * (size_t)j.cam_o, obs,
+            src, (size_t)j.row0 + r, u, v);
   out[(size_t)j.out0 + r] = make_double2(u, v);
 }
 
@@ -183,6 +202,323 @@ __global__ void __launch_bounds__(CAL_TB) k_calib_nearest(const CalBlock* __rest
   if (live) out[(size_t)j.out0 + r] = pj[index];
 }
 
+// ---- the batched fit: one workgroup fits the fitted camera's parameters to one set of rows ----------------------------
+struct CalCtl {
+  int32_t kind, directions, cam_a, cam_b;
+};
+
+constexpr int FIT_WAVES = CAL_FIT_TB / 64;
+constexpr int FIT_MAX_E = LM_MAX_TRI + LM_MAX_P + 3;  // the sums of one evaluation: A's triangle, g, sum r r, rows, sum |r|
+constexpr int FIT_RUNNING = 100;                     // (no LM_* status)
+
+struct FitArgs {
+  const CamDev* cams;          // [n_cams] the cameras at their own vectors
+  const CalCtl* ctl;           // [n_controls]
+  const int32_t* row_ctl;      // [N] the control of every row
+  const double2* obs;
+  const double* src;
+  const double2* observed;     // [N] what the predictions are compared with: obs, or the caller's
+  const double2* weights;      // [N], or null
+  const int64_t* set_offset;   // [S + 1]
+  const int32_t* set_rows;
+  double* x;                   // [S][p]
+  int32_t* status;             // [S]
+  double* mean_error;          // [S]
+  double base[GLH_CAM_LEN];    // the fitted camera's vector
+  double x0[LM_MAX_P], lb[LM_MAX_P], ub[LM_MAX_P], scale[LM_MAX_P];
+  int32_t slot[LM_MAX_P];
+  int32_t fit_cam, p, max_nfev, n_rows;
+  double ftol, xtol, gtol;
+};
+
+struct FitShared {
+  CamDev cam[LM_MAX_P + 1];                // the fitted camera at the point and with each parameter stepped
+  double vec[LM_MAX_P + 1][GLH_CAM_LEN];
+  double J[2][LM_MAX_P + 1][CAL_FIT_TB];   // [u, v][column, the last is r][thread]: a thread reads its own entries only
+  double part[FIT_WAVES][FIT_MAX_E];       // the waves' sums of one tile
+  double acc[FIT_MAX_E];                   // the sums of the last evaluation
+  double tri[LM_MAX_TRI], g[LM_MAX_P];     // A and g at x
+  double x[LM_MAX_P], xt[LM_MAX_P], dx[LM_MAX_P], y[LM_MAX_P];
+  double M[LM_MAX_P * LM_MAX_P], b[LM_MAX_P];
+  double cost, lambda, err_sum, count, len2;
+  int32_t state, rejects;
+};
+static_assert(sizeof(FitShared) <= 64 * 1024, "k_calib_fit's LDS");
+
+// glh_host.h's expand_camera (camera.py:239-280) on the device, for a camera that is not a raster grid: the rotation
+// matrix comes from the device's own cos and sin, so it is not NumPy's to the bit (the values that leave optimize.ransac
+// come from the host's fit).
+__device__ void camera_from_vector(const double* v, CamDev* c) {
+  const double d2r = M_PI / 180.0;
+  double C[3], S[3];
+  for (int i = 0; i < 3; ++i) {
+    const double r = v[3 + i] * d2r;
+    C[i] = cos(r);
+    S[i] = sin(r);
+    c->xyz[i] = v[i];
+  }
+  c->R[0] = C[0] * C[2] + S[0] * S[1] * S[2];
+  c->R[1] = C[0] * S[1] * S[2] - C[2] * S[0];
+  c->R[2] = -C[1] * S[2];
+  c->R[3] = C[2] * S[0] * S[1] - C[0] * S[2];
+  c->R[4] = S[0] * S[2] + C[0] * C[2] * S[1];
+  c->R[5] = -C[1] * C[2];
+  c->R[6] = C[1] * S[0];
+  c->R[7] = C[0] * C[1];
+  c->R[8] = S[1];
+  for (int i = 0; i < 2; ++i) {
+    c->imgsz[i] = v[6 + i];
+    c->f[i] = v[8 + i];
+    c->off[i] = v[6 + i] / 2 + v[10 + i];
+    c->p[i] = v[18 + i];
+  }
+  c->any_k = c->any_kden = 0;
+  for (int i = 0; i < 6; ++i) {
+    c->k[i] = v[12 + i];
+    if (v[12 + i] != 0.0) {
+      c->any_k = 1;
+      if (i >= 3) c->any_kden = 1;
+    }
+  }
+  c->any_p = (c->p[0] != 0.0 || c->p[1] != 0.0) ? 1 : 0;
+  c->has_corr = v[20] != 0.0;
+  c->radius = v[21];
+  c->refraction = v[22];
+  c->is_grid = 0;
+  c->pad_ = 0;
+}
+
+// The weighted residual of global row `row` with `fitted` in the fitted camera's place.
+__device__ __forceinline__ void fit_residual(const FitArgs& a, const CamDev& fitted, size_t row, double& ru, double& rv) {
+  const CalCtl c = a.ctl[a.row_ctl[row]];
+  const CamDev& ct = c.cam_a == a.fit_cam ? fitted : a.cams[c.cam_a];
+  const CamDev& co = c.cam_b == a.fit_cam ? fitted : a.cams[c.cam_b];
+  double u, v;
+  calib_row(c.kind, c.directions, 0, ct, co, ct.R, co.R, a.obs, a.src, row, u, v);
+  const double2 o = a.observed[row];
+  ru = u - o.x;
+  rv = v - o.y;
+  if (a.weights) {
+    const double2 w = a.weights[row];
+    ru = ru * w.x;
+    rv = rv * w.y;
+  }
+}
+
+// The sum over the wave, in the order of the butterfly: every lane ends with the same bits.
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// s.acc = the sums over the set's rows at the point xe (an array of s): A = J^T J (packed), g = J^T r, sum r r, the rows
+// that count and sum |r|, J in scaled variables by forward differences.  A row whose prediction is NaN at the point or
+// at a stepped point adds nothing.  Every thread of the workgroup calls this.
+__device__ void fit_evaluate(const FitArgs& a, FitShared& s, const double* xe, const int32_t* __restrict__ rows, int n) {
+  const int tid = (int)threadIdx.x, p = a.p;
+  const int nE = p * (p + 1) / 2 + p + 3;
+  __syncthreads();  // (xe is written, the last evaluation's sums are read)
+  if (tid <= p) {
+    double* v = s.vec[tid];
+    for (int k = 0; k < GLH_CAM_LEN; ++k) v[k] = a.base[k];
+    for (int i = 0; i < p; ++i) v[a.slot[i]] = xe[i];
+    if (tid > 0) {
+      const int i = tid - 1;
+      const double stepped = xe[i] + lm_fd_step(xe[i], a.lb[i], a.ub[i]);
+      v[a.slot[i]] = stepped;
+      s.dx[i] = stepped - xe[i];
+    }
+    camera_from_vector(v, &s.cam[tid]);
+  }
+  __syncthreads();
+  double sum[2] = {0.0, 0.0};  // entries tid and tid + CAL_FIT_TB
+  for (int first = 0; first < n; first += CAL_FIT_TB) {
+    const int k = first + tid;
+    bool ok = k < n;
+    double ru = 0.0, rv = 0.0;
+    if (ok) {
+      const size_t row = (size_t)rows[k];
+      fit_residual(a, s.cam[0], row, ru, rv);
+      ok = !(isnan(ru) || isnan(rv));
+      for (int j = 0; j < p; ++j) {
+        double su, sv;
+        fit_residual(a, s.cam[j + 1], row, su, sv);
+        const double ju = (su - ru) / s.dx[j] * a.scale[j], jv = (sv - rv) / s.dx[j] * a.scale[j];
+        ok = ok && !(isnan(ju) || isnan(jv));
+        s.J[0][j][tid] = ju;
+        s.J[1][j][tid] = jv;
+      }
+    }
+    if (!ok) {
+      ru = rv = 0.0;
+      for (int j = 0; j < p; ++j) s.J[0][j][tid] = s.J[1][j][tid] = 0.0;
+    }
+    s.J[0][p][tid] = ru;
+    s.J[1][p][tid] = rv;
+    const int wave = tid >> 6, lane = tid & 63;
+    int e = 0;
+    for (int i = 0; i < p; ++i)  // A's upper triangle row by row (lm_tri), then g: column p is r
+      for (int j = i; j < p; ++j, ++e) {
+        const double t = wave_sum(s.J[0][i][tid] * s.J[0][j][tid] + s.J[1][i][tid] * s.J[1][j][tid]);
+        if (lane == 0) s.part[wave][e] = t;
+      }
+    for (int i = 0; i <= p; ++i, ++e) {  // (the last of these is sum r r)
+      const double t = wave_sum(s.J[0][i][tid] * ru + s.J[1][i][tid] * rv);
+      if (lane == 0) s.part[wave][e] = t;
+    }
+    {
+      const double t = wave_sum(ok ? 1.0 : 0.0), h = wave_sum(ok ? hypot(ru, rv) : 0.0);
+      if (lane == 0) s.part[wave][e] = t, s.part[wave][e + 1] = h;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const int w = tid + q * CAL_FIT_TB;
+      if (w < nE) {
+        double t = s.part[0][w];
+        for (int k2 = 1; k2 < FIT_WAVES; ++k2) t += s.part[k2][w];
+        sum[q] += t;
+      }
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int q = 0; q < 2; ++q)
+    if (tid + q * CAL_FIT_TB < nE) s.acc[tid + q * CAL_FIT_TB] = sum[q];
+  __syncthreads();
+}
+
+// s.state as every thread of the workgroup sees it between two writes of thread 0.
+__device__ __forceinline__ int fit_state(FitShared& s) {
+  __syncthreads();
+  const int v = s.state;
+  __syncthreads();
+  return v;
+}
+
+// Thread 0: the evaluation in s.acc becomes the state at x.
+__device__ void fit_keep(FitShared& s, int p) {
+  const int nT = p * (p + 1) / 2;
+  for (int e = 0; e < nT; ++e) s.tri[e] = s.acc[e];
+  for (int i = 0; i < p; ++i) s.g[i] = s.acc[nT + i];
+  s.cost = 0.5 * s.acc[nT + p];
+  s.count = s.acc[nT + p + 1];
+  s.err_sum = s.acc[nT + p + 2];
+}
+
+__global__ void __launch_bounds__(CAL_FIT_TB) k_calib_fit(const FitArgs a) {
+  static_assert(FIT_MAX_E <= 2 * CAL_FIT_TB, "two sums per thread");
+  __shared__ FitShared s;
+  const int tid = (int)threadIdx.x, p = a.p, set = (int)blockIdx.x;
+  const int nT = p * (p + 1) / 2;
+  const int32_t* __restrict__ rows = a.set_rows + a.set_offset[set];
+  const int n = (int)(a.set_offset[set + 1] - a.set_offset[set]);
+  if (tid == 0) {
+    for (int i = 0; i < p; ++i) s.x[i] = a.x0[i];
+    s.lambda = LM_LAMBDA_START;
+    s.state = FIT_RUNNING;
+    s.rejects = 0;
+  }
+  fit_evaluate(a, s, s.x, rows, n);
+  if (tid == 0) {
+    fit_keep(s, p);
+    if (2.0 * s.count < (double)p)
+      s.state = LM_FEW_ROWS;
+    else if (!(s.cost < INFINITY))
+      s.state = LM_NOT_FINITE;
+  }
+  // one trial step per round: at most max_nfev rounds, whatever the residuals do
+  for (int it = 0; it < a.max_nfev; ++it) {
+    if (fit_state(s) != FIT_RUNNING) break;
+    if (tid == 0) {
+      uint32_t frozen = 0;
+      double gmax = 0.0;
+      for (int i = 0; i < p; ++i) {
+        if (lm_frozen(s.x[i], a.lb[i], a.ub[i], s.g[i]))
+          frozen |= 1u << i;
+        else
+          gmax = fmax(gmax, fabs(s.g[i]));
+      }
+      if (!(gmax >= a.gtol)) {
+        s.state = gmax == gmax ? LM_GTOL : LM_NOT_FINITE;
+      } else {
+        lm_system(p, s.tri, s.g, s.lambda, frozen, s.M, s.b);
+        if (!lm_solve(p, s.M, s.b)) {
+          s.state = LM_SINGULAR;
+        } else {
+          for (int i = 0; i < p; ++i) s.y[i] = s.b[i];
+          s.len2 = lm_clamp(p, s.x, a.scale, a.lb, a.ub, s.y, s.xt);
+          if (s.len2 == 0.0) s.state = LM_XTOL;
+        }
+      }
+    }
+    if (fit_state(s) != FIT_RUNNING) break;
+    fit_evaluate(a, s, s.xt, rows, n);
+    if (tid == 0) {
+      const double count = s.acc[nT + p + 1], cost = 0.5 * s.acc[nT + p];
+      double norm2 = 0.0;
+      for (int i = 0; i < p; ++i) norm2 += (s.x[i] / a.scale[i]) * (s.x[i] / a.scale[i]);
+      const bool is_short = sqrt(s.len2) < a.xtol * (a.xtol + sqrt(norm2));
+      // (a step that lowers the cost by losing rows -- points it pushes behind the camera -- is no improvement)
+      const bool accepted = count >= s.count && cost < s.cost;
+      s.lambda = lm_damping(s.lambda, accepted);
+      if (accepted) {
+        const double before = s.cost;
+        for (int i = 0; i < p; ++i) s.x[i] = s.xt[i];
+        fit_keep(s, p);
+        s.rejects = 0;
+        if (before - s.cost < a.ftol * before)
+          s.state = LM_FTOL;
+        else if (is_short)
+          s.state = LM_XTOL;
+      } else if (is_short) {
+        s.state = LM_XTOL;
+      } else if (++s.rejects >= LM_MAX_REJECT) {
+        s.state = LM_CAP;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    const int32_t status = s.state == FIT_RUNNING ? (int32_t)LM_CAP : s.state;
+    for (int i = 0; i < p; ++i) a.x[(size_t)set * p + i] = s.x[i];
+    a.status[set] = status;
+    // np.mean over the set's own rows: NaN as soon as one of them has no prediction
+    a.mean_error[set] = (status > 0 && s.count == (double)n) ? s.err_sum / s.count : NAN;
+  }
+}
+
+// inlier[set][row] = |weighted residual| < max_error under the set's fitted values, for every row of the handle: one
+// thread per (set, row), a workgroup within one set.  NaN is no inlier; a set whose fit failed has none.
+__global__ void __launch_bounds__(CAL_TB) k_calib_score(const FitArgs a, int blocks_per_set, double max_error,
+                                                        uint8_t* __restrict__ inlier) {
+  __shared__ CamDev cam;
+  __shared__ double vec[GLH_CAM_LEN];
+  const int set = (int)(blockIdx.x / (unsigned)blocks_per_set);
+  const int row = (int)(blockIdx.x % (unsigned)blocks_per_set) * CAL_TB + (int)threadIdx.x;
+  if (threadIdx.x == 0) {
+    for (int k = 0; k < GLH_CAM_LEN; ++k) vec[k] = a.base[k];
+    for (int i = 0; i < a.p; ++i) vec[a.slot[i]] = a.x[(size_t)set * a.p + i];
+    camera_from_vector(vec, &cam);
+  }
+  __syncthreads();
+  if (row >= a.n_rows) return;
+  uint8_t in = 0;
+  if (a.status[set] > 0) {
+    double ru, rv;
+    fit_residual(a, cam, (size_t)row, ru, rv);
+    in = hypot(ru, rv) < max_error ? 1 : 0;
+  }
+  inlier[(size_t)set * a.n_rows + row] = in;
+}
+
+// The set's own rows are its members (2), whatever their error: after k_calib_score on the same stream.
+__global__ void __launch_bounds__(CAL_TB) k_calib_members(const FitArgs a, uint8_t* __restrict__ inlier) {
+  const int set = (int)blockIdx.x;
+  const int64_t first = a.set_offset[set], last = a.set_offset[set + 1];
+  for (int64_t k = first + threadIdx.x; k < last; k += CAL_TB) inlier[(size_t)set * a.n_rows + a.set_rows[k]] = 2;
+}
+
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -196,6 +532,10 @@ struct glh_calib : glh::DeviceObject {
   glh::GrowBuf in, puv, out;  // (they only grow: the evaluations of a fit are all of one size)
   glh::StageEvents<glh::CAL_TIMES + 1> ev;
   std::vector<char> stage;
+  // the batched fit (calib_fit_sets): the control of every row and the controls' table, uploaded with the controls
+  glh::DevBuf ctl, row_ctl;
+  glh::GrowBuf fit_in, fit_out;
+  glh::StageEvents<glh::CAL_FIT_TIMES + 1> fit_ev;
 };
 
 namespace glh {
@@ -212,6 +552,15 @@ static int calib_fill(glh_calib* h, const CalibControls& c) {
   const double none[3] = {0.0, 0.0, 0.0};
   CHK(h->obs.up(N ? c.obs : none, (N ? N : 1) * 16));
   CHK(h->src.up(N ? c.src : none, (N ? N : 1) * 24));
+  CHK(h->fit_ev.create());
+  std::vector<CalCtl> ctl((size_t)c.n_controls + 1);  // (one more: an empty table still has an address)
+  std::vector<int32_t> row_ctl(N ? N : 1, 0);
+  for (int k = 0; k < c.n_controls; ++k) {
+    ctl[k] = CalCtl{c.kind[k], c.directions[k], c.cam_a[k], c.cam_b[k]};
+    for (int64_t r = c.row_offset[k]; r < c.row_offset[k + 1]; ++r) row_ctl[(size_t)r] = k;
+  }
+  CHK(h->ctl.up(ctl.data(), ctl.size() * sizeof(CalCtl)));
+  CHK(h->row_ctl.up(row_ctl.data(), row_ctl.size() * sizeof(int32_t)));
   return GLH_OK;
 }
 
@@ -336,6 +685,92 @@ int calib_eval(glh_calib* h, const CalibEval& e) {
   CHK(h->ev.record(5, s));
   HIPCHK(hipEventSynchronize(h->ev.e[5]));
   h->ev.report(e.times_ms, CAL_TIMES, CAL_TIMES);
+  return GLH_OK;
+}
+
+int calib_fit_sets(glh_calib* h, const CalibFit& f) {
+  CHK(h->use());
+  hipStream_t s = h->stream;
+  const size_t N = (size_t)h->row_offset[h->n_controls], S = (size_t)f.n_sets, T = (size_t)f.set_offset[f.n_sets];
+  const size_t p = (size_t)f.p;
+  // in: the cameras, the weights, the sets; out: x, mean_error, status, inlier
+  size_t at = 0;
+  const size_t i_cams = at;
+  at = align16(at + (size_t)h->n_cams * sizeof(CamDev));
+  const size_t i_weights = at;
+  at = align16(at + (f.weights ? N * 16 : 0));
+  const size_t i_observed = at;
+  at = align16(at + (f.observed ? N * 16 : 0));
+  const size_t i_offset = at;
+  at = align16(at + (S + 1) * 8);
+  const size_t i_rows = at;
+  at = align16(at + T * 4);
+  h->stage.resize(at);
+  char* st = h->stage.data();
+  std::memcpy(st + i_cams, f.cams, (size_t)h->n_cams * sizeof(CamDev));
+  if (f.weights) std::memcpy(st + i_weights, f.weights, N * 16);
+  if (f.observed) std::memcpy(st + i_observed, f.observed, N * 16);
+  std::memcpy(st + i_offset, f.set_offset, (S + 1) * 8);
+  int32_t* rows = reinterpret_cast<int32_t*>(st + i_rows);
+  for (size_t k = 0; k < T; ++k) rows[k] = (int32_t)f.set_rows[k];
+  size_t ot = 0;
+  const size_t o_x = ot;
+  ot = align16(ot + S * p * 8);
+  const size_t o_mean = ot;
+  ot = align16(ot + S * 8);
+  const size_t o_status = ot;
+  ot = align16(ot + S * 4);
+  const size_t o_inlier = ot;
+  ot = align16(ot + (f.score ? S * N : 0));
+  CHK(h->fit_in.reserve(h->stage.size()));
+  CHK(h->fit_out.reserve(ot));
+  CHK(h->fit_ev.record(0, s));
+  HIPCHK(hipMemcpy(h->fit_in.p, st, h->stage.size(), hipMemcpyHostToDevice));
+  CHK(h->fit_ev.record(1, s));
+  const char* d = h->fit_in.as<char>();
+  char* o = h->fit_out.as<char>();
+  FitArgs a{};
+  a.cams = reinterpret_cast<const CamDev*>(d + i_cams);
+  a.ctl = h->ctl.as<CalCtl>();
+  a.row_ctl = h->row_ctl.as<int32_t>();
+  a.obs = h->obs.as<double2>();
+  a.src = h->src.as<double>();
+  a.weights = f.weights ? reinterpret_cast<const double2*>(d + i_weights) : nullptr;
+  a.observed = f.observed ? reinterpret_cast<const double2*>(d + i_observed) : h->obs.as<double2>();
+  a.set_offset = reinterpret_cast<const int64_t*>(d + i_offset);
+  a.set_rows = reinterpret_cast<const int32_t*>(d + i_rows);
+  a.x = reinterpret_cast<double*>(o + o_x);
+  a.status = reinterpret_cast<int32_t*>(o + o_status);
+  a.mean_error = reinterpret_cast<double*>(o + o_mean);
+  std::memcpy(a.base, f.base, sizeof(a.base));
+  for (size_t i = 0; i < p; ++i)
+    a.x0[i] = f.x0[i], a.lb[i] = f.lb[i], a.ub[i] = f.ub[i], a.scale[i] = f.scale[i], a.slot[i] = f.slots[i];
+  a.fit_cam = f.fit_cam, a.p = f.p, a.max_nfev = f.max_nfev, a.n_rows = (int32_t)N;
+  a.ftol = f.ftol, a.xtol = f.xtol, a.gtol = f.gtol;
+  if (S) {
+    hipLaunchKernelGGL(k_calib_fit, dim3((unsigned)S), dim3(CAL_FIT_TB), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(h->fit_ev.record(2, s));
+  if (S && N && f.score) {
+    const int blocks_per_set = (int)((N + CAL_TB - 1) / CAL_TB);
+    uint8_t* inlier = reinterpret_cast<uint8_t*>(o + o_inlier);
+    hipLaunchKernelGGL(k_calib_score, dim3((unsigned)(S * (size_t)blocks_per_set)), dim3(CAL_TB), 0, s, a, blocks_per_set,
+                       f.max_error, inlier);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_calib_members, dim3((unsigned)S), dim3(CAL_TB), 0, s, a, inlier);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(h->fit_ev.record(3, s));
+  if (S) {
+    HIPCHK(hipMemcpy(f.x, o + o_x, S * p * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f.mean_error, o + o_mean, S * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f.status, o + o_status, S * 4, hipMemcpyDeviceToHost));
+    if (N && f.score) HIPCHK(hipMemcpy(f.inlier, o + o_inlier, S * N, hipMemcpyDeviceToHost));
+  }
+  CHK(h->fit_ev.record(4, s));
+  HIPCHK(hipEventSynchronize(h->fit_ev.e[4]));
+  h->fit_ev.report(f.times_ms, CAL_FIT_TIMES, CAL_FIT_TIMES);
   return GLH_OK;
 }
 

@@ -3113,6 +3113,79 @@ extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams,
   return calib_eval(handle, e);
 }
 
+// optimize.ransac(batched=True): every row set fitted, and scored, in one call.  Checked here, before a device is touched.
+extern "C" int glh_calib_fit_sets(glh_calib* handle, const double* cams, int fit_cam, int p, const int32_t* slots,
+                                  const double* x0, const double* lb, const double* ub, const double* x_scale,
+                                  const double* weights, const double* observed, int n_sets, const int64_t* set_offset,
+                                  const int64_t* set_rows,
+                                  int max_nfev, double ftol, double xtol, double gtol, int score, double max_error, double* x,
+                                  int32_t* status, double* mean_error, uint8_t* inlier, double* times_ms) {
+  if (!handle) return fail(GLH_E_INVALID, "calib fit: null handle");
+  const CalibTable table = calib_table(handle);
+  const int64_t N = table.row_offset[table.n_controls];
+  if (!cams || !slots || !x0 || !lb || !ub || !x_scale || !set_offset || !x || !status || !mean_error)
+    return fail(GLH_E_INVALID, "calib fit: null argument");
+  if (fit_cam < 0 || fit_cam >= table.n_cams) return fail(GLH_E_INVALID, "calib fit: camera %d of %d", fit_cam, table.n_cams);
+  if (p < 1 || p > 18) return fail(GLH_E_INVALID, "calib fit: %d parameters: 1 .. 18 are served", p);
+  uint32_t seen = 0;
+  for (int i = 0; i < p; ++i) {
+    // (imgsz, entries 6 and 7, is no parameter: optimize.Cameras' masks never hold it)
+    if (slots[i] < 0 || slots[i] >= 20 || slots[i] == 6 || slots[i] == 7 || ((seen >> slots[i]) & 1u))
+      return fail(GLH_E_INVALID, "calib fit: parameter %d is entry %d of the camera vector: distinct ones of 0 .. 5, 8 .. 19", i,
+                  slots[i]);
+    seen |= 1u << slots[i];
+    if (!(lb[i] <= x0[i] && x0[i] <= ub[i]) || !(std::fabs(x0[i]) < INFINITY))
+      return fail(GLH_E_INVALID, "calib fit: parameter %d starts at %g outside its bounds %g .. %g", i, x0[i], lb[i], ub[i]);
+    if (!(lb[i] < ub[i]))  // (as scipy.optimize.least_squares: no room for a difference step)
+      return fail(GLH_E_INVALID, "calib fit: parameter %d has the bounds %g .. %g: the lower one must be below the upper one", i,
+                  lb[i], ub[i]);
+    if (!(x_scale[i] > 0.0 && x_scale[i] < INFINITY)) return fail(GLH_E_INVALID, "calib fit: parameter %d has scale %g", i, x_scale[i]);
+  }
+  if (n_sets < 0 || n_sets >= (1 << 24)) return fail(GLH_E_INVALID, "calib fit: %d sets: fewer than 2^24 are served", n_sets);
+  if (max_nfev < 1 || !(ftol >= 0.0 && ftol < 1.0) || !(xtol >= 0.0 && xtol < 1.0) || !(gtol >= 0.0 && gtol < INFINITY))
+    return fail(GLH_E_INVALID, "calib fit: %d evaluations, ftol %g, xtol %g, gtol %g", max_nfev, ftol, xtol, gtol);
+  if (set_offset[0] != 0) return fail(GLH_E_INVALID, "calib fit: set_offset[0] is %lld, not 0", (long long)set_offset[0]);
+  for (int q = 0; q < n_sets; ++q)
+    if (set_offset[q + 1] < set_offset[q] || set_offset[q + 1] >= ((int64_t)1 << 31))
+      return fail(GLH_E_INVALID, "calib fit: set %d ends at row %lld after %lld: not decreasing, fewer than 2^31 rows in all", q,
+                  (long long)set_offset[q + 1], (long long)set_offset[q]);
+  const int64_t total = set_offset[n_sets];
+  if (total > 0 && !set_rows) return fail(GLH_E_INVALID, "calib fit: null set rows");
+  std::vector<char> is_lines((size_t)table.n_controls, 0);
+  bool any_lines = false;
+  for (int c = 0; c < table.n_controls; ++c) {
+    if (table.kind[c] == GLH_CALIB_ROTATION && table.row_offset[c + 1] > table.row_offset[c] && !observed)
+      return fail(GLH_E_INVALID, "calib fit: control %d is a ROTATION control, whose obs are camera coordinates: pass observed", c);
+    if (table.kind[c] == GLH_CALIB_LINES) {
+      is_lines[c] = 1;
+      if (table.row_offset[c + 1] > table.row_offset[c]) any_lines = true;
+    }
+  }
+  for (int64_t k = 0; k < total; ++k) {
+    const int64_t r = set_rows[k];
+    if (r < 0 || r >= N) return fail(GLH_E_INVALID, "calib fit: row %lld of %lld", (long long)r, (long long)N);
+    if (any_lines) {
+      const int c = (int)(std::upper_bound(table.row_offset, table.row_offset + table.n_controls + 1, r) - table.row_offset) - 1;
+      if (is_lines[c]) return fail(GLH_E_INVALID, "calib fit: row %lld belongs to control %d, a Lines control", (long long)r, c);
+    }
+  }
+  if (score) {
+    if (!inlier) return fail(GLH_E_INVALID, "calib fit: null inlier output");
+    if (!(max_error == max_error)) return fail(GLH_E_INVALID, "calib fit: max_error is NaN");
+    if (any_lines) return fail(GLH_E_INVALID, "calib fit: scoring covers every row, and the handle holds a Lines control");
+    if ((int64_t)n_sets * N >= ((int64_t)1 << 31))
+      return fail(GLH_E_INVALID, "calib fit: %d sets of %lld rows to score: fewer than 2^31 in all are served", n_sets, (long long)N);
+  }
+  std::vector<CamDev> cd((size_t)table.n_cams);
+  for (int i = 0; i < table.n_cams; ++i) {
+    if (cams[(size_t)i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "calib fit: camera %d is a raster grid", i);
+    expand_camera(cams + (size_t)i * GLH_CAM_LEN, &cd[i]);
+  }
+  const CalibFit f{cd.data(), cams + (size_t)fit_cam * GLH_CAM_LEN, fit_cam, p, slots, x0, lb, ub, x_scale, weights, observed,
+                   n_sets, set_offset, set_rows, max_nfev, ftol, xtol, gtol, score, max_error, x, status, mean_error, inlier, times_ms};
+  return calib_fit_sets(handle, f);
+}
+
 extern "C" int glh_calib_destroy(glh_calib* handle) {
   calib_destroy(handle);  // (nothing on null)
   return GLH_OK;

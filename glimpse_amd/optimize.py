@@ -36,6 +36,13 @@ for 8-bit input, pinned to the rule written out in INPUTS.md ("CLAHE: the rule")
 (tests/clahe_restated.py) in every bit.  The matcher hands the stage the image's channels, and their mean is formed on the
 device.  The reference's own forms (`clahe=True`, a `dict` for `cv2.createCLAHE`) are still refused.
 
+`ransac(model, ..., batched=True)` over a `Cameras` model with one fitted camera runs Random Sample Consensus with the loop
+over the samples on the GPU (`glh_calib_fit_sets`): one call fits every sample by a damped Gauss-Newton, one workgroup per
+sample, and scores every row under every fit; a second call refits every distinct consensus set.  The device only decides
+which set wins: the values returned come from `Cameras.fit` on that set, as on the host path (`batched=False`, the
+reference's loop, unchanged).  Point and match controls are served; everything else is refused, not run on the host
+(INPUTS.md, "Camera calibration").
+
 Not served: `cv2.SIFT` itself (the default `method` of `detect_keypoints` and `build_keypoints`), `cv2.createCLAHE` (`clahe=True`
 or a `dict`), a `mask` for the GPU matcher, the lmfit methods other than "least_squares" (lmfit is not a dependency) and
 plotting.
@@ -1606,10 +1613,18 @@ class Cameras:
         raise NotImplementedError(_NO_PLOT)
 
 
-def ransac(model, n, max_error, min_inliers, iterations=100, **kwargs):
+def ransac(model, n, max_error, min_inliers, iterations=100, batched=False, return_info=False, **kwargs):
     """optimize.py:2091-2150: (parameters, inlier indices) of `model` -- an object with `size`, `fit(index)` and
     `errors(params, index)` -- by Random Sample Consensus: fit to samples of `n`, keep the fit whose members within
-    `max_error` number more than `min_inliers` besides the sample and have the smallest mean error."""
+    `max_error` number more than `min_inliers` besides the sample and have the smallest mean error.
+
+    `batched`: the same answer with every sample fitted and scored in one device call and every distinct consensus set
+    refitted in a second one (`_ransac_batched`); the device decides which set wins, the values returned are
+    `model.fit`'s on that set.  `return_info` (with `batched`): a dict of what the device found is returned as well."""
+    if batched:
+        return _ransac_batched(model, n, max_error, min_inliers, iterations, return_info, kwargs)
+    if return_info:
+        raise ValueError("return_info describes the batched path: pass batched=True")
     params = None
     err = np.inf
     full = np.arange(model.size)
@@ -1633,6 +1648,131 @@ def ransac(model, n, max_error, min_inliers, iterations=100, **kwargs):
         raise ValueError("Best fit does not meet acceptance criteria")
     inliers = np.where(model.errors(params) <= max_error)[0]
     return params, inliers
+
+
+_BATCHED_KWARGS = ("ftol", "xtol", "gtol", "max_nfev", "nan_policy")
+
+
+def _batched_plan(model, kwargs):
+    """What `ransac(batched=True)` hands the device fit of `model`, or NotImplementedError naming what it does not serve
+    (there is no host fallback); made before any library call."""
+    no = "ransac(batched=True) does not serve "
+    if not isinstance(model, Cameras):
+        raise NotImplementedError(no + f"a {type(model).__name__} model: a Cameras model with one fitted camera")
+    if len(model.cams) != 1:
+        raise NotImplementedError(no + f"{len(model.cams)} fitted cameras: one")
+    if any(np.any(mask) for mask in model.group_masks):
+        raise NotImplementedError(no + "group_params: the parameters of one camera (cam_params)")
+    for key, value in kwargs.items():
+        if key not in _BATCHED_KWARGS or value is None or (key == "nan_policy" and value != "omit"):
+            raise NotImplementedError(no + f"{key}={value!r}: the device fit honours numbers for ftol, xtol, gtol and max_nfev "
+                                      "(and nan_policy='omit')")
+    slots = np.flatnonzero(model.cam_masks[0])
+    if not len(slots):
+        raise NotImplementedError(no + "a model without a parameter to fit")
+    cams = [model.cams[0]]
+    for control in model.controls:
+        if isinstance(control, Lines):
+            raise NotImplementedError(no + "a Lines control: Points and the match controls")
+        _kind_of(control)  # (RotationMatchesXYZ: NotImplementedError)
+        if isinstance(control, RotationMatches) and (slots >= 6).any():
+            raise NotImplementedError(no + "fitted internal parameters (f, c, k, p) under a RotationMatches control, whose "
+                                      "camera coordinates hold them fixed")
+        if (slots < 3).any() and (isinstance(control, Matches) or control.directions):
+            raise NotImplementedError(no + "a fitted position (xyz) under a match control or ray directions, which hold it fixed")
+        cams += [cam for cam in model._get_control_cams(control) if not any(cam is c for c in cams)]
+    for cam in cams:
+        if cam.vector24[23] != 0:
+            raise NotImplementedError(no + "a camera with a raster grid")
+    for control in model.controls:
+        model._job_table(control)  # (the checks `predicted` makes at the cameras' current state)
+    x0, lb, ub = model._values_bounds()
+    if np.any(lb >= ub):
+        raise ValueError("Each lower bound must be strictly less than each upper bound.")
+    if np.any((x0 < lb) | (x0 > ub)):
+        raise ValueError("`x0` violates bound constraints.")
+    scales = np.ones(len(slots)) if model.scales is None else np.asarray(model.scales, dtype=float)
+    weights = None if model.weights is None else np.ascontiguousarray(np.broadcast_to(model.weights, (model.size, 2)))
+    options = {key: kwargs[key] for key in ("ftol", "xtol", "gtol", "max_nfev") if key in kwargs}
+    # (a RotationMatches control keeps camera coordinates on the device and predicts image coordinates)
+    rotation = any(_kind_of(control) == _lib.CALIB_KINDS["rotation"] for control in model.controls)
+    observed = np.ascontiguousarray(model.observed(), dtype=float) if rotation else None
+    return dict(slots=slots, x0=x0, lb=lb, ub=ub, x_scale=scales, weights=weights, observed=observed, options=options)
+
+
+def _ransac_batched(model, n, max_error, min_inliers, iterations, return_info, kwargs):
+    """`ransac` with the loop over the samples on the device:
+
+    1. the samples H of `_ransac_samples`, drawn as the host path draws them (the same use of np.random);
+    2. ONE device call (`_lib.Calib.fit_sets`) fits every sample from the model's current values and scores all rows
+       under each fit: per hypothesis the values, a status and the consensus mask error < max_error outside the sample;
+    3. the hypotheses with more than `min_inliers` in consensus; sample and consensus as one set; equal sets merged, the
+       earliest hypothesis standing for its set;
+    4. ONE device call refits every distinct set and returns its mean error over its own rows;
+    5. the sets in order of mean error (ties to the earlier hypothesis): `model.fit(better_idx, **kwargs)` on the best,
+       `better_idx` built as the host path builds it; the next set if that fit fails.
+
+    The values returned are therefore scipy's, as on the host path; the device picks the set."""
+    import time
+
+    plan = _batched_plan(model, kwargs)
+    t = [time.perf_counter()]
+    samples = list(_ransac_samples(n=n, size=model.size, iterations=iterations))
+    set_offset = np.arange(len(samples) + 1, dtype=np.int64) * n
+    set_rows = np.array(samples, dtype=np.int64).reshape(-1)
+    fit = dict(fit_cam=0, slots=plan["slots"], x0=plan["x0"], lb=plan["lb"], ub=plan["ub"], x_scale=plan["x_scale"],
+               weights=plan["weights"], observed=plan["observed"], return_times=True, **plan["options"])
+    try:
+        handle = model.upload()
+        cams24 = np.array([cam.vector24 for cam in model._dev_cams])
+        t.append(time.perf_counter())
+        (values, status, _, inlier), times_fit = handle.fit_sets(cams24, set_offset=set_offset, set_rows=set_rows,
+                                                                 max_error=max_error, **fit)
+        t.append(time.perf_counter())
+        counts = (inlier == 1).sum(axis=1)
+        sets, owner = {}, []
+        for h in np.flatnonzero((status > 0) & (counts > min_inliers)):
+            members = np.flatnonzero(inlier[h])
+            if members.tobytes() not in sets:
+                sets[members.tobytes()] = members
+                owner.append(int(h))
+        sets = list(sets.values())
+        refit_offset = np.concatenate(([0], np.cumsum([len(rows) for rows in sets]))).astype(np.int64)
+        refit_rows = np.concatenate(sets) if sets else np.zeros(0, np.int64)
+        t.append(time.perf_counter())
+        (refit_values, refit_status, mean_errors), times_refit = handle.fit_sets(cams24, set_offset=refit_offset,
+                                                                                 set_rows=refit_rows, **fit)
+        t.append(time.perf_counter())
+    finally:
+        if model._handle is not None:
+            model._handle.close()
+            model._handle = None
+    # (a set whose refit failed, or with a row that has no prediction, is never chosen on the host path either)
+    order = [k for k in np.argsort(mean_errors, kind="stable") if refit_status[k] > 0 and not np.isnan(mean_errors[k])]
+    params, winner, full = None, None, np.arange(model.size)
+    for k in order:
+        maybe_idx = samples[owner[k]]
+        test_idx = np.delete(full, maybe_idx)
+        also_idx = test_idx[inlier[owner[k], test_idx] == 1]
+        better_idx = np.concatenate((maybe_idx, also_idx))
+        params = model.fit(better_idx, **kwargs)
+        if params is not None:
+            winner = int(k)
+            break
+    t.append(time.perf_counter())
+    if params is None:
+        raise ValueError("Best fit does not meet acceptance criteria")
+    inliers = np.where(model.errors(params) <= max_error)[0]
+    if not return_info:
+        return params, inliers
+    wall = np.diff(t) * 1e3
+    device = lambda d: d["fit"] + d["score"]  # noqa: E731
+    info = dict(values=values, status=status, consensus=counts, sets=sets, hypothesis=np.array(owner, dtype=int),
+                refit_values=refit_values, refit_status=refit_status, mean_errors=mean_errors, winner=winner,
+                times_ms=dict(upload=wall[0] + times_fit["upload"] + times_refit["upload"], fit_score=device(times_fit),
+                              refit=device(times_refit), download=times_fit["download"] + times_refit["download"],
+                              host=wall[2], final_fit=wall[4], calls=wall[1] + wall[3]))
+    return params, inliers, info
 
 
 def _ransac_samples(n, size, iterations=100):

@@ -789,6 +789,36 @@ int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams, const doub
                    const int32_t* job_control, const int32_t* job_set, const int32_t* job_side, const int64_t* job_seg,
                    const int64_t* seg_vertex, const int64_t* seg_count, const double* seg_par, int64_t n_vertices,
                    const double* vertex, double* predicted, double* times_ms);
+/* optimize.ransac(batched=True): fits the parameters of ONE camera, fit_cam, to each of n_sets sets of rows in one call,
+ * and can score every row of the handle under each fitted set.  cams [n_cams][GLH_CAM_LEN]: the cameras' vectors (the
+ * others keep theirs).  The p parameters (1 .. 18) are the entries slots[i] of the camera vector (distinct, of 0 .. 5 and
+ * 8 .. 19: not imgsz); each set starts from x0 [p] inside lb <= x0 <= ub (lb < ub), with the steps relative to x_scale [p] > 0 (as
+ * scipy.optimize.least_squares' x_scale).  weights: NULL or [N][2], multiplied into the residuals predicted - observed
+ * (a match control predicts in its first camera from its second camera's points, as glh_calib_eval's side 0).  observed:
+ * NULL -- the handle's obs, which is what every kind but ROTATION is compared with -- or [N][2]: a ROTATION control
+ * predicts image coordinates while its obs are camera coordinates, so a handle that holds one needs this.  Set q
+ * holds the rows set_rows[set_offset[q] .. set_offset[q + 1]] (int64; global row numbers over all controls; no row of a
+ * LINES control).
+ *   The fit: one workgroup per set runs a damped Gauss-Newton (Levenberg-Marquardt) on 0.5 sum r r: the Jacobian by
+ * scipy's 2-point forward differences, the rotation matrix rebuilt on the device from the stepped view direction (not
+ * NumPy's bits), J^T J and J^T r summed within each wave, then across the waves, in a fixed order (no atomics: a call
+ * repeated gives the same bytes), the p x p solve, the damping and the clamp into the bounds in csrc/glh_lm.h.  A row whose
+ * prediction is NaN adds nothing.  At most max_nfev trial steps, 16 rejected ones in a row; it stops on scipy's tests
+ * with ftol, xtol, gtol.  status [n_sets]: 1 gtol, 2 ftol, 3 xtol (scipy's numbers): converged; 0 the cap was reached,
+ * -1 fewer residuals than parameters, -2 a cost that is not finite, -3 a singular system: failed.  x [n_sets][p]: the
+ * values; mean_error [n_sets]: the mean of |r| over the set's own rows (NaN if the fit failed or a row has no prediction).
+ *   score != 0: inlier [n_sets][N] uint8, 1 where |r| < max_error (strict; NaN is none) under the set's values, 2 for the
+ * set's own rows, 0 throughout for a failed set.  The handle must hold no LINES rows then.
+ * times_ms (or NULL) [4]: HIP-event milliseconds -- [0] upload, [1] fit, [2] score, [3] download.
+ * GLH_E_INVALID (checked before a device is touched; the handle stays usable): null pointers, fit_cam or a row out of
+ * range, p outside 1 .. 18, slots that repeat or are no parameter, x0 outside its bounds, lb >= ub, a scale that is not positive,
+ * offsets that do not start at 0 or decrease, 2^31 set rows or scored (set, row) pairs or more, a LINES row, max_nfev < 1,
+ * tolerances outside [0, 1); GLH_E_UNSUPPORTED: a raster grid among the cameras.                                       */
+int glh_calib_fit_sets(glh_calib* handle, const double* cams, int fit_cam, int p, const int32_t* slots, const double* x0,
+                       const double* lb, const double* ub, const double* x_scale, const double* weights,
+                       const double* observed, int n_sets, const int64_t* set_offset, const int64_t* set_rows, int max_nfev, double ftol, double xtol,
+                       double gtol, int score, double max_error, double* x, int32_t* status, double* mean_error,
+                       uint8_t* inlier, double* times_ms);
 /* Frees the handle and its device memory (NULL: nothing).                                                              */
 int glh_calib_destroy(glh_calib* handle);
 
