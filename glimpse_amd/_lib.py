@@ -177,6 +177,9 @@ SIGNATURES = {
     "glh_calib_eval": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P]),
     "glh_calib_fit_sets": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _I, C.c_double, C.c_double, C.c_double, _I,
                                 C.c_double, _P, _P, _P, _P, _P]),
+    "glh_calib_ransac_groups": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, C.c_double, C.c_double,
+                                     C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "glh_ransac_chunks": (_I, [_I, _P, _P, C.c_int64, _P, _P]),
     "glh_calib_destroy": (_I, [_P]),
     "glh_match_create": (_I, [_I, _P]),
     "glh_match_put": (_I, [_P, _I, _I, _I, _I, _P]),
@@ -1468,6 +1471,62 @@ class Calib(_Handle):
         return _timed(out, CALIB_FIT_TIMES, times, return_times)
 
 
+    def ransac_groups(self, cams, group_control, group_cam, slots, x0, lb, ub, x_scale, hyp_offset, samples, max_error,
+                      min_inliers, weights=None, observed=None, max_nfev=None, ftol=1e-8, xtol=1e-8, gtol=1e-8,
+                      return_times=False):
+        """Random Sample Consensus over G groups in ONE device pass (glh_calib_ransac_groups; include/glimpse_hip.h says
+        how): group g is the match control `group_control[g]` with the camera `group_cam[g]` fitted in the entries `slots`
+        (p,) of its vector, from `x0` inside `lb` .. `ub` with the scales `x_scale`, each (G, p); it owns the hypotheses
+        hyp_offset[g] .. hyp_offset[g + 1], rows of `samples` (H, n) (global row numbers).  `weights`, `observed`: as
+        `fit_sets`.  Returns a dict: per hypothesis `values` (H, p), `status`, `consensus`, `refit_values`,
+        `refit_status`, `mean_errors`; per group `winner` (its hypothesis counted from the group's first, -1: none); per
+        row of the handle `inlier` (uint8)."""
+        handle = self._handle()
+        cams = _arr(cams, np.float64)
+        if cams.shape != (self.n_cams, CAM_LEN):
+            raise ValueError(f"expected camera vectors ({self.n_cams}, {CAM_LEN}), got {cams.shape}")
+        group_control = _arr(group_control, np.int32)
+        group_cam = _arr(group_cam, np.int32, group_control.shape)
+        slots = _arr(slots, np.int32)
+        if slots.ndim != 1 or group_control.ndim != 1:
+            raise ValueError("slots (p,) and group_control (G,)")
+        n_groups, p = len(group_control), len(slots)
+        x0, lb, ub, x_scale = (_arr(v, np.float64, (n_groups, p)) for v in (x0, lb, ub, x_scale))
+        hyp_offset = _arr(hyp_offset, np.int64, (n_groups + 1,))
+        samples = _arr(samples, np.int64)
+        n_hyp = int(hyp_offset.max(initial=0))
+        if samples.ndim != 2 or len(samples) < n_hyp:
+            raise ValueError("samples (H, n) with H >= hyp_offset.max()")
+        n_rows = int(self.rows.sum())
+        if weights is not None:
+            weights = _arr(weights, np.float64, (n_rows, 2))
+        if observed is not None:
+            observed = _arr(observed, np.float64, (n_rows, 2))
+        out = dict(values=np.empty((n_hyp, p)), status=np.empty(n_hyp, np.int32), consensus=np.empty(n_hyp, np.int32),
+                   refit_values=np.empty((n_hyp, p)), refit_status=np.empty(n_hyp, np.int32), mean_errors=np.empty(n_hyp),
+                   winner=np.empty(n_groups, np.int32), inlier=np.empty(n_rows, np.uint8))
+        times = np.zeros(len(CALIB_RANSAC_TIMES))
+        check(load().glh_calib_ransac_groups(
+            handle, _ptr(cams), n_groups, _ptr(group_control), _ptr(group_cam), p, _ptr(slots), _ptr(x0), _ptr(lb), _ptr(ub),
+            _ptr(x_scale), _ptr(weights), _ptr(observed), _ptr(hyp_offset), int(samples.shape[1]), _ptr(samples),
+            int(100 * p if max_nfev is None else max_nfev), float(ftol), float(xtol), float(gtol), float(max_error),
+            int(min(max(min_inliers, -1), 2 ** 62)), *[_ptr(out[key]) for key in ("values", "status", "consensus", "refit_values",
+                                                                                 "refit_status", "mean_errors", "winner", "inlier")],
+            _ptr(times)))
+        return _timed(out, CALIB_RANSAC_TIMES, times, return_times)
+
+
+def ransac_chunks(rows, hyps, budget):
+    """chunk_of (G,) int32: the call each group goes to when consecutive groups share a call while its consensus masks
+    (rows[g] * hyps[g] bytes each) stay at or below `budget` bytes (glh_ransac_chunks: host arithmetic, no device)."""
+    rows, hyps = _arr(rows, np.int64), _arr(hyps, np.int64, np.shape(rows))
+    chunk_of, n_chunks = np.zeros(len(rows), np.int32), C.c_int32(0)
+    check(load().glh_ransac_chunks(len(rows), _ptr(rows), _ptr(hyps), int(budget), _ptr(chunk_of), C.byref(n_chunks)))
+    return chunk_of
+
+
+CALIB_RANSAC_TIMES = ("upload", "fit", "score", "refit", "final_score", "download")
+CALIB_NOT_REFITTED = -100  # refit_status of a hypothesis that was not accepted (csrc/glh_ransac_plan.h)
 CALIB_FIT_TIMES = ("upload", "fit", "score", "download")
 CALIB_FIT_STATUS = {1: "gtol", 2: "ftol", 3: "xtol", 0: "the evaluation cap was reached", -1: "fewer residuals than parameters",
                     -2: "the cost is not finite", -3: "the system is singular"}

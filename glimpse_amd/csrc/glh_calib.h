@@ -1,4 +1,4 @@
-// glh_calib.h -- what glimpse_hip.hip (the C ABI: glh_calib_create / _eval / _fit_sets / _destroy) hands to glh_calib.hip (the
+// glh_calib.h -- what glimpse_hip.hip (the C ABI: glh_calib_create / _eval / _fit_sets / _ransac_groups / _destroy) hands to glh_calib.hip (the
 // predictions of the controls of optimize.Cameras -- Points, Lines and the match classes -- under many sets of camera
 // vectors at once).  Host-only declarations.
 #pragma once
@@ -29,6 +29,7 @@ struct CalibTable {  // what a handle keeps of its controls: an evaluation's job
   int n_cams, n_controls;
   const int32_t* kind;        // [n_controls]
   const int64_t* row_offset;  // [n_controls + 1]
+  const int32_t *cam_a, *cam_b;  // [n_controls]
 };
 
 struct CalibEval {
@@ -67,12 +68,39 @@ struct CalibFit {  // glh_calib_fit_sets' arguments (include/glimpse_hip.h), the
   double* times_ms;
 };
 
+struct CalibRansac {  // glh_calib_ransac_groups' arguments (include/glimpse_hip.h), checked by glh_ransac_plan.h's rg_check
+  const CamDev* cams;    // [n_cams], expanded by the caller
+  const double* vectors; // [n_cams][GLH_CAM_LEN]
+  int n_groups;
+  const int32_t *group_control, *group_cam;  // [G]
+  int p;
+  const int32_t* slots;                      // [p]
+  const double *x0, *lb, *ub, *scale;        // [G][p]
+  const double *weights, *observed;          // [N][2] or null
+  const int64_t* hyp_offset;                 // [G + 1]
+  int n;
+  const int64_t* samples;                    // [H][n]
+  int max_nfev;
+  double ftol, xtol, gtol, max_error;
+  int64_t min_inliers;
+  double* x;               // [H][p]
+  int32_t* status;         // [H]
+  int32_t* consensus;      // [H]
+  double* refit_x;         // [H][p]
+  int32_t* refit_status;   // [H]
+  double* mean_error;      // [H]
+  int32_t* winner;         // [G]
+  uint8_t* inlier;         // [N]
+  double* times_ms;
+};
+
 // The arguments have been checked (glimpse_hip.hip).  A GLH_* status, with the message left for glh_last_error() on
 // failure (glh_stage.h: fail).
 int calib_create(int device, const CalibControls& c, glh_calib** out);
 CalibTable calib_table(const glh_calib* h);
 int calib_eval(glh_calib* h, const CalibEval& e);
 int calib_fit_sets(glh_calib* h, const CalibFit& f);
+int calib_ransac_groups(glh_calib* h, const CalibRansac& r);
 void calib_destroy(glh_calib* h);
 
 }  // namespace glh

@@ -39,6 +39,9 @@
 //
 // These are not NumPy's bits (the rotation matrix is the device's) and need not be: the values optimize.ransac returns
 // come from the host's fit on the set the device picked.
+//
+// glh_calib_ransac_groups (optimize.ransac_pairs) runs the whole RANSAC of many one-camera models -- the groups of a
+// handle -- in one pass: k_rg_fit, k_rg_score, k_rg_winner and k_rg_final, described where they stand below.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -50,6 +53,7 @@
 #include "glh_math.h"
 #include "glh_calib.h"
 #include "glh_lm.h"
+#include "glh_ransac_plan.h"
 #include "glh_stage.h"
 
 namespace glh {
@@ -519,6 +523,402 @@ __global__ void __launch_bounds__(CAL_TB) k_calib_members(const FitArgs a, uint8
   for (int64_t k = first + threadIdx.x; k < last; k += CAL_TB) inlier[(size_t)set * a.n_rows + a.set_rows[k]] = 2;
 }
 
+// ---- glh_calib_ransac_groups: RANSAC over many groups in one pass --------------------------------------------------------
+// A group is one match control with one of its cameras fitted (glh_ransac_plan.h).  Four steps on one stream, nothing read
+// back in between:
+//
+//   k_rg_fit (hypotheses), one TEAM per sample of n rows: a team is one wave when n <= 64 -- several teams to a workgroup,
+//   the wave's butterfly is then the whole reduction and no workgroup barrier is used -- and a workgroup of two waves
+//   beyond.  The Gauss-Newton is k_calib_fit's, with calib_row, camera_from_vector and glh_lm.h as they are; what differs
+//   is that camera, start, bounds and scales are the group's, read from device arrays, and that the LDS is sized by the
+//   instantiation's largest p (3: a view direction; 18: everything).
+//   k_rg_score, one workgroup per hypothesis over the rows of ITS group: the mask byte (1: error < max_error, 2: a row of
+//   the sample) stays on the device, the count of 1s is the consensus.
+//   k_rg_fit (refits), one workgroup per hypothesis with status > 0 and consensus > min_inliers: it walks its group's rows
+//   in order and skips those whose mask byte is 0, so equal sets give equal bytes.
+//   k_rg_winner, one thread per group: the valid refit of smallest mean error, the earlier one of equal ones;
+//   k_rg_final, one workgroup per group: error <= max_error of every row under the winner's refitted values.
+struct RGroup {
+  int64_t row0;   // the group's first row in the handle
+  int64_t mask0;  // the first mask byte of its first hypothesis
+  int32_t n_rows, ctl, fit_cam, hyp0, n_hyp, pad_;
+};
+
+struct RArgs {
+  const CamDev* cams;        // [n_cams] the cameras at their own vectors
+  const double* vectors;     // [n_cams][GLH_CAM_LEN]
+  const CalCtl* ctl;         // [n_controls]
+  const double2* obs;
+  const double* src;
+  const double2* observed;   // [N]: obs, or the caller's
+  const double2* weights;    // [N], or null
+  const RGroup* groups;      // [G]
+  const int32_t* hyp_group;  // [H]
+  const int32_t* samples;    // [H][n] global rows
+  const double *x0, *lb, *ub, *scale;  // [G][p]
+  uint8_t* mask;
+  double* x;                 // [H][p]
+  double* refit_x;           // [H][p]
+  double* mean_error;        // [H]
+  int32_t *status, *consensus, *refit_status;  // [H]
+  int32_t* winner;           // [G]
+  uint8_t* inlier;           // [N]
+  int32_t slot[LM_MAX_P];
+  int32_t p, n, max_nfev, n_hyp, n_groups, min_inliers;
+  double ftol, xtol, gtol, max_error;
+};
+
+template <int MAXP, int TW>
+struct RFitShared {
+  static constexpr int TRI = MAXP * (MAXP + 1) / 2;
+  static constexpr int E = TRI + MAXP + 4;  // A's triangle, g, sum r r, rows that count, sum |r|, members
+  CamDev cam[MAXP + 1];
+  double vec[MAXP + 1][GLH_CAM_LEN];
+  double J[2][MAXP + 1][TW * 64];
+  double part[TW][E];
+  double acc[E];
+  double tri[TRI], g[MAXP];
+  double x[MAXP], xt[MAXP], dx[MAXP], y[MAXP];
+  double M[MAXP * MAXP], b[MAXP];
+  double cost, lambda, err_sum, count, members, len2;
+  int32_t state, rejects;
+};
+
+// What a team works on: its group, the group's control and parameters, and its set of rows -- a list (a sample), or the
+// rows of the group whose mask byte is not 0 (a refit).
+struct RTeam {
+  RGroup g;
+  CalCtl c;
+  const double *x0, *lb, *ub, *scale, *base;
+  const int32_t* rows;
+  const uint8_t* mask;
+  int n;
+};
+
+// Between the lanes of a team: a wave's LDS accesses execute in order, so one wave needs the compiler's fence alone.
+template <int TW>
+__device__ __forceinline__ void team_sync() {
+  if (TW == 1) {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  } else {
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ void rg_residual(const RArgs& a, const RTeam& w, const CamDev& fitted, size_t row, double& ru,
+                                            double& rv) {
+  const CamDev& ct = w.c.cam_a == w.g.fit_cam ? fitted : a.cams[w.c.cam_a];
+  const CamDev& co = w.c.cam_b == w.g.fit_cam ? fitted : a.cams[w.c.cam_b];
+  double u, v;
+  calib_row(w.c.kind, w.c.directions, 0, ct, co, ct.R, co.R, a.obs, a.src, row, u, v);
+  const double2 o = a.observed[row];
+  ru = u - o.x;
+  rv = v - o.y;
+  if (a.weights) {
+    const double2 wt = a.weights[row];
+    ru = ru * wt.x;
+    rv = rv * wt.y;
+  }
+}
+
+// fit_evaluate for a team: s.acc = the sums over the team's set at the point xe (an array of s).  t: the lane within the
+// team.  Every lane of the team calls this.
+template <int MAXP, int TW>
+__device__ void rg_evaluate(const RArgs& a, const RTeam& w, RFitShared<MAXP, TW>& s, const double* xe, int t) {
+  constexpr int TT = TW * 64, E = RFitShared<MAXP, TW>::E, Q = (E + TT - 1) / TT;
+  const int p = a.p;
+  const int nE = p * (p + 1) / 2 + p + 4;
+  team_sync<TW>();  // (xe is written, the last evaluation's sums are read)
+  if (t <= p) {
+    double* v = s.vec[t];
+    for (int k = 0; k < GLH_CAM_LEN; ++k) v[k] = w.base[k];
+    for (int i = 0; i < p; ++i) v[a.slot[i]] = xe[i];
+    if (t > 0) {
+      const int i = t - 1;
+      const double stepped = xe[i] + lm_fd_step(xe[i], w.lb[i], w.ub[i]);
+      v[a.slot[i]] = stepped;
+      s.dx[i] = stepped - xe[i];
+    }
+    camera_from_vector(v, &s.cam[t]);
+  }
+  team_sync<TW>();
+  double sum[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) sum[q] = 0.0;
+  const int wave = t >> 6, lane = t & 63;
+  for (int first = 0; first < w.n; first += TT) {
+    const int k = first + t;
+    bool member = k < w.n;
+    size_t row = 0;
+    if (member) {
+      if (w.rows) {
+        row = (size_t)w.rows[k];
+      } else {
+        row = (size_t)w.g.row0 + k;
+        member = w.mask[k] != 0;
+      }
+    }
+    bool ok = member;
+    double ru = 0.0, rv = 0.0;
+    if (ok) {
+      rg_residual(a, w, s.cam[0], row, ru, rv);
+      ok = !(isnan(ru) || isnan(rv));
+      for (int j = 0; j < p; ++j) {
+        double su, sv;
+        rg_residual(a, w, s.cam[j + 1], row, su, sv);
+        const double ju = (su - ru) / s.dx[j] * w.scale[j], jv = (sv - rv) / s.dx[j] * w.scale[j];
+        ok = ok && !(isnan(ju) || isnan(jv));
+        s.J[0][j][t] = ju;
+        s.J[1][j][t] = jv;
+      }
+    }
+    if (!ok) {
+      ru = rv = 0.0;
+      for (int j = 0; j < p; ++j) s.J[0][j][t] = s.J[1][j][t] = 0.0;
+    }
+    s.J[0][p][t] = ru;
+    s.J[1][p][t] = rv;
+    int e = 0;
+    for (int i = 0; i < p; ++i)  // A's upper triangle row by row (lm_tri), then g: column p is r
+      for (int j = i; j < p; ++j, ++e) {
+        const double v = wave_sum(s.J[0][i][t] * s.J[0][j][t] + s.J[1][i][t] * s.J[1][j][t]);
+        if (lane == 0) s.part[wave][e] = v;
+      }
+    for (int i = 0; i <= p; ++i, ++e) {  // (the last of these is sum r r)
+      const double v = wave_sum(s.J[0][i][t] * ru + s.J[1][i][t] * rv);
+      if (lane == 0) s.part[wave][e] = v;
+    }
+    {
+      const double c = wave_sum(ok ? 1.0 : 0.0), h = wave_sum(ok ? hypot(ru, rv) : 0.0), m = wave_sum(member ? 1.0 : 0.0);
+      if (lane == 0) s.part[wave][e] = c, s.part[wave][e + 1] = h, s.part[wave][e + 2] = m;
+    }
+    team_sync<TW>();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+      const int i = t + q * TT;
+      if (i < nE) {
+        double v = s.part[0][i];
+        for (int k2 = 1; k2 < TW; ++k2) v += s.part[k2][i];
+        sum[q] += v;
+      }
+    }
+    team_sync<TW>();
+  }
+#pragma unroll
+  for (int q = 0; q < Q; ++q)
+    if (t + q * TT < nE) s.acc[t + q * TT] = sum[q];
+  team_sync<TW>();
+}
+
+template <int MAXP, int TW>
+__device__ __forceinline__ int rg_state(RFitShared<MAXP, TW>& s) {
+  team_sync<TW>();
+  const int v = s.state;
+  team_sync<TW>();
+  return v;
+}
+
+// Lane 0: the evaluation in s.acc becomes the state at x.
+template <int MAXP, int TW>
+__device__ void rg_keep(RFitShared<MAXP, TW>& s, int p) {
+  const int nT = p * (p + 1) / 2;
+  for (int e = 0; e < nT; ++e) s.tri[e] = s.acc[e];
+  for (int i = 0; i < p; ++i) s.g[i] = s.acc[nT + i];
+  s.cost = 0.5 * s.acc[nT + p];
+  s.count = s.acc[nT + p + 1];
+  s.err_sum = s.acc[nT + p + 2];
+  s.members = s.acc[nT + p + 3];
+}
+
+// k_calib_fit's loop for one team.  Lane 0 leaves the values, the status and the mean error over the set's rows.
+template <int MAXP, int TW>
+__device__ void rg_fit(const RArgs& a, const RTeam& w, RFitShared<MAXP, TW>& s, int t, double* x, int32_t* status,
+                       double* mean_error) {
+  const int p = a.p, nT = p * (p + 1) / 2;
+  if (t == 0) {
+    for (int i = 0; i < p; ++i) s.x[i] = w.x0[i];
+    s.lambda = LM_LAMBDA_START;
+    s.state = FIT_RUNNING;
+    s.rejects = 0;
+  }
+  rg_evaluate<MAXP, TW>(a, w, s, s.x, t);
+  if (t == 0) {
+    rg_keep<MAXP, TW>(s, p);
+    if (2.0 * s.count < (double)p)
+      s.state = LM_FEW_ROWS;
+    else if (!(s.cost < INFINITY))
+      s.state = LM_NOT_FINITE;
+  }
+  for (int it = 0; it < a.max_nfev; ++it) {  // one trial step per round: bounded, whatever the residuals do
+    if (rg_state<MAXP, TW>(s) != FIT_RUNNING) break;
+    if (t == 0) {
+      uint32_t frozen = 0;
+      double gmax = 0.0;
+      for (int i = 0; i < p; ++i) {
+        if (lm_frozen(s.x[i], w.lb[i], w.ub[i], s.g[i]))
+          frozen |= 1u << i;
+        else
+          gmax = fmax(gmax, fabs(s.g[i]));
+      }
+      if (!(gmax >= a.gtol)) {
+        s.state = gmax == gmax ? LM_GTOL : LM_NOT_FINITE;
+      } else {
+        lm_system(p, s.tri, s.g, s.lambda, frozen, s.M, s.b);
+        if (!lm_solve(p, s.M, s.b)) {
+          s.state = LM_SINGULAR;
+        } else {
+          for (int i = 0; i < p; ++i) s.y[i] = s.b[i];
+          s.len2 = lm_clamp(p, s.x, w.scale, w.lb, w.ub, s.y, s.xt);
+          if (s.len2 == 0.0) s.state = LM_XTOL;
+        }
+      }
+    }
+    if (rg_state<MAXP, TW>(s) != FIT_RUNNING) break;
+    rg_evaluate<MAXP, TW>(a, w, s, s.xt, t);
+    if (t == 0) {
+      const double count = s.acc[nT + p + 1], cost = 0.5 * s.acc[nT + p];
+      double norm2 = 0.0;
+      for (int i = 0; i < p; ++i) norm2 += (s.x[i] / w.scale[i]) * (s.x[i] / w.scale[i]);
+      const bool is_short = sqrt(s.len2) < a.xtol * (a.xtol + sqrt(norm2));
+      const bool accepted = count >= s.count && cost < s.cost;
+      s.lambda = lm_damping(s.lambda, accepted);
+      if (accepted) {
+        const double before = s.cost;
+        for (int i = 0; i < p; ++i) s.x[i] = s.xt[i];
+        rg_keep<MAXP, TW>(s, p);
+        s.rejects = 0;
+        if (before - s.cost < a.ftol * before)
+          s.state = LM_FTOL;
+        else if (is_short)
+          s.state = LM_XTOL;
+      } else if (is_short) {
+        s.state = LM_XTOL;
+      } else if (++s.rejects >= LM_MAX_REJECT) {
+        s.state = LM_CAP;
+      }
+    }
+  }
+  team_sync<TW>();
+  if (t == 0) {
+    const int32_t st = s.state == FIT_RUNNING ? (int32_t)LM_CAP : s.state;
+    for (int i = 0; i < p; ++i) x[i] = s.x[i];
+    *status = st;
+    // np.mean over the set's own rows: NaN as soon as one of them has no prediction
+    if (mean_error) *mean_error = (st > 0 && s.count == s.members) ? s.err_sum / s.count : NAN;
+  }
+}
+
+// refit == 0: hypothesis h is fitted to its sample; refit != 0: to sample and consensus, if it was accepted.
+template <int MAXP, int TW, int TEAMS>
+__global__ void __launch_bounds__(TW * 64 * TEAMS) k_rg_fit(const RArgs a, int refit) {
+  static_assert(TW == 1 || TEAMS == 1, "teams that share a workgroup must not meet at a workgroup barrier");
+  __shared__ RFitShared<MAXP, TW> sh[TEAMS];
+  const int team = (int)threadIdx.x / (TW * 64), t = (int)threadIdx.x % (TW * 64);
+  const int h = (int)blockIdx.x * TEAMS + team;
+  if (h >= a.n_hyp) return;
+  const int gi = a.hyp_group[h];
+  RTeam w;
+  w.g = a.groups[gi];
+  w.c = a.ctl[w.g.ctl];
+  w.x0 = a.x0 + (size_t)gi * a.p, w.lb = a.lb + (size_t)gi * a.p, w.ub = a.ub + (size_t)gi * a.p;
+  w.scale = a.scale + (size_t)gi * a.p;
+  w.base = a.vectors + (size_t)w.g.fit_cam * GLH_CAM_LEN;
+  if (!refit) {
+    w.rows = a.samples + (size_t)h * a.n, w.mask = nullptr, w.n = a.n;
+    rg_fit<MAXP, TW>(a, w, sh[team], t, a.x + (size_t)h * a.p, a.status + h, nullptr);
+    return;
+  }
+  if (!(a.status[h] > 0 && a.consensus[h] > a.min_inliers)) {
+    if (t == 0) {
+      for (int i = 0; i < a.p; ++i) a.refit_x[(size_t)h * a.p + i] = NAN;
+      a.refit_status[h] = RANSAC_NOT_REFITTED;
+      a.mean_error[h] = NAN;
+    }
+    return;
+  }
+  w.rows = nullptr, w.mask = a.mask + w.g.mask0 + (size_t)(h - w.g.hyp0) * w.g.n_rows, w.n = w.g.n_rows;
+  rg_fit<MAXP, TW>(a, w, sh[team], t, a.refit_x + (size_t)h * a.p, a.refit_status + h, a.mean_error + h);
+}
+
+// The fitted camera of group g at the values x, by thread 0 into LDS (the caller synchronises).
+__device__ __forceinline__ void rg_camera(const RArgs& a, const RGroup& g, const double* x, double* vec, CamDev* cam) {
+  const double* base = a.vectors + (size_t)g.fit_cam * GLH_CAM_LEN;
+  for (int k = 0; k < GLH_CAM_LEN; ++k) vec[k] = base[k];
+  for (int i = 0; i < a.p; ++i) vec[a.slot[i]] = x[i];
+  camera_from_vector(vec, cam);
+}
+
+__global__ void __launch_bounds__(CAL_TB) k_rg_score(const RArgs a) {
+  __shared__ CamDev cam;
+  __shared__ double vec[GLH_CAM_LEN];
+  __shared__ int32_t count;
+  const int h = (int)blockIdx.x, tid = (int)threadIdx.x;
+  RTeam w;
+  w.g = a.groups[a.hyp_group[h]];
+  w.c = a.ctl[w.g.ctl];
+  uint8_t* __restrict__ m = a.mask + w.g.mask0 + (size_t)(h - w.g.hyp0) * w.g.n_rows;
+  const bool fitted = a.status[h] > 0;  // (a hypothesis whose fit failed has no consensus)
+  if (tid == 0) {
+    count = 0;
+    rg_camera(a, w.g, a.x + (size_t)h * a.p, vec, &cam);
+  }
+  __syncthreads();
+  for (int k = tid; k < w.g.n_rows; k += CAL_TB) {
+    uint8_t in = 0;
+    if (fitted) {
+      double ru, rv;
+      rg_residual(a, w, cam, (size_t)w.g.row0 + k, ru, rv);
+      in = hypot(ru, rv) < a.max_error ? 1 : 0;
+    }
+    m[k] = in;
+  }
+  __syncthreads();
+  if (fitted)
+    for (int k = tid; k < a.n; k += CAL_TB) m[(int64_t)a.samples[(size_t)h * a.n + k] - w.g.row0] = 2;
+  __syncthreads();
+  int local = 0;
+  for (int k = tid; k < w.g.n_rows; k += CAL_TB) local += m[k] == 1 ? 1 : 0;
+  for (int s = 32; s >= 1; s >>= 1) local += __shfl_xor(local, s);
+  if ((tid & 63) == 0) atomicAdd(&count, local);
+  __syncthreads();
+  if (tid == 0) a.consensus[h] = count;
+}
+
+__global__ void __launch_bounds__(CAL_TB) k_rg_winner(const RArgs a) {
+  const int gi = (int)(blockIdx.x * CAL_TB + threadIdx.x);
+  if (gi >= a.n_groups) return;
+  const RGroup g = a.groups[gi];
+  int best = -1;
+  double least = 0.0;
+  for (int k = 0; k < g.n_hyp; ++k) {
+    const double mean = a.mean_error[g.hyp0 + k];
+    if (a.refit_status[g.hyp0 + k] > 0 && mean == mean && (best < 0 || mean < least)) best = k, least = mean;
+  }
+  a.winner[gi] = best;
+}
+
+__global__ void __launch_bounds__(CAL_TB) k_rg_final(const RArgs a) {
+  __shared__ CamDev cam;
+  __shared__ double vec[GLH_CAM_LEN];
+  const int gi = (int)blockIdx.x, tid = (int)threadIdx.x;
+  RTeam w;
+  w.g = a.groups[gi];
+  w.c = a.ctl[w.g.ctl];
+  const int win = a.winner[gi];
+  if (tid == 0 && win >= 0) rg_camera(a, w.g, a.refit_x + (size_t)(w.g.hyp0 + win) * a.p, vec, &cam);
+  __syncthreads();
+  for (int k = tid; k < w.g.n_rows; k += CAL_TB) {
+    uint8_t in = 0;
+    if (win >= 0) {
+      double ru, rv;
+      rg_residual(a, w, cam, (size_t)w.g.row0 + k, ru, rv);
+      in = hypot(ru, rv) <= a.max_error ? 1 : 0;
+    }
+    a.inlier[(size_t)w.g.row0 + k] = in;
+  }
+}
+
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -536,6 +936,10 @@ struct glh_calib : glh::DeviceObject {
   glh::DevBuf ctl, row_ctl;
   glh::GrowBuf fit_in, fit_out;
   glh::StageEvents<glh::CAL_FIT_TIMES + 1> fit_ev;
+  // RANSAC over groups (calib_ransac_groups): its buffers, the masks apart, and its events, made by the first call
+  glh::GrowBuf rg_in, rg_out, rg_mask;
+  glh::StageEvents<glh::RANSAC_TIMES + 1> rg_ev;
+  bool rg_ready = false;
 };
 
 namespace glh {
@@ -568,7 +972,9 @@ int calib_create(int device, const CalibControls& c, glh_calib** out) {
   return create_object("calib", device, out, [&](glh_calib* h) { return calib_fill(h, c); });
 }
 
-CalibTable calib_table(const glh_calib* h) { return CalibTable{h->n_cams, h->n_controls, h->kind.data(), h->row_offset.data()}; }
+CalibTable calib_table(const glh_calib* h) {
+  return CalibTable{h->n_cams, h->n_controls, h->kind.data(), h->row_offset.data(), h->cam_a.data(), h->cam_b.data()};
+}
 
 int calib_eval(glh_calib* h, const CalibEval& e) {
   CHK(h->use());
@@ -771,6 +1177,141 @@ int calib_fit_sets(glh_calib* h, const CalibFit& f) {
   CHK(h->fit_ev.record(4, s));
   HIPCHK(hipEventSynchronize(h->fit_ev.e[4]));
   h->fit_ev.report(f.times_ms, CAL_FIT_TIMES, CAL_FIT_TIMES);
+  return GLH_OK;
+}
+
+template <int MAXP, int TW, int TEAMS>
+static void rg_launch(const RArgs& a, int refit, hipStream_t s) {
+  const unsigned blocks = (unsigned)((a.n_hyp + TEAMS - 1) / TEAMS);
+  hipLaunchKernelGGL((k_rg_fit<MAXP, TW, TEAMS>), dim3(blocks), dim3(TW * 64 * TEAMS), 0, s, a, refit);
+}
+
+int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
+  CHK(h->use());
+  hipStream_t s = h->stream;
+  if (!h->rg_ready) {
+    CHK(h->rg_ev.create());
+    h->rg_ready = true;
+  }
+  const size_t N = (size_t)h->row_offset[h->n_controls], G = (size_t)r.n_groups, H = G ? (size_t)r.hyp_offset[G] : 0;
+  const size_t p = (size_t)r.p, n = (size_t)r.n, C = (size_t)h->n_cams;
+  // the groups, and where their masks lie (glh_ransac_plan.h)
+  std::vector<RGroup> groups(G);
+  std::vector<int64_t> rows(G), hyps(G), mask_offset(G + 1);
+  for (size_t g = 0; g < G; ++g) {
+    const int c = r.group_control[g];
+    rows[g] = h->row_offset[c + 1] - h->row_offset[c];
+    hyps[g] = r.hyp_offset[g + 1] - r.hyp_offset[g];
+  }
+  const size_t mask_bytes = (size_t)rg_mask_offsets((int)G, rows.data(), hyps.data(), mask_offset.data());
+  for (size_t g = 0; g < G; ++g)
+    groups[g] = RGroup{h->row_offset[r.group_control[g]], mask_offset[g], (int32_t)rows[g], r.group_control[g], r.group_cam[g],
+                       (int32_t)r.hyp_offset[g], (int32_t)hyps[g], 0};
+  size_t at = 0;
+  auto place = [&at](size_t bytes) {
+    const size_t o = at;
+    at = align16(at + bytes);
+    return o;
+  };
+  const size_t i_cams = place(C * sizeof(CamDev)), i_vec = place(C * GLH_CAM_LEN * 8);
+  const size_t i_weights = place(r.weights ? N * 16 : 0), i_observed = place(r.observed ? N * 16 : 0);
+  const size_t i_groups = place(G * sizeof(RGroup)), i_hg = place(H * 4), i_samples = place(H * n * 4);
+  const size_t i_x0 = place(G * p * 8), i_lb = place(G * p * 8), i_ub = place(G * p * 8), i_scale = place(G * p * 8);
+  h->stage.resize(at ? at : 16);
+  char* st = h->stage.data();
+  std::memcpy(st + i_cams, r.cams, C * sizeof(CamDev));
+  std::memcpy(st + i_vec, r.vectors, C * GLH_CAM_LEN * 8);
+  if (r.weights) std::memcpy(st + i_weights, r.weights, N * 16);
+  if (r.observed) std::memcpy(st + i_observed, r.observed, N * 16);
+  if (G) {
+    std::memcpy(st + i_groups, groups.data(), G * sizeof(RGroup));
+    std::memcpy(st + i_x0, r.x0, G * p * 8);
+    std::memcpy(st + i_lb, r.lb, G * p * 8);
+    std::memcpy(st + i_ub, r.ub, G * p * 8);
+    std::memcpy(st + i_scale, r.scale, G * p * 8);
+  }
+  int32_t* hg = reinterpret_cast<int32_t*>(st + i_hg);
+  for (size_t g = 0; g < G; ++g)
+    for (int64_t k = r.hyp_offset[g]; k < r.hyp_offset[g + 1]; ++k) hg[k] = (int32_t)g;
+  int32_t* samples = reinterpret_cast<int32_t*>(st + i_samples);
+  for (size_t k = 0; k < H * n; ++k) samples[k] = (int32_t)r.samples[k];
+  // out, in the order of the download: the doubles, the int32s, the bytes
+  at = 0;
+  const size_t o_x = place(H * p * 8), o_refit = place(H * p * 8), o_mean = place(H * 8), o_status = place(H * 4);
+  const size_t o_consensus = place(H * 4), o_rstatus = place(H * 4), o_winner = place(G * 4), o_inlier = place(N);
+  const size_t out_bytes = at ? at : 16;
+  CHK(h->rg_in.reserve(h->stage.size()));
+  CHK(h->rg_out.reserve(out_bytes));
+  CHK(h->rg_mask.reserve(mask_bytes));
+  CHK(h->rg_ev.record(0, s));
+  HIPCHK(hipMemcpy(h->rg_in.p, st, h->stage.size(), hipMemcpyHostToDevice));
+  CHK(h->rg_ev.record(1, s));
+  const char* d = h->rg_in.as<char>();
+  char* o = h->rg_out.as<char>();
+  RArgs a{};
+  a.cams = reinterpret_cast<const CamDev*>(d + i_cams);
+  a.vectors = reinterpret_cast<const double*>(d + i_vec);
+  a.ctl = h->ctl.as<CalCtl>();
+  a.obs = h->obs.as<double2>();
+  a.src = h->src.as<double>();
+  a.observed = r.observed ? reinterpret_cast<const double2*>(d + i_observed) : h->obs.as<double2>();
+  a.weights = r.weights ? reinterpret_cast<const double2*>(d + i_weights) : nullptr;
+  a.groups = reinterpret_cast<const RGroup*>(d + i_groups);
+  a.hyp_group = reinterpret_cast<const int32_t*>(d + i_hg);
+  a.samples = reinterpret_cast<const int32_t*>(d + i_samples);
+  a.x0 = reinterpret_cast<const double*>(d + i_x0), a.lb = reinterpret_cast<const double*>(d + i_lb);
+  a.ub = reinterpret_cast<const double*>(d + i_ub), a.scale = reinterpret_cast<const double*>(d + i_scale);
+  a.mask = h->rg_mask.as<uint8_t>();
+  a.x = reinterpret_cast<double*>(o + o_x), a.refit_x = reinterpret_cast<double*>(o + o_refit);
+  a.mean_error = reinterpret_cast<double*>(o + o_mean);
+  a.status = reinterpret_cast<int32_t*>(o + o_status), a.consensus = reinterpret_cast<int32_t*>(o + o_consensus);
+  a.refit_status = reinterpret_cast<int32_t*>(o + o_rstatus), a.winner = reinterpret_cast<int32_t*>(o + o_winner);
+  a.inlier = reinterpret_cast<uint8_t*>(o + o_inlier);
+  for (size_t i = 0; i < p; ++i) a.slot[i] = r.slots[i];
+  a.p = r.p, a.n = r.n, a.max_nfev = r.max_nfev, a.n_hyp = (int32_t)H, a.n_groups = (int32_t)G;
+  // (a consensus is at most 2^31 - 1 rows, at least 0)
+  a.min_inliers = (int32_t)(r.min_inliers > INT32_MAX ? INT32_MAX : (r.min_inliers < -1 ? -1 : r.min_inliers));
+  a.ftol = r.ftol, a.xtol = r.xtol, a.gtol = r.gtol, a.max_error = r.max_error;
+  const bool small = r.p <= 3;
+  if (H) {
+    if (r.n <= 64)
+      small ? rg_launch<3, 1, 4>(a, 0, s) : rg_launch<LM_MAX_P, 1, 1>(a, 0, s);
+    else
+      small ? rg_launch<3, 2, 1>(a, 0, s) : rg_launch<LM_MAX_P, 2, 1>(a, 0, s);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(h->rg_ev.record(2, s));
+  if (H) {
+    hipLaunchKernelGGL(k_rg_score, dim3((unsigned)H), dim3(CAL_TB), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(h->rg_ev.record(3, s));
+  if (H) {
+    small ? rg_launch<3, 2, 1>(a, 1, s) : rg_launch<LM_MAX_P, 2, 1>(a, 1, s);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(h->rg_ev.record(4, s));
+  if (G) {
+    hipLaunchKernelGGL(k_rg_winner, dim3((unsigned)((G + CAL_TB - 1) / CAL_TB)), dim3(CAL_TB), 0, s, a);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_rg_final, dim3((unsigned)G), dim3(CAL_TB), 0, s, a);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(h->rg_ev.record(5, s));
+  h->stage.resize(out_bytes);
+  HIPCHK(hipMemcpy(h->stage.data(), h->rg_out.p, out_bytes, hipMemcpyDeviceToHost));
+  CHK(h->rg_ev.record(6, s));
+  HIPCHK(hipEventSynchronize(h->rg_ev.e[6]));
+  const char* b = h->stage.data();
+  std::memcpy(r.x, b + o_x, H * p * 8);
+  std::memcpy(r.refit_x, b + o_refit, H * p * 8);
+  std::memcpy(r.mean_error, b + o_mean, H * 8);
+  std::memcpy(r.status, b + o_status, H * 4);
+  std::memcpy(r.consensus, b + o_consensus, H * 4);
+  std::memcpy(r.refit_status, b + o_rstatus, H * 4);
+  std::memcpy(r.winner, b + o_winner, G * 4);
+  std::memcpy(r.inlier, b + o_inlier, N);
+  h->rg_ev.report(r.times_ms, RANSAC_TIMES, RANSAC_TIMES);
   return GLH_OK;
 }
 

@@ -20,6 +20,7 @@
 #include "glh_project_dem.h"
 #include "glh_horizon.h"
 #include "glh_calib.h"
+#include "glh_ransac_plan.h"
 #include "glh_match.h"
 #include "glh_sift.h"
 #include "glh_orient.h"
@@ -3184,6 +3185,51 @@ extern "C" int glh_calib_fit_sets(glh_calib* handle, const double* cams, int fit
   const CalibFit f{cd.data(), cams + (size_t)fit_cam * GLH_CAM_LEN, fit_cam, p, slots, x0, lb, ub, x_scale, weights, observed,
                    n_sets, set_offset, set_rows, max_nfev, ftol, xtol, gtol, score, max_error, x, status, mean_error, inlier, times_ms};
   return calib_fit_sets(handle, f);
+}
+
+// optimize.ransac_pairs: RANSAC over many groups (one match control, one fitted camera each) in one pass.  The checks are
+// glh_ransac_plan.h's rg_check, made before a device is touched.
+extern "C" int glh_calib_ransac_groups(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
+                                       const int32_t* group_cam, int p, const int32_t* slots, const double* x0, const double* lb,
+                                       const double* ub, const double* x_scale, const double* weights, const double* observed,
+                                       const int64_t* hyp_offset, int n, const int64_t* samples, int max_nfev, double ftol,
+                                       double xtol, double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status,
+                                       int32_t* consensus, double* refit_x, int32_t* refit_status, double* mean_error,
+                                       int32_t* winner, uint8_t* inlier, double* times_ms) {
+  if (!handle) return fail(GLH_E_INVALID, "ransac groups: null handle");
+  const CalibTable table = calib_table(handle);
+  if (!cams) return fail(GLH_E_INVALID, "ransac groups: null argument");
+  const RgCall call{table.n_cams, table.n_controls, table.kind, table.cam_a, table.cam_b, table.row_offset, n_groups, group_control,
+                    group_cam, p, slots, x0, lb, ub, x_scale, hyp_offset, n, samples, max_nfev, ftol, xtol, gtol, max_error,
+                    x && status && consensus && refit_x && refit_status && mean_error && winner && inlier};
+  char why[400];
+  if (!rg_check(call, why, sizeof(why))) return fail(GLH_E_INVALID, "%s", why);
+  for (int g = 0; g < n_groups; ++g)
+    if (table.kind[group_control[g]] == GLH_CALIB_ROTATION && !observed &&
+        table.row_offset[group_control[g] + 1] > table.row_offset[group_control[g]])
+      return fail(GLH_E_INVALID, "ransac groups: control %d is a ROTATION control, whose obs are camera coordinates: pass observed",
+                  group_control[g]);
+  std::vector<CamDev> cd((size_t)table.n_cams);
+  for (int i = 0; i < table.n_cams; ++i) {
+    if (cams[(size_t)i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "ransac groups: camera %d is a raster grid", i);
+    expand_camera(cams + (size_t)i * GLH_CAM_LEN, &cd[i]);
+  }
+  const CalibRansac r{cd.data(), cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed,
+                      hyp_offset, n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x,
+                      refit_status, mean_error, winner, inlier, times_ms};
+  return calib_ransac_groups(handle, r);
+}
+
+// How optimize.ransac_pairs cuts its pairs into calls (glh_ransac_plan.h: rg_chunks).  Host arithmetic only.
+extern "C" int glh_ransac_chunks(int n_groups, const int64_t* rows, const int64_t* hyps, int64_t budget, int32_t* chunk_of,
+                                 int32_t* n_chunks) {
+  if (n_groups < 0 || !n_chunks || (n_groups && (!rows || !hyps || !chunk_of)))
+    return fail(GLH_E_INVALID, "ransac chunks: %d groups or a null argument", n_groups);
+  for (int g = 0; g < n_groups; ++g)
+    if (rows[g] < 0 || hyps[g] < 0) return fail(GLH_E_INVALID, "ransac chunks: group %d has %lld rows and %lld hypotheses", g,
+                                                 (long long)rows[g], (long long)hyps[g]);
+  *n_chunks = rg_chunks(n_groups, rows, hyps, budget, chunk_of);
+  return GLH_OK;
 }
 
 extern "C" int glh_calib_destroy(glh_calib* handle) {

@@ -43,6 +43,11 @@ which set wins: the values returned come from `Cameras.fit` on that set, as on t
 reference's loop, unchanged).  Point and match controls are served; everything else is refused, not run on the host
 (INPUTS.md, "Camera calibration").
 
+`ransac_pairs(pairs, ...)` and `KeypointMatcher.ransac_matches(...)` run that RANSAC over every image pair of a sequence in
+one device pass (`glh_calib_ransac_groups`): each pair's second (or first) camera fitted from its own vector, the other
+held, every hypothesis of every pair fitted, scored over its pair's rows and refitted where accepted, the winner and the
+final inliers chosen on the device.  The values returned are the device's refit values, not SciPy's (INPUTS.md).
+
 Not served: `cv2.SIFT` itself (the default `method` of `detect_keypoints` and `build_keypoints`), `cv2.createCLAHE` (`clahe=True`
 or a `dict`), a `mask` for the GPU matcher, the lmfit methods other than "least_squares" (lmfit is not a dependency) and
 plotting.
@@ -930,6 +935,28 @@ class KeypointMatcher:
                 m.weights = None
             self.matches.data[i] = m
 
+    def ransac_matches(self, n, max_error, min_inliers, iterations=100, cam_params=None, **kwargs):
+        """Frees every pair's matches of outliers by `ransac_pairs` over `self.matches` (all pairs in one device pass; the
+        arguments are its own): a pair keeps its inliers -- `uvs`, `xys` and `weights` filtered together, as
+        `Matches.filter` does -- and a pair for which no fit is accepted is emptied to size 0 and stays in place, so that
+        `matches_per_image`, `images_per_image` and `match_breaks(min_matches)` report it.  Returns the inlier count per
+        pair, -1 for a rejected pair."""
+        self._test_matches()
+        results = ransac_pairs(self.matches, n, max_error, min_inliers, iterations=iterations, cam_params=cam_params, **kwargs)
+        counts = np.full(len(results), -1, dtype=int)
+        for k, (m, result) in enumerate(zip(self.matches.data, results)):
+            selected = np.zeros(m.size, dtype=bool)
+            if result is not None:
+                selected[result[1]] = True
+                counts[k] = len(result[1])
+            if m.uvs:
+                m.uvs = [uv[selected] for uv in m.uvs]
+            if getattr(m, "xys", None):
+                m.xys = [xy[selected] for xy in m.xys]
+            if m.weights is not None:
+                m.weights = np.asarray(m.weights)[selected]
+        return counts
+
     def _images_mask(self, imgs):
         if np.iterable(imgs):
             return np.isin(self.matches.row, imgs) | np.isin(self.matches.col, imgs)
@@ -1791,6 +1818,179 @@ def _ransac_samples(n, size, iterations=100):
         if sample not in samples:
             yield list(sample)
             samples.add(sample)
+
+
+RANSAC_PAIRS_BUDGET = 1 << 30  # bytes of consensus masks (hypotheses x rows) one device call of `ransac_pairs` may hold
+
+
+def _pairs_plan(pairs, fitted, cam_params, kwargs):
+    """What `ransac_pairs` hands the device for the pairs [(matches, i, j)]: the fitted entries `slots` of the camera vector
+    and per pair (x0, lb, ub, scales) as `Cameras([m.cams[fitted]], [m], cam_params=[cam_params])` makes them -- or
+    NotImplementedError / ValueError as `_batched_plan` raises them for that model.  Made before any library call."""
+    no = "ransac_pairs does not serve "
+    for key, value in kwargs.items():
+        if key not in _BATCHED_KWARGS or value is None or (key == "nan_policy" and value != "omit"):
+            raise NotImplementedError(no + f"{key}={value!r}: the device fit honours numbers for ftol, xtol, gtol and max_nfev "
+                                      "(and nan_policy='omit')")
+    if fitted not in (0, 1):
+        raise ValueError(f"fitted is 0 (the pair's first camera) or 1 (its second), got {fitted!r}")
+    mask = Cameras.parse_params(cam_params)[0]
+    slots = np.flatnonzero(mask)
+    if not len(slots):
+        raise NotImplementedError(no + "cam_params without a parameter to fit")
+    known, values = {}, []  # (what depends on the fitted camera alone is made once per camera)
+    for m, i, j in pairs:
+        if isinstance(m, RotationMatchesXYZ) or not isinstance(m, Matches):
+            raise NotImplementedError(no + f"a {type(m).__name__} for pair ({i}, {j}): Matches, RotationMatches and RotationMatchesXY")
+        if isinstance(m, RotationMatches) and (slots >= 6).any():
+            raise NotImplementedError(no + "fitted internal parameters (f, c, k, p) under a RotationMatches control, whose "
+                                      "camera coordinates hold them fixed")
+        if (slots < 3).any():
+            raise NotImplementedError(no + "a fitted position (xyz) under a match control, which holds it fixed")
+        for cam in m.cams:
+            if id(cam) not in known:
+                known[id(cam)] = None
+                if cam.vector24[23] != 0:
+                    raise NotImplementedError(no + "a camera with a raster grid")
+        m._test_position()
+        if isinstance(m, RotationMatches):
+            m._test_internals()
+        cam = m.cams[fitted]
+        if known[id(cam)] is None:
+            bounds = Cameras.parse_params(cam_params, default_bounds=Cameras.camera_bounds(cam))[1][mask]
+            x0, lb, ub = np.array(cam._vector[mask], dtype=float), bounds[:, 0], bounds[:, 1]
+            if np.any(lb >= ub):
+                raise ValueError("Each lower bound must be strictly less than each upper bound.")
+            if np.any((x0 < lb) | (x0 > ub)):
+                raise ValueError("`x0` violates bound constraints.")
+            known[id(cam)] = (x0, lb, ub, Cameras.camera_scales(cam)[mask])
+        values.append(known[id(cam)])
+    options = {key: kwargs[key] for key in ("ftol", "xtol", "gtol", "max_nfev") if key in kwargs}
+    return dict(slots=slots, values=values, options=options)
+
+
+def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=None, fitted=1, samples=None, budget=None,
+                 return_info=False, **kwargs):
+    """Random Sample Consensus over every image pair of `pairs` (whatever `match_pairs` accepts: `KeypointMatcher.matches`, a
+    dict {(i, j): matches}, an (n, n) object array; each entry a `Matches`, `RotationMatches` or `RotationMatchesXY`) in ONE
+    device pass per chunk of pairs (`glh_calib_ransac_groups`).  Returns a list in pair order of `(params, inliers)` as
+    `ransac` returns them, or None where `ransac` would raise for that pair (no fit meets the acceptance criteria, or the
+    pair has `n` rows or fewer): one bad pair does not end a sequence.
+
+    Pair k is treated as `ransac(Cameras([m.cams[fitted]], [m], cam_params=[cam_params]), n, max_error, min_inliers,
+    iterations, **kwargs)` treats it: the pair's second (`fitted=1`) or first (0) camera is fitted from its own current
+    vector with that model's bounds and scales, the other camera is held; consensus is error < max_error outside the
+    sample; a hypothesis with more than `min_inliers` in consensus is refitted on sample and consensus; the smallest mean
+    error wins, the earlier hypothesis of equal ones; the inliers are error <= max_error under the winner.  The pairs are
+    independent: a camera fitted in one pair and held in another is seen at its original vector by both, and no camera is
+    modified.
+
+    The samples are drawn on the host by `_ransac_samples`, pair after pair, so under one `np.random.seed` they are the
+    samples a loop of `ransac` over the pairs draws.  `samples`: instead, per pair an (H_k, n) integer array of row numbers
+    within the pair.  `params` are the DEVICE's refit values on the winning set (a damped Gauss-Newton, `glh_lm.h`), not
+    scipy's: they agree with `Cameras.fit` on that set to well within 1e-3 of each parameter's scale, and the host fit per
+    pair is the cost this call removes.  `budget`: an upper bound in bytes (default RANSAC_PAIRS_BUDGET) on the device memory
+    for the consensus masks, hypotheses x rows bytes per pair: the pairs are processed in consecutive chunks that stay
+    below it, a pair whose own masks exceed it in a chunk of its own; the result does not depend on the chunking.
+    `return_info`: also a dict with, per hypothesis, `values`, `status`, `consensus`, `refit_values`, `refit_status`,
+    `mean_errors` (hypotheses of pair k: hyp_offset[k] .. hyp_offset[k + 1]); per pair `winner` (counted from the pair's
+    first hypothesis, -1: none); and `times_ms`.
+
+    Refused with NotImplementedError, before any library call: what `_batched_plan` refuses for such a model (a fitted
+    position, internal parameters under a RotationMatches, a raster-grid camera, kwargs other than numeric ftol / xtol /
+    gtol / max_nfev and nan_policy="omit") and any control that is not one of the three match kinds.  ValueError: x0
+    outside its bounds, or a lower bound that is not below the upper."""
+    import time
+
+    t = [time.perf_counter()]
+    cam_params = {"viewdir": True} if cam_params is None else cam_params
+    pairs = [] if isinstance(pairs, (list, tuple)) and not len(pairs) else match_pairs(pairs)
+    plan = _pairs_plan(pairs, fitted, cam_params, kwargs)
+    if not pairs:
+        return ([], dict(winner=np.zeros(0, np.int32), hyp_offset=np.zeros(1, np.int64), times_ms={})) if return_info else []
+    if samples is not None and len(samples) != len(pairs):
+        raise ValueError(f"samples: one array per pair ({len(pairs)}), got {len(samples)}")
+    t.append(time.perf_counter())
+    drawn = []
+    for k, (m, _, _) in enumerate(pairs):
+        if m.size <= n:  # ("Sample size is larger or equal to total size")
+            drawn.append(None)
+        elif samples is None:
+            drawn.append(np.array(list(_ransac_samples(n=n, size=m.size, iterations=iterations)), dtype=np.int64).reshape(-1, n))
+        else:
+            rows = np.asarray(samples[k])
+            if rows.ndim != 2 or rows.shape[1] != n or not np.issubdtype(rows.dtype, np.integer) \
+                    or (rows.size and (rows.min() < 0 or rows.max() >= m.size)):
+                raise ValueError(f"samples[{k}]: an (H, {n}) integer array of row numbers below {m.size}")
+            drawn.append(rows.astype(np.int64))
+    t.append(time.perf_counter())
+    served = [k for k, rows in enumerate(drawn) if rows is not None]
+    sizes = np.array([pairs[k][0].size for k in served], dtype=np.int64)
+    counts = np.array([len(drawn[k]) for k in served], dtype=np.int64)
+    budget = RANSAC_PAIRS_BUDGET if budget is None else int(budget)
+    chunk_of = _lib.ransac_chunks(sizes, counts, min(max(budget, 0), 2 ** 31 - 1)) if served else np.zeros(0, np.int32)
+    p = len(plan["slots"])
+    keys = ("values", "status", "consensus", "refit_values", "refit_status", "mean_errors")
+    parts = {key: [] for key in keys}
+    winner = np.full(len(pairs), -1, dtype=np.int32)
+    results = [None] * len(pairs)
+    times = dict.fromkeys(("upload",) + _lib.CALIB_RANSAC_TIMES[1:], 0.0)
+    host = 0.0
+    for chunk in range(int(chunk_of.max()) + 1 if served else 0):
+        t0 = time.perf_counter()
+        members = [served[q] for q in np.flatnonzero(chunk_of == chunk)]
+        cams, where = [], {}
+        for k in members:
+            for cam in pairs[k][0].cams:
+                if id(cam) not in where:
+                    where[id(cam)] = len(cams)
+                    cams.append(cam)
+        kind = [_kind_of(pairs[k][0]) for k in members]
+        rotation = _lib.CALIB_KINDS["rotation"] in kind
+        obs, src, observed = [], [], []
+        for k, c in zip(members, kind):
+            m = pairs[k][0]
+            sides = m.uvs if c == _lib.CALIB_KINDS["matches"] else m.xys
+            obs.append(np.asarray(sides[0], dtype=float).reshape(-1, 2))
+            src.append(np.column_stack((sides[1], np.zeros(len(sides[1])))))
+            if rotation:  # (a RotationMatches keeps camera coordinates on the device and predicts image coordinates)
+                observed.append(np.asarray(m.observed(), dtype=float).reshape(-1, 2))
+        row_offset = np.concatenate(([0], np.cumsum([len(o) for o in obs]))).astype(np.int64)
+        hyp_offset = np.concatenate(([0], np.cumsum([len(drawn[k]) for k in members]))).astype(np.int64)
+        x0, lb, ub, scales = (np.array([plan["values"][k][q] for k in members]).reshape(-1, p) for q in range(4))
+        rows = np.concatenate([drawn[k] + row_offset[g] for g, k in enumerate(members)])
+        cams24 = np.array([cam.vector24 for cam in cams])
+        t1 = time.perf_counter()
+        handle = _lib.Calib(len(cams), kind, [where[id(pairs[k][0].cams[0])] for k in members],
+                            [where[id(pairs[k][0].cams[1])] for k in members], np.zeros(len(members), np.int32), row_offset,
+                            np.concatenate(obs), np.concatenate(src))
+        try:
+            t2 = time.perf_counter()
+            out, device = handle.ransac_groups(
+                cams24, np.arange(len(members)), [where[id(pairs[k][0].cams[fitted])] for k in members], plan["slots"], x0, lb,
+                ub, scales, hyp_offset, rows, max_error, min_inliers, observed=np.concatenate(observed) if rotation else None,
+                return_times=True, **plan["options"])
+        finally:
+            handle.close()
+        for key in keys:
+            parts[key].append(out[key])
+        for g, k in enumerate(members):
+            winner[k] = out["winner"][g]
+            if winner[k] >= 0:
+                inliers = np.flatnonzero(out["inlier"][row_offset[g]:row_offset[g + 1]])
+                results[k] = (out["refit_values"][hyp_offset[g] + winner[k]].copy(), inliers)
+        host += t1 - t0
+        times["upload"] += (t2 - t1) * 1e3 + device["upload"]
+        for key in _lib.CALIB_RANSAC_TIMES[1:]:
+            times[key] += device[key]
+    if not return_info:
+        return results
+    info = {key: (np.concatenate(parts[key]) if parts[key] else np.zeros((0, p) if "values" in key else 0)) for key in keys}
+    info["winner"] = winner
+    info["hyp_offset"] = np.concatenate(([0], np.cumsum([0 if rows is None else len(rows) for rows in drawn]))).astype(np.int64)
+    info["chunks"] = int(chunk_of.max()) + 1 if served else 0
+    info["times_ms"] = dict(sampling=(t[2] - t[1]) * 1e3, host=(t[1] - t[0] + host) * 1e3, **times)
+    return results, info
 
 
 def match_pairs(matches):

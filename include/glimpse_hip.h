@@ -819,6 +819,45 @@ int glh_calib_fit_sets(glh_calib* handle, const double* cams, int fit_cam, int p
                        const double* observed, int n_sets, const int64_t* set_offset, const int64_t* set_rows, int max_nfev, double ftol, double xtol,
                        double gtol, int score, double max_error, double* x, int32_t* status, double* mean_error,
                        uint8_t* inlier, double* times_ms);
+/* optimize.ransac_pairs: Random Sample Consensus over n_groups GROUPS in one pass on the device.  Group g is the match
+ * control group_control[g] of the handle (MATCHES, ROTATION or ROTATION_XY; the groups name distinct controls in ascending
+ * order, and every row of the handle belongs to one of them) with the camera group_cam[g], one of the control's two, fitted
+ * in the entries slots [p] of its vector (as glh_calib_fit_sets) from x0 inside lb .. ub with the scales x_scale, each
+ * [n_groups][p]; the control's other camera, and this camera where another group holds it, stay at cams
+ * [n_cams][GLH_CAM_LEN].  weights, observed: as glh_calib_fit_sets.  The group owns hypotheses hyp_offset[g] ..
+ * hyp_offset[g + 1] (int64 [n_groups + 1], from 0, not decreasing): hypothesis h samples the n rows samples[h][0 .. n)
+ * (int64, global row numbers, inside the group's control).
+ *   1. every hypothesis is fitted to its sample by glh_calib_fit_sets' damped Gauss-Newton (a sample of up to 64 rows by
+ *      one wave, several to a workgroup; the LDS sized for p <= 3 or p <= 18): x [H][p], status [H] (its codes);
+ *   2. every row of the hypothesis's own group is scored under x: consensus [H] int32 counts the rows outside the sample
+ *      with |r| < max_error (0 for a failed fit); the masks stay on the device, hypotheses times rows bytes per group;
+ *   3. a hypothesis with status > 0 and consensus > min_inliers is refitted on sample and consensus, the group's rows in
+ *      ascending order: refit_x [H][p], refit_status [H], mean_error [H] (the mean of |r| over that set; NaN if the refit
+ *      failed or a row has no prediction).  The others get NaN and refit_status -100;
+ *   4. winner [n_groups]: the group's hypothesis (counted from the group's first) with refit_status > 0 and the smallest
+ *      mean_error that is a number, the earlier of equal ones; -1 if there is none;
+ *   5. inlier [N] uint8: 1 where |r| <= max_error under the winner's refit_x, 0 elsewhere and in a group without a winner.
+ * float64, no contraction, no floating-point atomics: a call repeated gives the same bytes, and a group's results do not
+ * depend on the other groups of the call.  times_ms (or NULL) [6]: HIP-event milliseconds -- [0] upload, [1] fit,
+ * [2] score, [3] refit, [4] winner and final score, [5] download.
+ * GLH_E_INVALID (checked before a device is touched, by csrc/glh_ransac_plan.h; the handle stays usable): null pointers, a
+ * group's control or camera out of range, a camera that is neither of its control's, a POINTS or LINES control, controls
+ * that repeat or descend, rows of the handle outside every group, a sample row outside its group's control, p, slots,
+ * bounds, scales and tolerances as glh_calib_fit_sets, n < 1, offsets that do not start at 0 or decrease, 2^31 mask bytes
+ * or sample rows or more, a ROTATION control without observed; GLH_E_UNSUPPORTED: a raster grid among the cameras.    */
+int glh_calib_ransac_groups(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
+                            const int32_t* group_cam, int p, const int32_t* slots, const double* x0, const double* lb,
+                            const double* ub, const double* x_scale, const double* weights, const double* observed,
+                            const int64_t* hyp_offset, int n, const int64_t* samples, int max_nfev, double ftol, double xtol,
+                            double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status, int32_t* consensus,
+                            double* refit_x, int32_t* refit_status, double* mean_error, int32_t* winner, uint8_t* inlier,
+                            double* times_ms);
+/* chunk_of [n_groups]: the call of glh_calib_ransac_groups that each group of a longer list goes to, when consecutive
+ * groups share a call while its masks (rows[g] times hyps[g] bytes each) stay at or below budget bytes and a group whose
+ * own masks exceed it gets a call of its own; n_chunks: how many calls.  Host arithmetic; GLH_E_INVALID: null pointers, a
+ * negative count.                                                                                                       */
+int glh_ransac_chunks(int n_groups, const int64_t* rows, const int64_t* hyps, int64_t budget, int32_t* chunk_of,
+                      int32_t* n_chunks);
 /* Frees the handle and its device memory (NULL: nothing).                                                              */
 int glh_calib_destroy(glh_calib* handle);
 
