@@ -13,7 +13,7 @@ constexpr int CAL_TIMES = 5;   // entries of times_ms (include/glimpse_hip.h)
 constexpr int CAL_TB = 256;    // threads of a workgroup, all three kernels
 constexpr int CAL_TILE = 256;  // projected points of a Lines job held in LDS at a time (tests/calib_restated.py: TILE)
 constexpr int CAL_FIT_TIMES = 4;  // entries of glh_calib_fit_sets' times_ms
-constexpr int CAL_FIT_TB = 128;   // threads of k_calib_fit's workgroup: the rows of a set it takes at a time
+constexpr int CAL_FIT_TB = 128;   // threads of k_fit_sets' workgroup: the rows of a set it takes at a time
 
 struct CamDev;
 

@@ -27,12 +27,16 @@
 // float64, no contraction (-ffp-contract=off), no atomics: two evaluations give the same bytes, and
 // tests/calib_restated.py restates the Lines path in NumPy bit for bit.
 //
-// glh_calib_fit_sets (optimize.ransac(batched=True)) fits one camera's parameters to many sets of rows in one call:
+// Both batched entry points fit one camera's parameters to a set of rows with ONE fit, team_fit: a damped Gauss-Newton
+// run by a team of one or two waves, whose residuals and forward-difference columns come from calib_row, the device
+// function k_calib_rows runs, under cameras rebuilt on the device from the stepped vector (team_evaluate); J^T J and
+// J^T r are summed within each wave, then over the waves and the tiles in a fixed order; what to try, what to accept and
+// when to stop is glh_lm.h's state machine, run by lane 0 and driven on the CPU by tests/hostcheck/ransac_hostcheck.cpp.
+// Every loop is bounded.
 //
-//   k_calib_fit, one workgroup per set: a damped Gauss-Newton whose residuals and forward-difference columns come from
-//   calib_row, the device function k_calib_rows runs, under cameras rebuilt on the device from the stepped vector; J^T J
-//   and J^T r are summed within each wave, then over the waves and the tiles in a fixed order; the p x p solve, the
-//   damping and the clamp into the bounds are glh_lm.h's, run by thread 0.  Every loop is bounded.
+// glh_calib_fit_sets (optimize.ransac(batched=True)) fits many sets of rows in one call:
+//
+//   k_fit_sets, one team of two waves per set, whose rows may span controls;
 //
 //   k_calib_score, one thread per (set, row) over all rows of the handle: |weighted residual| < max_error under the set's
 //   fitted values; k_calib_members then marks the set's own rows.
@@ -81,9 +85,9 @@ struct CalBlock {
   int32_t job, first;
 };
 
-// `predicted` of one row of a Points or match control: what k_calib_rows stores and what k_calib_fit and k_calib_score
-// take their residuals from.  ct, co: the camera that predicts and the other one of a match; Rt, Ro: their rotation
-// matrices as the ROTATION kinds multiply by them.
+// `predicted` of one row of a Points or match control: what k_calib_rows stores and what the fits and the scores take
+// their residuals from (team_residual).  ct, co: the camera that predicts and the other one of a match; Rt, Ro: their
+// rotation matrices as the ROTATION kinds multiply by them.
 __device__ __forceinline__ void calib_row(int kind, int directions, int side, const CamDev& ct, const CamDev& co, const double* Rt,
                                           const double* Ro, const double2* __restrict__ obs, const double* __restrict__ src,
                                           size_t row, double& u, double& v) {
@@ -206,48 +210,53 @@ __global__ void __launch_bounds__(CAL_TB) k_calib_nearest(const CalBlock* __rest
   if (live) out[(size_t)j.out0 + r] = pj[index];
 }
 
-// ---- the batched fit: one workgroup fits the fitted camera's parameters to one set of rows ----------------------------
+// ---- the team fit: a team of one or two waves fits the fitted camera's parameters to one set of rows -------------------
 struct CalCtl {
   int32_t kind, directions, cam_a, cam_b;
 };
 
-constexpr int FIT_WAVES = CAL_FIT_TB / 64;
-constexpr int FIT_MAX_E = LM_MAX_TRI + LM_MAX_P + 3;  // the sums of one evaluation: A's triangle, g, sum r r, rows, sum |r|
-constexpr int FIT_RUNNING = 100;                     // (no LM_* status)
-
-struct FitArgs {
-  const CamDev* cams;          // [n_cams] the cameras at their own vectors
-  const CalCtl* ctl;           // [n_controls]
-  const int32_t* row_ctl;      // [N] the control of every row
+// What every fit and every score is given, whichever entry point it serves.  The fits hold one wave per SIMD and reload
+// kernel arguments in the tile loop, where nothing hides a scalar load: the order keeps src .. weights, and RArgs' x0 ..
+// scale behind this struct, each within one 64-byte line and the first on a 16-byte boundary (measured on the refits of
+// tools/ransac_pairs_probe.py: 0.7 % of their time).
+struct FitBase {
+  const CamDev* cams;        // [n_cams] the cameras at their own vectors
+  const CalCtl* ctl;         // [n_controls]
+  int32_t p, max_nfev;
   const double2* obs;
   const double* src;
-  const double2* observed;     // [N] what the predictions are compared with: obs, or the caller's
-  const double2* weights;      // [N], or null
-  const int64_t* set_offset;   // [S + 1]
-  const int32_t* set_rows;
-  double* x;                   // [S][p]
-  int32_t* status;             // [S]
-  double* mean_error;          // [S]
-  double base[GLH_CAM_LEN];    // the fitted camera's vector
-  double x0[LM_MAX_P], lb[LM_MAX_P], ub[LM_MAX_P], scale[LM_MAX_P];
-  int32_t slot[LM_MAX_P];
-  int32_t fit_cam, p, max_nfev, n_rows;
+  const double2* observed;   // [N] what the predictions are compared with: obs, or the caller's
+  const double2* weights;    // [N], or null
   double ftol, xtol, gtol;
+  int32_t slot[LM_MAX_P];
 };
 
-struct FitShared {
-  CamDev cam[LM_MAX_P + 1];                // the fitted camera at the point and with each parameter stepped
-  double vec[LM_MAX_P + 1][GLH_CAM_LEN];
-  double J[2][LM_MAX_P + 1][CAL_FIT_TB];   // [u, v][column, the last is r][thread]: a thread reads its own entries only
-  double part[FIT_WAVES][FIT_MAX_E];       // the waves' sums of one tile
-  double acc[FIT_MAX_E];                   // the sums of the last evaluation
-  double tri[LM_MAX_TRI], g[LM_MAX_P];     // A and g at x
-  double x[LM_MAX_P], xt[LM_MAX_P], dx[LM_MAX_P], y[LM_MAX_P];
-  double M[LM_MAX_P * LM_MAX_P], b[LM_MAX_P];
-  double cost, lambda, err_sum, count, len2;
-  int32_t state, rejects;
+// What a team works on: the fitted camera and its parameters, its set of rows -- a list, or the rows row0 + k, k < n,
+// whose mask byte is not 0 -- and the rows' control: one for all of them (c, kept in registers), or the one row_ctl names
+// for each (a set that spans controls).
+struct Team {
+  const double *x0, *lb, *ub, *scale;  // [p]
+  const double* base;                  // [GLH_CAM_LEN] the fitted camera's vector
+  const int32_t* rows;
+  const uint8_t* mask;
+  const int32_t* row_ctl;              // [N], or null
+  int64_t row0;
+  CalCtl c;
+  int32_t fit_cam, n;
 };
-static_assert(sizeof(FitShared) <= 64 * 1024, "k_calib_fit's LDS");
+
+// A team's LDS.  MAXP: the instantiation's largest p; TW: the team's waves.
+template <int MAXP, int TW>
+struct FitShared {
+  static constexpr int E = MAXP * (MAXP + 1) / 2 + MAXP + 4;  // lm_sums(MAXP)
+  CamDev cam[MAXP + 1];               // the fitted camera at the point and with each parameter stepped
+  double vec[MAXP + 1][GLH_CAM_LEN];
+  double J[2][MAXP + 1][TW * 64];     // [u, v][column, the last is r][lane]: a lane reads its own entries only
+  double part[TW][E];                 // the waves' sums of one tile
+  double acc[E];                      // the sums of the last evaluation
+  LmState<MAXP> lm;
+};
+static_assert(sizeof(FitShared<LM_MAX_P, 2>) <= 64 * 1024, "the largest team's LDS");
 
 // glh_host.h's expand_camera (camera.py:239-280) on the device, for a camera that is not a raster grid: the rotation
 // matrix comes from the device's own cos and sin, so it is not NumPy's to the bit (the values that leave optimize.ransac
@@ -292,309 +301,6 @@ __device__ void camera_from_vector(const double* v, CamDev* c) {
   c->pad_ = 0;
 }
 
-// The weighted residual of global row `row` with `fitted` in the fitted camera's place.
-__device__ __forceinline__ void fit_residual(const FitArgs& a, const CamDev& fitted, size_t row, double& ru, double& rv) {
-  const CalCtl c = a.ctl[a.row_ctl[row]];
-  const CamDev& ct = c.cam_a == a.fit_cam ? fitted : a.cams[c.cam_a];
-  const CamDev& co = c.cam_b == a.fit_cam ? fitted : a.cams[c.cam_b];
-  double u, v;
-  calib_row(c.kind, c.directions, 0, ct, co, ct.R, co.R, a.obs, a.src, row, u, v);
-  const double2 o = a.observed[row];
-  ru = u - o.x;
-  rv = v - o.y;
-  if (a.weights) {
-    const double2 w = a.weights[row];
-    ru = ru * w.x;
-    rv = rv * w.y;
-  }
-}
-
-// The sum over the wave, in the order of the butterfly: every lane ends with the same bits.
-__device__ __forceinline__ double wave_sum(double v) {
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-// s.acc = the sums over the set's rows at the point xe (an array of s): A = J^T J (packed), g = J^T r, sum r r, the rows
-// that count and sum |r|, J in scaled variables by forward differences.  A row whose prediction is NaN at the point or
-// at a stepped point adds nothing.  Every thread of the workgroup calls this.
-__device__ void fit_evaluate(const FitArgs& a, FitShared& s, const double* xe, const int32_t* __restrict__ rows, int n) {
-  const int tid = (int)threadIdx.x, p = a.p;
-  const int nE = p * (p + 1) / 2 + p + 3;
-  __syncthreads();  // (xe is written, the last evaluation's sums are read)
-  if (tid <= p) {
-    double* v = s.vec[tid];
-    for (int k = 0; k < GLH_CAM_LEN; ++k) v[k] = a.base[k];
-    for (int i = 0; i < p; ++i) v[a.slot[i]] = xe[i];
-    if (tid > 0) {
-      const int i = tid - 1;
-      const double stepped = xe[i] + lm_fd_step(xe[i], a.lb[i], a.ub[i]);
-      v[a.slot[i]] = stepped;
-      s.dx[i] = stepped - xe[i];
-    }
-    camera_from_vector(v, &s.cam[tid]);
-  }
-  __syncthreads();
-  double sum[2] = {0.0, 0.0};  // entries tid and tid + CAL_FIT_TB
-  for (int first = 0; first < n; first += CAL_FIT_TB) {
-    const int k = first + tid;
-    bool ok = k < n;
-    double ru = 0.0, rv = 0.0;
-    if (ok) {
-      const size_t row = (size_t)rows[k];
-      fit_residual(a, s.cam[0], row, ru, rv);
-      ok = !(isnan(ru) || isnan(rv));
-      for (int j = 0; j < p; ++j) {
-        double su, sv;
-        fit_residual(a, s.cam[j + 1], row, su, sv);
-        const double ju = (su - ru) / s.dx[j] * a.scale[j], jv = (sv - rv) / s.dx[j] * a.scale[j];
-        ok = ok && !(isnan(ju) || isnan(jv));
-        s.J[0][j][tid] = ju;
-        s.J[1][j][tid] = jv;
-      }
-    }
-    if (!ok) {
-      ru = rv = 0.0;
-      for (int j = 0; j < p; ++j) s.J[0][j][tid] = s.J[1][j][tid] = 0.0;
-    }
-    s.J[0][p][tid] = ru;
-    s.J[1][p][tid] = rv;
-    const int wave = tid >> 6, lane = tid & 63;
-    int e = 0;
-    for (int i = 0; i < p; ++i)  // A's upper triangle row by row (lm_tri), then g: column p is r
-      for (int j = i; j < p; ++j, ++e) {
-        const double t = wave_sum(s.J[0][i][tid] * s.J[0][j][tid] + s.J[1][i][tid] * s.J[1][j][tid]);
-        if (lane == 0) s.part[wave][e] = t;
-      }
-    for (int i = 0; i <= p; ++i, ++e) {  // (the last of these is sum r r)
-      const double t = wave_sum(s.J[0][i][tid] * ru + s.J[1][i][tid] * rv);
-      if (lane == 0) s.part[wave][e] = t;
-    }
-    {
-      const double t = wave_sum(ok ? 1.0 : 0.0), h = wave_sum(ok ? hypot(ru, rv) : 0.0);
-      if (lane == 0) s.part[wave][e] = t, s.part[wave][e + 1] = h;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const int w = tid + q * CAL_FIT_TB;
-      if (w < nE) {
-        double t = s.part[0][w];
-        for (int k2 = 1; k2 < FIT_WAVES; ++k2) t += s.part[k2][w];
-        sum[q] += t;
-      }
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int q = 0; q < 2; ++q)
-    if (tid + q * CAL_FIT_TB < nE) s.acc[tid + q * CAL_FIT_TB] = sum[q];
-  __syncthreads();
-}
-
-// s.state as every thread of the workgroup sees it between two writes of thread 0.
-__device__ __forceinline__ int fit_state(FitShared& s) {
-  __syncthreads();
-  const int v = s.state;
-  __syncthreads();
-  return v;
-}
-
-// Thread 0: the evaluation in s.acc becomes the state at x.
-__device__ void fit_keep(FitShared& s, int p) {
-  const int nT = p * (p + 1) / 2;
-  for (int e = 0; e < nT; ++e) s.tri[e] = s.acc[e];
-  for (int i = 0; i < p; ++i) s.g[i] = s.acc[nT + i];
-  s.cost = 0.5 * s.acc[nT + p];
-  s.count = s.acc[nT + p + 1];
-  s.err_sum = s.acc[nT + p + 2];
-}
-
-__global__ void __launch_bounds__(CAL_FIT_TB) k_calib_fit(const FitArgs a) {
-  static_assert(FIT_MAX_E <= 2 * CAL_FIT_TB, "two sums per thread");
-  __shared__ FitShared s;
-  const int tid = (int)threadIdx.x, p = a.p, set = (int)blockIdx.x;
-  const int nT = p * (p + 1) / 2;
-  const int32_t* __restrict__ rows = a.set_rows + a.set_offset[set];
-  const int n = (int)(a.set_offset[set + 1] - a.set_offset[set]);
-  if (tid == 0) {
-    for (int i = 0; i < p; ++i) s.x[i] = a.x0[i];
-    s.lambda = LM_LAMBDA_START;
-    s.state = FIT_RUNNING;
-    s.rejects = 0;
-  }
-  fit_evaluate(a, s, s.x, rows, n);
-  if (tid == 0) {
-    fit_keep(s, p);
-    if (2.0 * s.count < (double)p)
-      s.state = LM_FEW_ROWS;
-    else if (!(s.cost < INFINITY))
-      s.state = LM_NOT_FINITE;
-  }
-  // one trial step per round: at most max_nfev rounds, whatever the residuals do
-  for (int it = 0; it < a.max_nfev; ++it) {
-    if (fit_state(s) != FIT_RUNNING) break;
-    if (tid == 0) {
-      uint32_t frozen = 0;
-      double gmax = 0.0;
-      for (int i = 0; i < p; ++i) {
-        if (lm_frozen(s.x[i], a.lb[i], a.ub[i], s.g[i]))
-          frozen |= 1u << i;
-        else
-          gmax = fmax(gmax, fabs(s.g[i]));
-      }
-      if (!(gmax >= a.gtol)) {
-        s.state = gmax == gmax ? LM_GTOL : LM_NOT_FINITE;
-      } else {
-        lm_system(p, s.tri, s.g, s.lambda, frozen, s.M, s.b);
-        if (!lm_solve(p, s.M, s.b)) {
-          s.state = LM_SINGULAR;
-        } else {
-          for (int i = 0; i < p; ++i) s.y[i] = s.b[i];
-          s.len2 = lm_clamp(p, s.x, a.scale, a.lb, a.ub, s.y, s.xt);
-          if (s.len2 == 0.0) s.state = LM_XTOL;
-        }
-      }
-    }
-    if (fit_state(s) != FIT_RUNNING) break;
-    fit_evaluate(a, s, s.xt, rows, n);
-    if (tid == 0) {
-      const double count = s.acc[nT + p + 1], cost = 0.5 * s.acc[nT + p];
-      double norm2 = 0.0;
-      for (int i = 0; i < p; ++i) norm2 += (s.x[i] / a.scale[i]) * (s.x[i] / a.scale[i]);
-      const bool is_short = sqrt(s.len2) < a.xtol * (a.xtol + sqrt(norm2));
-      // (a step that lowers the cost by losing rows -- points it pushes behind the camera -- is no improvement)
-      const bool accepted = count >= s.count && cost < s.cost;
-      s.lambda = lm_damping(s.lambda, accepted);
-      if (accepted) {
-        const double before = s.cost;
-        for (int i = 0; i < p; ++i) s.x[i] = s.xt[i];
-        fit_keep(s, p);
-        s.rejects = 0;
-        if (before - s.cost < a.ftol * before)
-          s.state = LM_FTOL;
-        else if (is_short)
-          s.state = LM_XTOL;
-      } else if (is_short) {
-        s.state = LM_XTOL;
-      } else if (++s.rejects >= LM_MAX_REJECT) {
-        s.state = LM_CAP;
-      }
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const int32_t status = s.state == FIT_RUNNING ? (int32_t)LM_CAP : s.state;
-    for (int i = 0; i < p; ++i) a.x[(size_t)set * p + i] = s.x[i];
-    a.status[set] = status;
-    // np.mean over the set's own rows: NaN as soon as one of them has no prediction
-    a.mean_error[set] = (status > 0 && s.count == (double)n) ? s.err_sum / s.count : NAN;
-  }
-}
-
-// inlier[set][row] = |weighted residual| < max_error under the set's fitted values, for every row of the handle: one
-// thread per (set, row), a workgroup within one set.  NaN is no inlier; a set whose fit failed has none.
-__global__ void __launch_bounds__(CAL_TB) k_calib_score(const FitArgs a, int blocks_per_set, double max_error,
-                                                        uint8_t* __restrict__ inlier) {
-  __shared__ CamDev cam;
-  __shared__ double vec[GLH_CAM_LEN];
-  const int set = (int)(blockIdx.x / (unsigned)blocks_per_set);
-  const int row = (int)(blockIdx.x % (unsigned)blocks_per_set) * CAL_TB + (int)threadIdx.x;
-  if (threadIdx.x == 0) {
-    for (int k = 0; k < GLH_CAM_LEN; ++k) vec[k] = a.base[k];
-    for (int i = 0; i < a.p; ++i) vec[a.slot[i]] = a.x[(size_t)set * a.p + i];
-    camera_from_vector(vec, &cam);
-  }
-  __syncthreads();
-  if (row >= a.n_rows) return;
-  uint8_t in = 0;
-  if (a.status[set] > 0) {
-    double ru, rv;
-    fit_residual(a, cam, (size_t)row, ru, rv);
-    in = hypot(ru, rv) < max_error ? 1 : 0;
-  }
-  inlier[(size_t)set * a.n_rows + row] = in;
-}
-
-// The set's own rows are its members (2), whatever their error: after k_calib_score on the same stream.
-__global__ void __launch_bounds__(CAL_TB) k_calib_members(const FitArgs a, uint8_t* __restrict__ inlier) {
-  const int set = (int)blockIdx.x;
-  const int64_t first = a.set_offset[set], last = a.set_offset[set + 1];
-  for (int64_t k = first + threadIdx.x; k < last; k += CAL_TB) inlier[(size_t)set * a.n_rows + a.set_rows[k]] = 2;
-}
-
-// ---- glh_calib_ransac_groups: RANSAC over many groups in one pass --------------------------------------------------------
-// A group is one match control with one of its cameras fitted (glh_ransac_plan.h).  Four steps on one stream, nothing read
-// back in between:
-//
-//   k_rg_fit (hypotheses), one TEAM per sample of n rows: a team is one wave when n <= 64 -- several teams to a workgroup,
-//   the wave's butterfly is then the whole reduction and no workgroup barrier is used -- and a workgroup of two waves
-//   beyond.  The Gauss-Newton is k_calib_fit's, with calib_row, camera_from_vector and glh_lm.h as they are; what differs
-//   is that camera, start, bounds and scales are the group's, read from device arrays, and that the LDS is sized by the
-//   instantiation's largest p (3: a view direction; 18: everything).
-//   k_rg_score, one workgroup per hypothesis over the rows of ITS group: the mask byte (1: error < max_error, 2: a row of
-//   the sample) stays on the device, the count of 1s is the consensus.
-//   k_rg_fit (refits), one workgroup per hypothesis with status > 0 and consensus > min_inliers: it walks its group's rows
-//   in order and skips those whose mask byte is 0, so equal sets give equal bytes.
-//   k_rg_winner, one thread per group: the valid refit of smallest mean error, the earlier one of equal ones;
-//   k_rg_final, one workgroup per group: error <= max_error of every row under the winner's refitted values.
-struct RGroup {
-  int64_t row0;   // the group's first row in the handle
-  int64_t mask0;  // the first mask byte of its first hypothesis
-  int32_t n_rows, ctl, fit_cam, hyp0, n_hyp, pad_;
-};
-
-struct RArgs {
-  const CamDev* cams;        // [n_cams] the cameras at their own vectors
-  const double* vectors;     // [n_cams][GLH_CAM_LEN]
-  const CalCtl* ctl;         // [n_controls]
-  const double2* obs;
-  const double* src;
-  const double2* observed;   // [N]: obs, or the caller's
-  const double2* weights;    // [N], or null
-  const RGroup* groups;      // [G]
-  const int32_t* hyp_group;  // [H]
-  const int32_t* samples;    // [H][n] global rows
-  const double *x0, *lb, *ub, *scale;  // [G][p]
-  uint8_t* mask;
-  double* x;                 // [H][p]
-  double* refit_x;           // [H][p]
-  double* mean_error;        // [H]
-  int32_t *status, *consensus, *refit_status;  // [H]
-  int32_t* winner;           // [G]
-  uint8_t* inlier;           // [N]
-  int32_t slot[LM_MAX_P];
-  int32_t p, n, max_nfev, n_hyp, n_groups, min_inliers;
-  double ftol, xtol, gtol, max_error;
-};
-
-template <int MAXP, int TW>
-struct RFitShared {
-  static constexpr int TRI = MAXP * (MAXP + 1) / 2;
-  static constexpr int E = TRI + MAXP + 4;  // A's triangle, g, sum r r, rows that count, sum |r|, members
-  CamDev cam[MAXP + 1];
-  double vec[MAXP + 1][GLH_CAM_LEN];
-  double J[2][MAXP + 1][TW * 64];
-  double part[TW][E];
-  double acc[E];
-  double tri[TRI], g[MAXP];
-  double x[MAXP], xt[MAXP], dx[MAXP], y[MAXP];
-  double M[MAXP * MAXP], b[MAXP];
-  double cost, lambda, err_sum, count, members, len2;
-  int32_t state, rejects;
-};
-
-// What a team works on: its group, the group's control and parameters, and its set of rows -- a list (a sample), or the
-// rows of the group whose mask byte is not 0 (a refit).
-struct RTeam {
-  RGroup g;
-  CalCtl c;
-  const double *x0, *lb, *ub, *scale, *base;
-  const int32_t* rows;
-  const uint8_t* mask;
-  int n;
-};
-
 // Between the lanes of a team: a wave's LDS accesses execute in order, so one wave needs the compiler's fence alone.
 template <int TW>
 __device__ __forceinline__ void team_sync() {
@@ -606,12 +312,15 @@ __device__ __forceinline__ void team_sync() {
   }
 }
 
-__device__ __forceinline__ void rg_residual(const RArgs& a, const RTeam& w, const CamDev& fitted, size_t row, double& ru,
-                                            double& rv) {
-  const CamDev& ct = w.c.cam_a == w.g.fit_cam ? fitted : a.cams[w.c.cam_a];
-  const CamDev& co = w.c.cam_b == w.g.fit_cam ? fitted : a.cams[w.c.cam_b];
+// The weighted residual of global row `row` with `fitted` in the fitted camera's place.
+__device__ __forceinline__ void team_residual(const FitBase& a, const Team& w, const CamDev& fitted, size_t row, double& ru,
+                                              double& rv) {
+  CalCtl c = w.c;
+  if (w.row_ctl) c = a.ctl[w.row_ctl[row]];
+  const CamDev& ct = c.cam_a == w.fit_cam ? fitted : a.cams[c.cam_a];
+  const CamDev& co = c.cam_b == w.fit_cam ? fitted : a.cams[c.cam_b];
   double u, v;
-  calib_row(w.c.kind, w.c.directions, 0, ct, co, ct.R, co.R, a.obs, a.src, row, u, v);
+  calib_row(c.kind, c.directions, 0, ct, co, ct.R, co.R, a.obs, a.src, row, u, v);
   const double2 o = a.observed[row];
   ru = u - o.x;
   rv = v - o.y;
@@ -622,13 +331,21 @@ __device__ __forceinline__ void rg_residual(const RArgs& a, const RTeam& w, cons
   }
 }
 
-// fit_evaluate for a team: s.acc = the sums over the team's set at the point xe (an array of s).  t: the lane within the
-// team.  Every lane of the team calls this.
+// The sum over the wave, in the order of the butterfly: every lane ends with the same bits.
+__device__ __forceinline__ double wave_sum(double v) {
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// s.acc = the evaluation (glh_lm.h) of the team's set at the point xe: A = J^T J (packed), g = J^T r, sum r r, the rows
+// that count, sum |r| and the members, J in scaled variables by forward differences.  A row whose prediction is NaN at the
+// point or at a stepped point adds nothing.  Each sum is taken within the wave, then over the waves and the tiles in
+// order.  t: the lane within the team.  Every lane of the team calls this.
 template <int MAXP, int TW>
-__device__ void rg_evaluate(const RArgs& a, const RTeam& w, RFitShared<MAXP, TW>& s, const double* xe, int t) {
-  constexpr int TT = TW * 64, E = RFitShared<MAXP, TW>::E, Q = (E + TT - 1) / TT;
+__device__ void team_evaluate(const FitBase& a, const Team& w, FitShared<MAXP, TW>& s, const double* xe, int t) {
+  constexpr int TT = TW * 64, E = FitShared<MAXP, TW>::E, Q = (E + TT - 1) / TT;
   const int p = a.p;
-  const int nE = p * (p + 1) / 2 + p + 4;
+  const int nE = lm_sums(p);
   team_sync<TW>();  // (xe is written, the last evaluation's sums are read)
   if (t <= p) {
     double* v = s.vec[t];
@@ -638,7 +355,7 @@ __device__ void rg_evaluate(const RArgs& a, const RTeam& w, RFitShared<MAXP, TW>
       const int i = t - 1;
       const double stepped = xe[i] + lm_fd_step(xe[i], w.lb[i], w.ub[i]);
       v[a.slot[i]] = stepped;
-      s.dx[i] = stepped - xe[i];
+      s.lm.dx[i] = stepped - xe[i];
     }
     camera_from_vector(v, &s.cam[t]);
   }
@@ -655,19 +372,19 @@ __device__ void rg_evaluate(const RArgs& a, const RTeam& w, RFitShared<MAXP, TW>
       if (w.rows) {
         row = (size_t)w.rows[k];
       } else {
-        row = (size_t)w.g.row0 + k;
+        row = (size_t)w.row0 + k;
         member = w.mask[k] != 0;
       }
     }
     bool ok = member;
     double ru = 0.0, rv = 0.0;
     if (ok) {
-      rg_residual(a, w, s.cam[0], row, ru, rv);
+      team_residual(a, w, s.cam[0], row, ru, rv);
       ok = !(isnan(ru) || isnan(rv));
       for (int j = 0; j < p; ++j) {
         double su, sv;
-        rg_residual(a, w, s.cam[j + 1], row, su, sv);
-        const double ju = (su - ru) / s.dx[j] * w.scale[j], jv = (sv - rv) / s.dx[j] * w.scale[j];
+        team_residual(a, w, s.cam[j + 1], row, su, sv);
+        const double ju = (su - ru) / s.lm.dx[j] * w.scale[j], jv = (sv - rv) / s.lm.dx[j] * w.scale[j];
         ok = ok && !(isnan(ju) || isnan(jv));
         s.J[0][j][t] = ju;
         s.J[1][j][t] = jv;
@@ -711,122 +428,172 @@ __device__ void rg_evaluate(const RArgs& a, const RTeam& w, RFitShared<MAXP, TW>
   team_sync<TW>();
 }
 
+// The fit's state as every lane of the team sees it between two writes of lane 0.
 template <int MAXP, int TW>
-__device__ __forceinline__ int rg_state(RFitShared<MAXP, TW>& s) {
+__device__ __forceinline__ int team_state(FitShared<MAXP, TW>& s) {
   team_sync<TW>();
-  const int v = s.state;
+  const int v = s.lm.state;
   team_sync<TW>();
   return v;
 }
 
-// Lane 0: the evaluation in s.acc becomes the state at x.
+// The damped Gauss-Newton of one team on its set: the team evaluates, lane 0 decides (glh_lm.h) and leaves the values, the
+// status and, where asked for, the mean error over the set's rows.
 template <int MAXP, int TW>
-__device__ void rg_keep(RFitShared<MAXP, TW>& s, int p) {
-  const int nT = p * (p + 1) / 2;
-  for (int e = 0; e < nT; ++e) s.tri[e] = s.acc[e];
-  for (int i = 0; i < p; ++i) s.g[i] = s.acc[nT + i];
-  s.cost = 0.5 * s.acc[nT + p];
-  s.count = s.acc[nT + p + 1];
-  s.err_sum = s.acc[nT + p + 2];
-  s.members = s.acc[nT + p + 3];
-}
-
-// k_calib_fit's loop for one team.  Lane 0 leaves the values, the status and the mean error over the set's rows.
-template <int MAXP, int TW>
-__device__ void rg_fit(const RArgs& a, const RTeam& w, RFitShared<MAXP, TW>& s, int t, double* x, int32_t* status,
-                       double* mean_error) {
-  const int p = a.p, nT = p * (p + 1) / 2;
-  if (t == 0) {
-    for (int i = 0; i < p; ++i) s.x[i] = w.x0[i];
-    s.lambda = LM_LAMBDA_START;
-    s.state = FIT_RUNNING;
-    s.rejects = 0;
-  }
-  rg_evaluate<MAXP, TW>(a, w, s, s.x, t);
-  if (t == 0) {
-    rg_keep<MAXP, TW>(s, p);
-    if (2.0 * s.count < (double)p)
-      s.state = LM_FEW_ROWS;
-    else if (!(s.cost < INFINITY))
-      s.state = LM_NOT_FINITE;
-  }
+__device__ void team_fit(const FitBase& a, const Team& w, FitShared<MAXP, TW>& s, int t, double* x, int32_t* status,
+                         double* mean_error) {
+  const int p = a.p;
+  if (t == 0) lm_begin(s.lm, p, w.x0);
+  team_evaluate<MAXP, TW>(a, w, s, s.lm.x, t);
+  if (t == 0) lm_first(s.lm, p, s.acc);
   for (int it = 0; it < a.max_nfev; ++it) {  // one trial step per round: bounded, whatever the residuals do
-    if (rg_state<MAXP, TW>(s) != FIT_RUNNING) break;
-    if (t == 0) {
-      uint32_t frozen = 0;
-      double gmax = 0.0;
-      for (int i = 0; i < p; ++i) {
-        if (lm_frozen(s.x[i], w.lb[i], w.ub[i], s.g[i]))
-          frozen |= 1u << i;
-        else
-          gmax = fmax(gmax, fabs(s.g[i]));
-      }
-      if (!(gmax >= a.gtol)) {
-        s.state = gmax == gmax ? LM_GTOL : LM_NOT_FINITE;
-      } else {
-        lm_system(p, s.tri, s.g, s.lambda, frozen, s.M, s.b);
-        if (!lm_solve(p, s.M, s.b)) {
-          s.state = LM_SINGULAR;
-        } else {
-          for (int i = 0; i < p; ++i) s.y[i] = s.b[i];
-          s.len2 = lm_clamp(p, s.x, w.scale, w.lb, w.ub, s.y, s.xt);
-          if (s.len2 == 0.0) s.state = LM_XTOL;
-        }
-      }
-    }
-    if (rg_state<MAXP, TW>(s) != FIT_RUNNING) break;
-    rg_evaluate<MAXP, TW>(a, w, s, s.xt, t);
-    if (t == 0) {
-      const double count = s.acc[nT + p + 1], cost = 0.5 * s.acc[nT + p];
-      double norm2 = 0.0;
-      for (int i = 0; i < p; ++i) norm2 += (s.x[i] / w.scale[i]) * (s.x[i] / w.scale[i]);
-      const bool is_short = sqrt(s.len2) < a.xtol * (a.xtol + sqrt(norm2));
-      const bool accepted = count >= s.count && cost < s.cost;
-      s.lambda = lm_damping(s.lambda, accepted);
-      if (accepted) {
-        const double before = s.cost;
-        for (int i = 0; i < p; ++i) s.x[i] = s.xt[i];
-        rg_keep<MAXP, TW>(s, p);
-        s.rejects = 0;
-        if (before - s.cost < a.ftol * before)
-          s.state = LM_FTOL;
-        else if (is_short)
-          s.state = LM_XTOL;
-      } else if (is_short) {
-        s.state = LM_XTOL;
-      } else if (++s.rejects >= LM_MAX_REJECT) {
-        s.state = LM_CAP;
-      }
-    }
+    if (team_state<MAXP, TW>(s) != LM_RUNNING) break;
+    if (t == 0) lm_propose(s.lm, p, w.lb, w.ub, w.scale, a.gtol);
+    if (team_state<MAXP, TW>(s) != LM_RUNNING) break;
+    team_evaluate<MAXP, TW>(a, w, s, s.lm.xt, t);
+    if (t == 0) lm_judge(s.lm, p, w.scale, s.acc, a.ftol, a.xtol);
   }
   team_sync<TW>();
   if (t == 0) {
-    const int32_t st = s.state == FIT_RUNNING ? (int32_t)LM_CAP : s.state;
-    for (int i = 0; i < p; ++i) x[i] = s.x[i];
-    *status = st;
-    // np.mean over the set's own rows: NaN as soon as one of them has no prediction
-    if (mean_error) *mean_error = (st > 0 && s.count == s.members) ? s.err_sum / s.count : NAN;
+    for (int i = 0; i < p; ++i) x[i] = s.lm.x[i];
+    *status = lm_finish(s.lm, mean_error);
   }
+}
+
+// The fitted camera at the values x, by thread 0 into LDS (the caller synchronises).
+__device__ __forceinline__ void fitted_camera(const FitBase& a, const double* base, const double* x, double* vec, CamDev* cam) {
+  for (int k = 0; k < GLH_CAM_LEN; ++k) vec[k] = base[k];
+  for (int i = 0; i < a.p; ++i) vec[a.slot[i]] = x[i];
+  camera_from_vector(vec, cam);
+}
+
+// The instantiation's largest p: 3 (a view direction) or everything.
+constexpr int FIT_SMALL_P = 3;
+
+// ---- glh_calib_fit_sets: one team of two waves per set; a set may span controls ---------------------------------------
+struct SetArgs : FitBase {
+  const int32_t* row_ctl;      // [N] the control of every row
+  const int64_t* set_offset;   // [S + 1]
+  const int32_t* set_rows;
+  const double* par;           // x0, lb, ub, scale [p] each, then the fitted camera's vector
+  double* x;                   // [S][p]
+  int32_t* status;             // [S]
+  double* mean_error;          // [S]
+  int32_t fit_cam, n_rows;
+};
+
+// The team of every set of the call, its rows apart.
+__device__ __forceinline__ Team set_team(const SetArgs& a) {
+  Team w{};
+  w.x0 = a.par, w.lb = a.par + a.p, w.ub = a.par + 2 * a.p, w.scale = a.par + 3 * a.p, w.base = a.par + 4 * a.p;
+  w.row_ctl = a.row_ctl;
+  w.fit_cam = a.fit_cam;
+  return w;
+}
+
+// The tile is 128 rows for every p: the tile width fixes the order of the sums, and so the bytes.
+template <int MAXP>
+__global__ void __launch_bounds__(CAL_FIT_TB) k_fit_sets(const SetArgs a) {
+  static_assert(CAL_FIT_TB == 2 * 64, "a team of two waves");
+  __shared__ FitShared<MAXP, 2> s;
+  const int set = (int)blockIdx.x;
+  Team w = set_team(a);
+  w.rows = a.set_rows + a.set_offset[set];
+  w.n = (int)(a.set_offset[set + 1] - a.set_offset[set]);
+  team_fit<MAXP, 2>(a, w, s, (int)threadIdx.x, a.x + (size_t)set * a.p, a.status + set, a.mean_error + set);
+}
+
+// inlier[set][row] = |weighted residual| < max_error under the set's fitted values, for every row of the handle: one
+// thread per (set, row), a workgroup within one set.  NaN is no inlier; a set whose fit failed has none.
+__global__ void __launch_bounds__(CAL_TB) k_calib_score(const SetArgs a, int blocks_per_set, double max_error,
+                                                        uint8_t* __restrict__ inlier) {
+  __shared__ CamDev cam;
+  __shared__ double vec[GLH_CAM_LEN];
+  const int set = (int)(blockIdx.x / (unsigned)blocks_per_set);
+  const int row = (int)(blockIdx.x % (unsigned)blocks_per_set) * CAL_TB + (int)threadIdx.x;
+  const Team w = set_team(a);
+  if (threadIdx.x == 0) fitted_camera(a, w.base, a.x + (size_t)set * a.p, vec, &cam);
+  __syncthreads();
+  if (row >= a.n_rows) return;
+  uint8_t in = 0;
+  if (a.status[set] > 0) {
+    double ru, rv;
+    team_residual(a, w, cam, (size_t)row, ru, rv);
+    in = hypot(ru, rv) < max_error ? 1 : 0;
+  }
+  inlier[(size_t)set * a.n_rows + row] = in;
+}
+
+// The set's own rows are its members (2), whatever their error: after k_calib_score on the same stream.
+__global__ void __launch_bounds__(CAL_TB) k_calib_members(const SetArgs a, uint8_t* __restrict__ inlier) {
+  const int set = (int)blockIdx.x;
+  const int64_t first = a.set_offset[set], last = a.set_offset[set + 1];
+  for (int64_t k = first + threadIdx.x; k < last; k += CAL_TB) inlier[(size_t)set * a.n_rows + a.set_rows[k]] = 2;
+}
+
+// ---- glh_calib_ransac_groups: RANSAC over many groups in one pass --------------------------------------------------------
+// A group is one match control with one of its cameras fitted (glh_ransac_plan.h).  Four steps on one stream, nothing read
+// back in between:
+//
+//   k_rg_fit (hypotheses), one TEAM per sample of n rows: a team is one wave when n <= 64 -- several teams to a workgroup,
+//   the wave's butterfly is then the whole reduction and no workgroup barrier is used -- and a workgroup of two waves
+//   beyond.  The fit is team_fit, the one k_fit_sets runs; camera, start, bounds and scales are the group's, and the
+//   control is the group's for every row.
+//   k_rg_score, one workgroup per hypothesis over the rows of ITS group: the mask byte (1: error < max_error, 2: a row of
+//   the sample) stays on the device, the count of 1s is the consensus.
+//   k_rg_fit (refits), one workgroup per hypothesis with status > 0 and consensus > min_inliers: it walks its group's rows
+//   in order and skips those whose mask byte is 0, so equal sets give equal bytes.
+//   k_rg_winner, one thread per group: the valid refit of smallest mean error, the earlier one of equal ones;
+//   k_rg_final, one workgroup per group: error <= max_error of every row under the winner's refitted values.
+struct RGroup {
+  int64_t row0;   // the group's first row in the handle
+  int64_t mask0;  // the first mask byte of its first hypothesis
+  int32_t n_rows, ctl, fit_cam, hyp0, n_hyp, pad_;
+};
+
+struct RArgs : FitBase {
+  const double *x0, *lb, *ub, *scale;  // [G][p]
+  const double* vectors;     // [n_cams][GLH_CAM_LEN]
+  const RGroup* groups;      // [G]
+  const int32_t* hyp_group;  // [H]
+  const int32_t* samples;    // [H][n] global rows
+  uint8_t* mask;
+  double* x;                 // [H][p]
+  double* refit_x;           // [H][p]
+  double* mean_error;        // [H]
+  int32_t *status, *consensus, *refit_status;  // [H]
+  int32_t* winner;           // [G]
+  uint8_t* inlier;           // [N]
+  int32_t n, n_hyp, n_groups, min_inliers;
+  double max_error;
+};
+
+// The team of group gi, its set of rows apart.
+__device__ __forceinline__ Team group_team(const RArgs& a, int gi, const RGroup& g) {
+  Team w{};
+  w.x0 = a.x0 + (size_t)gi * a.p, w.lb = a.lb + (size_t)gi * a.p, w.ub = a.ub + (size_t)gi * a.p;
+  w.scale = a.scale + (size_t)gi * a.p;
+  w.base = a.vectors + (size_t)g.fit_cam * GLH_CAM_LEN;
+  w.row0 = g.row0;
+  w.c = a.ctl[g.ctl];
+  w.fit_cam = g.fit_cam;
+  return w;
 }
 
 // refit == 0: hypothesis h is fitted to its sample; refit != 0: to sample and consensus, if it was accepted.
 template <int MAXP, int TW, int TEAMS>
 __global__ void __launch_bounds__(TW * 64 * TEAMS) k_rg_fit(const RArgs a, int refit) {
   static_assert(TW == 1 || TEAMS == 1, "teams that share a workgroup must not meet at a workgroup barrier");
-  __shared__ RFitShared<MAXP, TW> sh[TEAMS];
+  __shared__ FitShared<MAXP, TW> sh[TEAMS];
   const int team = (int)threadIdx.x / (TW * 64), t = (int)threadIdx.x % (TW * 64);
   const int h = (int)blockIdx.x * TEAMS + team;
   if (h >= a.n_hyp) return;
   const int gi = a.hyp_group[h];
-  RTeam w;
-  w.g = a.groups[gi];
-  w.c = a.ctl[w.g.ctl];
-  w.x0 = a.x0 + (size_t)gi * a.p, w.lb = a.lb + (size_t)gi * a.p, w.ub = a.ub + (size_t)gi * a.p;
-  w.scale = a.scale + (size_t)gi * a.p;
-  w.base = a.vectors + (size_t)w.g.fit_cam * GLH_CAM_LEN;
+  const RGroup g = a.groups[gi];
+  Team w = group_team(a, gi, g);
   if (!refit) {
-    w.rows = a.samples + (size_t)h * a.n, w.mask = nullptr, w.n = a.n;
-    rg_fit<MAXP, TW>(a, w, sh[team], t, a.x + (size_t)h * a.p, a.status + h, nullptr);
+    w.rows = a.samples + (size_t)h * a.n, w.n = a.n;
+    team_fit<MAXP, TW>(a, w, sh[team], t, a.x + (size_t)h * a.p, a.status + h, nullptr);
     return;
   }
   if (!(a.status[h] > 0 && a.consensus[h] > a.min_inliers)) {
@@ -837,16 +604,8 @@ __global__ void __launch_bounds__(TW * 64 * TEAMS) k_rg_fit(const RArgs a, int r
     }
     return;
   }
-  w.rows = nullptr, w.mask = a.mask + w.g.mask0 + (size_t)(h - w.g.hyp0) * w.g.n_rows, w.n = w.g.n_rows;
-  rg_fit<MAXP, TW>(a, w, sh[team], t, a.refit_x + (size_t)h * a.p, a.refit_status + h, a.mean_error + h);
-}
-
-// The fitted camera of group g at the values x, by thread 0 into LDS (the caller synchronises).
-__device__ __forceinline__ void rg_camera(const RArgs& a, const RGroup& g, const double* x, double* vec, CamDev* cam) {
-  const double* base = a.vectors + (size_t)g.fit_cam * GLH_CAM_LEN;
-  for (int k = 0; k < GLH_CAM_LEN; ++k) vec[k] = base[k];
-  for (int i = 0; i < a.p; ++i) vec[a.slot[i]] = x[i];
-  camera_from_vector(vec, cam);
+  w.mask = a.mask + g.mask0 + (size_t)(h - g.hyp0) * g.n_rows, w.n = g.n_rows;
+  team_fit<MAXP, TW>(a, w, sh[team], t, a.refit_x + (size_t)h * a.p, a.refit_status + h, a.mean_error + h);
 }
 
 __global__ void __launch_bounds__(CAL_TB) k_rg_score(const RArgs a) {
@@ -854,31 +613,31 @@ __global__ void __launch_bounds__(CAL_TB) k_rg_score(const RArgs a) {
   __shared__ double vec[GLH_CAM_LEN];
   __shared__ int32_t count;
   const int h = (int)blockIdx.x, tid = (int)threadIdx.x;
-  RTeam w;
-  w.g = a.groups[a.hyp_group[h]];
-  w.c = a.ctl[w.g.ctl];
-  uint8_t* __restrict__ m = a.mask + w.g.mask0 + (size_t)(h - w.g.hyp0) * w.g.n_rows;
+  const int gi = a.hyp_group[h];
+  const RGroup g = a.groups[gi];
+  const Team w = group_team(a, gi, g);
+  uint8_t* __restrict__ m = a.mask + g.mask0 + (size_t)(h - g.hyp0) * g.n_rows;
   const bool fitted = a.status[h] > 0;  // (a hypothesis whose fit failed has no consensus)
   if (tid == 0) {
     count = 0;
-    rg_camera(a, w.g, a.x + (size_t)h * a.p, vec, &cam);
+    fitted_camera(a, w.base, a.x + (size_t)h * a.p, vec, &cam);
   }
   __syncthreads();
-  for (int k = tid; k < w.g.n_rows; k += CAL_TB) {
+  for (int k = tid; k < g.n_rows; k += CAL_TB) {
     uint8_t in = 0;
     if (fitted) {
       double ru, rv;
-      rg_residual(a, w, cam, (size_t)w.g.row0 + k, ru, rv);
+      team_residual(a, w, cam, (size_t)g.row0 + k, ru, rv);
       in = hypot(ru, rv) < a.max_error ? 1 : 0;
     }
     m[k] = in;
   }
   __syncthreads();
   if (fitted)
-    for (int k = tid; k < a.n; k += CAL_TB) m[(int64_t)a.samples[(size_t)h * a.n + k] - w.g.row0] = 2;
+    for (int k = tid; k < a.n; k += CAL_TB) m[(int64_t)a.samples[(size_t)h * a.n + k] - g.row0] = 2;
   __syncthreads();
   int local = 0;
-  for (int k = tid; k < w.g.n_rows; k += CAL_TB) local += m[k] == 1 ? 1 : 0;
+  for (int k = tid; k < g.n_rows; k += CAL_TB) local += m[k] == 1 ? 1 : 0;
   for (int s = 32; s >= 1; s >>= 1) local += __shfl_xor(local, s);
   if ((tid & 63) == 0) atomicAdd(&count, local);
   __syncthreads();
@@ -902,24 +661,21 @@ __global__ void __launch_bounds__(CAL_TB) k_rg_final(const RArgs a) {
   __shared__ CamDev cam;
   __shared__ double vec[GLH_CAM_LEN];
   const int gi = (int)blockIdx.x, tid = (int)threadIdx.x;
-  RTeam w;
-  w.g = a.groups[gi];
-  w.c = a.ctl[w.g.ctl];
+  const RGroup g = a.groups[gi];
+  const Team w = group_team(a, gi, g);
   const int win = a.winner[gi];
-  if (tid == 0 && win >= 0) rg_camera(a, w.g, a.refit_x + (size_t)(w.g.hyp0 + win) * a.p, vec, &cam);
+  if (tid == 0 && win >= 0) fitted_camera(a, w.base, a.refit_x + (size_t)(g.hyp0 + win) * a.p, vec, &cam);
   __syncthreads();
-  for (int k = tid; k < w.g.n_rows; k += CAL_TB) {
+  for (int k = tid; k < g.n_rows; k += CAL_TB) {
     uint8_t in = 0;
     if (win >= 0) {
       double ru, rv;
-      rg_residual(a, w, cam, (size_t)w.g.row0 + k, ru, rv);
+      team_residual(a, w, cam, (size_t)g.row0 + k, ru, rv);
       in = hypot(ru, rv) <= a.max_error ? 1 : 0;
     }
-    a.inlier[(size_t)w.g.row0 + k] = in;
+    a.inlier[(size_t)g.row0 + k] = in;
   }
 }
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 }  // namespace
 }  // namespace glh
@@ -1020,28 +776,13 @@ int calib_eval(glh_calib* h, const CalibEval& e) {
     out_rows += j.n_rows;
     puv_total += n_puv;
   }
-  size_t at = 0;
-  const size_t o_cams = at;
-  at = align16(at + n_cam_sets * sizeof(CamDev));
-  const size_t o_rot = at;
-  at = align16(at + n_cam_sets * 72);
-  const size_t o_jobs = at;
-  at = align16(at + jobs.size() * sizeof(CalJob));
-  const size_t o_segs = at;
-  at = align16(at + segs.size() * sizeof(CalSeg));
-  const size_t o_rows = at;
-  at = align16(at + rows_b.size() * sizeof(CalBlock));
-  const size_t o_points = at;
-  at = align16(at + points_b.size() * sizeof(CalBlock));
-  const size_t o_nearest = at;
-  at = align16(at + nearest_b.size() * sizeof(CalBlock));
-  const size_t o_vx = at;
-  at = align16(at + V * 8);
-  const size_t o_vy = at;
-  at = align16(at + V * 8);
-  const size_t o_vd = at;
-  at = align16(at + V * 8);
-  h->stage.resize(at ? at : 16);
+  StageLayout in;
+  const size_t o_cams = in.place(n_cam_sets * sizeof(CamDev)), o_rot = in.place(n_cam_sets * 72);
+  const size_t o_jobs = in.place(jobs.size() * sizeof(CalJob)), o_segs = in.place(segs.size() * sizeof(CalSeg));
+  const size_t o_rows = in.place(rows_b.size() * sizeof(CalBlock)), o_points = in.place(points_b.size() * sizeof(CalBlock));
+  const size_t o_nearest = in.place(nearest_b.size() * sizeof(CalBlock));
+  const size_t o_vx = in.place(V * 8), o_vy = in.place(V * 8), o_vd = in.place(V * 8);
+  h->stage.resize(in.size ? in.size : 16);
   char* st = h->stage.data();
   std::memcpy(st + o_cams, e.cams, n_cam_sets * sizeof(CamDev));
   std::memcpy(st + o_rot, e.rot, n_cam_sets * 72);
@@ -1099,19 +840,12 @@ int calib_fit_sets(glh_calib* h, const CalibFit& f) {
   hipStream_t s = h->stream;
   const size_t N = (size_t)h->row_offset[h->n_controls], S = (size_t)f.n_sets, T = (size_t)f.set_offset[f.n_sets];
   const size_t p = (size_t)f.p;
-  // in: the cameras, the weights, the sets; out: x, mean_error, status, inlier
-  size_t at = 0;
-  const size_t i_cams = at;
-  at = align16(at + (size_t)h->n_cams * sizeof(CamDev));
-  const size_t i_weights = at;
-  at = align16(at + (f.weights ? N * 16 : 0));
-  const size_t i_observed = at;
-  at = align16(at + (f.observed ? N * 16 : 0));
-  const size_t i_offset = at;
-  at = align16(at + (S + 1) * 8);
-  const size_t i_rows = at;
-  at = align16(at + T * 4);
-  h->stage.resize(at);
+  // in: the cameras, the weights, the sets, the fitted camera's parameters and vector; out: x, mean_error, status, inlier
+  StageLayout in, out;
+  const size_t i_cams = in.place((size_t)h->n_cams * sizeof(CamDev));
+  const size_t i_weights = in.place(f.weights ? N * 16 : 0), i_observed = in.place(f.observed ? N * 16 : 0);
+  const size_t i_offset = in.place((S + 1) * 8), i_rows = in.place(T * 4), i_par = in.place((4 * p + GLH_CAM_LEN) * 8);
+  h->stage.resize(in.size);
   char* st = h->stage.data();
   std::memcpy(st + i_cams, f.cams, (size_t)h->n_cams * sizeof(CamDev));
   if (f.weights) std::memcpy(st + i_weights, f.weights, N * 16);
@@ -1119,23 +853,19 @@ int calib_fit_sets(glh_calib* h, const CalibFit& f) {
   std::memcpy(st + i_offset, f.set_offset, (S + 1) * 8);
   int32_t* rows = reinterpret_cast<int32_t*>(st + i_rows);
   for (size_t k = 0; k < T; ++k) rows[k] = (int32_t)f.set_rows[k];
-  size_t ot = 0;
-  const size_t o_x = ot;
-  ot = align16(ot + S * p * 8);
-  const size_t o_mean = ot;
-  ot = align16(ot + S * 8);
-  const size_t o_status = ot;
-  ot = align16(ot + S * 4);
-  const size_t o_inlier = ot;
-  ot = align16(ot + (f.score ? S * N : 0));
+  double* par = reinterpret_cast<double*>(st + i_par);  // (set_team's order)
+  for (size_t i = 0; i < p; ++i) par[i] = f.x0[i], par[p + i] = f.lb[i], par[2 * p + i] = f.ub[i], par[3 * p + i] = f.scale[i];
+  std::memcpy(par + 4 * p, f.base, GLH_CAM_LEN * 8);
+  const size_t o_x = out.place(S * p * 8), o_mean = out.place(S * 8), o_status = out.place(S * 4);
+  const size_t o_inlier = out.place(f.score ? S * N : 0);
   CHK(h->fit_in.reserve(h->stage.size()));
-  CHK(h->fit_out.reserve(ot));
+  CHK(h->fit_out.reserve(out.size));
   CHK(h->fit_ev.record(0, s));
   HIPCHK(hipMemcpy(h->fit_in.p, st, h->stage.size(), hipMemcpyHostToDevice));
   CHK(h->fit_ev.record(1, s));
   const char* d = h->fit_in.as<char>();
   char* o = h->fit_out.as<char>();
-  FitArgs a{};
+  SetArgs a{};
   a.cams = reinterpret_cast<const CamDev*>(d + i_cams);
   a.ctl = h->ctl.as<CalCtl>();
   a.row_ctl = h->row_ctl.as<int32_t>();
@@ -1145,16 +875,18 @@ int calib_fit_sets(glh_calib* h, const CalibFit& f) {
   a.observed = f.observed ? reinterpret_cast<const double2*>(d + i_observed) : h->obs.as<double2>();
   a.set_offset = reinterpret_cast<const int64_t*>(d + i_offset);
   a.set_rows = reinterpret_cast<const int32_t*>(d + i_rows);
+  a.par = reinterpret_cast<const double*>(d + i_par);
   a.x = reinterpret_cast<double*>(o + o_x);
   a.status = reinterpret_cast<int32_t*>(o + o_status);
   a.mean_error = reinterpret_cast<double*>(o + o_mean);
-  std::memcpy(a.base, f.base, sizeof(a.base));
-  for (size_t i = 0; i < p; ++i)
-    a.x0[i] = f.x0[i], a.lb[i] = f.lb[i], a.ub[i] = f.ub[i], a.scale[i] = f.scale[i], a.slot[i] = f.slots[i];
+  for (size_t i = 0; i < p; ++i) a.slot[i] = f.slots[i];
   a.fit_cam = f.fit_cam, a.p = f.p, a.max_nfev = f.max_nfev, a.n_rows = (int32_t)N;
   a.ftol = f.ftol, a.xtol = f.xtol, a.gtol = f.gtol;
   if (S) {
-    hipLaunchKernelGGL(k_calib_fit, dim3((unsigned)S), dim3(CAL_FIT_TB), 0, s, a);
+    if (f.p <= FIT_SMALL_P)
+      hipLaunchKernelGGL(k_fit_sets<FIT_SMALL_P>, dim3((unsigned)S), dim3(CAL_FIT_TB), 0, s, a);
+    else
+      hipLaunchKernelGGL(k_fit_sets<LM_MAX_P>, dim3((unsigned)S), dim3(CAL_FIT_TB), 0, s, a);
     HIPCHK(hipGetLastError());
   }
   CHK(h->fit_ev.record(2, s));
@@ -1207,17 +939,12 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   for (size_t g = 0; g < G; ++g)
     groups[g] = RGroup{h->row_offset[r.group_control[g]], mask_offset[g], (int32_t)rows[g], r.group_control[g], r.group_cam[g],
                        (int32_t)r.hyp_offset[g], (int32_t)hyps[g], 0};
-  size_t at = 0;
-  auto place = [&at](size_t bytes) {
-    const size_t o = at;
-    at = align16(at + bytes);
-    return o;
-  };
-  const size_t i_cams = place(C * sizeof(CamDev)), i_vec = place(C * GLH_CAM_LEN * 8);
-  const size_t i_weights = place(r.weights ? N * 16 : 0), i_observed = place(r.observed ? N * 16 : 0);
-  const size_t i_groups = place(G * sizeof(RGroup)), i_hg = place(H * 4), i_samples = place(H * n * 4);
-  const size_t i_x0 = place(G * p * 8), i_lb = place(G * p * 8), i_ub = place(G * p * 8), i_scale = place(G * p * 8);
-  h->stage.resize(at ? at : 16);
+  StageLayout in, out;
+  const size_t i_cams = in.place(C * sizeof(CamDev)), i_vec = in.place(C * GLH_CAM_LEN * 8);
+  const size_t i_weights = in.place(r.weights ? N * 16 : 0), i_observed = in.place(r.observed ? N * 16 : 0);
+  const size_t i_groups = in.place(G * sizeof(RGroup)), i_hg = in.place(H * 4), i_samples = in.place(H * n * 4);
+  const size_t i_x0 = in.place(G * p * 8), i_lb = in.place(G * p * 8), i_ub = in.place(G * p * 8), i_scale = in.place(G * p * 8);
+  h->stage.resize(in.size ? in.size : 16);
   char* st = h->stage.data();
   std::memcpy(st + i_cams, r.cams, C * sizeof(CamDev));
   std::memcpy(st + i_vec, r.vectors, C * GLH_CAM_LEN * 8);
@@ -1236,10 +963,9 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   int32_t* samples = reinterpret_cast<int32_t*>(st + i_samples);
   for (size_t k = 0; k < H * n; ++k) samples[k] = (int32_t)r.samples[k];
   // out, in the order of the download: the doubles, the int32s, the bytes
-  at = 0;
-  const size_t o_x = place(H * p * 8), o_refit = place(H * p * 8), o_mean = place(H * 8), o_status = place(H * 4);
-  const size_t o_consensus = place(H * 4), o_rstatus = place(H * 4), o_winner = place(G * 4), o_inlier = place(N);
-  const size_t out_bytes = at ? at : 16;
+  const size_t o_x = out.place(H * p * 8), o_refit = out.place(H * p * 8), o_mean = out.place(H * 8), o_status = out.place(H * 4);
+  const size_t o_consensus = out.place(H * 4), o_rstatus = out.place(H * 4), o_winner = out.place(G * 4), o_inlier = out.place(N);
+  const size_t out_bytes = out.size ? out.size : 16;
   CHK(h->rg_in.reserve(h->stage.size()));
   CHK(h->rg_out.reserve(out_bytes));
   CHK(h->rg_mask.reserve(mask_bytes));
@@ -1272,12 +998,12 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   // (a consensus is at most 2^31 - 1 rows, at least 0)
   a.min_inliers = (int32_t)(r.min_inliers > INT32_MAX ? INT32_MAX : (r.min_inliers < -1 ? -1 : r.min_inliers));
   a.ftol = r.ftol, a.xtol = r.xtol, a.gtol = r.gtol, a.max_error = r.max_error;
-  const bool small = r.p <= 3;
+  const bool small = r.p <= FIT_SMALL_P;
   if (H) {
     if (r.n <= 64)
-      small ? rg_launch<3, 1, 4>(a, 0, s) : rg_launch<LM_MAX_P, 1, 1>(a, 0, s);
+      small ? rg_launch<FIT_SMALL_P, 1, 4>(a, 0, s) : rg_launch<LM_MAX_P, 1, 1>(a, 0, s);
     else
-      small ? rg_launch<3, 2, 1>(a, 0, s) : rg_launch<LM_MAX_P, 2, 1>(a, 0, s);
+      small ? rg_launch<FIT_SMALL_P, 2, 1>(a, 0, s) : rg_launch<LM_MAX_P, 2, 1>(a, 0, s);
     HIPCHK(hipGetLastError());
   }
   CHK(h->rg_ev.record(2, s));
@@ -1287,7 +1013,7 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   }
   CHK(h->rg_ev.record(3, s));
   if (H) {
-    small ? rg_launch<3, 2, 1>(a, 1, s) : rg_launch<LM_MAX_P, 2, 1>(a, 1, s);
+    small ? rg_launch<FIT_SMALL_P, 2, 1>(a, 1, s) : rg_launch<LM_MAX_P, 2, 1>(a, 1, s);
     HIPCHK(hipGetLastError());
   }
   CHK(h->rg_ev.record(4, s));

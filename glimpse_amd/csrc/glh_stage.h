@@ -83,6 +83,17 @@ struct GrowBuf : DevBuf {
   }
 };
 
+// Where the arrays of a staging buffer lie, one after another: place(bytes) is the next one's offset, a multiple of 16,
+// and `size` what the buffer holds after it.
+struct StageLayout {
+  size_t size = 0;
+  size_t place(size_t bytes) {
+    const size_t at = size;
+    size = (at + bytes + 15) & ~(size_t)15;
+    return at;
+  }
+};
+
 // What the handle of every device object starts with.
 struct DeviceObject {
   int device = 0;

@@ -247,6 +247,43 @@ def test_what_is_refused_is_refused_before_the_library(monkeypatch):
     assert optimize.ransac_pairs(np.full((3, 3), None, dtype=object), **call) == []
 
 
+def test_fit_sets_and_ransac_groups_fit_a_sample_to_the_same_bytes():
+    """Both entry points run one fit (glh_calib.hip: team_fit), so the same samples of the same rows give the same `values`
+    and `status`, byte for byte: through `fit_sets` as sets (always a team of two waves) and through `ransac_groups` as the
+    hypotheses of one group that accepts nothing (`min_inliers` above the row count; a team of one wave up to 64 rows,
+    whose sums equal the two-wave team's because the idle wave adds +0.0 to each).  One handle with the pair of
+    `six_parameters` (257 rows); samples of 2 .. 200 rows either side of a wave and of the tile of 128, four each; the
+    view direction (p = 3, the small instantiation) and the scene's five parameters (the general one), whose sizes start
+    at the scene's own 40: two rows are four residuals for five parameters, which the admission's rule (every sample
+    determines its values) excludes."""
+    from glimpse_amd import _lib
+    from glimpse_amd.optimize import _pairs_plan, match_pairs
+
+    cams, matches, d = pc.scene("six_parameters")
+    (m,) = matches.values()
+    rows = m.size
+    assert rows == 257
+    cams24 = np.array([cam.vector24 for cam in cams])
+    src = np.column_stack((m.uvs[1], np.zeros(rows)))
+    different = []
+    with _lib.Calib(2, [_lib.CALIB_KINDS["matches"]], [0], [1], [0], [0, rows], m.uvs[0], src) as handle:
+        for params, sizes in ((pc.VIEWDIR, (2, 63, 64, 65, 128, 129, 200)), (pc.GENERAL, (40, 63, 64, 65, 128, 129, 200))):
+            plan = _pairs_plan(match_pairs(matches), 1, params, {})
+            x0, lb, ub, scale = (np.array(v) for v in plan["values"][0])
+            for n in sizes:
+                rng = np.random.default_rng(n)
+                samples = np.array([rng.permutation(rows)[:n] for _ in range(4)], dtype=np.int64)
+                values, status, _ = handle.fit_sets(cams24, 1, plan["slots"], x0, lb, ub, scale, np.arange(5) * n,
+                                                    samples.reshape(-1))
+                groups = handle.ransac_groups(cams24, [0], [1], plan["slots"], x0[None], lb[None], ub[None], scale[None],
+                                              [0, 4], samples, max_error=3.0, min_inliers=rows + 1)
+                print("p", len(plan["slots"]), "n", n, "status", status, groups["status"])
+                assert (status > 0).all() and (groups["refit_status"] == _lib.CALIB_NOT_REFITTED).all()
+                if values.tobytes() != groups["values"].tobytes() or status.tobytes() != groups["status"].tobytes():
+                    different.append((len(plan["slots"]), n, float(np.abs(values - groups["values"]).max())))
+    assert not different, different
+
+
 def test_bad_arguments_leave_the_handle_usable():
     from glimpse_amd import _lib
     from glimpse_amd.optimize import _pairs_plan, match_pairs
