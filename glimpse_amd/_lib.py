@@ -179,7 +179,13 @@ SIGNATURES = {
                                 C.c_double, _P, _P, _P, _P, _P]),
     "glh_calib_ransac_groups": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, C.c_double, C.c_double,
                                      C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "glh_calib_ransac_groups_drawn": (_I, [_P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, C.c_double,
+                                           C.c_double, C.c_double, C.c_double, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                           C.c_uint32, C.c_uint32, _P, _P]),
     "glh_ransac_chunks": (_I, [_I, _P, _P, C.c_int64, _P, _P]),
+    "glh_ransac_hypotheses": (_I, [_I, _P, _I, C.c_int64, _P, _P]),
+    "glh_ransac_combinations": (_I, [C.c_int64, _I, C.c_int64, _P]),
+    "glh_stage_ransac_samples": (_I, [_I, _I, _P, _P, _P, _I, C.c_uint32, C.c_uint32, _P, _P]),
     "glh_calib_destroy": (_I, [_P]),
     "glh_match_create": (_I, [_I, _P]),
     "glh_match_put": (_I, [_P, _I, _I, _I, _I, _P]),
@@ -1473,14 +1479,19 @@ class Calib(_Handle):
 
     def ransac_groups(self, cams, group_control, group_cam, slots, x0, lb, ub, x_scale, hyp_offset, samples, max_error,
                       min_inliers, weights=None, observed=None, max_nfev=None, ftol=1e-8, xtol=1e-8, gtol=1e-8,
-                      return_times=False):
+                      return_times=False, group_id=None, drawn=None, seed=(0, 0), n=None):
         """Random Sample Consensus over G groups in ONE device pass (glh_calib_ransac_groups; include/glimpse_hip.h says
         how): group g is the match control `group_control[g]` with the camera `group_cam[g]` fitted in the entries `slots`
         (p,) of its vector, from `x0` inside `lb` .. `ub` with the scales `x_scale`, each (G, p); it owns the hypotheses
         hyp_offset[g] .. hyp_offset[g + 1], rows of `samples` (H, n) (global row numbers).  `weights`, `observed`: as
         `fit_sets`.  Returns a dict: per hypothesis `values` (H, p), `status`, `consensus`, `refit_values`,
         `refit_status`, `mean_errors`; per group `winner` (its hypothesis counted from the group's first, -1: none); per
-        row of the handle `inlier` (uint8)."""
+        row of the handle `inlier` (uint8).
+
+        `drawn` (G,) of 0 / 1 (glh_calib_ransac_groups_drawn): a group with 1 has its samples drawn on the device as those
+        of pair `group_id[g]` under the two 32-bit words `seed`, and `samples` (or None when every group is drawn) is not
+        read for it (`n`: the sample size then); the dict also has `samples` (H, n), the global rows of every hypothesis,
+        and the times `draw`."""
         handle = self._handle()
         cams = _arr(cams, np.float64)
         if cams.shape != (self.n_cams, CAM_LEN):
@@ -1493,10 +1504,12 @@ class Calib(_Handle):
         n_groups, p = len(group_control), len(slots)
         x0, lb, ub, x_scale = (_arr(v, np.float64, (n_groups, p)) for v in (x0, lb, ub, x_scale))
         hyp_offset = _arr(hyp_offset, np.int64, (n_groups + 1,))
-        samples = _arr(samples, np.int64)
         n_hyp = int(hyp_offset.max(initial=0))
-        if samples.ndim != 2 or len(samples) < n_hyp:
-            raise ValueError("samples (H, n) with H >= hyp_offset.max()")
+        if samples is not None or drawn is None:
+            samples = _arr(samples, np.int64)
+            if samples.ndim != 2 or len(samples) < n_hyp:
+                raise ValueError("samples (H, n) with H >= hyp_offset.max()")
+            n = samples.shape[1]
         n_rows = int(self.rows.sum())
         if weights is not None:
             weights = _arr(weights, np.float64, (n_rows, 2))
@@ -1505,15 +1518,58 @@ class Calib(_Handle):
         out = dict(values=np.empty((n_hyp, p)), status=np.empty(n_hyp, np.int32), consensus=np.empty(n_hyp, np.int32),
                    refit_values=np.empty((n_hyp, p)), refit_status=np.empty(n_hyp, np.int32), mean_errors=np.empty(n_hyp),
                    winner=np.empty(n_groups, np.int32), inlier=np.empty(n_rows, np.uint8))
-        times = np.zeros(len(CALIB_RANSAC_TIMES))
-        check(load().glh_calib_ransac_groups(
-            handle, _ptr(cams), n_groups, _ptr(group_control), _ptr(group_cam), p, _ptr(slots), _ptr(x0), _ptr(lb), _ptr(ub),
-            _ptr(x_scale), _ptr(weights), _ptr(observed), _ptr(hyp_offset), int(samples.shape[1]), _ptr(samples),
-            int(100 * p if max_nfev is None else max_nfev), float(ftol), float(xtol), float(gtol), float(max_error),
-            int(min(max(min_inliers, -1), 2 ** 62)), *[_ptr(out[key]) for key in ("values", "status", "consensus", "refit_values",
-                                                                                 "refit_status", "mean_errors", "winner", "inlier")],
-            _ptr(times)))
-        return _timed(out, CALIB_RANSAC_TIMES, times, return_times)
+        shared = (handle, _ptr(cams), n_groups, _ptr(group_control), _ptr(group_cam), p, _ptr(slots), _ptr(x0), _ptr(lb), _ptr(ub),
+                  _ptr(x_scale), _ptr(weights), _ptr(observed), _ptr(hyp_offset), int(n), _ptr(samples),
+                  int(100 * p if max_nfev is None else max_nfev), float(ftol), float(xtol), float(gtol), float(max_error),
+                  int(min(max(min_inliers, -1), 2 ** 62)), *[_ptr(out[key]) for key in ("values", "status", "consensus", "refit_values",
+                                                                                       "refit_status", "mean_errors", "winner", "inlier")])
+        if drawn is None:
+            names = CALIB_RANSAC_TIMES
+            times = np.zeros(len(names))
+            check(load().glh_calib_ransac_groups(*shared, _ptr(times)))
+        else:
+            names = CALIB_RANSAC_TIMES + ("draw",)
+            times = np.zeros(len(names))
+            drawn, group_id = _arr(drawn, np.uint8, (n_groups,)), _arr(group_id, np.int32, (n_groups,))
+            out["samples"] = np.empty((n_hyp, int(n)), np.int64)
+            check(load().glh_calib_ransac_groups_drawn(*shared, _ptr(group_id), _ptr(drawn), int(seed[0]), int(seed[1]),
+                                                       _ptr(out["samples"]), _ptr(times)))
+        return _timed(out, names, times, return_times)
+
+
+def ransac_hypotheses(rows, n, iterations):
+    """(hyps, enumerated), each (G,): min(iterations, C(rows[g], n)) hypotheses for a pair of rows[g] rows (0 for n rows or
+    fewer) and whether they are all its combinations, which `ransac_combinations` lists, or drawn on the device
+    (glh_ransac_hypotheses: host arithmetic, no device)."""
+    rows = _arr(rows, np.int64)
+    hyps, enumerated = np.zeros(len(rows), np.int64), np.zeros(len(rows), np.uint8)
+    check(load().glh_ransac_hypotheses(len(rows), _ptr(rows), int(n), int(iterations), _ptr(hyps), _ptr(enumerated)))
+    return hyps, enumerated.astype(bool)
+
+
+def ransac_combinations(rows, n, count):
+    """(count, n) int64: the first `count` combinations of `n` of `rows` rows in lexicographic order
+    (glh_ransac_combinations: host arithmetic, no device)."""
+    samples = np.empty((int(count), int(n)), np.int64)
+    check(load().glh_ransac_combinations(int(rows), int(n), int(count), _ptr(samples)))
+    return samples
+
+
+RANSAC_SAMPLES_TIMES = ("upload", "draw", "download")
+
+
+def stage_ransac_samples(device_id, rows, group_id, hyp_offset, n, seed, return_times=False):
+    """(H, n) int64: the samples `ransac_pairs(samples="device")` draws for G pairs of `rows[g]` rows that are the pairs
+    `group_id[g]` of its list, hypotheses hyp_offset[g] .. hyp_offset[g + 1], under the two 32-bit words `seed`: rows
+    within the pair, ascending (glh_stage_ransac_samples: the draw kernel alone)."""
+    rows = _arr(rows, np.int64)
+    group_id = _arr(group_id, np.int32, rows.shape)
+    hyp_offset = _arr(hyp_offset, np.int64, (len(rows) + 1,))
+    samples = np.empty((int(hyp_offset.max(initial=0)), int(n)), np.int64)
+    times = np.zeros(len(RANSAC_SAMPLES_TIMES))
+    check(load().glh_stage_ransac_samples(int(device_id), len(rows), _ptr(rows), _ptr(group_id), _ptr(hyp_offset), int(n),
+                                          int(seed[0]), int(seed[1]), _ptr(samples), _ptr(times)))
+    return _timed(samples, RANSAC_SAMPLES_TIMES, times, return_times)
 
 
 def ransac_chunks(rows, hyps, budget):

@@ -92,6 +92,23 @@ struct CalibRansac {  // glh_calib_ransac_groups' arguments (include/glimpse_hip
   int32_t* winner;         // [G]
   uint8_t* inlier;         // [N]
   double* times_ms;
+  // glh_calib_ransac_groups_drawn: a group with drawn[g] == 1 gets its samples from k_rg_draw as pair group_id[g]'s
+  // (glh_ransac_draw.h); times_ms then has RANSAC_DRAWN_TIMES entries
+  const uint8_t* drawn = nullptr;      // [G], or null: every group takes its rows from `samples`
+  const int32_t* group_id = nullptr;   // [G]
+  uint32_t seed0 = 0, seed1 = 0;
+  int64_t* samples_out = nullptr;      // [H][n] global rows of every hypothesis, or null
+};
+
+struct RansacDraw {  // glh_stage_ransac_samples' arguments (include/glimpse_hip.h), checked by the caller
+  int device, n_groups;
+  const int64_t* rows;        // [G]
+  const int32_t* group_id;    // [G]
+  const int64_t* hyp_offset;  // [G + 1]
+  int n;
+  uint32_t seed0, seed1;
+  int64_t* samples;           // [H][n] rows within the group
+  double* times_ms;           // [3] or null: upload, draw, download
 };
 
 // The arguments have been checked (glimpse_hip.hip).  A GLH_* status, with the message left for glh_last_error() on
@@ -101,6 +118,7 @@ CalibTable calib_table(const glh_calib* h);
 int calib_eval(glh_calib* h, const CalibEval& e);
 int calib_fit_sets(glh_calib* h, const CalibFit& f);
 int calib_ransac_groups(glh_calib* h, const CalibRansac& r);
+int ransac_draw_samples(const RansacDraw& r);
 void calib_destroy(glh_calib* h);
 
 }  // namespace glh

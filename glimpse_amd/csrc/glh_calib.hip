@@ -46,6 +46,8 @@
 //
 // glh_calib_ransac_groups (optimize.ransac_pairs) runs the whole RANSAC of many one-camera models -- the groups of a
 // handle -- in one pass: k_rg_fit, k_rg_score, k_rg_winner and k_rg_final, described where they stand below.
+// glh_calib_ransac_groups_drawn puts k_rg_draw in front: the samples of the groups it names are drawn on the device
+// (glh_ransac_draw.h), into the buffer the others read.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -57,6 +59,7 @@
 #include "glh_math.h"
 #include "glh_calib.h"
 #include "glh_lm.h"
+#include "glh_ransac_draw.h"
 #include "glh_ransac_plan.h"
 #include "glh_stage.h"
 
@@ -535,6 +538,8 @@ __global__ void __launch_bounds__(CAL_TB) k_calib_members(const SetArgs a, uint8
 // A group is one match control with one of its cameras fitted (glh_ransac_plan.h).  Four steps on one stream, nothing read
 // back in between:
 //
+//   k_rg_draw (glh_calib_ransac_groups_drawn alone), one thread per hypothesis of a drawn group: its sample, written into
+//   the buffer of samples before anything reads it (described where it stands, after the others);
 //   k_rg_fit (hypotheses), one TEAM per sample of n rows: a team is one wave when n <= 64 -- several teams to a workgroup,
 //   the wave's butterfly is then the whole reduction and no workgroup barrier is used -- and a workgroup of two waves
 //   beyond.  The fit is team_fit, the one k_fit_sets runs; camera, start, bounds and scales are the group's, and the
@@ -677,6 +682,29 @@ __global__ void __launch_bounds__(CAL_TB) k_rg_final(const RArgs a) {
   }
 }
 
+// One thread per hypothesis of a drawn group (`drawn` null: every group): it builds its sample in its own row of
+// `samples` by glh_ransac_draw.h's rd_draw, as hypothesis h - hyp0 of pair group_id[g] with the group's row count, in
+// global row numbers.  No thread reads what another writes; hypotheses of groups that are not drawn are left as uploaded.
+struct DrawArgs {
+  const RGroup* groups;      // [G]
+  const int32_t* hyp_group;  // [H]
+  const int32_t* group_id;   // [G]
+  const uint8_t* drawn;      // [G] or null
+  int32_t* samples;          // [H][n]
+  int32_t n, n_hyp;
+  uint32_t seed0, seed1;
+};
+
+__global__ void __launch_bounds__(CAL_TB) k_rg_draw(const DrawArgs a) {
+  const int64_t h = (int64_t)blockIdx.x * CAL_TB + threadIdx.x;
+  if (h >= a.n_hyp) return;
+  const int gi = a.hyp_group[h];
+  if (a.drawn && !a.drawn[gi]) return;
+  const RGroup g = a.groups[gi];
+  rd_draw(a.seed0, a.seed1, (uint32_t)a.group_id[gi], (uint32_t)((int32_t)h - g.hyp0), (uint32_t)g.n_rows, a.n, (int32_t)g.row0,
+          a.samples + (size_t)h * a.n);
+}
+
 }  // namespace
 }  // namespace glh
 
@@ -694,7 +722,7 @@ struct glh_calib : glh::DeviceObject {
   glh::StageEvents<glh::CAL_FIT_TIMES + 1> fit_ev;
   // RANSAC over groups (calib_ransac_groups): its buffers, the masks apart, and its events, made by the first call
   glh::GrowBuf rg_in, rg_out, rg_mask;
-  glh::StageEvents<glh::RANSAC_TIMES + 1> rg_ev;
+  glh::StageEvents<glh::RANSAC_DRAWN_TIMES + 1> rg_ev;  // (the last one: after the draw)
   bool rg_ready = false;
 };
 
@@ -943,6 +971,7 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   const size_t i_cams = in.place(C * sizeof(CamDev)), i_vec = in.place(C * GLH_CAM_LEN * 8);
   const size_t i_weights = in.place(r.weights ? N * 16 : 0), i_observed = in.place(r.observed ? N * 16 : 0);
   const size_t i_groups = in.place(G * sizeof(RGroup)), i_hg = in.place(H * 4), i_samples = in.place(H * n * 4);
+  const size_t i_id = in.place(r.drawn ? G * 4 : 0), i_drawn = in.place(r.drawn ? G : 0);
   const size_t i_x0 = in.place(G * p * 8), i_lb = in.place(G * p * 8), i_ub = in.place(G * p * 8), i_scale = in.place(G * p * 8);
   h->stage.resize(in.size ? in.size : 16);
   char* st = h->stage.data();
@@ -961,7 +990,17 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   for (size_t g = 0; g < G; ++g)
     for (int64_t k = r.hyp_offset[g]; k < r.hyp_offset[g + 1]; ++k) hg[k] = (int32_t)g;
   int32_t* samples = reinterpret_cast<int32_t*>(st + i_samples);
-  for (size_t k = 0; k < H * n; ++k) samples[k] = (int32_t)r.samples[k];
+  for (size_t g = 0; g < G; ++g) {
+    const size_t first = (size_t)r.hyp_offset[g] * n, last = (size_t)r.hyp_offset[g + 1] * n;
+    if (r.drawn && r.drawn[g])
+      std::memset(samples + first, 0, (last - first) * 4);  // (k_rg_draw's to fill)
+    else
+      for (size_t k = first; k < last; ++k) samples[k] = (int32_t)r.samples[k];
+  }
+  if (r.drawn && G) {
+    std::memcpy(st + i_id, r.group_id, G * 4);
+    std::memcpy(st + i_drawn, r.drawn, G);
+  }
   // out, in the order of the download: the doubles, the int32s, the bytes
   const size_t o_x = out.place(H * p * 8), o_refit = out.place(H * p * 8), o_mean = out.place(H * 8), o_status = out.place(H * 4);
   const size_t o_consensus = out.place(H * 4), o_rstatus = out.place(H * 4), o_winner = out.place(G * 4), o_inlier = out.place(N);
@@ -998,6 +1037,17 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   // (a consensus is at most 2^31 - 1 rows, at least 0)
   a.min_inliers = (int32_t)(r.min_inliers > INT32_MAX ? INT32_MAX : (r.min_inliers < -1 ? -1 : r.min_inliers));
   a.ftol = r.ftol, a.xtol = r.xtol, a.gtol = r.gtol, a.max_error = r.max_error;
+  const int drawn_at = RANSAC_DRAWN_TIMES;  // the event after the draw
+  if (r.drawn) {
+    if (H) {
+      // (the staging buffer is the device's to write once it is uploaded: the draw fills the rows the host left empty)
+      const DrawArgs da{a.groups, a.hyp_group, reinterpret_cast<const int32_t*>(d + i_id), reinterpret_cast<const uint8_t*>(d + i_drawn),
+                        reinterpret_cast<int32_t*>(h->rg_in.as<char>() + i_samples), a.n, a.n_hyp, r.seed0, r.seed1};
+      hipLaunchKernelGGL(k_rg_draw, dim3((unsigned)((H + CAL_TB - 1) / CAL_TB)), dim3(CAL_TB), 0, s, da);
+      HIPCHK(hipGetLastError());
+    }
+    CHK(h->rg_ev.record(drawn_at, s));
+  }
   const bool small = r.p <= FIT_SMALL_P;
   if (H) {
     if (r.n <= 64)
@@ -1024,6 +1074,11 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
     HIPCHK(hipGetLastError());
   }
   CHK(h->rg_ev.record(5, s));
+  if (r.samples_out && H) {
+    std::vector<int32_t> rows(H * n);
+    HIPCHK(hipMemcpy(rows.data(), d + i_samples, H * n * 4, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < H * n; ++k) r.samples_out[k] = rows[k];
+  }
   h->stage.resize(out_bytes);
   HIPCHK(hipMemcpy(h->stage.data(), h->rg_out.p, out_bytes, hipMemcpyDeviceToHost));
   CHK(h->rg_ev.record(6, s));
@@ -1038,6 +1093,45 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   std::memcpy(r.winner, b + o_winner, G * 4);
   std::memcpy(r.inlier, b + o_inlier, N);
   h->rg_ev.report(r.times_ms, RANSAC_TIMES, RANSAC_TIMES);
+  if (r.drawn && r.times_ms) {  // the fit began after the draw
+    r.times_ms[RANSAC_TIMES] = h->rg_ev.ms(1, drawn_at);
+    r.times_ms[1] = h->rg_ev.ms(drawn_at, 2);
+  }
+  return GLH_OK;
+}
+
+// glh_stage_ransac_samples: the draw alone, every group drawn, rows counted within the group.
+int ransac_draw_samples(const RansacDraw& r) {
+  HIPCHK(hipSetDevice(r.device));
+  const size_t G = (size_t)r.n_groups, H = G ? (size_t)r.hyp_offset[G] : 0, n = (size_t)r.n;
+  std::vector<RGroup> groups(G);
+  std::vector<int32_t> hyp_group(H);
+  for (size_t g = 0; g < G; ++g) {
+    groups[g] = RGroup{0, 0, (int32_t)r.rows[g], 0, 0, (int32_t)r.hyp_offset[g], (int32_t)(r.hyp_offset[g + 1] - r.hyp_offset[g]), 0};
+    for (int64_t k = r.hyp_offset[g]; k < r.hyp_offset[g + 1]; ++k) hyp_group[(size_t)k] = (int32_t)g;
+  }
+  StageEvents<4> ev;
+  CHK(ev.create());
+  DevBuf d_groups, d_hg, d_id, d_samples;
+  CHK(ev.record(0, nullptr));
+  CHK(d_groups.up(groups.data(), G * sizeof(RGroup)));
+  CHK(d_hg.up(hyp_group.data(), H * 4));
+  CHK(d_id.up(r.group_id, G * 4));
+  CHK(d_samples.alloc(H * n * 4));
+  CHK(ev.record(1, nullptr));
+  if (H) {
+    const DrawArgs da{d_groups.as<RGroup>(), d_hg.as<int32_t>(), d_id.as<int32_t>(), nullptr, d_samples.as<int32_t>(), (int32_t)n,
+                      (int32_t)H, r.seed0, r.seed1};
+    hipLaunchKernelGGL(k_rg_draw, dim3((unsigned)((H + CAL_TB - 1) / CAL_TB)), dim3(CAL_TB), 0, nullptr, da);
+    HIPCHK(hipGetLastError());
+  }
+  CHK(ev.record(2, nullptr));
+  std::vector<int32_t> rows(H * n);
+  if (H) CHK(d_samples.down(rows.data(), H * n * 4));
+  CHK(ev.record(3, nullptr));
+  HIPCHK(hipEventSynchronize(ev.e[3]));
+  for (size_t k = 0; k < H * n; ++k) r.samples[k] = rows[k];
+  ev.report(r.times_ms, 3, 3);
   return GLH_OK;
 }
 

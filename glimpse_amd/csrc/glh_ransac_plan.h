@@ -15,6 +15,7 @@
 namespace glh {
 
 constexpr int RANSAC_TIMES = 6;                          // entries of glh_calib_ransac_groups' times_ms
+constexpr int RANSAC_DRAWN_TIMES = RANSAC_TIMES + 1;     // of glh_calib_ransac_groups_drawn's: the draw, appended
 constexpr int64_t RANSAC_MASK_LIMIT = (int64_t)1 << 31;  // mask bytes of one call: fewer than this
 constexpr int RANSAC_KIND_MATCHES = 2;                   // GLH_CALIB_MATCHES: the first of the three match kinds
 constexpr int RANSAC_NOT_REFITTED = -100;                // refit_status of a hypothesis that was not accepted
@@ -36,7 +37,14 @@ struct RgCall {
   int max_nfev;
   double ftol, xtol, gtol, max_error;
   bool outputs;                           // every output pointer is there
+  // glh_calib_ransac_groups_drawn (`draws`): the samples of a group with drawn[g] == 1 are drawn on the device as those of
+  // pair group_id[g] (glh_ransac_draw.h) and its entries of `samples` are not read
+  bool draws = false;
+  const int32_t* group_id = nullptr;      // [G]
+  const uint8_t* drawn = nullptr;         // [G]
 };
+
+inline bool rg_drawn(const RgCall& c, int g) { return c.draws && c.drawn[g] != 0; }
 
 inline int64_t rg_rows(const RgCall& c, int g) {
   return c.row_offset[c.group_control[g] + 1] - c.row_offset[c.group_control[g]];
@@ -91,6 +99,7 @@ inline bool rg_check(const RgCall& c, char* msg, size_t cap) {
   if (!c.slots || !c.x0 || !c.lb || !c.ub || !c.x_scale || !c.hyp_offset || !c.outputs ||
       (c.n_groups && (!c.group_control || !c.group_cam)))
     RANSAC_FAIL("ransac groups: null argument");
+  if (c.draws && c.n_groups && (!c.group_id || !c.drawn)) RANSAC_FAIL("ransac groups: null argument: the groups' ids and drawn flags");
   if (c.p < 1 || c.p > 18) RANSAC_FAIL("ransac groups: %d parameters: 1 .. 18 are served", c.p);
   uint32_t seen = 0;
   for (int i = 0; i < c.p; ++i) {
@@ -123,6 +132,13 @@ inline bool rg_check(const RgCall& c, char* msg, size_t cap) {
       RANSAC_FAIL("ransac groups: group %d ends at hypothesis %lld after %lld: not decreasing, fewer than 2^31 in all", g,
               (long long)c.hyp_offset[g + 1], (long long)c.hyp_offset[g]);
     const int64_t rows = rg_rows(c, g), hyps = c.hyp_offset[g + 1] - c.hyp_offset[g];
+    if (c.draws) {
+      if (c.group_id[g] < 0) RANSAC_FAIL("ransac groups: group %d has the id %d: ids are not negative", g, c.group_id[g]);
+      if (c.drawn[g] > 1) RANSAC_FAIL("ransac groups: group %d has the drawn flag %d: 0 or 1", g, c.drawn[g]);
+      if (c.drawn[g] && hyps > 0 && rows <= c.n)
+        RANSAC_FAIL("ransac groups: group %d draws samples of %d of its %lld rows: a drawn group has more rows than that", g, c.n,
+                    (long long)rows);
+    }
     covered += rows;
     const int64_t b = rg_mask_bytes(rows, hyps);
     mask = mask >= RANSAC_MASK_LIMIT - b ? RANSAC_MASK_LIMIT : mask + b;
@@ -143,9 +159,12 @@ inline bool rg_check(const RgCall& c, char* msg, size_t cap) {
             (long long)c.row_offset[c.n_controls]);
   if (mask >= RANSAC_MASK_LIMIT) RANSAC_FAIL("ransac groups: the consensus masks take 2^31 bytes or more: fewer are served in one call");
   const int64_t H = c.n_groups ? c.hyp_offset[c.n_groups] : 0;
-  if (H > 0 && !c.samples) RANSAC_FAIL("ransac groups: null samples");
+  bool given = false;  // a group whose hypotheses come from `samples`
+  for (int g = 0; g < c.n_groups; ++g) given = given || (!rg_drawn(c, g) && c.hyp_offset[g + 1] > c.hyp_offset[g]);
+  if (given && !c.samples) RANSAC_FAIL("ransac groups: null samples");
   if (H > 0 && H > (RANSAC_MASK_LIMIT - 1) / c.n) RANSAC_FAIL("ransac groups: %lld samples of %d rows: fewer than 2^31 rows in all", (long long)H, c.n);
   for (int g = 0; g < c.n_groups; ++g) {
+    if (rg_drawn(c, g)) continue;
     const int64_t first = c.row_offset[c.group_control[g]], last = c.row_offset[c.group_control[g] + 1];
     for (int64_t k = c.hyp_offset[g] * c.n; k < c.hyp_offset[g + 1] * c.n; ++k)
       if (c.samples[k] < first || c.samples[k] >= last)

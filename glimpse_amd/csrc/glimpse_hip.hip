@@ -20,6 +20,7 @@
 #include "glh_project_dem.h"
 #include "glh_horizon.h"
 #include "glh_calib.h"
+#include "glh_ransac_draw.h"
 #include "glh_ransac_plan.h"
 #include "glh_match.h"
 #include "glh_sift.h"
@@ -3188,20 +3189,22 @@ extern "C" int glh_calib_fit_sets(glh_calib* handle, const double* cams, int fit
 }
 
 // optimize.ransac_pairs: RANSAC over many groups (one match control, one fitted camera each) in one pass.  The checks are
-// glh_ransac_plan.h's rg_check, made before a device is touched.
-extern "C" int glh_calib_ransac_groups(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
-                                       const int32_t* group_cam, int p, const int32_t* slots, const double* x0, const double* lb,
-                                       const double* ub, const double* x_scale, const double* weights, const double* observed,
-                                       const int64_t* hyp_offset, int n, const int64_t* samples, int max_nfev, double ftol,
-                                       double xtol, double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status,
-                                       int32_t* consensus, double* refit_x, int32_t* refit_status, double* mean_error,
-                                       int32_t* winner, uint8_t* inlier, double* times_ms) {
+// glh_ransac_plan.h's rg_check, made before a device is touched.  `draws`: glh_calib_ransac_groups_drawn's call, whose
+// groups with drawn[g] == 1 get their samples on the device.
+static int ransac_groups(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
+                         const int32_t* group_cam, int p, const int32_t* slots, const double* x0, const double* lb,
+                         const double* ub, const double* x_scale, const double* weights, const double* observed,
+                         const int64_t* hyp_offset, int n, const int64_t* samples, int max_nfev, double ftol, double xtol,
+                         double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status, int32_t* consensus,
+                         double* refit_x, int32_t* refit_status, double* mean_error, int32_t* winner, uint8_t* inlier,
+                         double* times_ms, bool draws, const int32_t* group_id, const uint8_t* drawn, uint32_t seed0,
+                         uint32_t seed1, int64_t* samples_out) {
   if (!handle) return fail(GLH_E_INVALID, "ransac groups: null handle");
   const CalibTable table = calib_table(handle);
   if (!cams) return fail(GLH_E_INVALID, "ransac groups: null argument");
   const RgCall call{table.n_cams, table.n_controls, table.kind, table.cam_a, table.cam_b, table.row_offset, n_groups, group_control,
                     group_cam, p, slots, x0, lb, ub, x_scale, hyp_offset, n, samples, max_nfev, ftol, xtol, gtol, max_error,
-                    x && status && consensus && refit_x && refit_status && mean_error && winner && inlier};
+                    x && status && consensus && refit_x && refit_status && mean_error && winner && inlier, draws, group_id, drawn};
   char why[400];
   if (!rg_check(call, why, sizeof(why))) return fail(GLH_E_INVALID, "%s", why);
   for (int g = 0; g < n_groups; ++g)
@@ -3214,10 +3217,95 @@ extern "C" int glh_calib_ransac_groups(glh_calib* handle, const double* cams, in
     if (cams[(size_t)i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "ransac groups: camera %d is a raster grid", i);
     expand_camera(cams + (size_t)i * GLH_CAM_LEN, &cd[i]);
   }
-  const CalibRansac r{cd.data(), cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed,
-                      hyp_offset, n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x,
-                      refit_status, mean_error, winner, inlier, times_ms};
+  CalibRansac r{cd.data(), cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed,
+                hyp_offset, n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x,
+                refit_status, mean_error, winner, inlier, times_ms};
+  if (draws) {
+    static const uint8_t none = 0;  // (no group: the flags still have an address, which is what says that the call draws)
+    r.drawn = n_groups ? drawn : &none, r.group_id = group_id, r.seed0 = seed0, r.seed1 = seed1, r.samples_out = samples_out;
+  }
   return calib_ransac_groups(handle, r);
+}
+
+extern "C" int glh_calib_ransac_groups(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
+                                       const int32_t* group_cam, int p, const int32_t* slots, const double* x0, const double* lb,
+                                       const double* ub, const double* x_scale, const double* weights, const double* observed,
+                                       const int64_t* hyp_offset, int n, const int64_t* samples, int max_nfev, double ftol,
+                                       double xtol, double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status,
+                                       int32_t* consensus, double* refit_x, int32_t* refit_status, double* mean_error,
+                                       int32_t* winner, uint8_t* inlier, double* times_ms) {
+  return ransac_groups(handle, cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed, hyp_offset,
+                       n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x, refit_status,
+                       mean_error, winner, inlier, times_ms, false, nullptr, nullptr, 0u, 0u, nullptr);
+}
+
+// The same with the samples of the groups it names drawn on the device (INPUTS.md, "Device samples: the rule").
+extern "C" int glh_calib_ransac_groups_drawn(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
+                                             const int32_t* group_cam, int p, const int32_t* slots, const double* x0,
+                                             const double* lb, const double* ub, const double* x_scale, const double* weights,
+                                             const double* observed, const int64_t* hyp_offset, int n, const int64_t* samples,
+                                             int max_nfev, double ftol, double xtol, double gtol, double max_error,
+                                             int64_t min_inliers, double* x, int32_t* status, int32_t* consensus, double* refit_x,
+                                             int32_t* refit_status, double* mean_error, int32_t* winner, uint8_t* inlier,
+                                             const int32_t* group_id, const uint8_t* drawn, uint32_t seed0, uint32_t seed1,
+                                             int64_t* samples_out, double* times_ms) {
+  return ransac_groups(handle, cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed, hyp_offset,
+                       n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x, refit_status,
+                       mean_error, winner, inlier, times_ms, true, group_id, drawn, seed0, seed1, samples_out);
+}
+
+// What optimize.ransac_pairs(samples="device") gives each pair (glh_ransac_draw.h: rd_hypotheses).  Host arithmetic only.
+extern "C" int glh_ransac_hypotheses(int n_groups, const int64_t* rows, int n, int64_t iterations, int64_t* hyps,
+                                     uint8_t* enumerated) {
+  if (n_groups < 0 || (n_groups && (!rows || !hyps || !enumerated)))
+    return fail(GLH_E_INVALID, "ransac hypotheses: %d groups or a null argument", n_groups);
+  if (n < 1 || iterations < 0 || iterations > RANSAC_DRAW_LIMIT)
+    return fail(GLH_E_INVALID, "ransac hypotheses: samples of %d rows, %lld iterations: at least 1 row, 0 .. 2^31 - 1 iterations", n,
+                (long long)iterations);
+  for (int g = 0; g < n_groups; ++g)
+    if (rows[g] < 0 || rows[g] > RANSAC_DRAW_LIMIT)
+      return fail(GLH_E_INVALID, "ransac hypotheses: group %d has %lld rows: 0 .. 2^31 - 1", g, (long long)rows[g]);
+  for (int g = 0; g < n_groups; ++g) {
+    bool all = false;
+    hyps[g] = rd_hypotheses(rows[g], n, iterations, &all);
+    enumerated[g] = all ? 1 : 0;
+  }
+  return GLH_OK;
+}
+
+// The hypotheses of an enumerated pair (glh_ransac_draw.h: rd_enumerate).  Host arithmetic only.
+extern "C" int glh_ransac_combinations(int64_t rows, int n, int64_t count, int64_t* samples) {
+  if (n < 1 || rows < n || rows > RANSAC_DRAW_LIMIT || count < 0 || count > RANSAC_DRAW_LIMIT || (count && !samples))
+    return fail(GLH_E_INVALID, "ransac combinations: %lld of %d of %lld rows, or a null argument", (long long)count, n, (long long)rows);
+  if (count > rd_combinations(rows, n, count))
+    return fail(GLH_E_INVALID, "ransac combinations: %lld of %d of %lld rows: there are fewer", (long long)count, n, (long long)rows);
+  rd_enumerate(rows, n, count, samples);
+  return GLH_OK;
+}
+
+// The draw alone, for tests and probes: every group drawn, rows counted within the group.
+extern "C" int glh_stage_ransac_samples(int dev, int n_groups, const int64_t* rows, const int32_t* group_id,
+                                        const int64_t* hyp_offset, int n, uint32_t seed0, uint32_t seed1, int64_t* samples,
+                                        double* times_ms) {
+  if (n_groups < 0 || n_groups >= (1 << 24) || !hyp_offset || (n_groups && (!rows || !group_id)))
+    return fail(GLH_E_INVALID, "ransac samples: %d groups (fewer than 2^24 are served) or a null argument", n_groups);
+  if (n < 1) return fail(GLH_E_INVALID, "ransac samples: samples of %d rows", n);
+  if (hyp_offset[0] != 0) return fail(GLH_E_INVALID, "ransac samples: hyp_offset[0] is %lld, not 0", (long long)hyp_offset[0]);
+  for (int g = 0; g < n_groups; ++g) {
+    if (hyp_offset[g + 1] < hyp_offset[g] || hyp_offset[g + 1] > RANSAC_DRAW_LIMIT / n)
+      return fail(GLH_E_INVALID, "ransac samples: group %d ends at hypothesis %lld after %lld: not decreasing, fewer than 2^31 rows "
+                                 "in all", g, (long long)hyp_offset[g + 1], (long long)hyp_offset[g]);
+    if (rows[g] <= n || rows[g] > RANSAC_DRAW_LIMIT)
+      return fail(GLH_E_INVALID, "ransac samples: group %d has %lld rows: more than the sample's %d, at most 2^31 - 1", g,
+                  (long long)rows[g], n);
+    if (group_id[g] < 0) return fail(GLH_E_INVALID, "ransac samples: group %d has the id %d: ids are not negative", g, group_id[g]);
+  }
+  if (n_groups && hyp_offset[n_groups] && !samples) return fail(GLH_E_INVALID, "ransac samples: null output");
+  if (!n_groups || !hyp_offset[n_groups]) {  // nothing to draw
+    if (times_ms) times_ms[0] = times_ms[1] = times_ms[2] = 0.0;
+    return GLH_OK;
+  }
+  return ransac_draw_samples(RansacDraw{dev, n_groups, rows, group_id, hyp_offset, n, seed0, seed1, samples, times_ms});
 }
 
 // How optimize.ransac_pairs cuts its pairs into calls (glh_ransac_plan.h: rg_chunks).  Host arithmetic only.

@@ -935,14 +935,16 @@ class KeypointMatcher:
                 m.weights = None
             self.matches.data[i] = m
 
-    def ransac_matches(self, n, max_error, min_inliers, iterations=100, cam_params=None, **kwargs):
+    def ransac_matches(self, n, max_error, min_inliers, iterations=100, cam_params=None, samples=None, seed=None, **kwargs):
         """Frees every pair's matches of outliers by `ransac_pairs` over `self.matches` (all pairs in one device pass; the
         arguments are its own): a pair keeps its inliers -- `uvs`, `xys` and `weights` filtered together, as
         `Matches.filter` does -- and a pair for which no fit is accepted is emptied to size 0 and stays in place, so that
-        `matches_per_image`, `images_per_image` and `match_breaks(min_matches)` report it.  Returns the inlier count per
-        pair, -1 for a rejected pair."""
+        `matches_per_image`, `images_per_image` and `match_breaks(min_matches)` report it.  `samples="device"` (and `seed`)
+        draws the samples on the device as well, which is what a long sequence wants.  Returns the inlier count per pair, -1
+        for a rejected pair."""
         self._test_matches()
-        results = ransac_pairs(self.matches, n, max_error, min_inliers, iterations=iterations, cam_params=cam_params, **kwargs)
+        results = ransac_pairs(self.matches, n, max_error, min_inliers, iterations=iterations, cam_params=cam_params,
+                               samples=samples, seed=seed, **kwargs)
         counts = np.full(len(results), -1, dtype=int)
         for k, (m, result) in enumerate(zip(self.matches.data, results)):
             selected = np.zeros(m.size, dtype=bool)
@@ -1870,7 +1872,7 @@ def _pairs_plan(pairs, fitted, cam_params, kwargs):
 
 
 def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=None, fitted=1, samples=None, budget=None,
-                 return_info=False, **kwargs):
+                 return_info=False, seed=None, **kwargs):
     """Random Sample Consensus over every image pair of `pairs` (whatever `match_pairs` accepts: `KeypointMatcher.matches`, a
     dict {(i, j): matches}, an (n, n) object array; each entry a `Matches`, `RotationMatches` or `RotationMatchesXY`) in ONE
     device pass per chunk of pairs (`glh_calib_ransac_groups`).  Returns a list in pair order of `(params, inliers)` as
@@ -1887,34 +1889,63 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
 
     The samples are drawn on the host by `_ransac_samples`, pair after pair, so under one `np.random.seed` they are the
     samples a loop of `ransac` over the pairs draws.  `samples`: instead, per pair an (H_k, n) integer array of row numbers
-    within the pair.  `params` are the DEVICE's refit values on the winning set (a damped Gauss-Newton, `glh_lm.h`), not
-    scipy's: they agree with `Cameras.fit` on that set to well within 1e-3 of each parameter's scale, and the host fit per
+    within the pair.  `samples="device"`: the samples are drawn on the device, in the pass that fits them (INPUTS.md,
+    "Device samples: the rule"): pair k gets min(iterations, C(size, n)) hypotheses, the binomial coefficient exact -- all
+    combinations in lexicographic order if there are no more than `iterations`, else each hypothesis drawn independently
+    (Floyd's algorithm on a Philox stream) as a function of (`seed`, k, the hypothesis's number, size, n) alone, so that
+    the result depends neither on the other pairs nor on `budget`; two hypotheses of a pair may then be the same sample,
+    which changes nothing but the count.  `seed`: an integer of 0 .. 2^64 - 1 for that mode; None takes two 32-bit words
+    from one call of `np.random.randint`, so that `np.random.seed` still makes a run reproducible.  The other modes do not
+    touch it, and their use of np.random is what it was.
+
+    `params` are the DEVICE's refit values on the winning set (a damped Gauss-Newton, `glh_lm.h`), not scipy's: they agree with `Cameras.fit` on that set to well within 1e-3 of each parameter's scale, and the host fit per
     pair is the cost this call removes.  `budget`: an upper bound in bytes (default RANSAC_PAIRS_BUDGET) on the device memory
     for the consensus masks, hypotheses x rows bytes per pair: the pairs are processed in consecutive chunks that stay
     below it, a pair whose own masks exceed it in a chunk of its own; the result does not depend on the chunking.
     `return_info`: also a dict with, per hypothesis, `values`, `status`, `consensus`, `refit_values`, `refit_status`,
     `mean_errors` (hypotheses of pair k: hyp_offset[k] .. hyp_offset[k + 1]); per pair `winner` (counted from the pair's
-    first hypothesis, -1: none); and `times_ms`.
+    first hypothesis, -1: none); `samples`, per pair the (H_k, n) rows sampled or None for a pair too short; `seed` in
+    device mode; and `times_ms` (with `draw` in device mode).
 
     Refused with NotImplementedError, before any library call: what `_batched_plan` refuses for such a model (a fitted
     position, internal parameters under a RotationMatches, a raster-grid camera, kwargs other than numeric ftol / xtol /
     gtol / max_nfev and nan_policy="omit") and any control that is not one of the three match kinds.  ValueError: x0
-    outside its bounds, or a lower bound that is not below the upper."""
+    outside its bounds, or a lower bound that is not below the upper; a string for `samples` other than "device", a `seed`
+    outside 0 .. 2^64 - 1, or a `seed` without samples="device"."""
     import time
 
     t = [time.perf_counter()]
+    on_device = isinstance(samples, str)
+    if on_device and samples != "device":
+        raise ValueError(f"samples: 'device', None or one array per pair, got {samples!r}")
+    if seed is not None:
+        if not on_device:
+            raise ValueError("seed: the seed of samples='device'; the other samples are np.random's or the caller's")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= int(seed) < 2 ** 64:
+            raise ValueError(f"seed: an integer of 0 .. 2^64 - 1, got {seed!r}")
     cam_params = {"viewdir": True} if cam_params is None else cam_params
     pairs = [] if isinstance(pairs, (list, tuple)) and not len(pairs) else match_pairs(pairs)
     plan = _pairs_plan(pairs, fitted, cam_params, kwargs)
     if not pairs:
-        return ([], dict(winner=np.zeros(0, np.int32), hyp_offset=np.zeros(1, np.int64), times_ms={})) if return_info else []
-    if samples is not None and len(samples) != len(pairs):
+        return ([], dict(winner=np.zeros(0, np.int32), hyp_offset=np.zeros(1, np.int64), samples=[], times_ms={})) if return_info else []
+    if samples is not None and not on_device and len(samples) != len(pairs):
         raise ValueError(f"samples: one array per pair ({len(pairs)}), got {len(samples)}")
+    if on_device and seed is None:  # (after the plan's checks, and the only use of np.random in this mode)
+        words = np.random.randint(0, 2 ** 32, size=2, dtype=np.uint64)
+        seed = int(words[0]) | int(words[1]) << 32
+    seed = None if seed is None else int(seed)
     t.append(time.perf_counter())
     drawn = []
+    # device mode: `device_drawn[k]`, pair k's samples come from the device; `drawn[k]` holds zeros until they are back
+    device_drawn = np.zeros(len(pairs), dtype=bool)
+    if on_device:
+        counts, enumerated = _lib.ransac_hypotheses([m.size for m, _, _ in pairs], n, iterations)
+        device_drawn = (counts > 0) & ~enumerated
     for k, (m, _, _) in enumerate(pairs):
         if m.size <= n:  # ("Sample size is larger or equal to total size")
             drawn.append(None)
+        elif on_device:
+            drawn.append(np.zeros((counts[k], n), np.int64) if device_drawn[k] else _lib.ransac_combinations(m.size, n, counts[k]))
         elif samples is None:
             drawn.append(np.array(list(_ransac_samples(n=n, size=m.size, iterations=iterations)), dtype=np.int64).reshape(-1, n))
         else:
@@ -1934,7 +1965,8 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
     parts = {key: [] for key in keys}
     winner = np.full(len(pairs), -1, dtype=np.int32)
     results = [None] * len(pairs)
-    times = dict.fromkeys(("upload",) + _lib.CALIB_RANSAC_TIMES[1:], 0.0)
+    device_times = _lib.CALIB_RANSAC_TIMES[1:] + (("draw",) if on_device else ())
+    times = dict.fromkeys(("upload",) + device_times, 0.0)
     host = 0.0
     for chunk in range(int(chunk_of.max()) + 1 if served else 0):
         t0 = time.perf_counter()
@@ -1958,7 +1990,10 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
         row_offset = np.concatenate(([0], np.cumsum([len(o) for o in obs]))).astype(np.int64)
         hyp_offset = np.concatenate(([0], np.cumsum([len(drawn[k]) for k in members]))).astype(np.int64)
         x0, lb, ub, scales = (np.array([plan["values"][k][q] for k in members]).reshape(-1, p) for q in range(4))
-        rows = np.concatenate([drawn[k] + row_offset[g] for g, k in enumerate(members)])
+        draw = dict(group_id=members, drawn=device_drawn[members], seed=(seed & 0xFFFFFFFF, seed >> 32), n=n) if on_device else {}
+        # (nothing to upload where the device draws every sample of the chunk)
+        rows = None if on_device and device_drawn[members].all() else \
+            np.concatenate([drawn[k] + row_offset[g] for g, k in enumerate(members)])
         cams24 = np.array([cam.vector24 for cam in cams])
         t1 = time.perf_counter()
         handle = _lib.Calib(len(cams), kind, [where[id(pairs[k][0].cams[0])] for k in members],
@@ -1969,9 +2004,12 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
             out, device = handle.ransac_groups(
                 cams24, np.arange(len(members)), [where[id(pairs[k][0].cams[fitted])] for k in members], plan["slots"], x0, lb,
                 ub, scales, hyp_offset, rows, max_error, min_inliers, observed=np.concatenate(observed) if rotation else None,
-                return_times=True, **plan["options"])
+                return_times=True, **draw, **plan["options"])
         finally:
             handle.close()
+        for g, k in enumerate(members):
+            if device_drawn[k]:
+                drawn[k] = out["samples"][hyp_offset[g]:hyp_offset[g + 1]] - row_offset[g]
         for key in keys:
             parts[key].append(out[key])
         for g, k in enumerate(members):
@@ -1981,7 +2019,7 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
                 results[k] = (out["refit_values"][hyp_offset[g] + winner[k]].copy(), inliers)
         host += t1 - t0
         times["upload"] += (t2 - t1) * 1e3 + device["upload"]
-        for key in _lib.CALIB_RANSAC_TIMES[1:]:
+        for key in device_times:
             times[key] += device[key]
     if not return_info:
         return results
@@ -1989,6 +2027,9 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
     info["winner"] = winner
     info["hyp_offset"] = np.concatenate(([0], np.cumsum([0 if rows is None else len(rows) for rows in drawn]))).astype(np.int64)
     info["chunks"] = int(chunk_of.max()) + 1 if served else 0
+    info["samples"] = drawn
+    if on_device:
+        info["seed"] = seed
     info["times_ms"] = dict(sampling=(t[2] - t[1]) * 1e3, host=(t[1] - t[0] + host) * 1e3, **times)
     return results, info
 

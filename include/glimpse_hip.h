@@ -852,6 +852,42 @@ int glh_calib_ransac_groups(glh_calib* handle, const double* cams, int n_groups,
                             double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status, int32_t* consensus,
                             double* refit_x, int32_t* refit_status, double* mean_error, int32_t* winner, uint8_t* inlier,
                             double* times_ms);
+/* optimize.ransac_pairs(samples="device"): glh_calib_ransac_groups with the samples of some groups drawn on the device
+ * (INPUTS.md, "Device samples: the rule"; csrc/glh_ransac_draw.h).  group_id [n_groups] int32 >= 0: the pair the group is
+ * in the caller's whole list, which with the hypothesis's number within the group, the group's row count, n and the seed
+ * words seed0, seed1 decides a drawn sample -- not the group's place in this call.  drawn [n_groups] uint8: 1, the
+ * group's hypotheses are drawn by Floyd's algorithm from Philox4x32 streams (the round count of the tracker's) and its
+ * entries of samples are not read -- it must have more than n rows; 0, they are read from samples as
+ * glh_calib_ransac_groups reads them (samples may be NULL if no group with a hypothesis has 0).  samples_out (or NULL)
+ * int64 [H][n]: the rows every hypothesis sampled, global row numbers, ascending within a drawn one.  Everything else, and
+ * every result, as glh_calib_ransac_groups for those samples.  times_ms (or NULL) [7]: its six -- [1] from the end of the
+ * draw -- and [6] the draw.
+ * GLH_E_INVALID, before a device is touched: as glh_calib_ransac_groups, and null group_id or drawn, a negative id, a flag
+ * above 1, a drawn group with hypotheses and n rows or fewer.                                                           */
+int glh_calib_ransac_groups_drawn(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
+                                  const int32_t* group_cam, int p, const int32_t* slots, const double* x0, const double* lb,
+                                  const double* ub, const double* x_scale, const double* weights, const double* observed,
+                                  const int64_t* hyp_offset, int n, const int64_t* samples, int max_nfev, double ftol,
+                                  double xtol, double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status,
+                                  int32_t* consensus, double* refit_x, int32_t* refit_status, double* mean_error,
+                                  int32_t* winner, uint8_t* inlier, const int32_t* group_id, const uint8_t* drawn,
+                                  uint32_t seed0, uint32_t seed1, int64_t* samples_out, double* times_ms);
+/* hyps [n_groups]: min(iterations, C(rows[g], n)) hypotheses for a group of rows[g] rows, the binomial coefficient exact;
+ * 0 for a group of n rows or fewer.  enumerated [n_groups] uint8: 1 where C(rows[g], n) <= iterations, a group whose
+ * hypotheses are all combinations (glh_ransac_combinations) and not drawn.  Host arithmetic; GLH_E_INVALID: null pointers,
+ * n < 1, rows or iterations outside 0 .. 2^31 - 1.                                                                       */
+int glh_ransac_hypotheses(int n_groups, const int64_t* rows, int n, int64_t iterations, int64_t* hyps, uint8_t* enumerated);
+/* samples [count][n] int64: the first count combinations of n of the rows 0 .. rows - 1 in lexicographic order.  Host
+ * arithmetic; GLH_E_INVALID: n < 1, rows < n or above 2^31 - 1, count negative or above C(rows, n), null output.       */
+int glh_ransac_combinations(int64_t rows, int n, int64_t count, int64_t* samples);
+/* The draw alone: samples int64 [H][n], for hypothesis h of group g (hyp_offset [n_groups + 1] from 0, not decreasing) the
+ * rows 0 .. rows[g] - 1 that glh_calib_ransac_groups_drawn draws for a group of that id, row count and seed, counted
+ * within the group.  times_ms (or NULL) [3]: upload, draw, download.  GLH_E_INVALID, before a device is touched: null
+ * pointers, 2^24 groups or more, n < 1, a group of n rows or fewer or of more than 2^31 - 1, a negative id, offsets that
+ * do not start at 0 or decrease, 2^31 sampled rows or more in all.                                                       */
+int glh_stage_ransac_samples(int device_id, int n_groups, const int64_t* rows, const int32_t* group_id,
+                             const int64_t* hyp_offset, int n, uint32_t seed0, uint32_t seed1, int64_t* samples,
+                             double* times_ms);
 /* chunk_of [n_groups]: the call of glh_calib_ransac_groups that each group of a longer list goes to, when consecutive
  * groups share a call while its masks (rows[g] times hyps[g] bytes each) stay at or below budget bytes and a group whose
  * own masks exceed it gets a call of its own; n_chunks: how many calls.  Host arithmetic; GLH_E_INVALID: null pointers, a

@@ -16,6 +16,10 @@ Per shape, after `--warmup` calls, the medians of `--reps` calls under one np.ra
   loop_ms         the loop of ransac(batched=True).  At the sequence shape it runs over the first `--loop-pairs` pairs only
                   and `loop_ms` is that time scaled by pairs / loop_pairs: `loop_pairs` and `loop_ms_measured` say so
   pairs, rows, hypotheses, accepted (refitted), winners, chunks
+  device_samples  the same call with samples="device" (the seed words from np.random under the same np.random.seed), beside
+                  the host leg: pairs_ms, split_ms (sampling: counting the hypotheses and enumerating short pairs on the
+                  host; draw: the device's draw kernel), hypotheses, accepted, winners, inliers_mean, and `sampling_ms`
+                  of both legs (sampling + draw)
 `device` is the runtime's name for the GPU, `box` the caller's.  Nothing here asserts a speed.
 """
 import argparse
@@ -75,11 +79,14 @@ def sequence(images=1000, neighbours=4, rows=2000, outliers=0.3, seed=1):
 def measure(matches, call, reps, warmup, loop_pairs=None, seed=0):
     from glimpse_amd import optimize
 
-    def pairs():
+    def pairs(**mode):
         np.random.seed(seed)
         t0 = time.perf_counter()
-        out = optimize.ransac_pairs(matches, return_info=True, **call)
+        out = optimize.ransac_pairs(matches, return_info=True, **call, **mode)
         return (time.perf_counter() - t0) * 1e3, out
+
+    def split(runs):
+        return {key: statistics.median(float(out[1]["times_ms"][key]) for _, out in runs) for key in runs[-1][1][1]["times_ms"]}
 
     subset = list(matches.values())[:loop_pairs]
 
@@ -98,15 +105,25 @@ def measure(matches, call, reps, warmup, loop_pairs=None, seed=0):
 
     for _ in range(warmup):
         pairs()
+        pairs(samples="device")
         loop()
     new = [pairs() for _ in range(reps)]
+    drawn = [pairs(samples="device") for _ in range(reps)]
     old = [loop() for _ in range(reps)]
+    results, info = drawn[-1][1]
+    device_split = split(drawn)
+    device = {"pairs_ms": statistics.median(t for t, _ in drawn), "pairs_ms_all": [t for t, _ in drawn], "split_ms": device_split,
+              "sampling_ms": device_split["sampling"] + device_split["draw"], "seed": info["seed"],
+              "hypotheses": len(info["status"]), "converged": int((info["status"] > 0).sum()),
+              "accepted": int((info["refit_status"] != -100).sum()), "winners": int((info["winner"] >= 0).sum()),
+              "chunks": info["chunks"],
+              "inliers_mean": float(np.mean([len(r[1]) for r in results if r is not None])) if any(r is not None for r in results) else 0.0}
     results, info = new[-1][1]
     measured = statistics.median(t for t, _ in old)
     accepted = int((info["refit_status"] != -100).sum())
     return {"pairs": len(matches), "rows": int(sum(m.size for m in matches.values())), "call": call,
             "pairs_ms": statistics.median(t for t, _ in new), "pairs_ms_all": [t for t, _ in new],
-            "split_ms": {key: statistics.median(float(out[1]["times_ms"][key]) for _, out in new) for key in info["times_ms"]},
+            "split_ms": split(new), "sampling_ms": split(new)["sampling"], "device_samples": device,
             "loop_pairs": len(subset), "loop_ms_measured": measured, "loop_ms_all": [t for t, _ in old],
             "loop_ms": measured * len(matches) / len(subset), "loop_scaled": len(subset) != len(matches),
             "loop_winners": old[-1][1],
