@@ -1448,34 +1448,38 @@ class Calib(_Handle):
         (CALIB_FIT_STATUS) -- and, with `max_error`, inlier (S, N) uint8: 1 where the row's error is < max_error under
         the set's values, 2 for the set's own rows."""
         handle = self._handle()
-        cams = _arr(cams, np.float64)
-        if cams.shape != (self.n_cams, CAM_LEN):
-            raise ValueError(f"expected camera vectors ({self.n_cams}, {CAM_LEN}), got {cams.shape}")
-        slots = _arr(slots, np.int32)
+        cams, slots, weights, observed, max_nfev, n_rows = self._fit_arguments(cams, slots, weights, observed, max_nfev)
         if slots.ndim != 1:
             raise ValueError("slots (p,)")
         x0, lb, ub, x_scale = (_arr(v, np.float64, slots.shape) for v in (x0, lb, ub, x_scale))
         set_offset, set_rows = _arr(set_offset, np.int64), _arr(set_rows, np.int64)
-        n_rows, n_sets = int(self.rows.sum()), len(set_offset) - 1
+        n_sets = len(set_offset) - 1
         if set_offset.ndim != 1 or n_sets < 0 or set_rows.ndim != 1 or len(set_rows) < set_offset.max(initial=0):
             raise ValueError("set_offset (S + 1,) and set_rows (set_offset.max(),)")
-        if weights is not None:
-            weights = _arr(weights, np.float64, (n_rows, 2))
-        if observed is not None:
-            observed = _arr(observed, np.float64, (n_rows, 2))
         score = max_error is not None
         x, status, mean_error = np.empty((n_sets, len(slots))), np.empty(n_sets, np.int32), np.empty(n_sets)
         inlier = np.empty((n_sets, n_rows), np.uint8) if score else None
         times = np.zeros(len(CALIB_FIT_TIMES))
         check(load().glh_calib_fit_sets(
             handle, _ptr(cams), int(fit_cam), len(slots), _ptr(slots), _ptr(x0), _ptr(lb), _ptr(ub), _ptr(x_scale),
-            _ptr(weights), _ptr(observed), n_sets, _ptr(set_offset), _ptr(set_rows),
-            int(100 * len(slots) if max_nfev is None else max_nfev), float(ftol), float(xtol), float(gtol), int(score),
+            _ptr(weights), _ptr(observed), n_sets, _ptr(set_offset), _ptr(set_rows), max_nfev, float(ftol), float(xtol), float(gtol), int(score),
             float(max_error) if score else 0.0, _ptr(x), _ptr(status), _ptr(mean_error), _ptr(inlier) if score else None,
             _ptr(times)))
         out = (x, status, mean_error, inlier) if score else (x, status, mean_error)
         return _timed(out, CALIB_FIT_TIMES, times, return_times)
 
+    def _fit_arguments(self, cams, slots, weights, observed, max_nfev):
+        """What `fit_sets` and `ransac_groups` take alike, as the library reads it (max_nfev: default 100 per parameter), and N."""
+        cams = _arr(cams, np.float64)
+        if cams.shape != (self.n_cams, CAM_LEN):
+            raise ValueError(f"expected camera vectors ({self.n_cams}, {CAM_LEN}), got {cams.shape}")
+        slots = _arr(slots, np.int32)
+        n_rows = int(self.rows.sum())
+        if weights is not None:
+            weights = _arr(weights, np.float64, (n_rows, 2))
+        if observed is not None:
+            observed = _arr(observed, np.float64, (n_rows, 2))
+        return cams, slots, weights, observed, int(100 * slots.size if max_nfev is None else max_nfev), n_rows
 
     def ransac_groups(self, cams, group_control, group_cam, slots, x0, lb, ub, x_scale, hyp_offset, samples, max_error,
                       min_inliers, weights=None, observed=None, max_nfev=None, ftol=1e-8, xtol=1e-8, gtol=1e-8,
@@ -1493,12 +1497,9 @@ class Calib(_Handle):
         read for it (`n`: the sample size then); the dict also has `samples` (H, n), the global rows of every hypothesis,
         and the times `draw`."""
         handle = self._handle()
-        cams = _arr(cams, np.float64)
-        if cams.shape != (self.n_cams, CAM_LEN):
-            raise ValueError(f"expected camera vectors ({self.n_cams}, {CAM_LEN}), got {cams.shape}")
+        cams, slots, weights, observed, max_nfev, n_rows = self._fit_arguments(cams, slots, weights, observed, max_nfev)
         group_control = _arr(group_control, np.int32)
         group_cam = _arr(group_cam, np.int32, group_control.shape)
-        slots = _arr(slots, np.int32)
         if slots.ndim != 1 or group_control.ndim != 1:
             raise ValueError("slots (p,) and group_control (G,)")
         n_groups, p = len(group_control), len(slots)
@@ -1510,17 +1511,12 @@ class Calib(_Handle):
             if samples.ndim != 2 or len(samples) < n_hyp:
                 raise ValueError("samples (H, n) with H >= hyp_offset.max()")
             n = samples.shape[1]
-        n_rows = int(self.rows.sum())
-        if weights is not None:
-            weights = _arr(weights, np.float64, (n_rows, 2))
-        if observed is not None:
-            observed = _arr(observed, np.float64, (n_rows, 2))
         out = dict(values=np.empty((n_hyp, p)), status=np.empty(n_hyp, np.int32), consensus=np.empty(n_hyp, np.int32),
                    refit_values=np.empty((n_hyp, p)), refit_status=np.empty(n_hyp, np.int32), mean_errors=np.empty(n_hyp),
                    winner=np.empty(n_groups, np.int32), inlier=np.empty(n_rows, np.uint8))
         shared = (handle, _ptr(cams), n_groups, _ptr(group_control), _ptr(group_cam), p, _ptr(slots), _ptr(x0), _ptr(lb), _ptr(ub),
                   _ptr(x_scale), _ptr(weights), _ptr(observed), _ptr(hyp_offset), int(n), _ptr(samples),
-                  int(100 * p if max_nfev is None else max_nfev), float(ftol), float(xtol), float(gtol), float(max_error),
+                  max_nfev, float(ftol), float(xtol), float(gtol), float(max_error),
                   int(min(max(min_inliers, -1), 2 ** 62)), *[_ptr(out[key]) for key in ("values", "status", "consensus", "refit_values",
                                                                                        "refit_status", "mean_errors", "winner", "inlier")])
         if drawn is None:

@@ -1,6 +1,8 @@
 // glh_calib.h -- what glimpse_hip.hip (the C ABI: glh_calib_create / _eval / _fit_sets / _ransac_groups / _destroy) hands to glh_calib.hip (the
 // predictions of the controls of optimize.Cameras -- Points, Lines and the match classes -- under many sets of camera
-// vectors at once).  Host-only declarations.
+// vectors at once): one struct per call, filled once from the ABI's arguments, checked on the host (glh_ransac_plan.h:
+// fs_check for CalibFit, rg_check for CalibRansac; CalibPar is what the two have in common) and served from.  Host-only
+// declarations without a HIP header, so that the checks compile for the CPU too.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -47,18 +49,22 @@ struct CalibEval {
   double* times_ms;
 };
 
-struct CalibFit {  // glh_calib_fit_sets' arguments (include/glimpse_hip.h), the cameras expanded by the caller
-  const CamDev* cams;  // [n_cams]
-  const double* base;  // the fitted camera's vector [GLH_CAM_LEN]
-  int fit_cam, p;
-  const int32_t* slots;                  // [p]
-  const double *x0, *lb, *ub, *scale;    // [p]
+struct CalibPar {  // what a fit is started from and stopped by: one block of p values for glh_calib_fit_sets, one per group for the groups
+  int p;
+  const int32_t* slots;                // [p]
+  const double *x0, *lb, *ub, *scale;  // [p] or [G][p]
+  int max_nfev;
+  double ftol, xtol, gtol;
+};
+
+struct CalibFit : CalibPar {  // glh_calib_fit_sets' arguments (include/glimpse_hip.h), checked by glh_ransac_plan.h's fs_check
+  const CamDev* cams;     // [n_cams], expanded once the call is checked (glimpse_hip.hip)
+  const double* vectors;  // [n_cams][GLH_CAM_LEN]
+  int fit_cam;
   const double* weights;                 // [N][2] or null
   const double* observed;                // [N][2] or null: the handle's obs
   int n_sets;
   const int64_t *set_offset, *set_rows;  // [n_sets + 1], [set_offset[n_sets]]
-  int max_nfev;
-  double ftol, xtol, gtol;
   int score;
   double max_error;
   double* x;           // [n_sets][p]
@@ -68,20 +74,16 @@ struct CalibFit {  // glh_calib_fit_sets' arguments (include/glimpse_hip.h), the
   double* times_ms;
 };
 
-struct CalibRansac {  // glh_calib_ransac_groups' arguments (include/glimpse_hip.h), checked by glh_ransac_plan.h's rg_check
-  const CamDev* cams;    // [n_cams], expanded by the caller
+struct CalibRansac : CalibPar {  // glh_calib_ransac_groups' arguments (include/glimpse_hip.h), checked by glh_ransac_plan.h's rg_check
+  const CamDev* cams;    // [n_cams], expanded once the call is checked (glimpse_hip.hip)
   const double* vectors; // [n_cams][GLH_CAM_LEN]
   int n_groups;
   const int32_t *group_control, *group_cam;  // [G]
-  int p;
-  const int32_t* slots;                      // [p]
-  const double *x0, *lb, *ub, *scale;        // [G][p]
   const double *weights, *observed;          // [N][2] or null
   const int64_t* hyp_offset;                 // [G + 1]
   int n;
   const int64_t* samples;                    // [H][n]
-  int max_nfev;
-  double ftol, xtol, gtol, max_error;
+  double max_error;
   int64_t min_inliers;
   double* x;               // [H][p]
   int32_t* status;         // [H]
@@ -92,10 +94,11 @@ struct CalibRansac {  // glh_calib_ransac_groups' arguments (include/glimpse_hip
   int32_t* winner;         // [G]
   uint8_t* inlier;         // [N]
   double* times_ms;
-  // glh_calib_ransac_groups_drawn: a group with drawn[g] == 1 gets its samples from k_rg_draw as pair group_id[g]'s
-  // (glh_ransac_draw.h); times_ms then has RANSAC_DRAWN_TIMES entries
-  const uint8_t* drawn = nullptr;      // [G], or null: every group takes its rows from `samples`
+  // glh_calib_ransac_groups_drawn (`draws`; once checked: `drawn` is not null): a group with drawn[g] == 1 gets its samples
+  // from k_rg_draw as pair group_id[g]'s (glh_ransac_draw.h), not from `samples`; times_ms then has RANSAC_DRAWN_TIMES entries
+  bool draws = false;
   const int32_t* group_id = nullptr;   // [G]
+  const uint8_t* drawn = nullptr;      // [G]
   uint32_t seed0 = 0, seed1 = 0;
   int64_t* samples_out = nullptr;      // [H][n] global rows of every hypothesis, or null
 };

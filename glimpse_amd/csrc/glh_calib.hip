@@ -804,55 +804,40 @@ int calib_eval(glh_calib* h, const CalibEval& e) {
     out_rows += j.n_rows;
     puv_total += n_puv;
   }
-  StageLayout in;
-  const size_t o_cams = in.place(n_cam_sets * sizeof(CamDev)), o_rot = in.place(n_cam_sets * 72);
-  const size_t o_jobs = in.place(jobs.size() * sizeof(CalJob)), o_segs = in.place(segs.size() * sizeof(CalSeg));
-  const size_t o_rows = in.place(rows_b.size() * sizeof(CalBlock)), o_points = in.place(points_b.size() * sizeof(CalBlock));
-  const size_t o_nearest = in.place(nearest_b.size() * sizeof(CalBlock));
-  const size_t o_vx = in.place(V * 8), o_vy = in.place(V * 8), o_vd = in.place(V * 8);
-  h->stage.resize(in.size ? in.size : 16);
-  char* st = h->stage.data();
-  std::memcpy(st + o_cams, e.cams, n_cam_sets * sizeof(CamDev));
-  std::memcpy(st + o_rot, e.rot, n_cam_sets * 72);
-  if (!jobs.empty()) std::memcpy(st + o_jobs, jobs.data(), jobs.size() * sizeof(CalJob));
-  if (!segs.empty()) std::memcpy(st + o_segs, segs.data(), segs.size() * sizeof(CalSeg));
-  if (!rows_b.empty()) std::memcpy(st + o_rows, rows_b.data(), rows_b.size() * sizeof(CalBlock));
-  if (!points_b.empty()) std::memcpy(st + o_points, points_b.data(), points_b.size() * sizeof(CalBlock));
-  if (!nearest_b.empty()) std::memcpy(st + o_nearest, nearest_b.data(), nearest_b.size() * sizeof(CalBlock));
-  double *vx = reinterpret_cast<double*>(st + o_vx), *vy = reinterpret_cast<double*>(st + o_vy),
-         *vd = reinterpret_cast<double*>(st + o_vd);
+  Stage in(h->stage);
+  const auto i_cams = in.put<const CamDev>(e.cams, n_cam_sets);
+  const auto i_rot = in.put<const double>(e.rot, n_cam_sets * 9);
+  const auto i_jobs = in.put<const CalJob>(jobs.data(), jobs.size());
+  const auto i_segs = in.put<const CalSeg>(segs.data(), segs.size());
+  const auto i_rows = in.put<const CalBlock>(rows_b.data(), rows_b.size()), i_points = in.put<const CalBlock>(points_b.data(), points_b.size()),
+             i_nearest = in.put<const CalBlock>(nearest_b.data(), nearest_b.size());
+  const auto i_vx = in.room<double>(V), i_vy = in.room<double>(V), i_vd = in.room<double>(V);
+  double *vx = in.host(i_vx), *vy = in.host(i_vy), *vd = in.host(i_vd);
   for (size_t k = 0; k < V; ++k) vx[k] = e.vertex[3 * k], vy[k] = e.vertex[3 * k + 1], vd[k] = e.vertex[3 * k + 2];
 
-  CHK(h->in.reserve(h->stage.size()));
+  CHK(h->in.reserve(in.bytes()));
   CHK(h->puv.reserve((size_t)(puv_total ? puv_total : 1) * 16));
   CHK(h->out.reserve((size_t)(out_rows ? out_rows : 1) * 16));
   CHK(h->ev.record(0, s));
-  HIPCHK(hipMemcpy(h->in.p, st, h->stage.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->in.p, in.hold(), in.bytes(), hipMemcpyHostToDevice));
   CHK(h->ev.record(1, s));
-  const char* d = h->in.as<char>();
-  const CalJob* d_jobs = reinterpret_cast<const CalJob*>(d + o_jobs);
-  const CamDev* d_cams = reinterpret_cast<const CamDev*>(d + o_cams);
+  void* d = h->in.p;
   if (!rows_b.empty()) {
-    hipLaunchKernelGGL(k_calib_rows, dim3((unsigned)rows_b.size()), dim3(CAL_TB), 0, s,
-                       reinterpret_cast<const CalBlock*>(d + o_rows), d_jobs, d_cams,
-                       reinterpret_cast<const double*>(d + o_rot), h->obs.as<double2>(), h->src.as<double>(),
-                       h->out.as<double2>());
+    hipLaunchKernelGGL(k_calib_rows, dim3((unsigned)rows_b.size()), dim3(CAL_TB), 0, s, in.on(d, i_rows), in.on(d, i_jobs),
+                       in.on(d, i_cams), in.on(d, i_rot), h->obs.as<double2>(), h->src.as<double>(), h->out.as<double2>());
     HIPCHK(hipGetLastError());
   }
   CHK(h->ev.record(2, s));
   if (!points_b.empty()) {
-    hipLaunchKernelGGL(k_calib_line_points, dim3((unsigned)points_b.size()), dim3(CAL_TB), 0, s,
-                       reinterpret_cast<const CalBlock*>(d + o_points), d_jobs, d_cams,
-                       reinterpret_cast<const CalSeg*>(d + o_segs), reinterpret_cast<const double*>(d + o_vx),
-                       reinterpret_cast<const double*>(d + o_vy), reinterpret_cast<const double*>(d + o_vd),
+    hipLaunchKernelGGL(k_calib_line_points, dim3((unsigned)points_b.size()), dim3(CAL_TB), 0, s, in.on(d, i_points),
+                       in.on(d, i_jobs), in.on(d, i_cams), in.on(d, i_segs), in.on(d, i_vx), in.on(d, i_vy), in.on(d, i_vd),
                        h->puv.as<double2>());
     HIPCHK(hipGetLastError());
   }
   CHK(h->ev.record(3, s));
   if (!nearest_b.empty()) {
-    hipLaunchKernelGGL(k_calib_nearest, dim3((unsigned)nearest_b.size()), dim3(CAL_TB), 0, s,
-                       reinterpret_cast<const CalBlock*>(d + o_nearest), d_jobs, h->obs.as<double2>(),
-                       h->puv.as<double2>(), h->out.as<double2>());
+    hipLaunchKernelGGL(k_calib_nearest, dim3((unsigned)nearest_b.size()), dim3(CAL_TB), 0, s, in.on(d, i_nearest),
+                       in.on(d, i_jobs), h->obs.as<double2>(), h->puv.as<double2>(), h->out.as<double2>());
     HIPCHK(hipGetLastError());
   }
   CHK(h->ev.record(4, s));
@@ -869,44 +854,41 @@ int calib_fit_sets(glh_calib* h, const CalibFit& f) {
   const size_t N = (size_t)h->row_offset[h->n_controls], S = (size_t)f.n_sets, T = (size_t)f.set_offset[f.n_sets];
   const size_t p = (size_t)f.p;
   // in: the cameras, the weights, the sets, the fitted camera's parameters and vector; out: x, mean_error, status, inlier
-  StageLayout in, out;
-  const size_t i_cams = in.place((size_t)h->n_cams * sizeof(CamDev));
-  const size_t i_weights = in.place(f.weights ? N * 16 : 0), i_observed = in.place(f.observed ? N * 16 : 0);
-  const size_t i_offset = in.place((S + 1) * 8), i_rows = in.place(T * 4), i_par = in.place((4 * p + GLH_CAM_LEN) * 8);
-  h->stage.resize(in.size);
-  char* st = h->stage.data();
-  std::memcpy(st + i_cams, f.cams, (size_t)h->n_cams * sizeof(CamDev));
-  if (f.weights) std::memcpy(st + i_weights, f.weights, N * 16);
-  if (f.observed) std::memcpy(st + i_observed, f.observed, N * 16);
-  std::memcpy(st + i_offset, f.set_offset, (S + 1) * 8);
-  int32_t* rows = reinterpret_cast<int32_t*>(st + i_rows);
+  Stage in(h->stage);
+  StagePlan out;  // (downloaded one by one into the caller's arrays)
+  const auto i_cams = in.put<const CamDev>(f.cams, (size_t)h->n_cams);
+  const auto i_weights = in.put<const double2>(f.weights, f.weights ? N : 0), i_observed = in.put<const double2>(f.observed, f.observed ? N : 0);
+  const auto i_offset = in.put<const int64_t>(f.set_offset, S + 1);
+  const auto i_rows = in.room<int32_t>(T);
+  int32_t* rows = in.host(i_rows);
   for (size_t k = 0; k < T; ++k) rows[k] = (int32_t)f.set_rows[k];
-  double* par = reinterpret_cast<double*>(st + i_par);  // (set_team's order)
+  const auto i_par = in.room<double>(4 * p + GLH_CAM_LEN);
+  double* par = in.host(i_par);  // (set_team's order)
   for (size_t i = 0; i < p; ++i) par[i] = f.x0[i], par[p + i] = f.lb[i], par[2 * p + i] = f.ub[i], par[3 * p + i] = f.scale[i];
-  std::memcpy(par + 4 * p, f.base, GLH_CAM_LEN * 8);
-  const size_t o_x = out.place(S * p * 8), o_mean = out.place(S * 8), o_status = out.place(S * 4);
-  const size_t o_inlier = out.place(f.score ? S * N : 0);
-  CHK(h->fit_in.reserve(h->stage.size()));
-  CHK(h->fit_out.reserve(out.size));
+  std::memcpy(par + 4 * p, f.vectors + (size_t)f.fit_cam * GLH_CAM_LEN, GLH_CAM_LEN * 8);
+  const auto o_x = out.place<double>(S * p), o_mean = out.place<double>(S);
+  const auto o_status = out.place<int32_t>(S);
+  const auto o_inlier = out.place<uint8_t>(f.score ? S * N : 0);
+  CHK(h->fit_in.reserve(in.bytes()));
+  CHK(h->fit_out.reserve(out.bytes(0)));
   CHK(h->fit_ev.record(0, s));
-  HIPCHK(hipMemcpy(h->fit_in.p, st, h->stage.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->fit_in.p, in.hold(), in.bytes(), hipMemcpyHostToDevice));
   CHK(h->fit_ev.record(1, s));
-  const char* d = h->fit_in.as<char>();
-  char* o = h->fit_out.as<char>();
+  void *d = h->fit_in.p, *o = h->fit_out.p;
   SetArgs a{};
-  a.cams = reinterpret_cast<const CamDev*>(d + i_cams);
+  a.cams = in.on(d, i_cams);
   a.ctl = h->ctl.as<CalCtl>();
   a.row_ctl = h->row_ctl.as<int32_t>();
   a.obs = h->obs.as<double2>();
   a.src = h->src.as<double>();
-  a.weights = f.weights ? reinterpret_cast<const double2*>(d + i_weights) : nullptr;
-  a.observed = f.observed ? reinterpret_cast<const double2*>(d + i_observed) : h->obs.as<double2>();
-  a.set_offset = reinterpret_cast<const int64_t*>(d + i_offset);
-  a.set_rows = reinterpret_cast<const int32_t*>(d + i_rows);
-  a.par = reinterpret_cast<const double*>(d + i_par);
-  a.x = reinterpret_cast<double*>(o + o_x);
-  a.status = reinterpret_cast<int32_t*>(o + o_status);
-  a.mean_error = reinterpret_cast<double*>(o + o_mean);
+  a.weights = f.weights ? in.on(d, i_weights) : nullptr;
+  a.observed = f.observed ? in.on(d, i_observed) : h->obs.as<double2>();
+  a.set_offset = in.on(d, i_offset);
+  a.set_rows = in.on(d, i_rows);
+  a.par = in.on(d, i_par);
+  a.x = out.on(o, o_x);
+  a.status = out.on(o, o_status);
+  a.mean_error = out.on(o, o_mean);
   for (size_t i = 0; i < p; ++i) a.slot[i] = f.slots[i];
   a.fit_cam = f.fit_cam, a.p = f.p, a.max_nfev = f.max_nfev, a.n_rows = (int32_t)N;
   a.ftol = f.ftol, a.xtol = f.xtol, a.gtol = f.gtol;
@@ -920,7 +902,7 @@ int calib_fit_sets(glh_calib* h, const CalibFit& f) {
   CHK(h->fit_ev.record(2, s));
   if (S && N && f.score) {
     const int blocks_per_set = (int)((N + CAL_TB - 1) / CAL_TB);
-    uint8_t* inlier = reinterpret_cast<uint8_t*>(o + o_inlier);
+    uint8_t* inlier = out.on(o, o_inlier);
     hipLaunchKernelGGL(k_calib_score, dim3((unsigned)(S * (size_t)blocks_per_set)), dim3(CAL_TB), 0, s, a, blocks_per_set,
                        f.max_error, inlier);
     HIPCHK(hipGetLastError());
@@ -929,10 +911,10 @@ int calib_fit_sets(glh_calib* h, const CalibFit& f) {
   }
   CHK(h->fit_ev.record(3, s));
   if (S) {
-    HIPCHK(hipMemcpy(f.x, o + o_x, S * p * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(f.mean_error, o + o_mean, S * 8, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(f.status, o + o_status, S * 4, hipMemcpyDeviceToHost));
-    if (N && f.score) HIPCHK(hipMemcpy(f.inlier, o + o_inlier, S * N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f.x, a.x, o_x.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f.mean_error, a.mean_error, o_mean.bytes(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f.status, a.status, o_status.bytes(), hipMemcpyDeviceToHost));
+    if (N && f.score) HIPCHK(hipMemcpy(f.inlier, out.on(o, o_inlier), o_inlier.bytes(), hipMemcpyDeviceToHost));
   }
   CHK(h->fit_ev.record(4, s));
   HIPCHK(hipEventSynchronize(h->fit_ev.e[4]));
@@ -967,29 +949,17 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   for (size_t g = 0; g < G; ++g)
     groups[g] = RGroup{h->row_offset[r.group_control[g]], mask_offset[g], (int32_t)rows[g], r.group_control[g], r.group_cam[g],
                        (int32_t)r.hyp_offset[g], (int32_t)hyps[g], 0};
-  StageLayout in, out;
-  const size_t i_cams = in.place(C * sizeof(CamDev)), i_vec = in.place(C * GLH_CAM_LEN * 8);
-  const size_t i_weights = in.place(r.weights ? N * 16 : 0), i_observed = in.place(r.observed ? N * 16 : 0);
-  const size_t i_groups = in.place(G * sizeof(RGroup)), i_hg = in.place(H * 4), i_samples = in.place(H * n * 4);
-  const size_t i_id = in.place(r.drawn ? G * 4 : 0), i_drawn = in.place(r.drawn ? G : 0);
-  const size_t i_x0 = in.place(G * p * 8), i_lb = in.place(G * p * 8), i_ub = in.place(G * p * 8), i_scale = in.place(G * p * 8);
-  h->stage.resize(in.size ? in.size : 16);
-  char* st = h->stage.data();
-  std::memcpy(st + i_cams, r.cams, C * sizeof(CamDev));
-  std::memcpy(st + i_vec, r.vectors, C * GLH_CAM_LEN * 8);
-  if (r.weights) std::memcpy(st + i_weights, r.weights, N * 16);
-  if (r.observed) std::memcpy(st + i_observed, r.observed, N * 16);
-  if (G) {
-    std::memcpy(st + i_groups, groups.data(), G * sizeof(RGroup));
-    std::memcpy(st + i_x0, r.x0, G * p * 8);
-    std::memcpy(st + i_lb, r.lb, G * p * 8);
-    std::memcpy(st + i_ub, r.ub, G * p * 8);
-    std::memcpy(st + i_scale, r.scale, G * p * 8);
-  }
-  int32_t* hg = reinterpret_cast<int32_t*>(st + i_hg);
+  Stage in(h->stage), out(h->stage);  // (one host buffer: the upload has left it when the download fills it)
+  const auto i_cams = in.put<const CamDev>(r.cams, C);
+  const auto i_vec = in.put<const double>(r.vectors, C * GLH_CAM_LEN);
+  const auto i_weights = in.put<const double2>(r.weights, r.weights ? N : 0), i_observed = in.put<const double2>(r.observed, r.observed ? N : 0);
+  const auto i_groups = in.put<const RGroup>(groups.data(), G);
+  const auto i_hg = in.room<int32_t>(H);
+  int32_t* hg = in.host(i_hg);
   for (size_t g = 0; g < G; ++g)
     for (int64_t k = r.hyp_offset[g]; k < r.hyp_offset[g + 1]; ++k) hg[k] = (int32_t)g;
-  int32_t* samples = reinterpret_cast<int32_t*>(st + i_samples);
+  const auto i_samples = in.room<int32_t>(H * n);
+  int32_t* samples = in.host(i_samples);
   for (size_t g = 0; g < G; ++g) {
     const size_t first = (size_t)r.hyp_offset[g] * n, last = (size_t)r.hyp_offset[g + 1] * n;
     if (r.drawn && r.drawn[g])
@@ -997,41 +967,37 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
     else
       for (size_t k = first; k < last; ++k) samples[k] = (int32_t)r.samples[k];
   }
-  if (r.drawn && G) {
-    std::memcpy(st + i_id, r.group_id, G * 4);
-    std::memcpy(st + i_drawn, r.drawn, G);
-  }
+  const auto i_id = in.put<const int32_t>(r.group_id, r.drawn ? G : 0);
+  const auto i_drawn = in.put<const uint8_t>(r.drawn, r.drawn ? G : 0);
+  const auto i_x0 = in.put<const double>(r.x0, G * p), i_lb = in.put<const double>(r.lb, G * p);
+  const auto i_ub = in.put<const double>(r.ub, G * p), i_scale = in.put<const double>(r.scale, G * p);
   // out, in the order of the download: the doubles, the int32s, the bytes
-  const size_t o_x = out.place(H * p * 8), o_refit = out.place(H * p * 8), o_mean = out.place(H * 8), o_status = out.place(H * 4);
-  const size_t o_consensus = out.place(H * 4), o_rstatus = out.place(H * 4), o_winner = out.place(G * 4), o_inlier = out.place(N);
-  const size_t out_bytes = out.size ? out.size : 16;
-  CHK(h->rg_in.reserve(h->stage.size()));
-  CHK(h->rg_out.reserve(out_bytes));
+  const auto o_x = out.place<double>(H * p), o_refit = out.place<double>(H * p), o_mean = out.place<double>(H);
+  const auto o_status = out.place<int32_t>(H), o_consensus = out.place<int32_t>(H), o_rstatus = out.place<int32_t>(H), o_winner = out.place<int32_t>(G);
+  const auto o_inlier = out.place<uint8_t>(N);
+  CHK(h->rg_in.reserve(in.bytes()));
+  CHK(h->rg_out.reserve(out.bytes()));
   CHK(h->rg_mask.reserve(mask_bytes));
   CHK(h->rg_ev.record(0, s));
-  HIPCHK(hipMemcpy(h->rg_in.p, st, h->stage.size(), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->rg_in.p, in.hold(), in.bytes(), hipMemcpyHostToDevice));
   CHK(h->rg_ev.record(1, s));
-  const char* d = h->rg_in.as<char>();
-  char* o = h->rg_out.as<char>();
+  void *d = h->rg_in.p, *o = h->rg_out.p;
   RArgs a{};
-  a.cams = reinterpret_cast<const CamDev*>(d + i_cams);
-  a.vectors = reinterpret_cast<const double*>(d + i_vec);
+  a.cams = in.on(d, i_cams);
+  a.vectors = in.on(d, i_vec);
   a.ctl = h->ctl.as<CalCtl>();
   a.obs = h->obs.as<double2>();
   a.src = h->src.as<double>();
-  a.observed = r.observed ? reinterpret_cast<const double2*>(d + i_observed) : h->obs.as<double2>();
-  a.weights = r.weights ? reinterpret_cast<const double2*>(d + i_weights) : nullptr;
-  a.groups = reinterpret_cast<const RGroup*>(d + i_groups);
-  a.hyp_group = reinterpret_cast<const int32_t*>(d + i_hg);
-  a.samples = reinterpret_cast<const int32_t*>(d + i_samples);
-  a.x0 = reinterpret_cast<const double*>(d + i_x0), a.lb = reinterpret_cast<const double*>(d + i_lb);
-  a.ub = reinterpret_cast<const double*>(d + i_ub), a.scale = reinterpret_cast<const double*>(d + i_scale);
+  a.observed = r.observed ? in.on(d, i_observed) : h->obs.as<double2>();
+  a.weights = r.weights ? in.on(d, i_weights) : nullptr;
+  a.groups = in.on(d, i_groups);
+  a.hyp_group = in.on(d, i_hg);
+  a.samples = in.on(d, i_samples);
+  a.x0 = in.on(d, i_x0), a.lb = in.on(d, i_lb), a.ub = in.on(d, i_ub), a.scale = in.on(d, i_scale);
   a.mask = h->rg_mask.as<uint8_t>();
-  a.x = reinterpret_cast<double*>(o + o_x), a.refit_x = reinterpret_cast<double*>(o + o_refit);
-  a.mean_error = reinterpret_cast<double*>(o + o_mean);
-  a.status = reinterpret_cast<int32_t*>(o + o_status), a.consensus = reinterpret_cast<int32_t*>(o + o_consensus);
-  a.refit_status = reinterpret_cast<int32_t*>(o + o_rstatus), a.winner = reinterpret_cast<int32_t*>(o + o_winner);
-  a.inlier = reinterpret_cast<uint8_t*>(o + o_inlier);
+  a.x = out.on(o, o_x), a.refit_x = out.on(o, o_refit), a.mean_error = out.on(o, o_mean);
+  a.status = out.on(o, o_status), a.consensus = out.on(o, o_consensus), a.refit_status = out.on(o, o_rstatus);
+  a.winner = out.on(o, o_winner), a.inlier = out.on(o, o_inlier);
   for (size_t i = 0; i < p; ++i) a.slot[i] = r.slots[i];
   a.p = r.p, a.n = r.n, a.max_nfev = r.max_nfev, a.n_hyp = (int32_t)H, a.n_groups = (int32_t)G;
   // (a consensus is at most 2^31 - 1 rows, at least 0)
@@ -1041,8 +1007,7 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   if (r.drawn) {
     if (H) {
       // (the staging buffer is the device's to write once it is uploaded: the draw fills the rows the host left empty)
-      const DrawArgs da{a.groups, a.hyp_group, reinterpret_cast<const int32_t*>(d + i_id), reinterpret_cast<const uint8_t*>(d + i_drawn),
-                        reinterpret_cast<int32_t*>(h->rg_in.as<char>() + i_samples), a.n, a.n_hyp, r.seed0, r.seed1};
+      const DrawArgs da{a.groups, a.hyp_group, in.on(d, i_id), in.on(d, i_drawn), in.on(d, i_samples), a.n, a.n_hyp, r.seed0, r.seed1};
       hipLaunchKernelGGL(k_rg_draw, dim3((unsigned)((H + CAL_TB - 1) / CAL_TB)), dim3(CAL_TB), 0, s, da);
       HIPCHK(hipGetLastError());
     }
@@ -1076,22 +1041,15 @@ int calib_ransac_groups(glh_calib* h, const CalibRansac& r) {
   CHK(h->rg_ev.record(5, s));
   if (r.samples_out && H) {
     std::vector<int32_t> rows(H * n);
-    HIPCHK(hipMemcpy(rows.data(), d + i_samples, H * n * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(rows.data(), in.on(d, i_samples), i_samples.bytes(), hipMemcpyDeviceToHost));
     for (size_t k = 0; k < H * n; ++k) r.samples_out[k] = rows[k];
   }
-  h->stage.resize(out_bytes);
-  HIPCHK(hipMemcpy(h->stage.data(), h->rg_out.p, out_bytes, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out.hold(), o, out.bytes(), hipMemcpyDeviceToHost));
   CHK(h->rg_ev.record(6, s));
   HIPCHK(hipEventSynchronize(h->rg_ev.e[6]));
-  const char* b = h->stage.data();
-  std::memcpy(r.x, b + o_x, H * p * 8);
-  std::memcpy(r.refit_x, b + o_refit, H * p * 8);
-  std::memcpy(r.mean_error, b + o_mean, H * 8);
-  std::memcpy(r.status, b + o_status, H * 4);
-  std::memcpy(r.consensus, b + o_consensus, H * 4);
-  std::memcpy(r.refit_status, b + o_rstatus, H * 4);
-  std::memcpy(r.winner, b + o_winner, G * 4);
-  std::memcpy(r.inlier, b + o_inlier, N);
+  out.take(r.x, o_x), out.take(r.refit_x, o_refit), out.take(r.mean_error, o_mean);
+  out.take(r.status, o_status), out.take(r.consensus, o_consensus), out.take(r.refit_status, o_rstatus);
+  out.take(r.winner, o_winner), out.take(r.inlier, o_inlier);
   h->rg_ev.report(r.times_ms, RANSAC_TIMES, RANSAC_TIMES);
   if (r.drawn && r.times_ms) {  // the fit began after the draw
     r.times_ms[RANSAC_TIMES] = h->rg_ev.ms(1, drawn_at);

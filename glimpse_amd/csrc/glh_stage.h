@@ -2,7 +2,8 @@
 // (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_filters.hip, glh_terrain.hip, glh_orient.hip, glh_calib.hip, glh_match.hip, glh_sift.hip, glh_clahe.hip) share to
 // report an error, to own device memory and to time their phases.  The four handle-based objects (glh_orient, glh_calib,
 // glh_match, glh_sift) also share what a handle is made of: a buffer that grows (GrowBuf), the device and the stream
-// (DeviceObject) and how a handle comes and goes (create_object, destroy_object).  Host-only.
+// (DeviceObject) and how a handle comes and goes (create_object, destroy_object).  The plain C++ of a staging buffer is
+// glh_stage_layout.h's: where its arrays lie (StageLayout), each array named once (StagePlan, Stage).  Host-only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include <new>
 
 #include "../../include/glimpse_hip.h"
+#include "glh_stage_layout.h"
 
 namespace glh {
 
@@ -80,17 +82,6 @@ struct GrowBuf : DevBuf {
     CHK(alloc(bytes));
     cap = bytes;
     return GLH_OK;
-  }
-};
-
-// Where the arrays of a staging buffer lie, one after another: place(bytes) is the next one's offset, a multiple of 16,
-// and `size` what the buffer holds after it.
-struct StageLayout {
-  size_t size = 0;
-  size_t place(size_t bytes) {
-    const size_t at = size;
-    size = (at + bytes + 15) & ~(size_t)15;
-    return at;
   }
 };
 

@@ -3062,6 +3062,16 @@ extern "C" int glh_calib_create(int dev, int n_cams, int n_controls, const int32
   return calib_create(dev, cc, handle);
 }
 
+// The camera vectors of a calibration call, expanded for the device; a raster-grid camera is refused in `who`'s name.
+static int calib_cameras(const char* who, const double* cams, size_t count, std::vector<CamDev>& out) {
+  out.resize(count);
+  for (size_t i = 0; i < count; ++i) {
+    if (cams[i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "%s: camera %zu is a raster grid", who, i);
+    expand_camera(cams + i * GLH_CAM_LEN, &out[i]);
+  }
+  return GLH_OK;
+}
+
 extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams, const double* rot, int n_jobs,
                               const int32_t* job_control, const int32_t* job_set, const int32_t* job_side,
                               const int64_t* job_seg, const int64_t* seg_vertex, const int64_t* seg_count,
@@ -3104,12 +3114,8 @@ extern "C" int glh_calib_eval(glh_calib* handle, int n_sets, const double* cams,
     return fail(GLH_E_INVALID, "calib: %lld rows, %lld points, %lld vertices: fewer than 2^31 of each are served", (long long)rows,
                 (long long)points, (long long)n_vertices);
   if (rows > 0 && !predicted) return fail(GLH_E_INVALID, "calib: null output");
-  const size_t n_cam_sets = (size_t)n_sets * table.n_cams;
-  std::vector<CamDev> cd(n_cam_sets);
-  for (size_t i = 0; i < n_cam_sets; ++i) {
-    if (cams[i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "calib: camera %zu is a raster grid", i);
-    expand_camera(cams + i * GLH_CAM_LEN, &cd[i]);
-  }
+  std::vector<CamDev> cd;
+  CHK(calib_cameras("calib", cams, (size_t)n_sets * table.n_cams, cd));
   const CalibEval e{n_sets, cd.data(), rot, n_jobs, job_control, job_set, job_side, job_seg, seg_vertex, seg_count, seg_par,
                     vertex, predicted, times_ms};
   return calib_eval(handle, e);
@@ -3124,106 +3130,29 @@ extern "C" int glh_calib_fit_sets(glh_calib* handle, const double* cams, int fit
                                   int32_t* status, double* mean_error, uint8_t* inlier, double* times_ms) {
   if (!handle) return fail(GLH_E_INVALID, "calib fit: null handle");
   const CalibTable table = calib_table(handle);
-  const int64_t N = table.row_offset[table.n_controls];
-  if (!cams || !slots || !x0 || !lb || !ub || !x_scale || !set_offset || !x || !status || !mean_error)
-    return fail(GLH_E_INVALID, "calib fit: null argument");
-  if (fit_cam < 0 || fit_cam >= table.n_cams) return fail(GLH_E_INVALID, "calib fit: camera %d of %d", fit_cam, table.n_cams);
-  if (p < 1 || p > 18) return fail(GLH_E_INVALID, "calib fit: %d parameters: 1 .. 18 are served", p);
-  uint32_t seen = 0;
-  for (int i = 0; i < p; ++i) {
-    // (imgsz, entries 6 and 7, is no parameter: optimize.Cameras' masks never hold it)
-    if (slots[i] < 0 || slots[i] >= 20 || slots[i] == 6 || slots[i] == 7 || ((seen >> slots[i]) & 1u))
-      return fail(GLH_E_INVALID, "calib fit: parameter %d is entry %d of the camera vector: distinct ones of 0 .. 5, 8 .. 19", i,
-                  slots[i]);
-    seen |= 1u << slots[i];
-    if (!(lb[i] <= x0[i] && x0[i] <= ub[i]) || !(std::fabs(x0[i]) < INFINITY))
-      return fail(GLH_E_INVALID, "calib fit: parameter %d starts at %g outside its bounds %g .. %g", i, x0[i], lb[i], ub[i]);
-    if (!(lb[i] < ub[i]))  // (as scipy.optimize.least_squares: no room for a difference step)
-      return fail(GLH_E_INVALID, "calib fit: parameter %d has the bounds %g .. %g: the lower one must be below the upper one", i,
-                  lb[i], ub[i]);
-    if (!(x_scale[i] > 0.0 && x_scale[i] < INFINITY)) return fail(GLH_E_INVALID, "calib fit: parameter %d has scale %g", i, x_scale[i]);
-  }
-  if (n_sets < 0 || n_sets >= (1 << 24)) return fail(GLH_E_INVALID, "calib fit: %d sets: fewer than 2^24 are served", n_sets);
-  if (max_nfev < 1 || !(ftol >= 0.0 && ftol < 1.0) || !(xtol >= 0.0 && xtol < 1.0) || !(gtol >= 0.0 && gtol < INFINITY))
-    return fail(GLH_E_INVALID, "calib fit: %d evaluations, ftol %g, xtol %g, gtol %g", max_nfev, ftol, xtol, gtol);
-  if (set_offset[0] != 0) return fail(GLH_E_INVALID, "calib fit: set_offset[0] is %lld, not 0", (long long)set_offset[0]);
-  for (int q = 0; q < n_sets; ++q)
-    if (set_offset[q + 1] < set_offset[q] || set_offset[q + 1] >= ((int64_t)1 << 31))
-      return fail(GLH_E_INVALID, "calib fit: set %d ends at row %lld after %lld: not decreasing, fewer than 2^31 rows in all", q,
-                  (long long)set_offset[q + 1], (long long)set_offset[q]);
-  const int64_t total = set_offset[n_sets];
-  if (total > 0 && !set_rows) return fail(GLH_E_INVALID, "calib fit: null set rows");
-  std::vector<char> is_lines((size_t)table.n_controls, 0);
-  bool any_lines = false;
-  for (int c = 0; c < table.n_controls; ++c) {
-    if (table.kind[c] == GLH_CALIB_ROTATION && table.row_offset[c + 1] > table.row_offset[c] && !observed)
-      return fail(GLH_E_INVALID, "calib fit: control %d is a ROTATION control, whose obs are camera coordinates: pass observed", c);
-    if (table.kind[c] == GLH_CALIB_LINES) {
-      is_lines[c] = 1;
-      if (table.row_offset[c + 1] > table.row_offset[c]) any_lines = true;
-    }
-  }
-  for (int64_t k = 0; k < total; ++k) {
-    const int64_t r = set_rows[k];
-    if (r < 0 || r >= N) return fail(GLH_E_INVALID, "calib fit: row %lld of %lld", (long long)r, (long long)N);
-    if (any_lines) {
-      const int c = (int)(std::upper_bound(table.row_offset, table.row_offset + table.n_controls + 1, r) - table.row_offset) - 1;
-      if (is_lines[c]) return fail(GLH_E_INVALID, "calib fit: row %lld belongs to control %d, a Lines control", (long long)r, c);
-    }
-  }
-  if (score) {
-    if (!inlier) return fail(GLH_E_INVALID, "calib fit: null inlier output");
-    if (!(max_error == max_error)) return fail(GLH_E_INVALID, "calib fit: max_error is NaN");
-    if (any_lines) return fail(GLH_E_INVALID, "calib fit: scoring covers every row, and the handle holds a Lines control");
-    if ((int64_t)n_sets * N >= ((int64_t)1 << 31))
-      return fail(GLH_E_INVALID, "calib fit: %d sets of %lld rows to score: fewer than 2^31 in all are served", n_sets, (long long)N);
-  }
-  std::vector<CamDev> cd((size_t)table.n_cams);
-  for (int i = 0; i < table.n_cams; ++i) {
-    if (cams[(size_t)i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "calib fit: camera %d is a raster grid", i);
-    expand_camera(cams + (size_t)i * GLH_CAM_LEN, &cd[i]);
-  }
-  const CalibFit f{cd.data(), cams + (size_t)fit_cam * GLH_CAM_LEN, fit_cam, p, slots, x0, lb, ub, x_scale, weights, observed,
-                   n_sets, set_offset, set_rows, max_nfev, ftol, xtol, gtol, score, max_error, x, status, mean_error, inlier, times_ms};
+  CalibFit f{{p, slots, x0, lb, ub, x_scale, max_nfev, ftol, xtol, gtol}, nullptr, cams, fit_cam, weights, observed, n_sets,
+             set_offset, set_rows, score, max_error, x, status, mean_error, inlier, times_ms};
+  char why[400];
+  if (!fs_check(table, f, why, sizeof(why))) return fail(GLH_E_INVALID, "%s", why);
+  std::vector<CamDev> cd;
+  CHK(calib_cameras("calib fit", cams, (size_t)table.n_cams, cd));
+  f.cams = cd.data();
   return calib_fit_sets(handle, f);
 }
 
-// optimize.ransac_pairs: RANSAC over many groups (one match control, one fitted camera each) in one pass.  The checks are
-// glh_ransac_plan.h's rg_check, made before a device is touched.  `draws`: glh_calib_ransac_groups_drawn's call, whose
-// groups with drawn[g] == 1 get their samples on the device.
-static int ransac_groups(glh_calib* handle, const double* cams, int n_groups, const int32_t* group_control,
-                         const int32_t* group_cam, int p, const int32_t* slots, const double* x0, const double* lb,
-                         const double* ub, const double* x_scale, const double* weights, const double* observed,
-                         const int64_t* hyp_offset, int n, const int64_t* samples, int max_nfev, double ftol, double xtol,
-                         double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status, int32_t* consensus,
-                         double* refit_x, int32_t* refit_status, double* mean_error, int32_t* winner, uint8_t* inlier,
-                         double* times_ms, bool draws, const int32_t* group_id, const uint8_t* drawn, uint32_t seed0,
-                         uint32_t seed1, int64_t* samples_out) {
+// optimize.ransac_pairs: RANSAC over many groups (one match control, one fitted camera each) in one pass, served from the
+// CalibRansac its entry point filled.  The checks are glh_ransac_plan.h's rg_check, made before a device is touched.
+static int ransac_groups(glh_calib* handle, CalibRansac& r) {
   if (!handle) return fail(GLH_E_INVALID, "ransac groups: null handle");
   const CalibTable table = calib_table(handle);
-  if (!cams) return fail(GLH_E_INVALID, "ransac groups: null argument");
-  const RgCall call{table.n_cams, table.n_controls, table.kind, table.cam_a, table.cam_b, table.row_offset, n_groups, group_control,
-                    group_cam, p, slots, x0, lb, ub, x_scale, hyp_offset, n, samples, max_nfev, ftol, xtol, gtol, max_error,
-                    x && status && consensus && refit_x && refit_status && mean_error && winner && inlier, draws, group_id, drawn};
+  if (!r.vectors) return fail(GLH_E_INVALID, "ransac groups: null argument");
   char why[400];
-  if (!rg_check(call, why, sizeof(why))) return fail(GLH_E_INVALID, "%s", why);
-  for (int g = 0; g < n_groups; ++g)
-    if (table.kind[group_control[g]] == GLH_CALIB_ROTATION && !observed &&
-        table.row_offset[group_control[g] + 1] > table.row_offset[group_control[g]])
-      return fail(GLH_E_INVALID, "ransac groups: control %d is a ROTATION control, whose obs are camera coordinates: pass observed",
-                  group_control[g]);
-  std::vector<CamDev> cd((size_t)table.n_cams);
-  for (int i = 0; i < table.n_cams; ++i) {
-    if (cams[(size_t)i * GLH_CAM_LEN + 23] != 0.0) return fail(GLH_E_UNSUPPORTED, "ransac groups: camera %d is a raster grid", i);
-    expand_camera(cams + (size_t)i * GLH_CAM_LEN, &cd[i]);
-  }
-  CalibRansac r{cd.data(), cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed,
-                hyp_offset, n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x,
-                refit_status, mean_error, winner, inlier, times_ms};
-  if (draws) {
-    static const uint8_t none = 0;  // (no group: the flags still have an address, which is what says that the call draws)
-    r.drawn = n_groups ? drawn : &none, r.group_id = group_id, r.seed0 = seed0, r.seed1 = seed1, r.samples_out = samples_out;
-  }
+  if (!rg_check(table, r, why, sizeof(why))) return fail(GLH_E_INVALID, "%s", why);
+  std::vector<CamDev> cd;
+  CHK(calib_cameras("ransac groups", r.vectors, (size_t)table.n_cams, cd));
+  r.cams = cd.data();
+  static const uint8_t none = 0;  // (no group: the flags still have an address, which is what says that the call draws)
+  if (r.draws && !r.n_groups) r.drawn = &none;
   return calib_ransac_groups(handle, r);
 }
 
@@ -3234,9 +3163,10 @@ extern "C" int glh_calib_ransac_groups(glh_calib* handle, const double* cams, in
                                        double xtol, double gtol, double max_error, int64_t min_inliers, double* x, int32_t* status,
                                        int32_t* consensus, double* refit_x, int32_t* refit_status, double* mean_error,
                                        int32_t* winner, uint8_t* inlier, double* times_ms) {
-  return ransac_groups(handle, cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed, hyp_offset,
-                       n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x, refit_status,
-                       mean_error, winner, inlier, times_ms, false, nullptr, nullptr, 0u, 0u, nullptr);
+  CalibRansac r{{p, slots, x0, lb, ub, x_scale, max_nfev, ftol, xtol, gtol}, nullptr, cams, n_groups, group_control, group_cam,
+                weights, observed, hyp_offset, n, samples, max_error, min_inliers, x, status, consensus, refit_x, refit_status,
+                mean_error, winner, inlier, times_ms};
+  return ransac_groups(handle, r);
 }
 
 // The same with the samples of the groups it names drawn on the device (INPUTS.md, "Device samples: the rule").
@@ -3249,9 +3179,10 @@ extern "C" int glh_calib_ransac_groups_drawn(glh_calib* handle, const double* ca
                                              int32_t* refit_status, double* mean_error, int32_t* winner, uint8_t* inlier,
                                              const int32_t* group_id, const uint8_t* drawn, uint32_t seed0, uint32_t seed1,
                                              int64_t* samples_out, double* times_ms) {
-  return ransac_groups(handle, cams, n_groups, group_control, group_cam, p, slots, x0, lb, ub, x_scale, weights, observed, hyp_offset,
-                       n, samples, max_nfev, ftol, xtol, gtol, max_error, min_inliers, x, status, consensus, refit_x, refit_status,
-                       mean_error, winner, inlier, times_ms, true, group_id, drawn, seed0, seed1, samples_out);
+  CalibRansac r{{p, slots, x0, lb, ub, x_scale, max_nfev, ftol, xtol, gtol}, nullptr, cams, n_groups, group_control, group_cam,
+                weights, observed, hyp_offset, n, samples, max_error, min_inliers, x, status, consensus, refit_x, refit_status,
+                mean_error, winner, inlier, times_ms, true, group_id, drawn, seed0, seed1, samples_out};
+  return ransac_groups(handle, r);
 }
 
 // What optimize.ransac_pairs(samples="device") gives each pair (glh_ransac_draw.h: rd_hypotheses).  Host arithmetic only.

@@ -1679,7 +1679,34 @@ def ransac(model, n, max_error, min_inliers, iterations=100, batched=False, retu
     return params, inliers
 
 
-_BATCHED_KWARGS = ("ftol", "xtol", "gtol", "max_nfev", "nan_policy")
+def _fit_options(no, kwargs):
+    """The device fit's options among `kwargs`; NotImplementedError (`no`: who refuses) for any other keyword or value."""
+    for key, value in kwargs.items():
+        if key not in ("ftol", "xtol", "gtol", "max_nfev", "nan_policy") or value is None or (key == "nan_policy" and value != "omit"):
+            raise NotImplementedError(no + f"{key}={value!r}: the device fit honours numbers for ftol, xtol, gtol and max_nfev "
+                                      "(and nan_policy='omit')")
+    return {key: kwargs[key] for key in ("ftol", "xtol", "gtol", "max_nfev") if key in kwargs}
+
+
+def _refuse_held(no, control, slots, position):
+    """`slots` fits what `control` holds fixed: internal parameters, or the position (`position` says so; None: it is free)."""
+    if isinstance(control, RotationMatches) and (slots >= 6).any():
+        raise NotImplementedError(no + "fitted internal parameters (f, c, k, p) under a RotationMatches control, whose "
+                                  "camera coordinates hold them fixed")
+    if position and (slots < 3).any():
+        raise NotImplementedError(no + position)
+
+
+def _refuse_raster_grid(no, cams):
+    if any(cam.vector24[23] != 0 for cam in cams):
+        raise NotImplementedError(no + "a camera with a raster grid")
+
+
+def _check_bounds(x0, lb, ub):
+    if np.any(lb >= ub):
+        raise ValueError("Each lower bound must be strictly less than each upper bound.")
+    if np.any((x0 < lb) | (x0 > ub)):
+        raise ValueError("`x0` violates bound constraints.")
 
 
 def _batched_plan(model, kwargs):
@@ -1692,10 +1719,7 @@ def _batched_plan(model, kwargs):
         raise NotImplementedError(no + f"{len(model.cams)} fitted cameras: one")
     if any(np.any(mask) for mask in model.group_masks):
         raise NotImplementedError(no + "group_params: the parameters of one camera (cam_params)")
-    for key, value in kwargs.items():
-        if key not in _BATCHED_KWARGS or value is None or (key == "nan_policy" and value != "omit"):
-            raise NotImplementedError(no + f"{key}={value!r}: the device fit honours numbers for ftol, xtol, gtol and max_nfev "
-                                      "(and nan_policy='omit')")
+    options = _fit_options(no, kwargs)
     slots = np.flatnonzero(model.cam_masks[0])
     if not len(slots):
         raise NotImplementedError(no + "a model without a parameter to fit")
@@ -1704,25 +1728,16 @@ def _batched_plan(model, kwargs):
         if isinstance(control, Lines):
             raise NotImplementedError(no + "a Lines control: Points and the match controls")
         _kind_of(control)  # (RotationMatchesXYZ: NotImplementedError)
-        if isinstance(control, RotationMatches) and (slots >= 6).any():
-            raise NotImplementedError(no + "fitted internal parameters (f, c, k, p) under a RotationMatches control, whose "
-                                      "camera coordinates hold them fixed")
-        if (slots < 3).any() and (isinstance(control, Matches) or control.directions):
-            raise NotImplementedError(no + "a fitted position (xyz) under a match control or ray directions, which hold it fixed")
+        held = "a fitted position (xyz) under a match control or ray directions, which hold it fixed"
+        _refuse_held(no, control, slots, held if isinstance(control, Matches) or control.directions else None)
         cams += [cam for cam in model._get_control_cams(control) if not any(cam is c for c in cams)]
-    for cam in cams:
-        if cam.vector24[23] != 0:
-            raise NotImplementedError(no + "a camera with a raster grid")
+    _refuse_raster_grid(no, cams)
     for control in model.controls:
         model._job_table(control)  # (the checks `predicted` makes at the cameras' current state)
     x0, lb, ub = model._values_bounds()
-    if np.any(lb >= ub):
-        raise ValueError("Each lower bound must be strictly less than each upper bound.")
-    if np.any((x0 < lb) | (x0 > ub)):
-        raise ValueError("`x0` violates bound constraints.")
+    _check_bounds(x0, lb, ub)
     scales = np.ones(len(slots)) if model.scales is None else np.asarray(model.scales, dtype=float)
     weights = None if model.weights is None else np.ascontiguousarray(np.broadcast_to(model.weights, (model.size, 2)))
-    options = {key: kwargs[key] for key in ("ftol", "xtol", "gtol", "max_nfev") if key in kwargs}
     # (a RotationMatches control keeps camera coordinates on the device and predicts image coordinates)
     rotation = any(_kind_of(control) == _lib.CALIB_KINDS["rotation"] for control in model.controls)
     observed = np.ascontiguousarray(model.observed(), dtype=float) if rotation else None
@@ -1830,10 +1845,7 @@ def _pairs_plan(pairs, fitted, cam_params, kwargs):
     and per pair (x0, lb, ub, scales) as `Cameras([m.cams[fitted]], [m], cam_params=[cam_params])` makes them -- or
     NotImplementedError / ValueError as `_batched_plan` raises them for that model.  Made before any library call."""
     no = "ransac_pairs does not serve "
-    for key, value in kwargs.items():
-        if key not in _BATCHED_KWARGS or value is None or (key == "nan_policy" and value != "omit"):
-            raise NotImplementedError(no + f"{key}={value!r}: the device fit honours numbers for ftol, xtol, gtol and max_nfev "
-                                      "(and nan_policy='omit')")
+    options = _fit_options(no, kwargs)
     if fitted not in (0, 1):
         raise ValueError(f"fitted is 0 (the pair's first camera) or 1 (its second), got {fitted!r}")
     mask = Cameras.parse_params(cam_params)[0]
@@ -1844,16 +1856,10 @@ def _pairs_plan(pairs, fitted, cam_params, kwargs):
     for m, i, j in pairs:
         if isinstance(m, RotationMatchesXYZ) or not isinstance(m, Matches):
             raise NotImplementedError(no + f"a {type(m).__name__} for pair ({i}, {j}): Matches, RotationMatches and RotationMatchesXY")
-        if isinstance(m, RotationMatches) and (slots >= 6).any():
-            raise NotImplementedError(no + "fitted internal parameters (f, c, k, p) under a RotationMatches control, whose "
-                                      "camera coordinates hold them fixed")
-        if (slots < 3).any():
-            raise NotImplementedError(no + "a fitted position (xyz) under a match control, which holds it fixed")
+        _refuse_held(no, m, slots, "a fitted position (xyz) under a match control, which holds it fixed")
+        _refuse_raster_grid(no, [cam for cam in m.cams if id(cam) not in known])
         for cam in m.cams:
-            if id(cam) not in known:
-                known[id(cam)] = None
-                if cam.vector24[23] != 0:
-                    raise NotImplementedError(no + "a camera with a raster grid")
+            known.setdefault(id(cam))
         m._test_position()
         if isinstance(m, RotationMatches):
             m._test_internals()
@@ -1861,14 +1867,59 @@ def _pairs_plan(pairs, fitted, cam_params, kwargs):
         if known[id(cam)] is None:
             bounds = Cameras.parse_params(cam_params, default_bounds=Cameras.camera_bounds(cam))[1][mask]
             x0, lb, ub = np.array(cam._vector[mask], dtype=float), bounds[:, 0], bounds[:, 1]
-            if np.any(lb >= ub):
-                raise ValueError("Each lower bound must be strictly less than each upper bound.")
-            if np.any((x0 < lb) | (x0 > ub)):
-                raise ValueError("`x0` violates bound constraints.")
+            _check_bounds(x0, lb, ub)
             known[id(cam)] = (x0, lb, ub, Cameras.camera_scales(cam)[mask])
         values.append(known[id(cam)])
-    options = {key: kwargs[key] for key in ("ftol", "xtol", "gtol", "max_nfev") if key in kwargs}
     return dict(slots=slots, values=values, options=options)
+
+
+def _pairs_samples(pairs, n, iterations, samples, on_device):
+    """Per pair the (H_k, n) rows of its samples (None: `n` rows or fewer), and whether the device draws them (zeros until then)."""
+    drawn, device_drawn = [], np.zeros(len(pairs), dtype=bool)
+    if on_device:
+        counts, enumerated = _lib.ransac_hypotheses([m.size for m, _, _ in pairs], n, iterations)
+        device_drawn = (counts > 0) & ~enumerated
+    for k, (m, _, _) in enumerate(pairs):
+        if m.size <= n:  # ("Sample size is larger or equal to total size")
+            drawn.append(None)
+        elif on_device:
+            drawn.append(np.zeros((counts[k], n), np.int64) if device_drawn[k] else _lib.ransac_combinations(m.size, n, counts[k]))
+        elif samples is None:
+            drawn.append(np.array(list(_ransac_samples(n=n, size=m.size, iterations=iterations)), dtype=np.int64).reshape(-1, n))
+        else:
+            rows = np.asarray(samples[k])
+            if rows.ndim != 2 or rows.shape[1] != n or not np.issubdtype(rows.dtype, np.integer) \
+                    or (rows.size and (rows.min() < 0 or rows.max() >= m.size)):
+                raise ValueError(f"samples[{k}]: an (H, {n}) integer array of row numbers below {m.size}")
+            drawn.append(rows.astype(np.int64))
+    return drawn, device_drawn
+
+
+def _pairs_chunk(pairs, members, plan, fitted, drawn, device_drawn, seed, n):
+    """One chunk, the pairs `members`: the arguments of `_lib.Calib` (its obs and src per pair, to be concatenated), the leading
+    ones and the keywords of its `ransac_groups` (`seed`: None unless the device draws), and where rows and hypotheses lie."""
+    ms = [pairs[k][0] for k in members]
+    cams = list({id(cam): cam for m in ms for cam in m.cams}.values())  # (each camera once, in the order met)
+    where = {id(cam): q for q, cam in enumerate(cams)}
+    kind = [_kind_of(m) for m in ms]
+    sides = [m.uvs if c == _lib.CALIB_KINDS["matches"] else m.xys for m, c in zip(ms, kind)]
+    obs = [np.asarray(s[0], dtype=float).reshape(-1, 2) for s in sides]
+    src = [np.column_stack((s[1], np.zeros(len(s[1])))) for s in sides]
+    row_offset = np.concatenate(([0], np.cumsum([len(o) for o in obs]))).astype(np.int64)
+    hyp_offset = np.concatenate(([0], np.cumsum([len(drawn[k]) for k in members]))).astype(np.int64)
+    values = (np.array([plan["values"][k][q] for k in members]).reshape(-1, len(plan["slots"])) for q in range(4))
+    keywords = dict(observed=None, **plan["options"])
+    if _lib.CALIB_KINDS["rotation"] in kind:  # (a RotationMatches keeps camera coordinates on the device and predicts image coordinates)
+        keywords["observed"] = np.concatenate([np.asarray(m.observed(), dtype=float).reshape(-1, 2) for m in ms])
+    if seed is not None:
+        keywords.update(group_id=members, drawn=device_drawn[members], seed=(seed & 0xFFFFFFFF, seed >> 32), n=n)
+    rows = None if seed is not None and device_drawn[members].all() else \
+        np.concatenate([drawn[k] + row_offset[g] for g, k in enumerate(members)])  # (None: the device draws every sample)
+    cam_a, cam_b = ([where[id(m.cams[side])] for m in ms] for side in (0, 1))
+    controls = (len(cams), kind, cam_a, cam_b, np.zeros(len(ms), np.int32), row_offset)
+    call = (np.array([cam.vector24 for cam in cams]), np.arange(len(ms)), (cam_a, cam_b)[fitted], plan["slots"], *values,
+            hyp_offset, rows)
+    return controls, (obs, src), call, keywords, row_offset, hyp_offset
 
 
 def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=None, fitted=1, samples=None, budget=None,
@@ -1935,84 +1986,31 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
         seed = int(words[0]) | int(words[1]) << 32
     seed = None if seed is None else int(seed)
     t.append(time.perf_counter())
-    drawn = []
-    # device mode: `device_drawn[k]`, pair k's samples come from the device; `drawn[k]` holds zeros until they are back
-    device_drawn = np.zeros(len(pairs), dtype=bool)
-    if on_device:
-        counts, enumerated = _lib.ransac_hypotheses([m.size for m, _, _ in pairs], n, iterations)
-        device_drawn = (counts > 0) & ~enumerated
-    for k, (m, _, _) in enumerate(pairs):
-        if m.size <= n:  # ("Sample size is larger or equal to total size")
-            drawn.append(None)
-        elif on_device:
-            drawn.append(np.zeros((counts[k], n), np.int64) if device_drawn[k] else _lib.ransac_combinations(m.size, n, counts[k]))
-        elif samples is None:
-            drawn.append(np.array(list(_ransac_samples(n=n, size=m.size, iterations=iterations)), dtype=np.int64).reshape(-1, n))
-        else:
-            rows = np.asarray(samples[k])
-            if rows.ndim != 2 or rows.shape[1] != n or not np.issubdtype(rows.dtype, np.integer) \
-                    or (rows.size and (rows.min() < 0 or rows.max() >= m.size)):
-                raise ValueError(f"samples[{k}]: an (H, {n}) integer array of row numbers below {m.size}")
-            drawn.append(rows.astype(np.int64))
+    drawn, device_drawn = _pairs_samples(pairs, n, iterations, samples, on_device)
     t.append(time.perf_counter())
     served = [k for k, rows in enumerate(drawn) if rows is not None]
-    sizes = np.array([pairs[k][0].size for k in served], dtype=np.int64)
-    counts = np.array([len(drawn[k]) for k in served], dtype=np.int64)
-    budget = RANSAC_PAIRS_BUDGET if budget is None else int(budget)
-    chunk_of = _lib.ransac_chunks(sizes, counts, min(max(budget, 0), 2 ** 31 - 1)) if served else np.zeros(0, np.int32)
-    p = len(plan["slots"])
-    keys = ("values", "status", "consensus", "refit_values", "refit_status", "mean_errors")
-    parts = {key: [] for key in keys}
+    budget = min(max(RANSAC_PAIRS_BUDGET if budget is None else int(budget), 0), 2 ** 31 - 1)
+    chunk_of = _lib.ransac_chunks([pairs[k][0].size for k in served], [len(drawn[k]) for k in served], budget) if served else np.zeros(0, np.int32)
+    chunks = int(chunk_of.max()) + 1 if served else 0
     winner = np.full(len(pairs), -1, dtype=np.int32)
-    results = [None] * len(pairs)
+    results, outs = [None] * len(pairs), []
     device_times = _lib.CALIB_RANSAC_TIMES[1:] + (("draw",) if on_device else ())
-    times = dict.fromkeys(("upload",) + device_times, 0.0)
-    host = 0.0
-    for chunk in range(int(chunk_of.max()) + 1 if served else 0):
+    host, times = 0.0, dict.fromkeys(("upload",) + device_times, 0.0)
+    for chunk in range(chunks):
         t0 = time.perf_counter()
         members = [served[q] for q in np.flatnonzero(chunk_of == chunk)]
-        cams, where = [], {}
-        for k in members:
-            for cam in pairs[k][0].cams:
-                if id(cam) not in where:
-                    where[id(cam)] = len(cams)
-                    cams.append(cam)
-        kind = [_kind_of(pairs[k][0]) for k in members]
-        rotation = _lib.CALIB_KINDS["rotation"] in kind
-        obs, src, observed = [], [], []
-        for k, c in zip(members, kind):
-            m = pairs[k][0]
-            sides = m.uvs if c == _lib.CALIB_KINDS["matches"] else m.xys
-            obs.append(np.asarray(sides[0], dtype=float).reshape(-1, 2))
-            src.append(np.column_stack((sides[1], np.zeros(len(sides[1])))))
-            if rotation:  # (a RotationMatches keeps camera coordinates on the device and predicts image coordinates)
-                observed.append(np.asarray(m.observed(), dtype=float).reshape(-1, 2))
-        row_offset = np.concatenate(([0], np.cumsum([len(o) for o in obs]))).astype(np.int64)
-        hyp_offset = np.concatenate(([0], np.cumsum([len(drawn[k]) for k in members]))).astype(np.int64)
-        x0, lb, ub, scales = (np.array([plan["values"][k][q] for k in members]).reshape(-1, p) for q in range(4))
-        draw = dict(group_id=members, drawn=device_drawn[members], seed=(seed & 0xFFFFFFFF, seed >> 32), n=n) if on_device else {}
-        # (nothing to upload where the device draws every sample of the chunk)
-        rows = None if on_device and device_drawn[members].all() else \
-            np.concatenate([drawn[k] + row_offset[g] for g, k in enumerate(members)])
-        cams24 = np.array([cam.vector24 for cam in cams])
+        controls, obs_src, call, keywords, row_offset, hyp_offset = _pairs_chunk(pairs, members, plan, fitted, drawn, device_drawn, seed, n)
         t1 = time.perf_counter()
-        handle = _lib.Calib(len(cams), kind, [where[id(pairs[k][0].cams[0])] for k in members],
-                            [where[id(pairs[k][0].cams[1])] for k in members], np.zeros(len(members), np.int32), row_offset,
-                            np.concatenate(obs), np.concatenate(src))
+        handle = _lib.Calib(*controls, *(np.concatenate(v) for v in obs_src))  # (the copies: counted with the upload)
         try:
             t2 = time.perf_counter()
-            out, device = handle.ransac_groups(
-                cams24, np.arange(len(members)), [where[id(pairs[k][0].cams[fitted])] for k in members], plan["slots"], x0, lb,
-                ub, scales, hyp_offset, rows, max_error, min_inliers, observed=np.concatenate(observed) if rotation else None,
-                return_times=True, **draw, **plan["options"])
+            out, device = handle.ransac_groups(*call, max_error, min_inliers, return_times=True, **keywords)
         finally:
             handle.close()
+        outs.append(out)
         for g, k in enumerate(members):
             if device_drawn[k]:
                 drawn[k] = out["samples"][hyp_offset[g]:hyp_offset[g + 1]] - row_offset[g]
-        for key in keys:
-            parts[key].append(out[key])
-        for g, k in enumerate(members):
             winner[k] = out["winner"][g]
             if winner[k] >= 0:
                 inliers = np.flatnonzero(out["inlier"][row_offset[g]:row_offset[g + 1]])
@@ -2023,10 +2021,11 @@ def ransac_pairs(pairs, n, max_error, min_inliers, iterations=100, cam_params=No
             times[key] += device[key]
     if not return_info:
         return results
-    info = {key: (np.concatenate(parts[key]) if parts[key] else np.zeros((0, p) if "values" in key else 0)) for key in keys}
+    info = {key: (np.concatenate([out[key] for out in outs]) if outs else np.zeros((0, len(plan["slots"])) if "values" in key else 0))
+            for key in ("values", "status", "consensus", "refit_values", "refit_status", "mean_errors")}
     info["winner"] = winner
     info["hyp_offset"] = np.concatenate(([0], np.cumsum([0 if rows is None else len(rows) for rows in drawn]))).astype(np.int64)
-    info["chunks"] = int(chunk_of.max()) + 1 if served else 0
+    info["chunks"] = chunks
     info["samples"] = drawn
     if on_device:
         info["seed"] = seed

@@ -122,17 +122,25 @@ struct Case {
   std::vector<uint8_t> drawn{0, 1, 0};
   int n_cams = 4, n_controls = 4, n_groups = 3, p = 2, n = 3, max_nfev = 10;
   bool draws = true, no_samples = false, no_ids = false, no_flags = false;
-  RgCall call() const {
-    return RgCall{n_cams, n_controls, kind.data(), cam_a.data(), cam_b.data(), row_offset.data(), n_groups, group_control.data(),
-                  group_cam.data(), p, slots.data(), x0.data(), lb.data(), ub.data(), scale.data(), hyp_offset.data(), n,
-                  no_samples ? nullptr : samples.data(), max_nfev, 1e-8, 1e-8, 1e-8, 3.0, true, draws,
-                  no_ids ? nullptr : group_id.data(), no_flags ? nullptr : drawn.data()};
+  // (what the check only asks to be there: the cameras' vectors, the observations of the ROTATION control, the outputs)
+  double vectors[1] = {0.0}, observed[1] = {0.0}, f64[3] = {};
+  int32_t i32[4] = {};
+  uint8_t u8[1] = {};
+  CalibTable table() const { return CalibTable{n_cams, n_controls, kind.data(), row_offset.data(), cam_a.data(), cam_b.data()}; }
+  CalibRansac call() {
+    return CalibRansac{{p, slots.data(), x0.data(), lb.data(), ub.data(), scale.data(), max_nfev, 1e-8, 1e-8, 1e-8}, nullptr, vectors,
+                       n_groups, group_control.data(), group_cam.data(), nullptr, observed, hyp_offset.data(), n,
+                       no_samples ? nullptr : samples.data(), 3.0, 0, f64, i32, i32 + 1, f64 + 1, i32 + 2, f64 + 2, i32 + 3, u8, nullptr,
+                       draws, no_ids ? nullptr : group_id.data(), no_flags ? nullptr : drawn.data()};
   }
 };
 
-static bool served(const Case& c, const char* word = nullptr) {
-  char msg[400] = "";
-  const bool ok = rg_check(c.call(), msg, sizeof(msg));
+static char last[400];  // the message of the last refusal
+
+static bool served(Case& c, const char* word = nullptr) {
+  char* msg = last;
+  msg[0] = 0;
+  const bool ok = rg_check(c.table(), c.call(), msg, sizeof(last));
   if (!ok && std::strncmp(msg, "ransac groups:", 14) != 0) EXPECT(!"a refusal without a message");
   if (!ok && word && !std::strstr(msg, word)) {
     std::printf("FAILED: expected \"%s\" in \"%s\"\n", word, msg);
@@ -147,6 +155,16 @@ static void refused(const char* word, const std::function<void(Case&)>& change) 
   change(c);
   if (served(c, word)) {
     std::printf("FAILED: not refused: %s\n", word);
+    ++failures;
+  }
+}
+
+// The whole message of a refusal, as rg_check's format strings gave it before its checks were shared with fs_check.
+static void says(const char* message, const std::function<void(Case&)>& change) {
+  Case c;
+  change(c);
+  if (served(c) || std::strcmp(last, message) != 0) {
+    std::printf("FAILED: expected \"%s\", got \"%s\"\n", message, last);
     ++failures;
   }
 }
@@ -183,6 +201,21 @@ static void check_plan() {
   accepted([](Case& c) { c.draws = false, c.no_ids = c.no_flags = true, c.samples = {0, 1, 63, 5, 5, 5, 64, 65, 128, 100, 101, 102, 64, 64, 64}; });
   accepted([](Case& c) { c.n_groups = 0, c.row_offset = {0, 0, 0, 0, 0}, c.no_ids = c.no_flags = c.no_samples = true; });
   EXPECT(RANSAC_DRAWN_TIMES == RANSAC_TIMES + 1);
+  // the whole messages of the refusals above
+  says("ransac groups: null argument: the groups' ids and drawn flags", [](Case& c) { c.no_ids = true; });
+  says("ransac groups: null argument: the groups' ids and drawn flags", [](Case& c) { c.no_flags = true; });
+  says("ransac groups: group 2 has the id -1: ids are not negative", [](Case& c) { c.group_id[2] = -1; });
+  says("ransac groups: group 0 has the drawn flag 2: 0 or 1", [](Case& c) { c.drawn[0] = 2; });
+  says("ransac groups: group 2 has the drawn flag 255: 0 or 1", [](Case& c) { c.drawn[2] = 255; });
+  says("ransac groups: group 0 draws samples of 64 of its 64 rows: a drawn group has more rows than that",
+       [](Case& c) { c.drawn = {1, 1, 1}, c.no_samples = true, c.n = 64; });
+  says("ransac groups: group 1 draws samples of 3 of its 3 rows: a drawn group has more rows than that",
+       [](Case& c) { c.row_offset = {0, 64, 67, 67, 67}; });
+  says("ransac groups: null samples", [](Case& c) { c.no_samples = true; });
+  says("ransac groups: null samples", [](Case& c) { c.no_samples = true, c.drawn = {1, 0, 0}; });
+  says("ransac groups: hypothesis 0 of group 0 samples row 64 outside its control's rows 0 .. 64", [](Case& c) { c.samples[2] = 64; });
+  says("ransac groups: hypothesis 2 of group 1 samples row -1 outside its control's rows 64 .. 129", [](Case& c) { c.drawn = {0, 0, 0}; });
+  says("ransac groups: hypothesis 2 of group 1 samples row -1 outside its control's rows 64 .. 129", [](Case& c) { c.draws = false; });
 }
 
 int main() {

@@ -35,22 +35,43 @@ struct Case {
   int n_cams = 4, n_controls = 4, n_groups = 3, p = 2, n = 3, max_nfev = 10;
   double ftol = 1e-8, xtol = 1e-8, gtol = 1e-8, max_error = 3.0;
   bool outputs = true;
-  RgCall call() const {
-    return RgCall{n_cams, n_controls, kind.data(), cam_a.data(), cam_b.data(), row_offset.data(), n_groups, group_control.data(),
-                  group_cam.data(), p, slots.data(), x0.data(), lb.data(), ub.data(), scale.data(), hyp_offset.data(), n,
-                  samples.data(), max_nfev, ftol, xtol, gtol, max_error, outputs};
+  // (what the check only asks to be there: the cameras' vectors, the observations of the ROTATION control, the outputs)
+  double vectors[1] = {0.0}, observed[1] = {0.0}, f64[3] = {};
+  int32_t i32[4] = {};
+  uint8_t u8[1] = {};
+  CalibTable table() const { return CalibTable{n_cams, n_controls, kind.data(), row_offset.data(), cam_a.data(), cam_b.data()}; }
+  CalibRansac call() {
+    return CalibRansac{{p, slots.data(), x0.data(), lb.data(), ub.data(), scale.data(), max_nfev, ftol, xtol, gtol}, nullptr, vectors,
+                       n_groups, group_control.data(), group_cam.data(), nullptr, observed, hyp_offset.data(), n, samples.data(),
+                       max_error, 0, f64, i32, i32 + 1, f64 + 1, i32 + 2, f64 + 2, i32 + 3, outputs ? u8 : nullptr, nullptr};
   }
 };
 
-static bool served(const Case& c, const char* word = nullptr) {
-  char msg[400] = "";
-  const bool ok = rg_check(c.call(), msg, sizeof(msg));
+static char last[400];  // the message of the last refusal
+
+static bool served(Case& c, const char* word = nullptr) {
+  char* msg = last;
+  msg[0] = 0;
+  const bool ok = rg_check(c.table(), c.call(), msg, sizeof(last));
   if (!ok && (std::strlen(msg) == 0 || std::strncmp(msg, "ransac groups:", 14) != 0)) EXPECT(!"a refusal without a message");
   if (!ok && word && !std::strstr(msg, word)) {
     std::printf("expected \"%s\" in \"%s\"\n", word, msg);
     ++failures;
   }
   return ok;
+}
+
+// The whole message of a refusal, as the format strings of rg_check gave it before its checks were shared with fs_check.
+static void says(const char* message, const std::function<void(Case&)>& change) {
+  Case c;
+  EXPECT(served(c));
+  change(c);
+  if (served(c) || std::strcmp(last, message) != 0) {
+    std::printf("FAILED: expected \"%s\", got \"%s\"\n", message, last);
+    ++failures;
+  }
+  Case again;
+  EXPECT(served(again));
 }
 
 static void refused(const char* word, const std::function<void(Case&)>& change) {
@@ -110,28 +131,88 @@ static void check_refusals() {
   refused("samples row", [](Case& c) { c.samples[0] = -1; });
   {  // null pointers, one at a time
     Case c;
+    const CalibTable t = c.table();
+    char msg[400];
     for (int which = 0; which < 8; ++which) {
-      RgCall r = c.call();
+      CalibRansac r = c.call();
       const int32_t** i32[] = {&r.group_control, &r.group_cam, &r.slots};
-      const double** f64[] = {&r.x0, &r.lb, &r.ub, &r.x_scale};
+      const double** f64[] = {&r.x0, &r.lb, &r.ub, &r.scale};
       if (which < 3)
         *i32[which] = nullptr;
       else if (which < 7)
         *f64[which - 3] = nullptr;
       else
         r.hyp_offset = nullptr;
-      char msg[400];
-      EXPECT(!rg_check(r, msg, sizeof(msg)) && std::strstr(msg, "null"));
+      EXPECT(!rg_check(t, r, msg, sizeof(msg)) && std::strcmp(msg, "ransac groups: null argument") == 0);
     }
-    RgCall r = c.call();
+    for (int which = 0; which < 8; ++which) {  // every output is asked for
+      CalibRansac r = c.call();
+      void** out[] = {(void**)&r.x, (void**)&r.status, (void**)&r.consensus, (void**)&r.refit_x, (void**)&r.refit_status,
+                      (void**)&r.mean_error, (void**)&r.winner, (void**)&r.inlier};
+      *out[which] = nullptr;
+      EXPECT(!rg_check(t, r, msg, sizeof(msg)) && std::strcmp(msg, "ransac groups: null argument") == 0);
+    }
+    CalibRansac r = c.call();
     r.samples = nullptr;
-    char msg[400];
-    EXPECT(!rg_check(r, msg, sizeof(msg)) && std::strstr(msg, "null samples"));
+    EXPECT(!rg_check(t, r, msg, sizeof(msg)) && std::strcmp(msg, "ransac groups: null samples") == 0);
     r = c.call();
-    r.row_offset = nullptr;
-    EXPECT(!rg_check(r, msg, sizeof(msg)));
-    EXPECT(rg_check(c.call(), msg, sizeof(msg)));
+    r.observed = nullptr;  // (control 1 is a ROTATION control with rows)
+    EXPECT(!rg_check(t, r, msg, sizeof(msg)) &&
+           std::strcmp(msg, "ransac groups: control 1 is a ROTATION control, whose obs are camera coordinates: pass observed") == 0);
+    CalibTable none = t;
+    none.row_offset = nullptr;
+    EXPECT(!rg_check(none, c.call(), msg, sizeof(msg)) && std::strcmp(msg, "ransac groups: a handle without controls") == 0);
+    EXPECT(rg_check(t, c.call(), msg, sizeof(msg)));
   }
+  // the whole messages of the refusals above, one fault each
+  says("ransac groups: null argument", [](Case& c) { c.outputs = false; });
+  says("ransac groups: -1 groups: fewer than 2^24 are served", [](Case& c) { c.n_groups = -1; });
+  says("ransac groups: 16777216 groups: fewer than 2^24 are served", [](Case& c) { c.n_groups = 1 << 24; });
+  says("ransac groups: 0 parameters: 1 .. 18 are served", [](Case& c) { c.p = 0; });
+  says("ransac groups: 19 parameters: 1 .. 18 are served", [](Case& c) { c.p = 19; });
+  says("ransac groups: parameter 1 is entry 3 of the camera vector: distinct ones of 0 .. 5, 8 .. 19", [](Case& c) { c.slots = {3, 3}; });
+  says("ransac groups: parameter 1 is entry 6 of the camera vector: distinct ones of 0 .. 5, 8 .. 19", [](Case& c) { c.slots = {3, 6}; });
+  says("ransac groups: parameter 0 is entry 7 of the camera vector: distinct ones of 0 .. 5, 8 .. 19", [](Case& c) { c.slots = {7, 4}; });
+  says("ransac groups: parameter 1 is entry 20 of the camera vector: distinct ones of 0 .. 5, 8 .. 19", [](Case& c) { c.slots = {3, 20}; });
+  says("ransac groups: parameter 0 is entry -1 of the camera vector: distinct ones of 0 .. 5, 8 .. 19", [](Case& c) { c.slots = {-1, 4}; });
+  says("ransac groups: samples of 0 rows", [](Case& c) { c.n = 0; });
+  says("ransac groups: 0 evaluations, ftol 1e-08, xtol 1e-08, gtol 1e-08", [](Case& c) { c.max_nfev = 0; });
+  says("ransac groups: 10 evaluations, ftol -1, xtol 1e-08, gtol 1e-08", [](Case& c) { c.ftol = -1.0; });
+  says("ransac groups: 10 evaluations, ftol 1, xtol 1e-08, gtol 1e-08", [](Case& c) { c.ftol = 1.0; });
+  says("ransac groups: 10 evaluations, ftol 1e-08, xtol nan, gtol 1e-08", [nan](Case& c) { c.xtol = nan; });
+  says("ransac groups: 10 evaluations, ftol 1e-08, xtol 1e-08, gtol inf", [inf](Case& c) { c.gtol = inf; });
+  says("ransac groups: max_error is NaN", [nan](Case& c) { c.max_error = nan; });
+  says("ransac groups: hyp_offset[0] is 1, not 0", [](Case& c) { c.hyp_offset[0] = 1; });
+  says("ransac groups: group 1 ends at hypothesis 2 after 3: not decreasing, fewer than 2^31 in all",
+       [](Case& c) { c.hyp_offset = {0, 3, 2, 5}; });
+  says("ransac groups: group 1 ends at hypothesis 2147483648 after 2: not decreasing, fewer than 2^31 in all",
+       [](Case& c) { c.hyp_offset = {0, 2, (int64_t)1 << 31, (int64_t)1 << 31}; });
+  says("ransac groups: group 2 is control 4 of 4", [](Case& c) { c.group_control[2] = 4; });
+  says("ransac groups: group 0 is control -1 of 4", [](Case& c) { c.group_control[0] = -1; });
+  says("ransac groups: group 2 is control 3, a POINTS or LINES control: the match kinds are served", [](Case& c) { c.group_control[2] = 3; });
+  says("ransac groups: group 1 is control 1, a POINTS or LINES control: the match kinds are served", [](Case& c) { c.kind[1] = 1; });
+  says("ransac groups: group 1 is control 0 after control 1: the groups name distinct controls in ascending order",
+       [](Case& c) { c.group_control = {1, 0, 2}; });
+  says("ransac groups: group 2 is control 1 after control 1: the groups name distinct controls in ascending order",
+       [](Case& c) { c.group_control = {0, 1, 1}; });
+  says("ransac groups: group 0 fits camera 4 of 4", [](Case& c) { c.group_cam[0] = 4; });
+  says("ransac groups: group 0 fits camera -1 of 4", [](Case& c) { c.group_cam[0] = -1; });
+  says("ransac groups: group 0 fits camera 2, which is neither camera (0, 1) of its control", [](Case& c) { c.group_cam[0] = 2; });
+  says("ransac groups: group 2 fits camera 0, which is neither camera (2, 3) of its control", [](Case& c) { c.group_cam[2] = 0; });
+  says("ransac groups: group 1, parameter 1 starts at 10 outside its bounds 0 .. 9", [](Case& c) { c.x0[3] = 10.0; });
+  says("ransac groups: group 0, parameter 0 starts at -1 outside its bounds 0 .. 9", [](Case& c) { c.x0[0] = -1.0; });
+  says("ransac groups: group 2, parameter 1 starts at nan outside its bounds 0 .. 9", [nan](Case& c) { c.x0[5] = nan; });
+  says("ransac groups: group 2, parameter 1 starts at inf outside its bounds 0 .. inf", [inf](Case& c) { c.x0[5] = inf, c.ub[5] = inf; });
+  says("ransac groups: group 1, parameter 0 has the bounds 3 .. 3: the lower one must be below the upper one",
+       [](Case& c) { c.lb[2] = c.ub[2] = c.x0[2]; });
+  says("ransac groups: group 2, parameter 0 has scale 0", [](Case& c) { c.scale[4] = 0.0; });
+  says("ransac groups: group 2, parameter 0 has scale nan", [nan](Case& c) { c.scale[4] = nan; });
+  says("ransac groups: group 0, parameter 1 has scale inf", [inf](Case& c) { c.scale[1] = inf; });
+  says("ransac groups: the groups hold 64 of the handle's 129 rows: every row belongs to exactly one group", [](Case& c) { c.n_groups = 1; });
+  says("ransac groups: hypothesis 0 of group 0 samples row 64 outside its control's rows 0 .. 64", [](Case& c) { c.samples[2] = 64; });
+  says("ransac groups: hypothesis 2 of group 1 samples row 63 outside its control's rows 64 .. 129", [](Case& c) { c.samples[6] = 63; });
+  says("ransac groups: hypothesis 4 of group 1 samples row 129 outside its control's rows 64 .. 129", [](Case& c) { c.samples[14] = 129; });
+  says("ransac groups: hypothesis 0 of group 0 samples row -1 outside its control's rows 0 .. 64", [](Case& c) { c.samples[0] = -1; });
   {  // no group and no row: served; a degenerate sample (one row n times) is the fit's business, not the plan's
     Case c;
     c.row_offset = {0, 0, 0, 0, 0};
@@ -151,6 +232,7 @@ static void check_mask_limit() {
   c.hyp_offset = {0, (int64_t)1 << 15};
   c.samples.assign((size_t)1 << 15, 7);
   EXPECT(!served(c, "2^31"));
+  EXPECT(std::strcmp(last, "ransac groups: the consensus masks take 2^31 bytes or more: fewer are served in one call") == 0);
   c.hyp_offset = {0, ((int64_t)1 << 15) - 1};
   EXPECT(served(c));
   EXPECT(rg_mask_bytes((int64_t)1 << 16, (int64_t)1 << 15) == RANSAC_MASK_LIMIT);

@@ -282,6 +282,34 @@ def test_bad_arguments_leave_the_handle_usable():
     rotation._handle = None
 
 
+def test_no_job_and_no_set_leave_the_handle_as_a_fresh_one():
+    """`Calib.eval` without a job and `fit_sets` without a set: empty outputs, and the calls that follow on that handle return
+    the bytes they return on a fresh handle."""
+    from glimpse_amd.camera import rotations
+    from glimpse_amd.optimize import _batched_plan
+
+    model, _ = rc.model("viewdir_64")
+    plan = _batched_plan(model, {})
+    fit = dict(fit_cam=0, slots=plan["slots"], x0=plan["x0"], lb=plan["lb"], ub=plan["ub"], x_scale=plan["x_scale"], max_error=3.0)
+    sets, _, jobs = model._jacobian_plan()
+
+    def served(handle, cams24):
+        return [*model._evaluate(handle, sets, jobs), *handle.fit_sets(cams24, set_offset=[0, 4, 10], set_rows=np.arange(10), **fit)]
+
+    with model.upload() as handle:
+        cams24 = np.array([cam.vector24 for cam in model._dev_cams])
+        fresh = served(handle, cams24)
+    model._handle = None
+    with model.upload() as handle:
+        rot = rotations(cams24[:, 3:6])[0].reshape(1, len(cams24), 3, 3)
+        assert handle.eval(cams24[None], rot, [], []).shape == (0, 2)
+        x, status, mean_error, inlier = handle.fit_sets(cams24, set_offset=[0], set_rows=[], **fit)
+        assert x.shape == (0, len(plan["slots"])) and status.shape == mean_error.shape == (0,) and inlier.shape == (0, model.size)
+        again = served(handle, cams24)
+    model._handle = None
+    assert len(fresh) == len(again) == len(jobs) + 4 and all(a.tobytes() == b.tobytes() for a, b in zip(fresh, again))
+
+
 def test_the_references_scenario():
     """The reference's one test of optimize (its tests/test_optimize.py) on a synthetic frame of 400 x 268: the frame
     projected into a camera turned by (2, 2, 2), SIFT on both, matched with max_ratio=0.8, and RANSAC over

@@ -36,7 +36,7 @@ CHI2_999 = {14: 36.12, 99: 148.23}  # the 99.9 % quantiles of chi-square by degr
 def program_lines():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
     csrc = os.path.join(ROOT, "glimpse_amd", "csrc")
-    deps = [SRC] + [os.path.join(csrc, name) for name in ("glh_ransac_draw.h", "glh_ransac_plan.h", "glh_math.h")]
+    deps = [SRC] + [os.path.join(csrc, name) for name in ("glh_ransac_draw.h", "glh_ransac_plan.h", "glh_calib.h", "glh_math.h")]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", "-o", OUT, SRC], check=True)

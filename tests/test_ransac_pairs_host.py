@@ -13,7 +13,7 @@ OUT = os.path.join(ROOT, "tests", "hostcheck", "_build", "ransac_pairs_hostcheck
 
 def test_refusals_offsets_and_chunks_under_the_sanitizers():
     os.makedirs(os.path.dirname(OUT), exist_ok=True)
-    deps = [SRC, os.path.join(ROOT, "glimpse_amd", "csrc", "glh_ransac_plan.h")]
+    deps = [SRC, *(os.path.join(ROOT, "glimpse_amd", "csrc", name) for name in ("glh_ransac_plan.h", "glh_calib.h"))]
     if not os.path.exists(OUT) or any(os.path.getmtime(d) > os.path.getmtime(OUT) for d in deps):
         subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-fsanitize=address,undefined",
                         "-fno-sanitize-recover=all", "-o", OUT, SRC], check=True)
