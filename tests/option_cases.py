@@ -43,6 +43,19 @@ def float_map(frame16, dtype):
     return (np.power(frame16.astype(np.float64) / 65535.0, 0.8) * 3.5 - 1.25).astype(dtype)
 
 
+def render(scene, cam, t, ftype, channels, levels):
+    """The frame of a scene at time t in one of FRAME_TYPES: synth's 8-bit rendering, its 16-bit one (whole, squeezed into
+    300 levels offset from zero, or quantised to 300 steps), or float_map of the latter."""
+    if ftype == "uint8":
+        return scene.render(cam, float(t), channels=channels)
+    f = scene.render(cam, float(t), channels=channels, bits=16)
+    if levels == "300":  # a narrow range of levels, offset from zero
+        return (f.astype(np.uint32) * 300 // 65535 + 1000).astype(np.uint16)
+    if levels == "quantised":
+        f = (f.astype(np.uint32) * 300 // 65535 * 218).astype(np.uint16)
+    return f if ftype == "uint16" else float_map(f, np.dtype(ftype))
+
+
 def _orders(seed, fused):
     if fused:
         return FUSED_ORDERS[(seed // 2 + seed // 10) % 2]
@@ -133,17 +146,7 @@ def case(seed):
     if seed % 6 == 4:
         taus, times = -taus, -times
 
-    def frame(cam, t):
-        if ftype == "uint8":
-            return scene.render(cam, float(t), channels=channels)
-        f = scene.render(cam, float(t), channels=channels, bits=16)
-        if levels == "300":  # a narrow range of levels, offset from zero
-            return (f.astype(np.uint32) * 300 // 65535 + 1000).astype(np.uint16)
-        if levels == "quantised":
-            f = (f.astype(np.uint32) * 300 // 65535 * 218).astype(np.uint16)
-        return f if ftype == "uint16" else float_map(f, np.dtype(ftype))
-
-    frames = [[frame(cam, t) for t in times] for cam in cams]
+    frames = [[render(scene, cam, t, ftype, channels, levels) for t in times] for cam in cams]
     # ---- points every camera sees with room for the template and the search tile
     xy = []
     margin = 0.5 * max(tile) + (75.0 if wide else 45.0)
@@ -265,10 +268,15 @@ def _clean(cs, run):
 
 @functools.lru_cache(maxsize=None)
 def admit(seed):
+    """The admission rule on case(seed): admit_case."""
+    return admit_case(case(seed))
+
+
+def admit_case(cs, keep_run=False):
     """The admission rule.  Returns dict(ok, why, ref, facts): `ref` the row_f32 run's means (T, P, 6), sigmas and indices
     (T - 1, P, N) -- the reference the device is compared with --, `spread` the relative tolerance (beside atol 1e-8) at
-    which the two runs' moments agree, `facts` what the case exercises (largest SSD surface, levels and repeats inside the first template)."""
-    cs = case(seed)
+    which the two runs' moments agree, `facts` what the case exercises (largest SSD surface, levels and repeats inside the
+    first template); with `keep_run` also `run`, the row_f32 run itself (oracle_run's results and traces)."""
     try:
         runs = {ssd: oracle_run(cs, ssd) for ssd in ("f64", "row_f32")}
     except (IndexError, ValueError) as e:
@@ -300,7 +308,10 @@ def admit(seed):
                  frame_levels=int(len(np.unique(cs["frames"][0][0]))),
                  template_repeats=int(raw.size // cs["channels"] - len(first["histogram"][0])))
     ref = dict(means=mom["row_f32"][:, :, 0:6], sigmas=mom["row_f32"][:, :, 6:12], idx=idx["row_f32"])
-    return dict(ok=True, why="", ref=ref, spread=spread, facts=facts)
+    out = dict(ok=True, why="", ref=ref, spread=spread, facts=facts)
+    if keep_run:
+        out["run"] = runs["row_f32"]
+    return out
 
 
 def admitted(count, limit=200):

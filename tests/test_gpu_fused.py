@@ -76,7 +76,10 @@ def test_fused_step_equals_staged_and_reference(lib, golden, name):
                                  ("C3", 2, 12000, 1), ("C2", 5, 777, 3), ("C5", 3, 1500, 3)])
 def test_fused_step_equals_staged_with_device_rng(lib, cfg):
     """Philox mode (what large runs use): re-evolving the gathered sources from the counter-based
-    noise gives exactly the state the staged kernels store and gather."""
+    noise gives exactly the state the staged kernels store and gather.  At N = 12 000 the plan refuses the fused kernel
+    (glh_point_plan.h: beyond 10 976 particles), so every mode is the staged kernels there and the entry compares them
+    with themselves: it shows that set_fused(1) and (2) fall through cleanly, and the profile says which kernels ran.  The
+    staged-only counts against the oracle: tests/test_gpu_wide_cases.py."""
     from glimpse_amd import workloads
 
     name, P, N, channels = cfg
@@ -98,6 +101,9 @@ def test_fused_step_equals_staged_with_device_rng(lib, cfg):
             assert (ctx.observer_status() == lib.OBS_OK).all()
             assert (ctx.point_status() == 0).all()
             res.append((ctx.get_particles(), ctx.get_weights(), ctx.get_moments(0, T)))
+            ran = {k for k, v in ctx.profile_get().items() if v[1] > 0}
+            assert ("point_step" in ran) == (mode != 0 and N != 12000), (mode, N, sorted(ran))
+            assert ("resample" in ran) == (mode == 0 or N == 12000), (mode, N, sorted(ran))
     for other in (1, 2):
         np.testing.assert_array_equal(res[0][0], res[other][0])
         np.testing.assert_array_equal(res[0][1], res[other][1])
@@ -114,7 +120,8 @@ def test_track_equals_the_same_steps(lib, cfg):
     """glh_track (the frame loop of tracker.py:326-357 in one call) leaves exactly what the same glh_step calls
     leave: particles, weights, every row of the moments history, statuses.  Includes
     frames an observer skips (image None), tiles forced to the HBM workspaces, non-unit and negative time steps,
-    and more tracks than resident workgroups."""
+    and more tracks than resident workgroups.  At N = 12 000 the plan refuses the fused kernel, so that entry is
+    glh_track over the staged kernels: no point_step in the profile."""
     from glimpse_amd import workloads
 
     name, P, N, channels, mode = cfg
@@ -147,6 +154,8 @@ def test_track_equals_the_same_steps(lib, cfg):
                 ctx.step(fr[5], taus[5], images[5], seed=11)
             res.append((ctx.get_particles(), ctx.get_weights(), ctx.get_moments(0, T), ctx.point_status(),
                         ctx.observer_status(), ctx.search_boxes()))
+            ran = {k for k, v in ctx.profile_get().items() if v[1] > 0}
+            assert ("point_step" in ran) == (N != 12000), (how, N, sorted(ran))
     assert (res[0][3] == 0).all()
     for other in (1, 2):
         for k in range(6):

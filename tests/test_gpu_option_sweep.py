@@ -50,8 +50,9 @@ def run_case(cs, math, fused=1):
             ctx.step(i, cs["taus"][i - 1], cs["matching"][i], normals=d["evolve"][i - 1], u=d["u"][i - 1])
             idx.append(ctx.resample_indices())
             variants.append(ctx.last_variant())
+        stages = {k: v[1] for k, v in ctx.profile_get().items() if v[1] > 0}  # stage -> launches
         return dict(idx=np.stack(idx), moments=ctx.get_moments(0, T), status=ctx.point_status(),
-                    obs_status=ctx.observer_status_frames(1, T - 1), variants=variants)
+                    obs_status=ctx.observer_status_frames(1, T - 1), variants=variants, stages=stages)
 
 
 def check_case(seed, math):

@@ -60,7 +60,10 @@ def test_stage_ssd_matches_oracle(lib):
                              (40, 41, 16, 16), (33, 50, 12, 20), (45, 28, 20, 8), (60, 70, 48, 48), (62, 61, 49, 49),
                              (75, 80, 63, 63), (20, 90, 7, 63), (90, 20, 63, 7),
                              # 1 x 1, 2 x 2 and 4 x 4 surfaces
-                             (15, 15, 15, 15), (32, 32, 31, 31), (12, 14, 9, 11)]:
+                             (15, 15, 15, 15), (32, 32, 31, 31), (12, 14, 9, 11),
+                             # a surface above 255 cells a side (286 x 276: 9 x 18 output tiles of 32 x 16) and the widest
+                             # strip a 16-bit workspace holds (1103 x 46)
+                             (290, 300, 15, 15), (60, 1117, 15, 15)]:
         s = rng.standard_normal((hs, ws)).astype(np.float32)
         t = rng.standard_normal((th, tw)).astype(np.float32)
         want = ossd.match_template_sqdiff(s, t)
@@ -95,7 +98,8 @@ def test_stage_resample_bit_exact(lib, golden):
         idx = lib.stage_resample(w, float(g[f"r{i}_u"]))
         np.testing.assert_array_equal(idx, g[f"r{i}_idx"])
     rng = np.random.default_rng(11)
-    for n in [64, 255, 256, 257, 3000, 8192, 8193, 12000]:
+    # (10 977: the first count the fused step leaves to this kernel; 14 950: the last one glh_create takes)
+    for n in [64, 255, 256, 257, 3000, 8192, 8193, 12000, 10977, 14950]:
         for trial in range(3):
             w = np.exp(-rng.random(n) * rng.choice([1.0, 20.0, 200.0])) + 1e-300
             u = rng.random()

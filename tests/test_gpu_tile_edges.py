@@ -177,18 +177,23 @@ def test_template_and_likelihood_stages_for_every_frame_type(lib, seed):
 def test_stage_sample_against_scipy_at_the_sizes_where_the_fit_changes(lib, orders):
     """_lib.stage_sample against scipy.interpolate.RectBivariateSpline itself (the call of Observer.sample_tile,
     observer.py:201-214) on surfaces of 4, 5, 39, 40, 41 and 64 cells a side, square and not -- around the 40 coefficients
-    at which the dense fit gives way to the banded one --, sampled on the first and the last data site, on interior knots
-    (data sites), between the box's edge and the outermost sites, and at random points; atol 5e-12."""
+    at which the dense fit gives way to the banded one --, and of 128, 255, 256 and 300 cells a side and 1100 x 40 (what a
+    wide prior asks of the banded fit: the surfaces of tests/wide_cases.py), sampled on the first and the last data site,
+    on interior knots (data sites), between the box's edge and the outermost sites, and at random points; atol 5e-12.
+    The bowl keeps the depth it has at 64 cells on the larger surfaces, so that the bound means the same there (an SSE of
+    normalised tiles does not grow with the surface)."""
     rng = np.random.default_rng(9)
     kx, ky = orders or (3, 3)
     sides = (4, 5, 39, 40, 41, 64)
     shapes = [(s, s) for s in sides] + [(4, 64), (64, 5), (39, 41), (41, 40), (40, 39), (5, 40)]
+    shapes += [(128, 128), (255, 255), (256, 256), (300, 300), (40, 1100)]
     for ho, wo in shapes:
         if ho < kx + 1 or wo < ky + 1:
             continue
         # an SSE-like surface: a bowl with texture, as float32
         yy, xx = np.mgrid[0:ho, 0:wo]
-        sse = (0.3 + 0.002 * ((xx - 0.4 * wo) ** 2 + (yy - 0.6 * ho) ** 2) + 0.2 * rng.random((ho, wo))).astype(np.float32)
+        curv = 0.002 * min(1.0, (64.0 / max(ho, wo)) ** 2)
+        sse = (0.3 + curv * ((xx - 0.4 * wo) ** 2 + (yy - 0.6 * ho) ** 2) + 0.2 * rng.random((ho, wo))).astype(np.float32)
         box = np.array([100.5, 200.5, 100.5 + wo, 200.5 + ho])
         cu, cv = ospline.cell_centres(box, sse.shape)
         sites = np.array([(cu[0], cv[0]), (cu[-1], cv[-1]), (cu[0], cv[-1]), (cu[-1], cv[0]), (cu[1], cv[2]),
