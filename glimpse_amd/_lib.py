@@ -162,6 +162,7 @@ SIGNATURES = {
     "glh_stage_raster_interpolate": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _D, _D, _D, _D, _P, _P, _P]),
     "glh_stage_project_dem": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "glh_stage_rasterize": (_I, [_I, _P, _I, _P, _I, _I, _P, _P]),
+    "glh_stage_orthorectify": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "glh_stage_gaussian_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_fill_crevasses": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
@@ -1184,6 +1185,43 @@ def stage_rasterize(keys, values, n_pixels, device_id=0, return_times=False):
     check(load().glh_stage_rasterize(device_id, _ptr(keys), len(keys), _ptr(values), values.shape[1], int(n_pixels),
                                      _ptr(out), _ptr(times) if return_times else None))
     return _timed(out, PD_TIMES, times, return_times)
+
+
+def stage_orthorectify(frames, cams, z, x, y, seen=None, seen_of=None, method="linear", device_id=0,
+                       return_kernel_ms=False):
+    """Image.orthorectify over a batch: `frames` (n, h, w, channels) of uint8 / uint16 / float32 / float64, one or three
+    channels, each frame with its own camera `cams` (n, CAM_LEN), resampled onto the DEM `z` (ny, nx) float64 / float32
+    with the cell centres `x` (nx,), `y` (ny,) -> (n, ny, nx, channels), float32 for float32 frames and float64 for every
+    other, NaN where a cell is not seen.  `seen`: None, or (m, ny, nx) masks (the caller's mask and viewshed of a cell)
+    with `seen_of` (n,) naming each frame's (None: the first).  One library call: the DEM and the masks are uploaded once
+    and the frames' copies overlap their neighbours' kernels.  `return_kernel_ms`: also the summed kernel time (HIP
+    events)."""
+    if method not in REPROJECT_METHODS:
+        raise ValueError(f"Method '{method}' is not defined")
+    frames = np.ascontiguousarray(frames)
+    if frames.ndim != 4:
+        raise ValueError("frames must be (n, rows, cols, channels)")
+    if frames.dtype.name not in REPROJECT_DTYPES:
+        raise TypeError(f"frames of dtype {frames.dtype}: uint8, uint16, float32 or float64")
+    bits, is_float = REPROJECT_DTYPES[frames.dtype.name]
+    n, h, w, ch = frames.shape
+    cams = _arr(cams, np.float64, (n, CAM_LEN))
+    z, flag, nx, ny = _float_array(np.asarray(z))
+    x, y = _arr(x, np.float64, (nx,)), _arr(y, np.float64, (ny,))
+    if seen is not None:
+        seen = _arr(seen, np.uint8)
+        if seen.ndim != 3 or seen.shape[1:] != (ny, nx) or len(seen) < 1:
+            raise ValueError(f"seen must be (m, {ny}, {nx}) with m >= 1, got {seen.shape}")
+        if seen_of is not None:
+            seen_of = _arr(seen_of, np.int32, (n,))
+    elif seen_of is not None:
+        raise ValueError("seen_of without seen")
+    out = np.empty((n, ny, nx, ch), dtype=np.float32 if frames.dtype == np.float32 else np.float64)
+    ms = C.c_double(0.0)
+    check(load().glh_stage_orthorectify(device_id, _ptr(frames), bits, is_float, w, h, ch, n, _ptr(cams), _ptr(z), flag, nx,
+                                        ny, _ptr(x), _ptr(y), _ptr(seen), 0 if seen is None else len(seen), _ptr(seen_of),
+                                        REPROJECT_METHODS[method], _ptr(out), C.byref(ms) if return_kernel_ms else None))
+    return (out, ms.value) if return_kernel_ms else out
 
 
 FILTER_F64, FILTER_F32 = F64, F32

@@ -13,6 +13,7 @@
 #include "glh_math.h"
 #include "glh_median.h"
 #include "glh_point_plan.h"  // ssd_twp
+#include "glh_rpj_sample.h"
 
 namespace glh {
 
@@ -2850,20 +2851,7 @@ __global__ __launch_bounds__(BLK) void k_raster_sample(RasterDev r, const double
 // Image.project (image.py:301-361): a frame resampled into another camera at the same position
 // ------------------------------------------------------------------------------------------
 #ifndef GLH_POINT_TU  // (the fused kernel's own translation units carry none of the staged kernels)
-constexpr int RPJ_BX = 32, RPJ_BY = 8;  // one workgroup: 32 x 8 target pixels, a wave = two rows of 32 neighbours
-enum { RPJ_LINEAR = 0, RPJ_NEAREST = 1 };
-
-// find_indices of scipy's RegularGridInterpolator (interpolate/_rgi_cython.pyx) on the grid of pixel centres
-// g[j] = j + 0.5 (np.linspace(0.5, n - 0.5, n): step exactly 1, so g[j] is exact): the interval i with g[i] <= x < g[i + 1],
-// clipped to [0, n - 2]; t = (x - g[i]) / (g[i + 1] - g[i]), whose denominator is exactly 1.  The caller has tested
-// 0.5 <= x <= n - 0.5 (x - 0.5 is exact there).
-GLH_HD int rpj_interval(double x, int n, double& t) {
-  int i = (int)floor(x - 0.5);
-  i = i < 0 ? 0 : (i > n - 2 ? n - 2 : i);
-  t = x - ((double)i + 0.5);
-  return i;
-}
-
+// (RPJ_BX x RPJ_BY, the methods and the sampler itself: glh_rpj_sample.h, shared with k_orthorectify)
 template <typename T>
 GLH_HD T rpj_fill() {  // np.full(..., np.nan, dtype): NaN for float frames; the invalid cast of NaN to an unsigned integer is 0 on x86
   if constexpr (sizeof(T) >= 4) return (T)NAN; else return (T)0;
@@ -2872,13 +2860,9 @@ GLH_HD T rpj_fill() {  // np.full(..., np.nan, dtype): NaN for float frames; the
 // One thread per target pixel, all C channels of it.  Target pixel centre -> ray through the target camera (what
 // k_unproject_points computes with directions = 1) -> uv in the frame's own camera (k_project_points, directions) -> a
 // bilinear or nearest sample of the frame, as RegularGridInterpolator((pv, pu), array[:, :, c], method,
-// bounds_error=False) evaluates it:
-//  * 8 / 16-bit and float64 frames take scipy's two-dimensional float64 path (evaluate_linear_2d): every corner is
-//    value * w_row * w_col, left to right, summed in the order (i, j), (i, j + 1), (i + 1, j), (i + 1, j + 1);
-//  * float32 frames take its general path: value * (w_row * w_col) in float64, summed from 0.0 in the same order; the
-//    float64 result is rounded once to float32 (NumPy's assignment into the float32 result).
-// Unsigned frames: the float64 sample truncated toward zero (NumPy's cast).  A batch is one launch per frame, so that a
-// frame's copies overlap its neighbours' kernels (glh_stage_reproject).
+// bounds_error=False) evaluates it (rpj_sample, glh_rpj_sample.h), converted to the frame's type: a float32 frame's
+// float64 sample is rounded once to float32, an unsigned frame's is truncated toward zero (NumPy's cast).  A batch is one
+// launch per frame, so that a frame's copies overlap its neighbours' kernels (glh_stage_reproject).
 template <typename T, int C>
 __global__ __launch_bounds__(RPJ_BX * RPJ_BY) void k_reproject(const CamDev* __restrict__ src_cam,
                                                                const CamDev* __restrict__ dst_cam,
@@ -2890,41 +2874,9 @@ __global__ __launch_bounds__(RPJ_BX * RPJ_BY) void k_reproject(const CamDev* __r
   unproject(*dst_cam, cam_flags(*dst_cam), (double)col + 0.5, (double)row + 0.5, 1.0, 1, d);
   project_f(*src_cam, cam_flags(*src_cam) | CAM_F_DIRECTIONS, d[0], d[1], d[2], u, v);
   T* o = out + ((size_t)row * dw + col) * C;
-  // (NaN uv -- behind the camera -- fail every comparison: fill)
-  if (!(u >= 0.5 && u <= (double)sw - 0.5 && v >= 0.5 && v <= (double)sh - 0.5)) {
+  if (!rpj_sample<T, C, T>(src, sw, sh, u, v, method, o)) {
 #pragma unroll
     for (int c = 0; c < C; ++c) o[c] = rpj_fill<T>();
-    return;
-  }
-  double tu, tv;
-  const int iu = rpj_interval(u, sw, tu), iv = rpj_interval(v, sh, tv);
-  if (method == RPJ_NEAREST) {
-    const T* s = src + ((size_t)(tv <= 0.5 ? iv : iv + 1) * sw + (tu <= 0.5 ? iu : iu + 1)) * C;
-#pragma unroll
-    for (int c = 0; c < C; ++c) o[c] = s[c];
-    return;
-  }
-  const T* s0 = src + ((size_t)iv * sw + iu) * C;
-  const T* s1 = s0 + (size_t)sw * C;
-  const double wv0 = 1.0 - tv, wu0 = 1.0 - tu;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const double a00 = (double)s0[c], a01 = (double)s0[C + c], a10 = (double)s1[c], a11 = (double)s1[C + c];
-    double r;
-    if constexpr (sizeof(T) == 4) {
-      r = 0.0;
-      r += a00 * (wv0 * wu0);
-      r += a01 * (wv0 * tu);
-      r += a10 * (tv * wu0);
-      r += a11 * (tv * tu);
-    } else {
-      r = 0.0;
-      r += a00 * wv0 * wu0;
-      r += a01 * wv0 * tu;
-      r += a10 * tv * wu0;
-      r += a11 * tv * tu;
-    }
-    o[c] = (T)r;
   }
 }
 #endif

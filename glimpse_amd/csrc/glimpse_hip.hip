@@ -25,9 +25,11 @@
 #include "glh_match.h"
 #include "glh_sift.h"
 #include "glh_orient.h"
+#include "glh_ortho.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
+#include "glh_frame_ring.h"
 #include "glh_clahe.h"
 #include "glh_terrain.h"
 #include "glh_stage.h"
@@ -2376,34 +2378,9 @@ extern "C" int glh_stage_unproject(int dev, const double* cam, const double* uv,
   return dx.down(xyz, (size_t)n * 3 * sizeof(double));
 }
 
-// Image.project over a batch of frames.  Three slots, each a pinned input and output staging buffer and a device source
-// and target frame; three streams (upload, kernel, download) chained by events, so that frame k + 1's upload and frame
-// k - 1's download overlap frame k's kernel -- the staging ring of glh_observer_upload_frame_async, in both directions.
+// Image.project over a batch of frames, through the staging ring of glh_frame_ring.h: three slots and three streams, so
+// that frame k + 1's upload and frame k - 1's download overlap frame k's kernel.
 namespace {
-struct ReprojectRing {
-  static constexpr int NSLOT = 3;
-  hipStream_t up = nullptr, run = nullptr, down = nullptr;
-  hipEvent_t uploaded[NSLOT] = {}, computed[NSLOT] = {}, downloaded[NSLOT] = {};
-  std::vector<hipEvent_t> k0, k1;  // around every kernel (timing)
-  uint8_t *pin_in[NSLOT] = {}, *pin_out[NSLOT] = {}, *dev_in[NSLOT] = {}, *dev_out[NSLOT] = {};
-  ~ReprojectRing() {
-    for (hipStream_t s : {up, run, down})
-      if (s) (void)hipStreamSynchronize(s);
-    for (int k = 0; k < NSLOT; ++k) {
-      for (hipEvent_t e : {uploaded[k], computed[k], downloaded[k]})
-        if (e) (void)hipEventDestroy(e);
-      if (pin_in[k]) (void)hipHostFree(pin_in[k]);
-      if (pin_out[k]) (void)hipHostFree(pin_out[k]);
-      if (dev_in[k]) (void)hipFree(dev_in[k]);
-      if (dev_out[k]) (void)hipFree(dev_out[k]);
-    }
-    for (hipEvent_t e : k0) (void)hipEventDestroy(e);
-    for (hipEvent_t e : k1) (void)hipEventDestroy(e);
-    for (hipStream_t s : {up, run, down})
-      if (s) (void)hipStreamDestroy(s);
-  }
-};
-
 template <typename T>
 void launch_reproject(hipStream_t s, int channels, const CamDev* src_cam, const CamDev* dst_cam, const void* src, int sw,
                       int sh, int dw, int dh, int method, void* out) {
@@ -2451,45 +2428,10 @@ extern "C" int glh_stage_reproject(int dev, const void* frames, int depth_bits, 
   const size_t in_bytes = (size_t)width * height * px, out_bytes = (size_t)dst_width * dst_height * px;
   DevBuf dcams;
   CHK(dcams.up(cams.data(), cams.size() * sizeof(CamDev)));
-  ReprojectRing r;
-  const int nslot = n_frames < ReprojectRing::NSLOT ? n_frames : ReprojectRing::NSLOT;
-  HIPCHK(hipStreamCreateWithFlags(&r.up, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&r.run, hipStreamNonBlocking));
-  HIPCHK(hipStreamCreateWithFlags(&r.down, hipStreamNonBlocking));
-  for (int k = 0; k < nslot; ++k) {
-    HIPCHK(hipEventCreateWithFlags(&r.uploaded[k], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&r.computed[k], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&r.downloaded[k], hipEventDisableTiming));
-    HIPCHK(hipHostMalloc((void**)&r.pin_in[k], in_bytes, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc((void**)&r.pin_out[k], out_bytes, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&r.dev_in[k], in_bytes));
-    HIPCHK(hipMalloc((void**)&r.dev_out[k], out_bytes));
-  }
-  if (kernel_ms) {
-    r.k0.resize(n_frames, nullptr);
-    r.k1.resize(n_frames, nullptr);
-    for (int i = 0; i < n_frames; ++i) {
-      HIPCHK(hipEventCreate(&r.k0[i]));
-      HIPCHK(hipEventCreate(&r.k1[i]));
-    }
-  }
-  const uint8_t* in = static_cast<const uint8_t*>(frames);
-  uint8_t* res = static_cast<uint8_t*>(out);
+  FrameRing r;
+  CHK(r.open(n_frames, in_bytes, out_bytes, kernel_ms != nullptr));
   const CamDev* dc = dcams.as<CamDev>();
-  auto collect = [&](int frame) {  // the finished frame of this slot, from its pinned buffer to the caller's array
-    const int k = frame % nslot;
-    HIPCHK(hipEventSynchronize(r.downloaded[k]));
-    memcpy(res + (size_t)frame * out_bytes, r.pin_out[k], out_bytes);
-    return (int)GLH_OK;
-  };
-  for (int i = 0; i < n_frames; ++i) {
-    const int k = i % nslot;
-    if (i >= nslot) CHK(collect(i - nslot));  // (its download is over, so its kernel and upload are: the slot is free)
-    memcpy(r.pin_in[k], in + (size_t)i * in_bytes, in_bytes);
-    HIPCHK(hipMemcpyAsync(r.dev_in[k], r.pin_in[k], in_bytes, hipMemcpyHostToDevice, r.up));
-    HIPCHK(hipEventRecord(r.uploaded[k], r.up));
-    HIPCHK(hipStreamWaitEvent(r.run, r.uploaded[k], 0));
-    if (kernel_ms) HIPCHK(hipEventRecord(r.k0[i], r.run));
+  auto launch = [&](int i, int k) {
     if (depth_bits == 8)
       launch_reproject<uint8_t>(r.run, channels, dc + i, dc + n_frames, r.dev_in[k], width, height, dst_width, dst_height,
                                 method, r.dev_out[k]);
@@ -2502,24 +2444,8 @@ extern "C" int glh_stage_reproject(int dev, const void* frames, int depth_bits, 
     else
       launch_reproject<double>(r.run, channels, dc + i, dc + n_frames, r.dev_in[k], width, height, dst_width, dst_height,
                                method, r.dev_out[k]);
-    HIPCHK(hipGetLastError());
-    if (kernel_ms) HIPCHK(hipEventRecord(r.k1[i], r.run));
-    HIPCHK(hipEventRecord(r.computed[k], r.run));
-    HIPCHK(hipStreamWaitEvent(r.down, r.computed[k], 0));
-    HIPCHK(hipMemcpyAsync(r.pin_out[k], r.dev_out[k], out_bytes, hipMemcpyDeviceToHost, r.down));
-    HIPCHK(hipEventRecord(r.downloaded[k], r.down));
-  }
-  for (int i = n_frames > nslot ? n_frames - nslot : 0; i < n_frames; ++i) CHK(collect(i));
-  if (kernel_ms) {
-    double total = 0.0;
-    for (int i = 0; i < n_frames; ++i) {
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, r.k0[i], r.k1[i]));
-      total += ms;
-    }
-    *kernel_ms = total;
-  }
-  return GLH_OK;
+  };
+  return r.process(frames, n_frames, out, launch, kernel_ms);
 }
 
 static int check_box(const int32_t* box, int width, int height) {
@@ -3395,6 +3321,41 @@ extern "C" int glh_stage_rasterize(int dev, const int32_t* keys, int n, const do
       return fail(GLH_E_INVALID, "rasterize: key %d of point %d outside [0, %d)", keys[i], i, n_pixels);
   const RasterizeJob job{dev, keys, n, values, layers, n_pixels, out, times_ms};
   return rasterize_run(job);
+}
+
+// Image.orthorectify: the arguments are checked here, before a device is touched; the kernel and the launches are
+// glh_ortho.hip's.
+extern "C" int glh_stage_orthorectify(int dev, const void* frames, int depth_bits, int is_float, int width, int height,
+                                      int channels, int n_frames, const double* cams, const void* z, int z_dtype, int nx,
+                                      int ny, const double* x, const double* y, const uint8_t* seen, int n_seen,
+                                      const int32_t* seen_of, int method, void* out, double* kernel_ms) {
+  if (!frames || !cams || !z || !x || !y || !out || n_frames < 1) return fail(GLH_E_INVALID, "orthorectify: bad argument");
+  if (!((!is_float && (depth_bits == 8 || depth_bits == 16)) || (is_float && (depth_bits == 32 || depth_bits == 64))))
+    return fail(GLH_E_UNSUPPORTED, "orthorectify: frames of %d bits (%s): uint8, uint16, float32 or float64", depth_bits,
+                is_float ? "float" : "integer");
+  if (channels != 1 && channels != 3) return fail(GLH_E_UNSUPPORTED, "orthorectify: 1 or 3 channels");
+  if (method != RPJ_LINEAR && method != RPJ_NEAREST)
+    return fail(GLH_E_UNSUPPORTED, "orthorectify: method %d: 0 linear, 1 nearest", method);
+  // (the interpolator needs two grid points on an axis; the pixel index arithmetic is 32-bit)
+  if (width < 2 || height < 2 || width > 32768 || height > 32768)
+    return fail(GLH_E_INVALID, "orthorectify: a frame of %d x %d: at least 2 x 2, at most 32768 on a side", width, height);
+  CHK(check_grid("orthorectify", nx, ny, 1));
+  CHK(check_float_dtype("orthorectify", "z_dtype", z_dtype));
+  if (seen ? n_seen < 1 : seen_of != nullptr)
+    return fail(GLH_E_INVALID, "orthorectify: %d masks %s", n_seen, seen ? "given" : "chosen from none");
+  std::vector<CamDev> cd(n_frames);
+  for (int i = 0; i < n_frames; ++i) {
+    const double* v = cams + (size_t)i * GLH_CAM_LEN;
+    if (v[23] != 0.0) return fail(GLH_E_UNSUPPORTED, "orthorectify: frame %d is a raster grid, not a camera", i);
+    if ((int)v[6] != width || (int)v[7] != height)
+      return fail(GLH_E_INVALID, "orthorectify: camera %d imgsz (%g, %g) != frame size (%d, %d)", i, v[6], v[7], width, height);
+    if (seen && seen_of && (seen_of[i] < 0 || seen_of[i] >= n_seen))
+      return fail(GLH_E_INVALID, "orthorectify: frame %d takes mask %d of %d", i, seen_of[i], n_seen);
+    expand_camera(v, &cd[i]);
+  }
+  const OrthoJob job{dev, frames, depth_bits, is_float, width, height, channels, n_frames, cd.data(), z, z_dtype == GLH_PD_F32,
+                     nx, ny, x, y, seen, n_seen, seen_of, method, out, kernel_ms};
+  return orthorectify_run(job);
 }
 
 // helpers.maximum_filter, helpers.gaussian_filter (helpers.py:347-430) and Raster.fill_crevasses (raster.py:1266-1291): the

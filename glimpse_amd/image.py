@@ -7,8 +7,9 @@ time-lapse camera gives the same samples).  A read at another size than the file
 is GDAL's default RasterIO resampling -- nearest neighbour, destination pixel i from source column
 floor((i + 0.5) * src / dst) -- on the decoded array; GDAL itself is absent here, and for JPEG files it would first pick
 one of the decoder's built-in 1/2, 1/4, 1/8 overviews, which this does not reproduce (parity unpinned for resized
-reads).  `project` (image.py:301-361) resamples the frame into another camera on the GPU.  EXIF parsing, `write` and
-`plot` are out of scope.
+reads).  `project` (image.py:301-361) resamples the frame into another camera on the GPU; `orthorectify`, which the reference
+leaves to its users, resamples it onto a DEM's grid there.  EXIF parsing, `write` and `plot` are out of scope (SURVEY.md
+section 2).
 """
 import numpy as np
 
@@ -141,3 +142,65 @@ class Image:
         self._check_project(cam, method)
         frame = self._project_frame()
         return _lib.stage_reproject(frame[None], self.cam.vector24[None], cam.vector24, cam.imgsz, method)[0]
+
+    def _check_orthorectify(self, dem, viewshed, mask, method, name="The image"):
+        """The argument checks of `orthorectify`, made before anything touches the library."""
+        if method not in ("linear", "nearest"):
+            raise ValueError(f"Method '{method}' is not defined")  # (scipy's RegularGridInterpolator says the same)
+        if np.ndim(dem.array) != 2:
+            raise ValueError(f"a DEM is two-dimensional, got {np.shape(dem.array)}")
+        if mask is not None and np.shape(mask) != np.shape(dem.array):
+            raise ValueError("mask does not have the same 2-d shape as dem")
+        if viewshed is not None and not isinstance(viewshed, (bool, np.bool_)) and np.shape(viewshed) != np.shape(dem.array):
+            raise ValueError("viewshed does not have the same 2-d shape as dem")
+        if np.asarray(self.cam.vector24)[23] != 0:
+            raise ValueError(f"{name}'s camera is a raster grid, which has no position to see from")
+
+    def orthorectify(self, dem, viewshed=None, mask=None, method="linear"):
+        """This image on the grid of `dem` (a Raster with a 2-D array of elevations): the orthophoto of one oblique frame,
+        the inverse of `Camera.project_dem`.  The reference has no single function for it; the rule (INPUTS.md,
+        "Orthorectification: the rule") is composed of its calls.  For every cell (r, c): xyz = (dem.x[c], dem.y[r],
+        dem.array[r, c]), the cell's centre in whichever direction the raster's axes run; uv = `cam.xyz_to_uv(xyz)`; the
+        cell is seen when its elevation is not NaN, `cam.inframe(uv)`, `mask[r, c]` (where a mask is given) and
+        `viewshed[r, c]` (where one is given); a seen cell's value is RegularGridInterpolator over the pixel centres,
+        `method` = "linear" or "nearest", bounds_error=False, at uv, channel by channel -- the interpolator of `project`,
+        so a seen cell within half a pixel of the frame's edge is NaN; every other cell is NaN.  `viewshed`: None (no
+        visibility test), a boolean array of the DEM's shape, or True for `dem.viewshed(cam.xyz, correction=
+        cam.correction)`.  Returns (dem rows, dem columns, channels), float32 for float32 pixels (the interpolator's
+        float64 rounded once, as `project` returns them) and float64 for uint8, uint16 and float64 pixels; nothing is cast back to integers, so NaN always means
+        "not seen".  One kernel on the GPU (`glh_stage_orthorectify`); `Observer.orthorectify` is the batch form."""
+        self._check_orthorectify(dem, viewshed, mask, method)
+        return orthorectify([self], dem, viewshed, mask, method)[0]
+
+
+def orthorectify(images, dem, viewshed, mask, method):
+    """`Image.orthorectify` of `images` (checked by their `_check_orthorectify`, one pixel shape and dtype) as one array
+    (images, dem rows, dem columns, channels), through one library call.  The caller's mask and the viewshed are combined
+    here, one boolean per cell; with `viewshed=True` one viewshed is computed per distinct camera position (and
+    elevation correction) among the images."""
+    frames = [img._project_frame() for img in images]
+    if len({(f.shape, f.dtype) for f in frames}) != 1:
+        raise ValueError("Images differ in shape or dtype: " + str(sorted({(f.shape, str(f.dtype)) for f in frames})))
+    array = np.asarray(dem.array)
+    z = array if array.dtype == np.float32 else np.asarray(array, dtype=np.float64)  # (what xyz_to_uv makes of a cell)
+    allowed = None if mask is None else np.asarray(mask, dtype=bool)
+    seen = seen_of = None
+    if isinstance(viewshed, (bool, np.bool_)):
+        viewshed = True if viewshed else None  # (False: no visibility test either)
+    if viewshed is True:
+        masks, seen_of = {}, []
+        for img in images:
+            corr = img.cam.correction
+            key = (tuple(img.cam.xyz), tuple(sorted(corr.items())) if isinstance(corr, dict) else bool(corr))
+            if key not in masks:
+                visible = dem.viewshed(img.cam.xyz, correction=corr)
+                masks[key] = (len(masks), visible if allowed is None else visible & allowed)
+            seen_of.append(masks[key][0])
+        seen = np.stack([m for _, m in masks.values()])
+    elif viewshed is not None:
+        visible = np.asarray(viewshed, dtype=bool)
+        seen = (visible if allowed is None else visible & allowed)[None]
+    elif allowed is not None:
+        seen = allowed[None]
+    return _lib.stage_orthorectify(frames[0][None] if len(frames) == 1 else np.stack(frames),
+                                   np.stack([img.cam.vector24 for img in images]), z, dem.x, dem.y, seen, seen_of, method)

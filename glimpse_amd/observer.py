@@ -5,6 +5,7 @@ import datetime
 import numpy as np
 
 from . import _lib
+from .image import orthorectify
 from .timeutil import select_datetimes
 
 
@@ -127,6 +128,21 @@ class Observer:
             raise ValueError("Images differ in shape or dtype: " + str(sorted({(f.shape, str(f.dtype)) for f in frames})))
         return _lib.stage_reproject(np.stack(frames), np.stack([img.cam.vector24 for img in images]), cam.vector24,
                                     cam.imgsz, method)
+
+    def orthorectify(self, dem, index=slice(None), viewshed=None, mask=None, method="linear"):
+        """`Image.orthorectify(dem, viewshed, mask, method)` of the images `index` selects (a slice, or a list of
+        positions), each through its own camera, as one array (frames, dem rows, dem columns, channels): a georeferenced
+        image sequence on the DEM's grid.  The frames go through one library call -- the DEM, its coordinates and the mask
+        are uploaded once, and a frame's copies overlap its neighbours' kernels -- and every frame equals the per-image
+        call bit for bit.  With `viewshed=True` one viewshed is computed per distinct camera position among the chosen
+        images, normally one.  The images must share one pixel shape and dtype."""
+        images = self._pick(index)
+        if not images:
+            raise ValueError("No images selected")
+        positions = np.arange(len(self.images))[index]
+        for i, img in zip(positions, images):
+            img._check_orthorectify(dem, viewshed, mask, method, name=f"Image {i}")
+        return orthorectify(images, dem, viewshed, mask, method)
 
     def subset(self, **kwargs):
         """observer.py:455-464: a new Observer over the images select_datetimes(**kwargs) keeps."""

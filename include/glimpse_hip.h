@@ -577,6 +577,23 @@ int glh_stage_project_dem(int device_id, const double* cam, const void* z, int z
  * n_pixels < 1, a key outside [0, n_pixels).                                                                          */
 int glh_stage_rasterize(int device_id, const int32_t* keys, int n, const double* values, int layers, int n_pixels,
                         double* out, double* times_ms);
+/* Image.orthorectify (the inverse of Camera.project_dem; the reference has no single function for it -- the rule is
+ * INPUTS.md, "Orthorectification: the rule"): n_frames >= 1 frames of one shape [n_frames][height][width][channels]
+ * (depth_bits / is_float and channels as for glh_stage_reproject), each with its own camera cams [n_frames][GLH_CAM_LEN],
+ * resampled onto the grid of the DEM z [ny][nx] (z_dtype GLH_PD_F64 / GLH_PD_F32) whose cell centres are x [nx] by
+ * y [ny], in whichever direction they run: out [n_frames][ny][nx][channels], float32 for float32 frames and float64 for
+ * every other.  A cell's value is the frame at Camera.xyz_to_uv((x, y, z)), method 0 = linear, 1 = nearest, on the grid
+ * of the pixel centres as scipy.interpolate.RegularGridInterpolator(bounds_error=False) evaluates them; NaN where the
+ * elevation is NaN, the cell is behind the camera or lands off the pixel centres, or its mask is 0.  seen (or NULL:
+ * every cell) [n_seen][ny][nx]: the caller's mask and viewshed of a cell; seen_of [n_frames] (or NULL: the first) names
+ * each frame's.  The DEM and the masks are uploaded once; frames travel as in glh_stage_reproject, one kernel each.
+ * kernel_ms (or NULL): the sum of the kernels' durations, from events.  Before a device is touched, GLH_E_UNSUPPORTED: a
+ * raster grid as camera, another type, channel count or method; GLH_E_INVALID: null pointers, a camera imgsz that
+ * differs from the frame size, a frame below 2 x 2 or a grid of 2^31 cells, seen_of outside [0, n_seen).               */
+int glh_stage_orthorectify(int device_id, const void* frames, int depth_bits, int is_float, int width, int height,
+                           int channels, int n_frames, const double* cams, const void* z, int z_dtype, int nx, int ny,
+                           const double* x, const double* y, const uint8_t* seen, int n_seen, const int32_t* seen_of,
+                           int method, void* out, double* kernel_ms);
 /* helpers.maximum_filter(a, mask, fill, size, mode) (helpers.py:390-430; scipy.ndimage.maximum_filter) of a [ny][nx],
  * float64 (dtype GLH_FILTER_F64) or float32 (GLH_FILTER_F32), into out [ny][nx] of the same dtype.  The window is size_y
  * rows x size_x columns, each 1 .. 31 (a tile and its halo live in LDS), reaching size / 2 cells back and size - 1 - size / 2
