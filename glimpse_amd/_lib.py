@@ -163,6 +163,8 @@ SIGNATURES = {
     "glh_stage_project_dem": (_I, [_I, _P, _P, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
     "glh_stage_rasterize": (_I, [_I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_orthorectify": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
+    "glh_stage_raycast": (_I, [_I, _P, _I, _I, _I, _P, _P, _D, _D, _I, _P, _P, _I, _P, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P,
+                               _P]),
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "glh_stage_gaussian_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_fill_crevasses": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
@@ -1224,8 +1226,65 @@ def stage_orthorectify(frames, cams, z, x, y, seen=None, seen_of=None, method="l
     return (out, ms.value) if return_kernel_ms else out
 
 
+RAYCAST_TIMES = ("upload_ms", "pyramid_ms", "march_ms", "download_ms")
+RAYCAST_DIRECTIONS, RAYCAST_UV, RAYCAST_GRID = 0, 1, 2
+RAYCAST_STATUS = ("hit", "misses the domain", "enters below the surface", "leaves without a hit", "invalid")
+
+
+def stage_raycast(z, x, y, d, origins=None, directions=None, cam=None, uv=None, step=None, correction=None, block=16,
+                  device_id=0, return_times=False):
+    """Rays cast onto the bilinear surface between the cell centres `x` (nx,), `y` (ny,) of the DEM `z` (ny, nx) float64 /
+    float32, `d` its signed cell sizes (INPUTS.md, "Ray casting: the rule").  The rays are `directions` (n, 3) from
+    `origins` (3,) or (n, 3); or the image coordinates `uv` (n, 2) of the camera `cam` (CAM_LEN,), unprojected on the
+    device; or, with `step`, the camera's pixel centres step / 2 + k step, made on the device in row-major order.
+    `correction`: None / False, True or the arguments of helpers.elevation_corrections.  `block`: 0 marches every patch,
+    a power of two lets rays skip blocks of that many patches a side (the results do not depend on it).  Returns
+    (t (n,), xyz (n, 3), patch (n,) int32, status (n,) uint8 indexing RAYCAST_STATUS); `return_times`: also a dict of
+    RAYCAST_TIMES."""
+    on, radius, refraction = viewshed_correction(correction)
+    z, flag, nx, ny = _float_array(np.asarray(z))
+    x, y = _arr(x, np.float64, (nx,)), _arr(y, np.float64, (ny,))
+    block = int(block)
+    if block < 0 or block & (block - 1):
+        raise ValueError(f"block is 0 or a power of two, got {block}")
+    if (directions is not None) + (uv is not None) + (step is not None) != 1:
+        raise ValueError("one of directions, uv and step names the rays")
+    rays = cam24 = None
+    n_origins = 1
+    if directions is not None:
+        mode, rays = RAYCAST_DIRECTIONS, _arr(directions, np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 3 or len(rays) < 1:
+            raise ValueError(f"directions must be (n, 3) with n >= 1, got {rays.shape}")
+        origins = _arr(np.atleast_2d(np.asarray(origins, dtype=np.float64)), np.float64)
+        if origins.shape not in ((1, 3), (len(rays), 3)):
+            raise ValueError(f"origins must be (3,) or ({len(rays)}, 3), got {origins.shape}")
+        n, n_origins = len(rays), len(origins)
+    else:
+        cam24, origins = _arr(cam, np.float64, (CAM_LEN,)), None
+        if uv is not None:
+            mode, rays = RAYCAST_UV, _arr(uv, np.float64)
+            if rays.ndim != 2 or rays.shape[1] != 2 or len(rays) < 1:
+                raise ValueError(f"uv must be (n, 2) with n >= 1, got {rays.shape}")
+            n = len(rays)
+        else:
+            mode, step = RAYCAST_GRID, int(step)
+            if step < 1:
+                raise ValueError(f"step must be at least 1, got {step}")
+            n = (int(cam24[6]) // step) * (int(cam24[7]) // step)
+            if n < 1:
+                raise ValueError(f"step {step} leaves no pixel of an image of {int(cam24[6])} x {int(cam24[7])}")
+    t, xyz = np.empty(n), np.empty((n, 3))
+    patch, status = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.uint8)
+    times = np.zeros(len(RAYCAST_TIMES))
+    check(load().glh_stage_raycast(device_id, _ptr(z), flag, nx, ny, _ptr(x), _ptr(y), float(d[0]), float(d[1]), mode,
+                                   _ptr(cam24), _ptr(origins), n_origins, _ptr(rays), n, step or 0, int(on), radius,
+                                   refraction, block, _ptr(t), _ptr(xyz), _ptr(patch), _ptr(status),
+                                   _ptr(times) if return_times else None))
+    return _timed((t, xyz, patch, status), RAYCAST_TIMES, times, return_times, extend=True)
+
+
 FILTER_F64, FILTER_F32 = F64, F32
-FILTER_TIMES = ("upload_ms", "max_ms", "gauss0_ms", "gauss1_ms", "download_ms")
+FILTER_TIMES =("upload_ms", "max_ms", "gauss0_ms", "gauss1_ms", "download_ms")
 
 
 def _filter_array(a, mask):

@@ -8,7 +8,8 @@ and the Oulu undistortion, :1198-1337) runs on the GPU as well (`glh_stage_unpro
 the per-frame path.  Of the rendering methods, `project_dem` (camera.py:967-1129: the image and the depth map a
 camera records of a DEM) and `rasterize` (:858-883: points to a mean image) are served, on the GPU
 (`glh_stage_project_dem`, `glh_stage_rasterize`); `project_dem` without the per-tile rescaling (`scale_limits` other than
-(1, 1), which fails in the reference itself).  `Rprime` and the camera-coordinate halves of the projection (`_uv_to_xy`
+(1, 1), which fails in the reference itself).  `uv_to_dem` and `xyz_map` go the other way, from pixels to the terrain
+they see (`glh_stage_raycast`: the reference has the parts and leaves the ray cast to its users).  `Rprime` and the camera-coordinate halves of the projection (`_uv_to_xy`
 on the GPU, `_xy_to_uv`, `_xy_to_xyz`, `_xyz_to_xy` on the host) and `edges` serve `glimpse_amd.optimize`.
 """
 import numpy as np
@@ -275,6 +276,46 @@ class Camera:
         uv = np.atleast_2d(np.asarray(uv, dtype=float))
         d = None if (isinstance(depth, (int, float)) and depth == 1) else depth
         return _lib.stage_unproject(self.vector24, uv, depth=d, directions=directions)
+
+    # ---- pixels to terrain (GPU): the reference leaves the ray cast to its users
+    def uv_to_dem(self, uv, dem, return_depth=False, return_status=False, block=16):
+        """The world points the image coordinates `uv` (n, 2) see on `dem` (a Raster with a 2-D array of elevations):
+        xyz (n, 3), NaN where a pixel's ray meets no terrain.  The ray of a pixel is `xyz + t uv_to_xyz(uv,
+        directions=True)`, unprojected on the device, so t -- returned beside xyz with `return_depth` -- is the depth
+        along the optical axis, the unit of `xyz_to_uv(return_depth=True)` and `project_dem(return_depth=True)`.  The
+        surface, the traversal and the hit are `Raster.intersect_rays`' (INPUTS.md, "Ray casting: the rule"); the
+        elevation correction is this camera's own.  Without one, `xyz_to_uv` of a hit returns its pixel.  With one, xyz
+        is the point of the ray, on the apparent surface: the terrain under it differs by
+        helpers.elevation_corrections of its squared horizontal distance, and it is that terrain point `xyz_to_uv`
+        projects back to the pixel.  `return_status`: also, per ray, an index into `_lib.RAYCAST_STATUS`.  One thread per
+        ray on the GPU (`glh_stage_raycast`)."""
+        uv = np.atleast_2d(np.asarray(uv, dtype=float))
+        if uv.ndim != 2 or uv.shape[1] != 2:
+            raise ValueError(f"uv must be (n, 2), got {uv.shape}")
+        if len(uv) == 0:
+            t, xyz, status = np.empty(0), np.empty((0, 3)), np.empty(0, dtype=np.uint8)
+        else:
+            t, xyz, _, status = dem._cast_rays(self.correction, block, cam=self.vector24, uv=uv)
+        result = (xyz,) + ((t,) if return_depth else ()) + ((status,) if return_status else ())
+        return result[0] if len(result) == 1 else result
+
+    def xyz_map(self, dem, step=1, return_depth=False, block=16):
+        """The world point every pixel sees on `dem`: (rows, cols, 3) for the pixel centres (step / 2 + c step,
+        step / 2 + r step), c < imgsz[0] // step, r < imgsz[1] // step, NaN where a pixel sees no terrain; with
+        `return_depth` also the depth map (rows, cols) along the optical axis.  `uv_to_dem` of those pixel centres, which
+        are made on the device: nothing but the DEM is uploaded, and a wave takes an 8 x 8 block of pixels, whose rays
+        cross neighbouring patches."""
+        if isinstance(step, bool) or int(step) != step or step < 1:
+            raise ValueError(f"step must be a positive integer, got {step}")
+        step = int(step)
+        cols, rows = (int(v) // step for v in self.imgsz)
+        if cols < 1 or rows < 1:
+            raise ValueError(f"step {step} leaves no pixel of an image of {tuple(int(v) for v in self.imgsz)}")
+        if cols * rows >= 2 ** 31:
+            raise NotImplementedError(f"{cols} x {rows} pixels: fewer than 2^31 rays are served")
+        t, xyz, _, _ = dem._cast_rays(self.correction, block, cam=self.vector24, step=step)
+        xyz = xyz.reshape(rows, cols, 3)
+        return (xyz, t.reshape(rows, cols)) if return_depth else xyz
 
     # ---- the halves of the projection either side of the camera coordinates (camera.py:1138-1196, :1435-1519)
     def _distort(self, xy):

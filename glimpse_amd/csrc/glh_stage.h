@@ -1,5 +1,5 @@
 // glh_stage.h -- the host scaffold of a device stage: what glimpse_hip.hip (the C ABI) and the stage files
-// (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_ortho.hip, glh_filters.hip, glh_terrain.hip, glh_orient.hip, glh_calib.hip, glh_match.hip, glh_sift.hip, glh_clahe.hip) share to
+// (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_ortho.hip, glh_raycast.hip, glh_filters.hip, glh_terrain.hip, glh_orient.hip, glh_calib.hip, glh_match.hip, glh_sift.hip, glh_clahe.hip) share to
 // report an error, to own device memory and to time their phases.  The four handle-based objects (glh_orient, glh_calib,
 // glh_match, glh_sift) also share what a handle is made of: a buffer that grows (GrowBuf), the device and the stream
 // (DeviceObject) and how a handle comes and goes (create_object, destroy_object).  The plain C++ of a staging buffer is

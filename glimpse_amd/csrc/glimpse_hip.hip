@@ -26,6 +26,7 @@
 #include "glh_sift.h"
 #include "glh_orient.h"
 #include "glh_ortho.h"
+#include "glh_raycast.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
@@ -3356,6 +3357,64 @@ extern "C" int glh_stage_orthorectify(int dev, const void* frames, int depth_bit
   const OrthoJob job{dev, frames, depth_bits, is_float, width, height, channels, n_frames, cd.data(), z, z_dtype == GLH_PD_F32,
                      nx, ny, x, y, seen, n_seen, seen_of, method, out, kernel_ms};
   return orthorectify_run(job);
+}
+
+// Raster.intersect_rays, Camera.uv_to_dem and Camera.xyz_map: the arguments are checked here, before a device is touched;
+// the kernels and the launches are glh_raycast.hip's.
+static int check_raycast_axis(const char* name, const double* g, int n, double d) {
+  for (int k = 0; k < n; ++k) {
+    if (!std::isfinite(g[k])) return fail(GLH_E_INVALID, "raycast: %s[%d] is not finite", name, k);
+    if (!(std::fabs(g[k] - (g[0] + (double)k * d)) < 0.25 * std::fabs(d)))
+      return fail(GLH_E_UNSUPPORTED, "raycast: %s[%d] = %g is not on the uniform grid %g + k * %g", name, k, g[k], g[0], d);
+  }
+  return GLH_OK;
+}
+
+extern "C" int glh_stage_raycast(int dev, const void* z, int z_dtype, int nx, int ny, const double* x, const double* y,
+                                 double d0, double d1, int mode, const double* cam, const double* origins, int n_origins,
+                                 const double* rays, int n, int step, int correction, double radius, double refraction,
+                                 int block, double* t, double* xyz, int32_t* patch, uint8_t* status, double* times_ms) {
+  if (!z || !x || !y || !t || !xyz || !patch || !status) return fail(GLH_E_INVALID, "raycast: null argument");
+  if (nx < 1 || ny < 1 || n < 1) return fail(GLH_E_INVALID, "raycast: %d x %d cells, %d rays: at least one of each", nx, ny, n);
+  if (mode != GLH_RAYCAST_DIRECTIONS && mode != GLH_RAYCAST_UV && mode != GLH_RAYCAST_GRID)
+    return fail(GLH_E_UNSUPPORTED, "raycast: mode %d: 0 directions, 1 uv, 2 pixel grid", mode);
+  if (mode == GLH_RAYCAST_DIRECTIONS ? (!origins || !rays) : (!cam || (mode == GLH_RAYCAST_UV && !rays)))
+    return fail(GLH_E_INVALID, "raycast: null argument for mode %d", mode);
+  if (mode == GLH_RAYCAST_DIRECTIONS && n_origins != 1 && n_origins != n)
+    return fail(GLH_E_INVALID, "raycast: %d origins for %d rays: one, or one each", n_origins, n);
+  if (nx < 2 || ny < 2)
+    return fail(GLH_E_UNSUPPORTED, "raycast: a DEM of %d x %d cells has no patch between cell centres", nx, ny);
+  if ((int64_t)nx * ny >= ((int64_t)1 << 31))
+    return fail(GLH_E_UNSUPPORTED, "raycast: %d x %d cells: fewer than 2^31 are served (32-bit cell indices)", nx, ny);
+  if (block < 0 || block > 32768 || (block & (block - 1)))
+    return fail(GLH_E_UNSUPPORTED, "raycast: block %d: 0, or a power of two up to 32768", block);
+  CHK(check_float_dtype("raycast", "z_dtype", z_dtype));
+  if (!(std::isfinite(d0) && std::isfinite(d1) && d0 != 0.0 && d1 != 0.0))
+    return fail(GLH_E_INVALID, "raycast: cell size (%g, %g)", d0, d1);
+  CHK(check_raycast_axis("x", x, nx, d0));
+  CHK(check_raycast_axis("y", y, ny, d1));
+  CHK(check_correction("raycast", correction, radius, refraction));
+  CamDev cd;
+  int cols = 0, rows = 0;
+  if (mode != GLH_RAYCAST_DIRECTIONS) {
+    if (cam[23] != 0.0) return fail(GLH_E_UNSUPPORTED, "raycast: the camera is a raster grid, which has no position to see from");
+    expand_camera(cam, &cd);
+  }
+  if (mode == GLH_RAYCAST_GRID) {
+    const double w = cam[6], h = cam[7];
+    if (step < 1) return fail(GLH_E_INVALID, "raycast: a pixel grid of step %d", step);
+    if (!(w >= 1.0 && h >= 1.0 && w == std::floor(w) && h == std::floor(h) && w < 2147483648.0 && h < 2147483648.0))
+      return fail(GLH_E_INVALID, "raycast: imgsz (%g, %g) is not a positive integer size", w, h);
+    cols = (int)w / step, rows = (int)h / step;
+    if ((int64_t)cols * rows >= ((int64_t)1 << 31))
+      return fail(GLH_E_UNSUPPORTED, "raycast: %d x %d pixels: fewer than 2^31 rays are served", cols, rows);
+    if ((int64_t)cols * rows != n)
+      return fail(GLH_E_INVALID, "raycast: %d rays for a grid of %d x %d pixels", n, cols, rows);
+  }
+  const RaycastJob job{dev, z, z_dtype == GLH_PD_F32, nx, ny, x[0], y[0], d0, d1, mode,
+                       mode == GLH_RAYCAST_DIRECTIONS ? nullptr : &cd, origins, mode == GLH_RAYCAST_DIRECTIONS ? n_origins : 1,
+                       rays, n, step, cols, rows, correction != 0, radius, refraction, block, t, xyz, patch, status, times_ms};
+  return raycast_run(job);
 }
 
 // helpers.maximum_filter, helpers.gaussian_filter (helpers.py:347-430) and Raster.fill_crevasses (raster.py:1266-1291): the

@@ -163,6 +163,24 @@ def intersect_rays_box(origin, directions, box, t=False):
     return origin + tmin[:, None] * directions, origin + tmax[:, None] * directions
 
 
+def intersect_rays_plane(rays, plane):
+    """helpers.py:1053-1101: where the rays (n, 6) = (x0, y0, z0, dx, dy, dz) meet the infinite plane
+    (x0, y0, z0, dx1, dy1, dz1, dx2, dy2, dz2) through a point and along two directions: (n, 3), NaN for a ray that is
+    parallel to the plane (|normal . direction| <= 1e-14, a ray lying in the plane included) or that has the plane behind
+    it.  The sea-level companion of `Raster.intersect_rays`."""
+    rays = np.atleast_2d(np.asarray(rays, dtype=float))
+    plane = np.asarray(plane, dtype=float)
+    normal = np.cross(plane[3:6], plane[6:9])
+    along = (normal * rays[:, 3:6]).sum(axis=1)
+    points = np.full((len(rays), 3), np.nan)
+    meets = np.abs(along) > 1e-14
+    t = (normal * (plane[0:3] - rays[meets, 0:3])).sum(axis=1) / along[meets]
+    ahead = t >= 0
+    meets[meets] = ahead
+    points[meets] = rays[meets, 0:3] + t[ahead, None] * rays[meets, 3:6]
+    return points
+
+
 def intersect_edge_box(origin, distance, box):
     """helpers.py:890-916: the multiple of `distance` in (0, 1) at which the edge from `origin` meets the box, or None."""
     import warnings

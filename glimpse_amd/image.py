@@ -113,6 +113,13 @@ class Image:
     def uv_to_xyz(self, uv, directions=False, **kwargs):
         return self.cam.uv_to_xyz(uv, directions=directions, **kwargs)
 
+    def uv_to_dem(self, uv, dem, **kwargs):
+        """`Camera.uv_to_dem` of this image's camera: the world points its pixels `uv` see on `dem`.  An image whose
+        camera is a raster grid (an orthophoto) has no position to cast rays from."""
+        if np.asarray(self.cam.vector24)[23] != 0:
+            raise NotImplementedError("The image's camera is a raster grid, which has no position to cast rays from")
+        return self.cam.uv_to_dem(uv, dem, **kwargs)
+
     def inbounds(self, uv):
         """image.py:297-299."""
         return self.cam.inframe(uv)

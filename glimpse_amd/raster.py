@@ -25,6 +25,8 @@ The rest of the raster tooling is served too: `gradient` (:1465-1474, `glh_stage
 `rasterize_polygons` (:1121-1147) makes masks with `helpers.polygons_to_mask` (`glh_stage_polygon_mask`), by a stated
 even-odd rule on cell centres where the reference calls GDAL; `rasterize` (:1103-1119) takes its per-cell means from
 `glh_stage_rasterize`.  `fill_circle`, `shift`, `data_extent` and `crop_to_data` are restated on the host.
+`intersect_rays(origin, directions, correction)`, which the reference leaves to its users, casts rays onto the bilinear
+surface between the cell centres (`glh_stage_raycast`, by the rule of INPUTS.md); `Camera.uv_to_dem` and `xyz_map` use it.
 File I/O (GDAL), `plot`, masked arrays and rasters with a singleton dimension (the reference's 1-D `interp1d` path) are out
 of scope.
 """
@@ -331,6 +333,56 @@ class Raster:
             splits[0] = np.concatenate((splits[-1], splits[0]), axis=0)
             splits.pop(-1)
         return splits[int(mask[0])::2]
+
+    def _cast_rays(self, correction, block, return_times=False, **rays):
+        """(t, xyz, patch, status) of `_lib.stage_raycast` for rays cast onto this raster as a DEM, after the checks that
+        come before any library call.  `rays`: `origins` and `directions`, or `cam` (a vector24) with `uv` or `step`."""
+        if np.ndim(self.array) != 2:
+            raise ValueError(f"a DEM is two-dimensional, got {np.shape(self.array)}")
+        if min(self.array.shape) < 2:
+            raise NotImplementedError(f"a DEM of {self.array.shape} cells has no patch between cell centres "
+                                      "(rasters with a singleton dimension are not served)")
+        block = int(block)
+        if block < 0 or block & (block - 1):
+            raise ValueError(f"block is 0 or a power of two, got {block}")
+        listed = rays.get("directions", rays.get("uv"))
+        if listed is not None and len(listed) >= 2 ** 31:
+            raise NotImplementedError(f"{len(listed)} rays: fewer than 2^31 are served")
+        _lib.viewshed_correction(correction)  # (a TypeError for an unknown argument comes before anything else)
+        array = np.asarray(self.array)
+        if array.dtype.kind not in "iuf" or array.dtype.itemsize > 8 or array.dtype == np.float16:
+            raise TypeError(f"a DEM of dtype {array.dtype}: float64, float32 or integers")
+        z = array if array.dtype == np.float32 else np.asarray(array, dtype=np.float64)
+        return _lib.stage_raycast(z, self.x, self.y, self.d, correction=correction, block=block, return_times=return_times,
+                                  **rays)
+
+    def intersect_rays(self, origin, directions, correction=False, return_depth=False, return_status=False, block=16):
+        """Where rays hit this raster as a DEM: xyz (n, 3) of the first intersection of each ray `origin + t directions`
+        (t >= 0) with the surface, NaN where there is none.  `origin`: (3,) for every ray, or (n, 3) one each (sun rays
+        for a shadow map); `directions` (n, 3), of any length.  The surface is the bilinear patches between the cell
+        centres -- what `sample(order=1)` interpolates -- over the rectangle of the outer cell centres; the half-cell rim
+        beyond them is not part of it.  The reference has the parts (helpers.intersect_rays_box, intersect_rays_plane,
+        bresenham_line) and no such function; the rule is INPUTS.md, "Ray casting: the rule".  `correction` as in
+        `viewshed`: the apparent surface sinks by helpers.elevation_corrections of the squared horizontal distance along
+        the ray, as Camera.xyz_to_uv sees it.  `return_depth`: also t (n,), in units of the directions' length;
+        `return_status`: also, per ray, an index into `_lib.RAYCAST_STATUS` (hit, misses the domain, enters below the
+        surface, leaves without a hit, invalid).  `block`: the side, in patches, of the blocks whose highest cell lets a
+        ray skip them (0: every patch is marched); the result does not depend on it.  One thread per ray on the GPU
+        (`glh_stage_raycast`).  A ray that dips under the surface and comes back out within one patch is not seen."""
+        directions = np.asarray(directions, dtype=np.float64)
+        if directions.ndim == 1:
+            directions = directions[None, :]
+        if directions.ndim != 2 or directions.shape[1] != 3:
+            raise ValueError(f"directions must be (n, 3), got {directions.shape}")
+        origin = np.asarray(origin, dtype=np.float64)
+        if origin.shape not in ((3,), (1, 3), (len(directions), 3)):
+            raise ValueError(f"origin must be (3,) or ({len(directions)}, 3), got {origin.shape}")
+        if len(directions) == 0:
+            t, xyz, status = np.empty(0), np.empty((0, 3)), np.empty(0, dtype=np.uint8)
+        else:
+            t, xyz, _, status = self._cast_rays(correction, block, origins=origin, directions=directions)
+        result = (xyz,) + ((t,) if return_depth else ()) + ((status,) if return_status else ())
+        return result[0] if len(result) == 1 else result
 
     def fill_crevasses(self, maximum={"size": 5}, gaussian={"sigma": 5}, mask=None, fill=False):
         """A maximum filter of the values, then Gaussian smoothing (raster.py:1266-1291), in place: `array` becomes

@@ -594,6 +594,46 @@ int glh_stage_orthorectify(int device_id, const void* frames, int depth_bits, in
                            int channels, int n_frames, const double* cams, const void* z, int z_dtype, int nx, int ny,
                            const double* x, const double* y, const uint8_t* seen, int n_seen, const int32_t* seen_of,
                            int method, void* out, double* kernel_ms);
+/* Raster.intersect_rays, Camera.uv_to_dem and Camera.xyz_map: n rays P(t) = o + t d cast onto the bilinear surface between
+ * the cell centres of the DEM z [ny][nx] (z_dtype GLH_PD_F64 / GLH_PD_F32; float32 is widened, all arithmetic is float64).
+ * The reference has no such function; the rule is INPUTS.md, "Ray casting: the rule", restated in tests/raycast_rule.py,
+ * which the device equals bit for bit.  x [nx], y [ny] are the cell centres from the first column / row to the last, in
+ * either direction, and d0, d1 the raster's signed cell sizes: a ray is marched in grid coordinates (x - x[0]) / d0,
+ * (y - y[0]) / d1 over the domain of the outer cell centres (the half-cell rim beyond them is not part of the surface).
+ * The rays come from one of three sources (`mode`):
+ *   GLH_RAYCAST_DIRECTIONS  rays [n][3] are directions, origins [n_origins][3] their origins, one each or one for all
+ *                           (n_origins == 1); cam is NULL.
+ *   GLH_RAYCAST_UV          rays [n][2] are image coordinates of the camera cam [GLH_CAM_LEN], unprojected on the device:
+ *                           o = the camera's position, d = Camera.uv_to_xyz(uv, directions=True), so t is the depth along
+ *                           the optical axis; origins is NULL.
+ *   GLH_RAYCAST_GRID        the pixel centres (step / 2 + c step, step / 2 + r step) of the camera, c < imgsz[0] / step,
+ *                           r < imgsz[1] / step, made on the device, ray r * cols + c; n must be cols * rows; rays and
+ *                           origins are NULL.
+ * correction != 0 lowers the apparent surface by helpers.elevation_corrections(t^2 (dx^2 + dy^2), radius, refraction), as
+ * Camera.xyz_to_uv applies it.  block = 0 marches every patch; block = B, a power of two, first reduces the DEM to the
+ * maxima of its B x B blocks of patches and lets a ray skip the blocks it clears: the results do not depend on it.
+ * Per ray: t [n] (NaN without a hit), xyz [n][3] = o + t d, patch [n] = row * (nx - 1) + column of the patch hit (-1
+ * without one) and status [n], one of GLH_RAYCAST_HIT, _MISS (the ray misses the domain), _BELOW (it enters the domain
+ * below the surface), _LEAVES (it leaves the domain without a hit), _INVALID (a uv, direction or origin that is not
+ * finite, or a direction of zero).
+ * times_ms (or NULL) [4]: HIP-event milliseconds -- [0] upload, [1] pyramid (the block maxima), [2] march, [3] download.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, nx, ny or n < 1, step < 1, n_origins neither 1 nor
+ * n, n that is not the grid's size, coordinates or cell sizes that are not finite, a cell size of 0, radius 0 with
+ * correction), GLH_E_UNSUPPORTED (an unknown z_dtype or mode, a raster grid as camera, a DEM with a singleton dimension,
+ * coordinates that are not those of a uniform grid to a quarter cell, 2^31 or more cells or rays, a block that is neither
+ * 0 nor a power of two up to 32768).  A failed device allocation is GLH_E_NOMEM.                                     */
+#define GLH_RAYCAST_DIRECTIONS 0
+#define GLH_RAYCAST_UV 1
+#define GLH_RAYCAST_GRID 2
+#define GLH_RAYCAST_HIT 0
+#define GLH_RAYCAST_MISS 1
+#define GLH_RAYCAST_BELOW 2
+#define GLH_RAYCAST_LEAVES 3
+#define GLH_RAYCAST_INVALID 4
+int glh_stage_raycast(int device_id, const void* z, int z_dtype, int nx, int ny, const double* x, const double* y,
+                      double d0, double d1, int mode, const double* cam, const double* origins, int n_origins,
+                      const double* rays, int n, int step, int correction, double radius, double refraction, int block,
+                      double* t, double* xyz, int32_t* patch, uint8_t* status, double* times_ms);
 /* helpers.maximum_filter(a, mask, fill, size, mode) (helpers.py:390-430; scipy.ndimage.maximum_filter) of a [ny][nx],
  * float64 (dtype GLH_FILTER_F64) or float32 (GLH_FILTER_F32), into out [ny][nx] of the same dtype.  The window is size_y
  * rows x size_x columns, each 1 .. 31 (a tile and its halo live in LDS), reaching size / 2 cells back and size - 1 - size / 2
