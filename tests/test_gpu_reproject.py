@@ -200,18 +200,43 @@ def test_identity_nearest_returns_the_frame():
         assert same_bits(np.ascontiguousarray(got[1:-1, 1:-1]), np.ascontiguousarray(frame[1:-1, 1:-1]))
 
 
-def test_observer_project_equals_the_per_image_calls():
-    from glimpse_amd import Camera, Observer
+def wandering_images(dtype, channels):
+    """(target camera, nine images at its position whose view direction wanders)."""
+    from glimpse_amd import Camera
 
-    rng = np.random.default_rng(4)
     target = Camera(imgsz=(96, 80), f=(150.0, 150.0), xyz=(1.0, 2.0, 3.0), viewdir=(10.0, 5.0, 0.0))
+    images = []
+    for i in range(9):
+        cam = Camera(imgsz=(128, 96), f=(160.0, 165.0), c=(2.5, -1.5), k=(0.1, -0.05, 0.01, 0.0, 0.0, 0.0),
+                     xyz=(1.0, 2.0, 3.0), viewdir=(10.0 + 0.8 * np.sin(i), 5.0 + 0.5 * np.cos(2 * i), 0.3 * i - 1.0))
+        frame = (texture(96, 128, channels, seed=10 + i) * 250.0).astype(dtype)
+        images.append(image(frame if channels == 3 else frame[:, :, 0], cam, day=i))
+    return target, images
+
+
+def test_the_timed_ring_of_reproject_returns_the_same_bytes_and_a_kernel_time():
+    """`return_kernel_ms=True` adds a pair of events around every frame's kernel (glh_frame_ring.h); seven frames go
+    twice round the ring's three slots and one further.  No bound on the time itself."""
+    from glimpse_amd import _lib
+
+    for dtype, channels, method in ((np.uint8, 3, "linear"), (np.float32, 1, "nearest")):
+        target, images = wandering_images(dtype, channels)
+        frames = np.stack([img._project_frame() for img in images[1:8]])
+        cams = np.stack([img.cam.vector24 for img in images[1:8]])
+        plain = _lib.stage_reproject(frames, cams, target.vector24, target.imgsz, method)
+        timed, kernel_ms = _lib.stage_reproject(frames, cams, target.vector24, target.imgsz, method, return_kernel_ms=True)
+        print(f"reproject, seven frames, timed ring: kernel_ms {kernel_ms:.4f}")
+        assert plain.shape == (7, 80, 96, channels) and same_bits(timed, plain)
+        assert np.isfinite(kernel_ms) and kernel_ms > 0.0
+        for i, img in enumerate(images[1:8]):
+            assert same_bits(np.ascontiguousarray(timed[i]), img.project(target, method=method)), i
+
+
+def test_observer_project_equals_the_per_image_calls():
+    from glimpse_amd import Observer
+
     for dtype, channels, method in ((np.uint8, 3, "linear"), (np.float32, 1, "linear"), (np.uint16, 3, "nearest")):
-        images = []
-        for i in range(9):
-            cam = Camera(imgsz=(128, 96), f=(160.0, 165.0), c=(2.5, -1.5), k=(0.1, -0.05, 0.01, 0.0, 0.0, 0.0),
-                         xyz=(1.0, 2.0, 3.0), viewdir=(10.0 + 0.8 * np.sin(i), 5.0 + 0.5 * np.cos(2 * i), 0.3 * i - 1.0))
-            frame = (texture(96, 128, channels, seed=10 + i) * 250.0).astype(dtype)
-            images.append(image(frame if channels == 3 else frame[:, :, 0], cam, day=i))
+        target, images = wandering_images(dtype, channels)
         obs = Observer(images)
         batch = obs.project(target, method=method)
         assert batch.shape == (9, 80, 96, channels) and batch.dtype == np.dtype(dtype)
