@@ -13,6 +13,7 @@ glimpse_amd/lib/libglimpse_hip.so, bound with ctypes in glimpse_amd._lib).  Ther
 fallback: build the library with `python -m glimpse_amd.build`.
 """
 from .camera import Camera
+from .displacements import displacements
 from .filters import gaussian_filter, maximum_filter
 from .image import Image
 from .motion import (CartesianMotion, CylindricalMotion, Motion, TangentCartesianMotion,
@@ -28,5 +29,6 @@ from .tracks import Tracks
 __all__ = ["Camera", "Image", "Observer", "Motion", "CartesianMotion", "CylindricalMotion",
            "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "RasterInterpolant", "Tracker", "Tracks", "maximum_filter",
            "gaussian_filter", "optimize", "Matches", "RotationMatches", "RotationMatchesXY", "RotationMatchesXYZ",
-           "ObserverCameras", "Cameras", "Points", "Lines", "Polynomial", "ransac", "KeypointMatcher", "match_keypoints"]
+           "ObserverCameras", "Cameras", "Points", "Lines", "Polynomial", "ransac", "KeypointMatcher", "match_keypoints",
+           "displacements"]
 __version__ = "0.1.0"

@@ -165,6 +165,8 @@ SIGNATURES = {
     "glh_stage_orthorectify": (_I, [_I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
     "glh_stage_raycast": (_I, [_I, _P, _I, _I, _I, _P, _P, _D, _D, _I, _P, _P, _I, _P, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P,
                                _P]),
+    "glh_stage_displacements": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,
+                                     _P]),
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "glh_stage_gaussian_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_fill_crevasses": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
@@ -1281,6 +1283,49 @@ def stage_raycast(z, x, y, d, origins=None, directions=None, cam=None, uv=None, 
                                    refraction, block, _ptr(t), _ptr(xyz), _ptr(patch), _ptr(status),
                                    _ptr(times) if return_times else None))
     return _timed((t, xyz, patch, status), RAYCAST_TIMES, times, return_times, extend=True)
+
+
+DISPLACEMENTS_TIMES = ("upload_ms", "kernel_ms", "download_ms")
+DISPLACEMENT_STATUS = ("matched", "peak on the edge", "no valid offset", "flat template", "template outside")
+DISPLACEMENT_GUESS_LIMIT = 1 << 24  # whole pixels; beyond it no window of any frame the library takes is inside
+
+
+def stage_displacements(frames, pairs, corners, valid, guess, size, reach, subpixel=True, return_surface=False,
+                        device_id=0, return_times=False):
+    """Dense template matching (INPUTS.md, "Displacements: the rule"): `frames` (F, h, w) uint8 (the integer path) or
+    float32; `pairs` (P, 2) int32, the frame a pair's templates are cut from and the frame they are looked for in;
+    `corners` (n, 2) int32, the (l, t) of each template box, with `valid` (n,) 0 where the box leaves the frame; `guess`
+    None, or whole pixels (n, 2) / (P, n, 2) int32; `size` = (w, h) of the template, `reach` = (rx, ry).  Returns
+    (duv (P, n, 2), score (P, n), status (P, n) uint8 indexing DISPLACEMENT_STATUS), with `return_surface` also the
+    scores of every offset (P, n, 2 ry + 1, 2 rx + 1), with `return_times` also a dict of DISPLACEMENTS_TIMES."""
+    frames = np.ascontiguousarray(frames)
+    if frames.ndim != 3 or frames.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+        raise TypeError(f"frames (F, rows, cols) of uint8 or float32 (got {frames.dtype}, {frames.ndim} dimensions)")
+    pairs = _arr(pairs, np.int32)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or len(pairs) < 1:
+        raise ValueError(f"pairs must be (P, 2) with P >= 1, got {pairs.shape}")
+    corners = _arr(corners, np.int32)
+    if corners.ndim != 2 or corners.shape[1] != 2 or len(corners) < 1:
+        raise ValueError(f"corners must be (n, 2) with n >= 1, got {corners.shape}")
+    n, p = len(corners), len(pairs)
+    valid = _arr(valid, np.uint8, (n,))
+    per_pair = 0
+    if guess is not None:
+        guess = _arr(guess, np.int32)
+        if guess.shape not in ((n, 2), (p, n, 2)):
+            raise ValueError(f"guess must be ({n}, 2) or ({p}, {n}, 2), got {guess.shape}")
+        per_pair = int(guess.ndim == 3)
+    (w, h), (rx, ry) = (int(v) for v in size), (int(v) for v in reach)
+    duv, score = np.empty((p, n, 2)), np.empty((p, n))
+    status = np.empty((p, n), dtype=np.uint8)
+    surface = np.empty((p, n, 2 * ry + 1, 2 * rx + 1)) if return_surface else None
+    times = np.zeros(len(DISPLACEMENTS_TIMES))
+    check(load().glh_stage_displacements(device_id, _ptr(frames), int(frames.dtype == np.float32), frames.shape[2],
+                                         frames.shape[1], frames.shape[0], _ptr(pairs), p, _ptr(corners), _ptr(valid), n,
+                                         _ptr(guess), per_pair, w, h, rx, ry, int(bool(subpixel)), _ptr(duv), _ptr(score),
+                                         _ptr(status), _ptr(surface), _ptr(times) if return_times else None))
+    result = (duv, score, status, surface) if return_surface else (duv, score, status)
+    return _timed(result, DISPLACEMENTS_TIMES, times, return_times, extend=True)
 
 
 FILTER_F64, FILTER_F32 = F64, F32

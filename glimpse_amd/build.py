@@ -29,7 +29,8 @@ LIB = os.path.join(LIBDIR, "libglimpse_hip.so")
 # one object each, beside the fused kernel's instantiations; what each is for is at the head of the file
 SOURCES = ["glimpse_hip.hip", "glh_viewshed.hip", "glh_horizon.hip", "glh_regrid.hip", "glh_project_dem.hip",
            "glh_filters.hip", "glh_terrain.hip", "glh_orient.hip", "glh_calib.hip",
-           "glh_match.hip", "glh_sift.hip", "glh_clahe.hip", "glh_ortho.hip", "glh_raycast.hip"]
+           "glh_match.hip", "glh_sift.hip", "glh_clahe.hip", "glh_ortho.hip", "glh_raycast.hip",
+           "glh_displace.hip"]
 
 
 def includes(path, seen=None):

@@ -27,6 +27,7 @@
 #include "glh_orient.h"
 #include "glh_ortho.h"
 #include "glh_raycast.h"
+#include "glh_displace.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
@@ -3415,6 +3416,38 @@ extern "C" int glh_stage_raycast(int dev, const void* z, int z_dtype, int nx, in
                        mode == GLH_RAYCAST_DIRECTIONS ? nullptr : &cd, origins, mode == GLH_RAYCAST_DIRECTIONS ? n_origins : 1,
                        rays, n, step, cols, rows, correction != 0, radius, refraction, block, t, xyz, patch, status, times_ms};
   return raycast_run(job);
+}
+
+// glimpse_amd.displacements: the arguments are checked here, before a device is touched; the kernels and the launch are
+// glh_displace.hip's.
+extern "C" int glh_stage_displacements(int dev, const void* frames, int is_float, int width, int height, int n_frames,
+                                       const int32_t* pairs, int n_pairs, const int32_t* corners, const uint8_t* valid, int n,
+                                       const int32_t* guess, int guess_per_pair, int w, int h, int rx, int ry, int subpixel,
+                                       double* duv, double* score, uint8_t* status, double* surface, double* times_ms) {
+  if (!frames || !pairs || !corners || !valid || !duv || !score || !status)
+    return fail(GLH_E_INVALID, "displacements: null argument");
+  if (width < 1 || height < 1 || n_frames < 1 || n_pairs < 1 || n < 1)
+    return fail(GLH_E_INVALID, "displacements: %d frames of %d x %d, %d pairs, %d points: at least one of each", n_frames,
+                width, height, n_pairs, n);
+  if (width > 32768 || height > 32768)
+    return fail(GLH_E_UNSUPPORTED, "displacements: a frame of %d x %d: at most 32768 on a side", width, height);
+  if (n_pairs > 65535) return fail(GLH_E_UNSUPPORTED, "displacements: %d pairs: up to 65535 in one call", n_pairs);
+  if (w < DP_MIN_SIDE || w > DP_MAX_SIDE || h < DP_MIN_SIDE || h > DP_MAX_SIDE)
+    return fail(GLH_E_UNSUPPORTED, "displacements: a template of %d x %d: sides of %d .. %d", w, h, DP_MIN_SIDE, DP_MAX_SIDE);
+  if (rx < 1 || rx > DP_MAX_REACH || ry < 1 || ry > DP_MAX_REACH)
+    return fail(GLH_E_UNSUPPORTED, "displacements: a reach of (%d, %d): 1 .. %d per axis", rx, ry, DP_MAX_REACH);
+  for (int k = 0; k < 2 * n_pairs; ++k)
+    if (pairs[k] < 0 || pairs[k] >= n_frames)
+      return fail(GLH_E_INVALID, "displacements: pair %d names frame %d of %d", k / 2, pairs[k], n_frames);
+  if (guess) {
+    const size_t count = (size_t)(guess_per_pair ? n_pairs : 1) * n * 2;
+    for (size_t k = 0; k < count; ++k)
+      if (guess[k] < -(1 << 24) || guess[k] > (1 << 24))
+        return fail(GLH_E_INVALID, "displacements: a guess of %d pixels: within +-2^24", guess[k]);
+  }
+  const DisplaceJob job{dev, frames, is_float != 0, width, height, n_frames, pairs, n_pairs, corners, valid, n, guess,
+                        guess_per_pair != 0, w, h, rx, ry, subpixel != 0, duv, score, status, surface, times_ms};
+  return displacements_run(job);
 }
 
 // helpers.maximum_filter, helpers.gaussian_filter (helpers.py:347-430) and Raster.fill_crevasses (raster.py:1266-1291): the

@@ -179,6 +179,12 @@ class Image:
         self._check_orthorectify(dem, viewshed, mask, method)
         return orthorectify([self], dem, viewshed, mask, method)[0]
 
+    def displacements(self, other, uv, **kwargs):
+        """`glimpse_amd.displacements(self.read(), other.read(), uv, **kwargs)`: where the surroundings of this image's
+        points `uv` are in the image `other` -- (duv, score, status), the position in `other` being uv + duv."""
+        from .displacements import displacements
+        return displacements(self.read(), other.read(), uv, **kwargs)
+
 
 def orthorectify(images, dem, viewshed, mask, method):
     """`Image.orthorectify` of `images` (checked by their `_check_orthorectify`, one pixel shape and dtype) as one array

@@ -144,6 +144,19 @@ class Observer:
             img._check_orthorectify(dem, viewshed, mask, method, name=f"Image {i}")
         return orthorectify(images, dem, viewshed, mask, method)
 
+    def displacements(self, uv, index=slice(None), step=1, **kwargs):
+        """`Image.displacements` from image k to image k + `step` of the images `index` selects (a slice, or a list of
+        positions), for the same points `uv` (n, 2): (duv (pairs, n, 2), score (pairs, n), status (pairs, n)), the pairs
+        being (0, step), (1, 1 + step), ... of the chosen images.  One library call in which every frame is uploaded
+        once; every pair equals the two-image call bit for bit.  `guess` may be (n, 2), the same for every pair, or
+        (pairs, n, 2); the other keywords are those of `glimpse_amd.displacements`.  The images must share one pixel
+        shape and dtype."""
+        from .displacements import sequence_displacements
+        images = self._pick(index)
+        if not images:
+            raise ValueError("No images selected")
+        return sequence_displacements([img.read(cache=self.cache) for img in images], uv, step=step, **kwargs)
+
     def subset(self, **kwargs):
         """observer.py:455-464: a new Observer over the images select_datetimes(**kwargs) keeps."""
         keep = select_datetimes(self.datetimes, **kwargs)

@@ -634,6 +634,32 @@ int glh_stage_raycast(int device_id, const void* z, int z_dtype, int nx, int ny,
                       double d0, double d1, int mode, const double* cam, const double* origins, int n_origins,
                       const double* rays, int n, int step, int correction, double radius, double refraction, int block,
                       double* t, double* xyz, int32_t* patch, uint8_t* status, double* times_ms);
+/* glimpse_amd.displacements, Image.displacements and Observer.displacements: dense template matching between frames by
+ * zero-normalised cross-correlation.  The reference has no such function; the rule is INPUTS.md, "Displacements: the
+ * rule", restated in tests/displacement_rule.py, which the device equals bit for bit.  frames [n_frames][height][width],
+ * uint8 (is_float == 0, the integer path) or float32 (is_float != 0); pairs [n_pairs][2] name, for each pair, the frame
+ * the templates are cut from and the frame they are looked for in.  corners [n][2] are the (l, t) of each point's
+ * template box [l, l + w) x [t, t + h), valid [n] is 0 where the caller found the box outside the frame (the device
+ * checks the corners of the others again); guess (or NULL: none) holds whole-pixel guesses [n][2], or
+ * [n_pairs][n][2] with guess_per_pair != 0, each within +-2^24.  The offsets searched are (i, j), |i| <= rx, |j| <= ry,
+ * around the guess.  Per pair and point: duv [n_pairs][n][2], score [n_pairs][n], status [n_pairs][n], one of
+ * GLH_DISPLACE_MATCHED, _EDGE (matched, but the peak lies on the border of the range or beside an invalid offset: no
+ * sub-pixel term on that axis), _NO_OFFSET, _FLAT, _OUTSIDE (the last three: duv and score NaN); surface (or NULL)
+ * [n_pairs][n][2 ry + 1][2 rx + 1], the score of every offset, NaN where it is invalid.  subpixel == 0: whole pixels,
+ * never _EDGE.
+ * times_ms (or NULL) [3]: HIP-event milliseconds -- [0] upload, [1] kernel, [2] download.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, sizes < 1, a pair outside [0, n_frames), a guess
+ * beyond +-2^24), GLH_E_UNSUPPORTED (w or h outside 3 .. 63, rx or ry outside 1 .. 32, a frame side above 32768, more
+ * than 65535 pairs).  A failed device allocation is GLH_E_NOMEM.                                                       */
+#define GLH_DISPLACE_MATCHED 0
+#define GLH_DISPLACE_EDGE 1
+#define GLH_DISPLACE_NO_OFFSET 2
+#define GLH_DISPLACE_FLAT 3
+#define GLH_DISPLACE_OUTSIDE 4
+int glh_stage_displacements(int device_id, const void* frames, int is_float, int width, int height, int n_frames,
+                            const int32_t* pairs, int n_pairs, const int32_t* corners, const uint8_t* valid, int n,
+                            const int32_t* guess, int guess_per_pair, int w, int h, int rx, int ry, int subpixel,
+                            double* duv, double* score, uint8_t* status, double* surface, double* times_ms);
 /* helpers.maximum_filter(a, mask, fill, size, mode) (helpers.py:390-430; scipy.ndimage.maximum_filter) of a [ny][nx],
  * float64 (dtype GLH_FILTER_F64) or float32 (GLH_FILTER_F32), into out [ny][nx] of the same dtype.  The window is size_y
  * rows x size_x columns, each 1 .. 31 (a tile and its halo live in LDS), reaching size / 2 cells back and size - 1 - size / 2
