@@ -27,6 +27,9 @@
 //                   apart with wstride = nxo (mod 32), which makes the addresses of consecutive offsets consecutive
 //                   banks across a row change.
 //
+// Where the parts of a workgroup's LDS lie and how far apart the rows are is glh_displace_plan.h's (dp_layout, dp_plan),
+// checked on the CPU for every template and reach by tests/hostcheck/displace_plan_hostcheck.cpp.
+//
 // Every loop is bounded by the template and reach, both checked by the caller (DP_MAX_SIDE, DP_MAX_REACH); every global
 // read is bounds-checked against the frame (pixels outside are staged as 0 and their offsets are invalid by geometry).
 #include <hip/hip_runtime.h>
@@ -36,15 +39,14 @@
 
 #include "../../include/glimpse_hip.h"
 #include "glh_displace.h"
+#include "glh_displace_plan.h"
 #include "glh_stage.h"
 
 namespace glh {
 namespace {
 
-constexpr int DP_TB = 256;
 constexpr int DP_WAVES = DP_TB / 64;
 constexpr int DP_FB = 4;  // offsets a thread of the float path runs at once
-constexpr size_t DP_LDS_LIMIT = 160 * 1024;
 
 struct DpArgs {
   const void* frames;
@@ -62,30 +64,6 @@ struct DpArgs {
   uint8_t* status;
   double* surface;
 };
-
-// LDS is one dynamic region (no static beside it, which would shift its base off 16 bytes); every part starts on a
-// multiple of 16 bytes.  The head is the reduction's scratch, the flat flag and the template's row sums; then the
-// template, the window, the offsets' sums (integer path) and the score surface, which on the integer path first holds
-// the row sums.
-constexpr int DP_RED_SCORE = 0, DP_RED_INDEX = 32, DP_FLAT = 48, DP_TROWS = 64, DP_HEAD = DP_TROWS + 8 * 64;
-
-struct DpLayout {
-  int tpl, win, sums, surf, total;  // byte offsets into the region, and its size
-};
-
-__host__ __device__ inline int dp_up16(int v) { return (v + 15) & ~15; }
-
-// pitch: of a window row; tpitch: of a template row (both in 4-byte units)
-__host__ __device__ inline DpLayout dp_layout(bool is_float, int h, int rx, int ry, int pitch, int tpitch) {
-  const int nxo = 2 * rx + 1, noff = nxo * (2 * ry + 1), sh = h + 2 * ry;
-  DpLayout l;
-  l.tpl = DP_HEAD;
-  l.win = l.tpl + dp_up16(4 * h * tpitch);
-  l.sums = l.win + dp_up16(4 * sh * pitch);
-  l.surf = l.sums + (is_float ? 0 : dp_up16(8 * noff));
-  l.total = l.surf + dp_up16(8 * (is_float ? noff : sh * nxo));  // (sh >= 2 ry + 1: the row sums are the larger)
-  return l;
-}
 
 // What a workgroup learns about its point before it touches a pixel.
 struct DpPoint {
@@ -253,9 +231,6 @@ __device__ __forceinline__ uint32_t dp_dot(const uint32_t* win, const uint32_t* 
   }
   return acc0 + acc1;
 }
-
-// The template's row pitch on the integer path: whole 16-byte reads.
-__host__ __device__ inline int dp_tpitch_u8(int w) { return (((w + 3) >> 2) + 3) & ~3; }
 
 __global__ __launch_bounds__(DP_TB) void k_displace_u8(const DpArgs a) {
   extern __shared__ __attribute__((aligned(16))) char dp_lds[];
@@ -427,46 +402,16 @@ __global__ __launch_bounds__(DP_TB) void k_displace_f32(const DpArgs a) {
   dp_finish(a, p, dp_lds, surf, best, bidx);
 }
 
-// The smallest pitch >= `need` that is `rem` modulo 32.
-int dp_pitch(int need, int rem) { return need + ((rem - need) % 32 + 32) % 32; }
-
-// The window's row pitch in words on the integer path.  The lanes of a 32-lane group own consecutive offsets: within one
-// row of offsets they read `span` consecutive words (at most min(nxo, 32) + 3 bytes, whatever the phase), and they reach
-// over `rows` rows of offsets, `pitch` words apart.  The smallest pitch >= `need` for which those bank ranges are
-// pairwise disjoint modulo the 32 banks of a 4-byte read; an odd pitch where none is.
-int dp_pitch_u8(int need, int nxo) {
-  const int lanes = nxo < 32 ? nxo : 32;
-  const int span = (lanes + 3 + 3) / 4, rows = nxo >= 32 ? 2 : 32 / nxo + 2;
-  for (int p = need; p < need + 32; ++p) {
-    bool ok = true;
-    for (int k = 1; k < rows && ok; ++k) {
-      const int d = (k * p) % 32;
-      ok = d >= span && 32 - d >= span;
-    }
-    if (ok) return p;
-  }
-  return need | 1;
-}
-
 }  // namespace
 
 int displacements_run(const DisplaceJob& j) {
   const size_t plane = (size_t)j.width * j.height, n = (size_t)j.n, np = (size_t)j.n_pairs;
   const size_t fbytes = plane * j.n_frames * (j.is_float ? 4 : 1);
   const int nxo = 2 * j.rx + 1, nyo = 2 * j.ry + 1, noff = nxo * nyo;
-  const int sw = j.w + 2 * j.rx;
   const size_t gbytes = j.guess ? (j.guess_per_pair ? np : 1) * n * 8 : 0;
-  int pitch, tpitch;
-  if (j.is_float) {
-    pitch = dp_pitch(sw, nxo % 32), tpitch = j.w;
-    if ((size_t)dp_layout(true, j.h, j.rx, j.ry, pitch, tpitch).total > DP_LDS_LIMIT) pitch = sw;
-  } else {
-    // (a row holds the bytes before the first column and every word the last step of dp_dot reads: the template's
-    // padded row and one more)
-    tpitch = dp_tpitch_u8(j.w);
-    pitch = dp_pitch_u8((2 * j.rx + 3) / 4 + tpitch + 1, nxo);
-  }
-  const size_t lds = (size_t)dp_layout(j.is_float != 0, j.h, j.rx, j.ry, pitch, tpitch).total;
+  const DpPlan plan = dp_plan(j.is_float != 0, j.w, j.h, j.rx, j.ry);
+  const int pitch = plan.pitch;
+  const size_t lds = plan.lds;
   if (lds > DP_LDS_LIMIT) return fail(GLH_E_UNSUPPORTED, "displacements: %zu bytes of LDS for one point", lds);
   HIPCHK(hipSetDevice(j.device));
   hipStream_t s = nullptr;  // (the null stream: every copy below is ordered with the kernel)

@@ -148,6 +148,15 @@ def noise_u8(shape=(61, 97), seed=0):
     return np.random.default_rng(seed).integers(0, 256, size=shape, dtype=np.uint8)
 
 
+def moved(frame, dx, dy, out):
+    """`out` with the content of `frame` at (x, y) written to (x + dx, y + dy); what moves in keeps `out`'s pixels."""
+    rows, cols = frame.shape
+    ys, yd = (slice(0, rows - dy), slice(dy, rows)) if dy >= 0 else (slice(-dy, rows), slice(0, rows + dy))
+    xs, xd = (slice(0, cols - dx), slice(dx, cols)) if dx >= 0 else (slice(-dx, cols), slice(0, cols + dx))
+    out[yd, xd] = frame[ys, xs]
+    return out
+
+
 def shifted(frame, dx, dy, seed=1):
     """`frame` moved by whole pixels (content at (x, y) goes to (x + dx, y + dy)); what moves in is fresh noise."""
     rng = np.random.default_rng(seed)
@@ -155,10 +164,80 @@ def shifted(frame, dx, dy, seed=1):
         out = rng.integers(0, 256, size=frame.shape, dtype=np.uint8)
     else:
         out = rng.random(frame.shape).astype(frame.dtype)
-    rows, cols = frame.shape
-    ys, yd = (slice(0, rows - dy), slice(dy, rows)) if dy >= 0 else (slice(-dy, rows), slice(0, rows + dy))
-    xs, xd = (slice(0, cols - dx), slice(dx, cols)) if dx >= 0 else (slice(-dx, cols), slice(0, cols + dx))
-    out[yd, xd] = frame[ys, xs]
+    return moved(frame, dx, dy, out)
+
+
+def periodic_u8(shape=(61, 97), period=(7, 5), seed=5):
+    """A random cell of period[1] rows x period[0] columns tiled over the frame: matched against itself, every offset
+    that is a whole number of periods from the true one has the same window, hence the same score in every bit."""
+    px, py = period
+    rows, cols = shape
+    cell = np.random.default_rng(seed).integers(0, 256, size=(py, px), dtype=np.uint8)
+    return np.tile(cell, (rows // py + 1, cols // px + 1))[:rows, :cols].copy()
+
+
+def half_striped_u8(shape=(61, 97), split=40, seed=5):
+    """periodic_u8 up to column `split`; from there on every row is constant (rows of period 5).  Against itself, a
+    template from the striped part ties with every window that lies in that part: the first of them has a lower
+    neighbour before it and a tied one after it."""
+    frame = periodic_u8(shape, (7, 5), seed)
+    frame[:, split:] = periodic_u8(shape, (1, 5), seed + 1)[:, split:]
+    return frame
+
+
+SATURATED_SHIFT = (2, -1)
+
+
+def saturated_u8(shape=(130, 160), seed=3):
+    """(a, b): pixels drawn from {254, 255}, and the frame moved by SATURATED_SHIFT, where what moves in is noise of
+    250 .. 255: the sums of a window are as large as uint8 pixels make them."""
+    a = np.random.default_rng(seed).integers(254, 256, size=shape, dtype=np.uint8)
+    return a, np.maximum(shifted(a, *SATURATED_SHIFT, seed=seed + 1), 250)
+
+
+def holes_u8(shape=(130, 160), seed=4, spacing=32):
+    """(a, b): all 255 but for single pixels of 0, one at a random place of every spacing x spacing cell, and the frame
+    moved by SATURATED_SHIFT (255 moves in): n sum(S^2) - sum(S)^2 is a small integer under the largest sum(S^2)."""
+    rng = np.random.default_rng(seed)
+    rows, cols = shape
+    a = np.full(shape, 255, dtype=np.uint8)
+    for y in range(0, rows, spacing):
+        for x in range(0, cols, spacing):
+            a[min(rows - 1, y + rng.integers(spacing)), min(cols - 1, x + rng.integers(spacing))] = 0
+    return a, moved(a, *SATURATED_SHIFT, np.full(shape, 255, dtype=np.uint8))
+
+
+SUBNORMAL_UNIT = np.float32(1e-42)  # 714 times the smallest float32 subnormal; 256 of them stay far below 2^-126
+SUBNORMAL_SHIFT = (1, -2)
+
+
+def subnormal_f32(shape=(61, 97), seed=6):
+    """(a, b): white noise of 1 .. 256 times SUBNORMAL_UNIT, every pixel a nonzero float32 subnormal, and the frame
+    moved by SUBNORMAL_SHIFT (such noise moves in)."""
+    a = noise_u8(shape, seed)
+    b = shifted(a, *SUBNORMAL_SHIFT, seed=seed + 1)
+    return tuple((f.astype(np.float32) + np.float32(1)) * SUBNORMAL_UNIT for f in (a, b))
+
+
+HUGE_UNIT = np.float32(3e37)
+
+
+def huge_f32(shape=(61, 97), seed=8):
+    """(a, b): white noise of 1/32 .. 8 times HUGE_UNIT (up to 2.4e38, float32 ends at 3.4e38) and the frame moved by
+    SUBNORMAL_SHIFT: the products of two pixels reach 5.8e76 and every sum of the rule stays finite in float64."""
+    a = noise_u8(shape, seed)
+    b = shifted(a, *SUBNORMAL_SHIFT, seed=seed + 1)
+    return tuple((f.astype(np.float32) + np.float32(1)) / np.float32(32) * HUGE_UNIT for f in (a, b))
+
+
+def tied(surface):
+    """[the offsets o = j * nxo + i whose score equals the surface's largest in every bit] for each point of
+    `surface` (n, nyo, nxo); empty where a point has no valid offset."""
+    flat = np.asarray(surface).reshape(len(surface), -1)
+    out = []
+    for row in flat:
+        valid = ~np.isnan(row)
+        out.append(np.flatnonzero(valid & (row == row[valid].max())) if valid.any() else np.empty(0, dtype=np.int64))
     return out
 
 
