@@ -25,10 +25,11 @@ from .optimize import (Cameras, KeypointMatcher, Lines, Matches, ObserverCameras
 from .raster import Raster, RasterInterpolant
 from .tracker import Tracker
 from .tracks import Tracks
+from .velocity import velocity_field
 
 __all__ = ["Camera", "Image", "Observer", "Motion", "CartesianMotion", "CylindricalMotion",
            "TangentCartesianMotion", "TangentCylindricalMotion", "Raster", "RasterInterpolant", "Tracker", "Tracks", "maximum_filter",
            "gaussian_filter", "optimize", "Matches", "RotationMatches", "RotationMatchesXY", "RotationMatchesXYZ",
            "ObserverCameras", "Cameras", "Points", "Lines", "Polynomial", "ransac", "KeypointMatcher", "match_keypoints",
-           "displacements"]
+           "displacements", "velocity_field"]
 __version__ = "0.1.0"

@@ -167,6 +167,8 @@ SIGNATURES = {
                                _P]),
     "glh_stage_displacements": (_I, [_I, _P, _I, _I, _I, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P,
                                      _P]),
+    "glh_stage_velocity_field": (_I, [_I, _P, _P, _P, _I, _I, _I, _I, _P, _D, _D, _D, _I, _I, _I, _D, _D, _I, _P, _P, _P, _P,
+                                      _P]),
     "glh_stage_max_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _P]),
     "glh_stage_gaussian_filter": (_I, [_I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P, _P]),
     "glh_stage_fill_crevasses": (_I, [_I, _P, _I, _I, _I, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P, _P]),
@@ -1326,6 +1328,33 @@ def stage_displacements(frames, pairs, corners, valid, guess, size, reach, subpi
                                          _ptr(status), _ptr(surface), _ptr(times) if return_times else None))
     result = (duv, score, status, surface) if return_surface else (duv, score, status)
     return _timed(result, DISPLACEMENTS_TIMES, times, return_times, extend=True)
+
+
+VELOCITY_FIELD_TIMES = ("upload_ms", "test_ms", "stack_ms", "download_ms")
+
+
+def stage_velocity_field(duv, score, status, grid, dt, scale, min_score, accept_edge, radius, min_neighbors, threshold,
+                         epsilon, min_count, device_id=0, return_times=False):
+    """Displacements tested against their neighbours and stacked over the pairs (INPUTS.md, "Velocity field: the rule"):
+    `duv` (P, n, 2) float64, `score` (P, n) float64 and `status` (P, n) uint8 as `stage_displacements` returns them, at the
+    n = rows * cols nodes of `grid` = (rows, cols) in row-major order; `dt` (P,) float64, `scale` a pair.  Returns
+    (v (n, 2), sigma (n, 2), count (n,) int32, kept (P, n) bool), with `return_times` also a dict of VELOCITY_FIELD_TIMES.
+    glimpse_amd.velocity checks what the caller gave."""
+    duv = _arr(duv, np.float64)
+    if duv.ndim != 3 or duv.shape[2] != 2 or duv.shape[0] < 1 or duv.shape[1] < 1:
+        raise ValueError(f"duv must be (P, n, 2) with P, n >= 1, got {duv.shape}")
+    p, n = duv.shape[:2]
+    score, status, dt = _arr(score, np.float64, (p, n)), _arr(status, np.uint8, (p, n)), _arr(dt, np.float64, (p,))
+    rows, cols = (int(v) for v in grid)
+    v, sigma = np.empty((n, 2)), np.empty((n, 2))
+    count, kept = np.empty(n, dtype=np.int32), np.empty((p, n), dtype=np.uint8)
+    times = np.zeros(len(VELOCITY_FIELD_TIMES))
+    check(load().glh_stage_velocity_field(device_id, _ptr(duv), _ptr(score), _ptr(status), p, rows, cols, n, _ptr(dt),
+                                          float(scale[0]), float(scale[1]), float(min_score), int(bool(accept_edge)),
+                                          int(radius), int(min_neighbors), float(threshold), float(epsilon),
+                                          int(min_count), _ptr(v), _ptr(sigma), _ptr(count), _ptr(kept),
+                                          _ptr(times) if return_times else None))
+    return _timed((v, sigma, count, kept.view(np.bool_)), VELOCITY_FIELD_TIMES, times, return_times, extend=True)
 
 
 FILTER_F64, FILTER_F32 = F64, F32

@@ -30,7 +30,7 @@ LIB = os.path.join(LIBDIR, "libglimpse_hip.so")
 SOURCES = ["glimpse_hip.hip", "glh_viewshed.hip", "glh_horizon.hip", "glh_regrid.hip", "glh_project_dem.hip",
            "glh_filters.hip", "glh_terrain.hip", "glh_orient.hip", "glh_calib.hip",
            "glh_match.hip", "glh_sift.hip", "glh_clahe.hip", "glh_ortho.hip", "glh_raycast.hip",
-           "glh_displace.hip"]
+           "glh_displace.hip", "glh_velocity.hip"]
 
 
 def includes(path, seen=None):

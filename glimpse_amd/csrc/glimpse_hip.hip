@@ -28,6 +28,8 @@
 #include "glh_ortho.h"
 #include "glh_raycast.h"
 #include "glh_displace.h"
+#include "glh_velocity.h"
+#include "glh_velocity_plan.h"
 #include "glh_regrid.h"
 #include "glh_viewshed.h"
 #include "glh_filters.h"
@@ -3448,6 +3450,42 @@ extern "C" int glh_stage_displacements(int dev, const void* frames, int is_float
   const DisplaceJob job{dev, frames, is_float != 0, width, height, n_frames, pairs, n_pairs, corners, valid, n, guess,
                         guess_per_pair != 0, w, h, rx, ry, subpixel != 0, duv, score, status, surface, times_ms};
   return displacements_run(job);
+}
+
+// glimpse_amd.velocity_field: the arguments are checked here, before a device is touched; the kernels and the launch are
+// glh_velocity.hip's.
+extern "C" int glh_stage_velocity_field(int dev, const double* duv, const double* score, const uint8_t* status, int n_pairs,
+                                        int rows, int cols, int n, const double* dt, double scale_u, double scale_v,
+                                        double min_score, int accept_edge, int radius, int min_neighbors, double threshold,
+                                        double epsilon, int min_count, double* v, double* sigma, int32_t* count,
+                                        uint8_t* kept, double* times_ms) {
+  if (!duv || !score || !status || !dt || !v || !sigma || !count || !kept)
+    return fail(GLH_E_INVALID, "velocity_field: null argument");
+  if (n_pairs < 1 || rows < 1 || cols < 1 || n < 1 || (int64_t)rows * cols != n)
+    return fail(GLH_E_INVALID, "velocity_field: %d pairs, %d nodes on a grid of %d x %d: at least one of each, rows * cols nodes",
+                n_pairs, n, rows, cols);
+  if (n_pairs > VF_MAX_PAIRS)
+    return fail(GLH_E_UNSUPPORTED, "velocity_field: %d pairs: up to %d in one call", n_pairs, VF_MAX_PAIRS);
+  if (n > VF_MAX_NODES) return fail(GLH_E_UNSUPPORTED, "velocity_field: %d nodes: up to %d in one call", n, VF_MAX_NODES);
+  if (radius < 0 || radius > VF_MAX_RADIUS)
+    return fail(GLH_E_UNSUPPORTED, "velocity_field: a radius of %d: 0 .. %d", radius, VF_MAX_RADIUS);
+  if (radius > 0) {
+    const int most = (2 * radius + 1) * (2 * radius + 1) - 1;
+    if (min_neighbors < 1 || min_neighbors > most)
+      return fail(GLH_E_INVALID, "velocity_field: min_neighbors %d: 1 .. %d at radius %d", min_neighbors, most, radius);
+    if (!(std::isfinite(threshold) && threshold > 0.0 && std::isfinite(epsilon) && epsilon > 0.0))
+      return fail(GLH_E_INVALID, "velocity_field: threshold %g, epsilon %g: finite and positive", threshold, epsilon);
+  }
+  if (min_count < 1) return fail(GLH_E_INVALID, "velocity_field: min_count %d: at least 1", min_count);
+  if (!(std::isfinite(scale_u) && std::isfinite(scale_v)))
+    return fail(GLH_E_INVALID, "velocity_field: a scale of (%g, %g) is not finite", scale_u, scale_v);
+  for (int p = 0; p < n_pairs; ++p)
+    if (!(std::isfinite(dt[p]) && dt[p] != 0.0))
+      return fail(GLH_E_INVALID, "velocity_field: dt[%d] = %g: finite and not zero", p, dt[p]);
+  const VelocityJob job{dev, duv, score, status, n_pairs, rows, cols, dt, {scale_u, scale_v}, min_score,
+                        accept_edge ? GLH_DISPLACE_EDGE : GLH_DISPLACE_MATCHED, radius, min_neighbors, threshold, epsilon,
+                        min_count, v, sigma, count, kept, times_ms};
+  return velocity_field_run(job);
 }
 
 // helpers.maximum_filter, helpers.gaussian_filter (helpers.py:347-430) and Raster.fill_crevasses (raster.py:1266-1291): the

@@ -157,6 +157,20 @@ class Observer:
             raise ValueError("No images selected")
         return sequence_displacements([img.read(cache=self.cache) for img in images], uv, step=step, **kwargs)
 
+    def velocity_field(self, uv, grid, index=slice(None), step=1, scale=(1.0, 1.0), displacements=None, **kwargs):
+        """`glimpse_amd.velocity_field` of `self.displacements(uv, index, step, **displacements)`: (v (n, 2), sigma (n, 2),
+        count (n,)) at the points `uv` (n, 2), the nodes of a regular grid of `grid` = (rows, cols) in row-major order.
+        `dt` is the time from image k to image k + `step` of the chosen images, in seconds, so v is in units of `scale`
+        (for example a DEM's cell size `dem.d`, for orthophotos) per second; `displacements` holds keywords of
+        `Observer.displacements` (size, reach, guess, subpixel), the other keywords are those of
+        `glimpse_amd.velocity_field`."""
+        from .velocity import velocity_field
+        step = int(step)
+        duv, score, status = self.displacements(uv, index, step, **(displacements or {}))[:3]
+        times = [img.datetime for img in self._pick(index)]
+        dt = [times[k + step] - times[k] for k in range(len(times) - step)]
+        return velocity_field(duv, score, status, grid, dt=dt, scale=scale, **kwargs)
+
     def subset(self, **kwargs):
         """observer.py:455-464: a new Observer over the images select_datetimes(**kwargs) keeps."""
         keep = select_datetimes(self.datetimes, **kwargs)

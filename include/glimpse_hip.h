@@ -660,6 +660,28 @@ int glh_stage_displacements(int device_id, const void* frames, int is_float, int
                             const int32_t* pairs, int n_pairs, const int32_t* corners, const uint8_t* valid, int n,
                             const int32_t* guess, int guess_per_pair, int w, int h, int rx, int ry, int subpixel,
                             double* duv, double* score, uint8_t* status, double* surface, double* times_ms);
+/* glimpse_amd.velocity_field and Observer.velocity_field: the displacements of n_pairs image pairs at the n = rows * cols
+ * nodes of a regular grid (row-major), tested against their neighbours and stacked over the pairs.  The reference has no
+ * such function; the rule is INPUTS.md, "Velocity field: the rule", restated in tests/velocity_field_rule.py, which the
+ * device equals bit for bit.  duv [n_pairs][n][2], score [n_pairs][n] and status [n_pairs][n] are what
+ * glh_stage_displacements wrote.  A vector is a candidate when its status is GLH_DISPLACE_MATCHED (or _EDGE, with
+ * accept_edge != 0), its score >= min_score and both components are finite.  A candidate is kept (kept [n_pairs][n], 1 or 0)
+ * when at least min_neighbors of the nodes within `radius` rows and columns of it are candidates of the same pair and, on
+ * both components, |x - med| / (res + epsilon) <= threshold, med the median of the neighbours' values and res the median
+ * of their absolute deviations from it (Westerweel & Scarano, 2005); radius 0: every candidate is kept, and
+ * min_neighbors, threshold and epsilon are not read.  Per node and component, over the kept pairs: x = duv * scale / dt[p]
+ * (scale_u, scale_v; dt [n_pairs]), v [n][2] the median of x, sigma [n][2] 1.4826 times the median of |x - v|,
+ * count [n] their number; a count below min_count gives NaN in v and sigma.
+ * times_ms (or NULL) [4]: HIP-event milliseconds -- [0] upload, [1] the neighbour test, [2] the stack, [3] download.
+ * Checked before a device is touched: GLH_E_INVALID (null pointers, sizes < 1, rows * cols != n, min_neighbors outside
+ * 1 .. (2 radius + 1)^2 - 1, a threshold or epsilon that is not finite and positive, min_count < 1, a scale that is not
+ * finite, a dt that is zero or not finite), GLH_E_UNSUPPORTED (more than 1024 pairs, a radius outside 0 .. 2, more than
+ * 2^24 nodes).  A failed device allocation is GLH_E_NOMEM.                                                             */
+int glh_stage_velocity_field(int device_id, const double* duv, const double* score, const uint8_t* status, int n_pairs,
+                             int rows, int cols, int n, const double* dt, double scale_u, double scale_v,
+                             double min_score, int accept_edge, int radius, int min_neighbors, double threshold,
+                             double epsilon, int min_count, double* v, double* sigma, int32_t* count, uint8_t* kept,
+                             double* times_ms);
 /* helpers.maximum_filter(a, mask, fill, size, mode) (helpers.py:390-430; scipy.ndimage.maximum_filter) of a [ny][nx],
  * float64 (dtype GLH_FILTER_F64) or float32 (GLH_FILTER_F32), into out [ny][nx] of the same dtype.  The window is size_y
  * rows x size_x columns, each 1 .. 31 (a tile and its halo live in LDS), reaching size / 2 cells back and size - 1 - size / 2
