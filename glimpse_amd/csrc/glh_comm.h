@@ -17,6 +17,8 @@
 
 #include <string>
 
+#include "glh_stage.h"
+
 namespace glh {
 
 struct RcclApi {
@@ -81,10 +83,9 @@ inline RcclApi* rccl_api() {
 struct Comm {
   ncclComm_t comm = nullptr;
   int rank = 0, world = 1;
-  double* stage = nullptr;   // root: [sum_r n_frames * P_r * 12] doubles, then [sum_r P_r] status words
-  size_t stage_bytes = 0;
+  GrowBuf stage;  // root: [sum_r n_frames * P_r * 12] doubles, then [sum_r P_r] status words
   size_t gathered_doubles = 0, gathered_points = 0, gathered_status_off = 0;  // what the last gather left in `stage`
-  double* scalar = nullptr;  // one double / one int for the barrier and the max-reduction
+  DevArray<double> scalar;  // one double / one int for the barrier and the max-reduction
 };
 
 }  // namespace glh

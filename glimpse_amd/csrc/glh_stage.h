@@ -1,9 +1,13 @@
-// glh_stage.h -- the host scaffold of a device stage: what glimpse_hip.hip (the C ABI) and the stage files
-// (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_ortho.hip, glh_raycast.hip, glh_filters.hip, glh_terrain.hip, glh_orient.hip, glh_calib.hip, glh_match.hip, glh_sift.hip, glh_clahe.hip) share to
-// report an error, to own device memory and to time their phases.  The four handle-based objects (glh_orient, glh_calib,
-// glh_match, glh_sift) also share what a handle is made of: a buffer that grows (GrowBuf), the device and the stream
-// (DeviceObject) and how a handle comes and goes (create_object, destroy_object).  The plain C++ of a staging buffer is
-// glh_stage_layout.h's: where its arrays lie (StageLayout), each array named once (StagePlan, Stage).  Host-only.
+// glh_stage.h -- the host scaffold of a device stage: what glimpse_hip.hip (the C ABI and its tracking context, glh_ctx)
+// and the stage files (glh_viewshed.hip, glh_horizon.hip, glh_regrid.hip, glh_project_dem.hip, glh_ortho.hip,
+// glh_raycast.hip, glh_filters.hip, glh_terrain.hip, glh_displace.hip, glh_velocity.hip, glh_orient.hip, glh_calib.hip,
+// glh_match.hip, glh_sift.hip, glh_clahe.hip) share to report an error, to own device memory and to time their phases.
+// Everything that has to be given back to HIP is a member that gives it back (glh_owned.h: Owned): device memory (DevBuf,
+// GrowBuf, DevArray<T>), pinned host memory (PinnedBuf), a stream (Stream) and an event (Event).  The four handle-based
+// objects (glh_orient, glh_calib, glh_match, glh_sift) also share what a handle is made of: a buffer that grows
+// (GrowBuf), the device and the stream (DeviceObject) and how a handle comes and goes (create_object, destroy_object).
+// The plain C++ of a staging buffer is glh_stage_layout.h's: where its arrays lie (StageLayout), each array named once
+// (StagePlan, Stage).  Host-only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,6 +16,7 @@
 #include <new>
 
 #include "../../include/glimpse_hip.h"
+#include "glh_owned.h"
 #include "glh_stage_layout.h"
 
 namespace glh {
@@ -40,24 +45,39 @@ int fail(int code, const char* fmt, ...);
 
 namespace glh {
 
+struct DeviceFree {
+  void operator()(void* p) const { (void)hipFree(p); }
+};
+struct HostFree {
+  void operator()(void* p) const { (void)hipHostFree(p); }
+};
+struct StreamDestroy {
+  void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
+};
+struct EventDestroy {
+  void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); }
+};
+
 // A device allocation that is freed with its scope.
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
+struct DevBuf : Owned<void*, DeviceFree> {
   template <typename T>
   T* as() const {
     return static_cast<T*>(p);
   }
-  int alloc(size_t bytes) {
+  // hipMalloc's one report: *out is the memory, or null with the bytes asked for in the message
+  static int acquire(size_t bytes, void** out) {
     if (bytes == 0) bytes = 8;  // (an empty array still gets an address)
-    hipError_t e = hipMalloc(&p, bytes);
+    hipError_t e = hipMalloc(out, bytes);
     if (e != hipSuccess) {
+      *out = nullptr;
       (void)hipGetLastError();  // (the error is sticky: the next launch check would report it again)
       return fail(GLH_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
     }
     return GLH_OK;
+  }
+  int alloc(size_t bytes) {  // (in place of what was held)
+    reset();
+    return acquire(bytes, &p);
   }
   int up(const void* src, size_t bytes) {
     CHK(alloc(bytes));
@@ -76,11 +96,51 @@ struct DevBuf {
 struct GrowBuf : DevBuf {
   size_t cap = 0;  // the bytes last asked for
   int reserve(size_t bytes) {
-    if (bytes <= cap && p) return GLH_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr, cap = 0;
-    CHK(alloc(bytes));
-    cap = bytes;
+    return grow(*this, cap, bytes, DevBuf::acquire);
+  }
+};
+
+// A device array of T: a GrowBuf counted in elements, which reads as the T* it holds (a kernel argument, `if (!a)`).
+// alloc(count) replaces what is held, reserve(count) only when it holds fewer; an array of 0 elements has room for one.
+template <typename T>
+struct DevArray : GrowBuf {
+  T* get() const { return static_cast<T*>(p); }
+  operator T*() const { return get(); }
+  int alloc(size_t count) {
+    cap = 0;
+    CHK(DevBuf::alloc(bytes_of(count)));
+    cap = bytes_of(count);  // (a reserve of no more keeps it)
+    return GLH_OK;
+  }
+  int reserve(size_t count) { return GrowBuf::reserve(bytes_of(count)); }
+  static size_t bytes_of(size_t count) { return (count ? count : 1) * sizeof(T); }
+};
+
+// Pinned host memory that grows like a GrowBuf.
+struct PinnedBuf : Owned<void*, HostFree> {
+  size_t cap = 0;  // the bytes last asked for
+  int reserve(size_t bytes) {
+    return grow(*this, cap, bytes, [](size_t n, void** out) {
+      HIPCHK(hipHostMalloc(out, n, hipHostMallocDefault));
+      return GLH_OK;
+    });
+  }
+};
+
+// A non-blocking stream and an event, made on first use by create() and destroyed with their owner.
+struct Stream : Owned<hipStream_t, StreamDestroy> {
+  operator hipStream_t() const { return p; }
+  int create() {
+    reset();
+    HIPCHK(hipStreamCreateWithFlags(&p, hipStreamNonBlocking));
+    return GLH_OK;
+  }
+};
+struct Event : Owned<hipEvent_t, EventDestroy> {
+  operator hipEvent_t() const { return p; }
+  int create(unsigned flags = hipEventDefault) {
+    reset();
+    HIPCHK(hipEventCreateWithFlags(&p, flags));
     return GLH_OK;
   }
 };
@@ -128,13 +188,9 @@ void destroy_object(H* h) {
 // The N events a stage records between its phases; times_ms of the C ABI is made of the spans between them.
 template <int N>
 struct StageEvents {
-  hipEvent_t e[N] = {};
-  ~StageEvents() {
-    for (hipEvent_t v : e)
-      if (v) (void)hipEventDestroy(v);
-  }
+  Event e[N];
   int create() {
-    for (hipEvent_t& v : e) HIPCHK(hipEventCreate(&v));
+    for (Event& v : e) CHK(v.create());
     return GLH_OK;
   }
   int record(int k, hipStream_t stream) {

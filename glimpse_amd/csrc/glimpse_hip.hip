@@ -116,29 +116,32 @@ struct Observer {
   int bits = 8;  // bits per sample of the frames: 8 or 16 (unsigned integers), 32 (float32), 64 (float64): glh_observer_set_depth
   size_t frame_bytes() const { return (size_t)width * height * channels * (bits / 8); }
   double sigma = 0.3;
-  CamDev* cams = nullptr;               // device [n_images]
+  DevArray<CamDev> cams;                // device [n_images]
   std::vector<CamDev> cams_host;        // same, for kernels that take the camera by value
-  std::vector<const uint8_t*> frames;   // device pointers (owned or borrowed)
-  std::vector<uint8_t*> owned;          // owned allocations (same indexing; null if borrowed)
+  std::vector<const uint8_t*> frames;   // device pointers (owned or borrowed: a borrowed frame is never freed here)
+  std::vector<DevArray<uint8_t>> owned; // owned allocations (same indexing; null if borrowed)
 };
 
+// Every member that holds device memory, pinned memory, a stream or an event owns it (glh_stage.h) and gives it back
+// when the context is deleted.  Members go in reverse order of declaration: the streams come first, so they outlive
+// every buffer and event that work enqueued on them uses.
 struct glh_ctx {
   glh_config cfg{};
-  hipStream_t stream = nullptr;
-  // frame ingest (glh_observer_upload_frame_async): a copy stream and a ring of pinned staging buffers
+  Stream stream;
+  Stream copy_stream;        // frame ingest; opened with upload_done on the first async or pinned upload (open_copy_stream)
+  Stream extra_streams[3];   // streams 2 .. 4 of glh_track
+  // frame ingest (glh_observer_upload_frame_async): the copy stream and a ring of pinned staging buffers
   static constexpr int NSTAGE = 4;
-  hipStream_t copy_stream = nullptr;
-  uint8_t* stage[NSTAGE] = {nullptr, nullptr, nullptr, nullptr};
-  size_t stage_bytes[NSTAGE] = {0, 0, 0, 0};
-  hipEvent_t stage_done[NSTAGE] = {nullptr, nullptr, nullptr, nullptr};
+  PinnedBuf stage[NSTAGE];
+  Event stage_done[NSTAGE];
   bool stage_busy[NSTAGE] = {false, false, false, false};
   int stage_next = 0;
   // uploads from caller-registered host memory (glh_observer_upload_frame_pinned): ticket t has event pin_ev[t % NPIN]
   static constexpr int NPIN = 64;
-  hipEvent_t pin_ev[NPIN] = {nullptr};
+  Event pin_ev[NPIN];
   int64_t pin_next = 0, pin_completed = 0;  // tickets handed out; every ticket below pin_completed has finished
-  hipEvent_t upload_done = nullptr;  // recorded on copy_stream after the latest upload
-  bool uploads_pending = false;      // the compute stream has not yet been ordered after upload_done
+  Event upload_done;             // recorded on copy_stream after the latest upload
+  bool uploads_pending = false;  // the compute stream has not yet been ordered after upload_done
   int P = 0, N = 0, tw = 0, th = 0, NB = 0;
   int cur = 0;  // current particle/weight buffer
   int frame = 0;
@@ -157,76 +160,74 @@ struct glh_ctx {
   int tile_cap = 0, search_cap = 0, sse_cap = 0, ssd_blocks = 2;
   Observer obs[MAX_OBS];
   // device buffers
-  double *particles[2] = {nullptr, nullptr}, *weights[2] = {nullptr, nullptr};
-  double *motion = nullptr, *uv = nullptr, *bbox_part = nullptr, *normals = nullptr, *u = nullptr;
-  double *mean6 = nullptr, *moments = nullptr;
+  DevArray<double> particles[2], weights[2];
+  DevArray<double> motion, uv, bbox_part, normals, u;
+  DevArray<double> mean6, moments;
   struct RasterBuf {
-    double *z = nullptr, *gx = nullptr, *gy = nullptr;
+    DevArray<double> z, gx, gy;
     RasterDev dev{};
     std::vector<double> hgx, hgy;  // host copies of the coordinates (same_grid below)
   } rasters[3];  // GLH_RASTER_DEM, _DEM_SIGMA, _VIEWSHED
   bool same_grid = false;  // the dem and dem_sigma rasters have bit-identical coordinate arrays (Surfaces::same_grid)
-  double* covariances = nullptr;  // [max_frames][P][36], allocated on first use
-  double* uj = nullptr;           // [P][N] host-fed per-particle uniforms (stratified / choice)
-  double* extra_ll = nullptr;     // [P][N] caller-computed log-likelihood term of the next glh_update_weights, or null
+  DevArray<double> covariances;  // [max_frames][P][36], allocated on first use
+  DevArray<double> uj;           // [P][N] host-fed per-particle uniforms (stratified / choice)
+  DevArray<double> extra_ll;     // [P][N] caller-computed log-likelihood term of the next glh_update_weights, or null
   bool have_extra = false;
-  uint8_t *obs_mask = nullptr, *active = nullptr;
-  uint32_t* pt_status = nullptr;
-  int32_t *pt_err_frame = nullptr, *box = nullptr, *idx = nullptr;
-  int32_t* obs_status_all = nullptr;  // [max_frames][O][P]: the per-(observer, point) status of every frame
-  int32_t *tmpl_box = nullptr, *tmpl_hist_n = nullptr, *tmpl_valid = nullptr;
-  double *tmpl_duv = nullptr, *tmpl_tile64 = nullptr, *tmpl_hist_v = nullptr, *tmpl_hist_q = nullptr;
-  float *tmpl_tile32 = nullptr, *search = nullptr;
-  unsigned long long* stamps = nullptr;  // phase stamps of the fused kernel (diagnostic)
-  uint16_t* uidx[2] = {nullptr, nullptr};  // [P][N] record of every particle in particles[b] / weights[b] when compact
+  DevArray<uint8_t> obs_mask, active;
+  DevArray<uint32_t> pt_status;
+  DevArray<int32_t> pt_err_frame, box, idx;
+  DevArray<int32_t> obs_status_all;  // [max_frames][O][P]: the per-(observer, point) status of every frame
+  DevArray<int32_t> tmpl_box, tmpl_hist_n, tmpl_valid;
+  DevArray<double> tmpl_duv, tmpl_tile64, tmpl_hist_v, tmpl_hist_q;
+  DevArray<float> tmpl_tile32, search;
+  DevArray<unsigned long long> stamps;  // phase stamps of the fused kernel (diagnostic)
+  DevArray<uint16_t> uidx[2];  // [P][N] record of every particle in particles[b] / weights[b] when compact
   bool compact = false;  // particles[cur] / weights[cur] are run-length compact (left by the fused step)
-  int32_t* resid_draws = nullptr;  // [P] uniforms consumed by the last residual resampling
-  uint32_t* bins16 = nullptr;   // [P][65535 * 3 + 1] key histograms of 16-bit frames (staged tile kernels), on first use
-  double* fwork = nullptr;      // [P][2 D^2] tile workspace of float64 frames (staged tile kernels), on first use
-  double* tracks_tmp = nullptr; // means | sigmas in the caller's layout (glh_get_tracks), on first use
-  size_t tracks_tmp_n = 0;
-  uint16_t* ws_keys = nullptr;  // raw-key workspace of the fused kernel for tiles that do not fit in LDS
+  DevArray<int32_t> resid_draws;  // [P] uniforms consumed by the last residual resampling
+  DevArray<uint32_t> bins16;    // [P][65535 * 3 + 1] key histograms of 16-bit frames (staged tile kernels), on first use
+  DevArray<double> fwork;       // [P][2 D^2] tile workspace of float64 frames (staged tile kernels), on first use
+  DevArray<double> tracks_tmp;  // means | sigmas in the caller's layout (glh_get_tracks), grown on use
+  DevArray<uint16_t> ws_keys;   // raw-key workspace of the fused kernel for tiles that do not fit in LDS
   int keys_cap = 0;
   int plan_N = 0;  // the N the pairwise-sum plan on the device was made for (0: none)
   bool track_covariances = false;  // glh_track_covariances
   // glh_track on two streams (glh_set_track_streams): 0 = automatic (two when the batch is at least two rounds of
   // workgroups per half), 1 = always one, 2 = two whenever the fused step runs
   int track_streams = 0;
-  hipStream_t extra_streams[3] = {nullptr, nullptr, nullptr};  // streams 2 .. 4 of glh_track
-  hipEvent_t ev_fork = nullptr, ev_join[3] = {nullptr, nullptr, nullptr};
+  Event ev_fork, ev_join[3];   // the extra streams start behind ev_fork; the context's stream ends behind ev_join
   int last_track_streams = 1;  // streams the last glh_track used
   int n_cus = 256;             // compute units of the device (hipDeviceProp: glh_create)
   // diagnostic (GLH_PT_STOP="stamp:frame", read by glh_create): the fused launches of that frame end at that phase stamp
   int stop_stamp = -1, stop_frame = -1;
-  double *sse = nullptr, *sse_copy = nullptr, *ll_dbg = nullptr;
-  double* lu = nullptr;
-  double* poly = nullptr;
-  int64_t* lu_off = nullptr;
-  double* spl_inv = nullptr;  // explicit inverses of the collocation matrices, sides 4 .. GLH_SPL_DENSE_MAX
-  int32_t *leaf_off = nullptr, *leaf_len = nullptr, *sum_ops = nullptr, *level_off = nullptr, *roots = nullptr;
+  DevArray<double> sse, sse_copy, ll_dbg;
+  DevArray<double> lu;
+  DevArray<double> poly;
+  DevArray<int64_t> lu_off;
+  DevArray<double> spl_inv;  // explicit inverses of the collocation matrices, sides 4 .. GLH_SPL_DENSE_MAX
+  DevArray<int32_t> leaf_off, leaf_len, sum_ops, level_off, roots;
   int nleaves = 0, nnodes = 0, nlevels = 0, nroots = 0;
   int moments_frame = -1;  // history slot already filled by the fused resample kernel
   int interp_k = 3;  // interpolation order of the surface sampling: 3 (bicubic, the default), 1 (bilinear), or 0: the
                      // general orders interp_kx (rows axis) / interp_ky (columns axis) (glh_set_interpolation)
   int interp_kx = 3, interp_ky = 3;
-  double* glu[2] = {nullptr, nullptr};       // general orders: spline_lu_general factors for degree kx / ky by size
-  int64_t* glu_off[2] = {nullptr, nullptr};  // [max_search_dim + 1]
+  DevArray<double> glu[2];       // general orders: spline_lu_general factors for degree kx / ky by size
+  DevArray<int64_t> glu_off[2];  // [max_search_dim + 1]
   int32_t last_variant[4] = {0, 0, 0, 0};  // fused kernel instantiation of the last step: TB, PPT, NOBS, fast | general << 1
-  size_t normals_cap = 0;
-  // profiling
+  // profiling: a timed launch takes its two events from the pool (StageTimer), leaves them in `pending`, and
+  // drain_profile puts them back
   bool profiling = false;
   struct Ev {
-    hipEvent_t a, b;
+    Event a, b;
     int stage;
   };
   std::vector<Ev> pending;
-  std::vector<hipEvent_t> pool;
+  std::vector<Event> pool;
   double ms[ST_COUNT] = {0};
   int64_t launches[ST_COUNT] = {0};
   std::vector<float> launch_ms[ST_COUNT];  // duration of every timed launch since the last reset (bounded)
   // GPU time a stage spans since the last reset: from the start of its first timed launch to the end of its last one,
   // on whichever stream (launches of glh_track's two streams overlap: their durations do not add up to it)
-  hipEvent_t span_a[ST_COUNT] = {nullptr};
+  Event span_a[ST_COUNT];
   float span_ms[ST_COUNT] = {0};
   // multi-GPU (glh_comm.h)
   Comm* comm = nullptr;
@@ -237,36 +238,21 @@ static int32_t* cur_status(const glh_ctx* c) {
   return c->obs_status_all + (size_t)c->frame * c->cfg.n_observers * c->P;
 }
 
-template <typename T>
-static int dalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e != hipSuccess)
-    return fail(GLH_E_NOMEM, "hipMalloc(%zu bytes) failed: %s", count * sizeof(T), hipGetErrorString(e));
-  return GLH_OK;
-}
-template <typename T>
-static void dfree(T*& p) {
-  if (p) (void)hipFree((void*)p);
-  p = nullptr;
-}
-
 struct StageTimer {
   glh_ctx* c;
   int stage;
-  hipEvent_t a = nullptr, b = nullptr;
+  Event a, b;
   hipStream_t s;
-  StageTimer(glh_ctx* ctx, int st, hipStream_t on = nullptr) : c(ctx), stage(st), s(on ? on : ctx->stream) {
+  StageTimer(glh_ctx* ctx, int st, hipStream_t on = nullptr) : c(ctx), stage(st), s(on ? on : ctx->stream.get()) {
     c->launches[st]++;
     if (!c->profiling) return;
     auto get = [&]() {
-      hipEvent_t e;
+      Event e;
       if (!c->pool.empty()) {
-        e = c->pool.back();
+        e = std::move(c->pool.back());
         c->pool.pop_back();
       } else {
-        (void)hipEventCreate(&e);
+        (void)e.create();
       }
       return e;
     };
@@ -277,7 +263,7 @@ struct StageTimer {
   ~StageTimer() {
     if (!a) return;
     (void)hipEventRecord(b, s);
-    c->pending.push_back({a, b, stage});
+    c->pending.push_back({std::move(a), std::move(b), stage});
   }
 };
 
@@ -290,13 +276,12 @@ static int drain_profile(glh_ctx* c) {
       c->ms[e.stage] += ms;
       if (c->launch_ms[e.stage].size() < (1u << 16)) c->launch_ms[e.stage].push_back(ms);
     }
-    if (!c->span_a[e.stage]) {
-      c->span_a[e.stage] = e.a;  // (kept until the next reset)
-    }
+    Event& first = c->span_a[e.stage];
+    if (!first) first = std::move(e.a);  // (kept until the next reset)
     float t = 0.f;
-    if (hipEventElapsedTime(&t, c->span_a[e.stage], e.b) == hipSuccess && t > c->span_ms[e.stage]) c->span_ms[e.stage] = t;
-    if (c->span_a[e.stage] != e.a) c->pool.push_back(e.a);
-    c->pool.push_back(e.b);
+    if (hipEventElapsedTime(&t, first, e.b) == hipSuccess && t > c->span_ms[e.stage]) c->span_ms[e.stage] = t;
+    if (e.a) c->pool.push_back(std::move(e.a));
+    if (e.b) c->pool.push_back(std::move(e.b));  // (null when the timer could not create it)
   }
   c->pending.clear();
   return GLH_OK;
@@ -332,59 +317,21 @@ extern "C" int glh_device_compute_units(int device_id, int* count) {
   return GLH_OK;
 }
 
+// What is left to say once the members free themselves: nothing may still run on the streams when they go.
 extern "C" int glh_destroy(glh_ctx* c) {
   if (!c) return GLH_OK;
   (void)hipSetDevice(c->cfg.device_id);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
-  if (c->comm) (void)glh_comm_destroy(c);
   if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
-  for (auto e : c->pin_ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : c->pending) {
-    (void)hipEventDestroy(e.a);
-    (void)hipEventDestroy(e.b);
-  }
-  for (auto e : c->pool) (void)hipEventDestroy(e);
-  for (int i = 0; i < ST_COUNT; ++i)
-    if (c->span_a[i]) (void)hipEventDestroy(c->span_a[i]);  // (kept out of the pool since the last reset)
-  for (int q = 0; q < 3; ++q)
-    if (c->extra_streams[q]) (void)hipStreamSynchronize(c->extra_streams[q]);
-  for (int o = 0; o < MAX_OBS; ++o) {
-    dfree(c->obs[o].cams);
-    for (auto& p : c->obs[o].owned) dfree(p);
-  }
-  for (int i = 0; i < 2; ++i) {
-    dfree(c->particles[i]);
-    dfree(c->weights[i]);
-  }
-  dfree(c->motion); dfree(c->uv); dfree(c->bbox_part); dfree(c->normals); dfree(c->u);
-  dfree(c->mean6); dfree(c->moments); dfree(c->covariances); dfree(c->uj); dfree(c->extra_ll);
-  for (auto& r : c->rasters) {
-    dfree(r.z); dfree(r.gx); dfree(r.gy);
-  } dfree(c->obs_mask); dfree(c->active); dfree(c->pt_status);
-  dfree(c->pt_err_frame); dfree(c->obs_status_all); dfree(c->box); dfree(c->idx); dfree(c->tmpl_box);
-  dfree(c->tmpl_hist_n); dfree(c->tmpl_valid); dfree(c->tmpl_duv); dfree(c->tmpl_tile64);
-  dfree(c->tmpl_hist_v); dfree(c->tmpl_hist_q); dfree(c->tmpl_tile32); dfree(c->search); dfree(c->ws_keys); dfree(c->bins16); dfree(c->fwork); dfree(c->tracks_tmp); dfree(c->resid_draws); dfree(c->uidx[0]); dfree(c->uidx[1]); dfree(c->stamps);
-  dfree(c->sse); dfree(c->sse_copy); dfree(c->ll_dbg); dfree(c->lu); dfree(c->poly); dfree(c->lu_off); dfree(c->spl_inv); dfree(c->glu[0]); dfree(c->glu[1]); dfree(c->glu_off[0]); dfree(c->glu_off[1]); dfree(c->leaf_off);
-  dfree(c->leaf_len); dfree(c->sum_ops); dfree(c->level_off); dfree(c->roots);
-  if (c->copy_stream) {
-    (void)hipStreamSynchronize(c->copy_stream);
-    (void)hipStreamDestroy(c->copy_stream);
-  }
-  for (int k = 0; k < glh_ctx::NSTAGE; ++k) {
-    if (c->stage[k]) (void)hipHostFree(c->stage[k]);
-    if (c->stage_done[k]) (void)hipEventDestroy(c->stage_done[k]);
-  }
-  if (c->upload_done) (void)hipEventDestroy(c->upload_done);
-  for (int q = 0; q < 3; ++q) {
-    if (c->extra_streams[q]) (void)hipStreamDestroy(c->extra_streams[q]);
-    if (c->ev_join[q]) (void)hipEventDestroy(c->ev_join[q]);
-  }
-  if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  for (const Stream& s : c->extra_streams)
+    if (s) (void)hipStreamSynchronize(s);
+  if (c->comm) (void)glh_comm_destroy(c);
   delete c;
   return GLH_OK;
 }
+struct CtxDestroy {
+  void operator()(glh_ctx* c) const { (void)glh_destroy(c); }
+};
 
 extern "C" int glh_create(const glh_config* cfg, glh_ctx** out) {
   if (!cfg || !out) return fail(GLH_E_INVALID, "null argument");
@@ -407,7 +354,9 @@ extern "C" int glh_create(const glh_config* cfg, glh_ctx** out) {
   if (k.device_id < 0 || k.device_id >= ndev)
     return fail(GLH_E_INVALID, "device_id %d out of range (%d devices)", k.device_id, ndev);
   HIPCHK(hipSetDevice(k.device_id));
-  glh_ctx* c = new (std::nothrow) glh_ctx();
+  // (a return below destroys the context with what it has so far; glh_destroy leaves glh_last_error() alone)
+  Owned<glh_ctx*, CtxDestroy> made(new (std::nothrow) glh_ctx());
+  glh_ctx* c = made.get();
   if (!c) return fail(GLH_E_NOMEM, "out of host memory");
   c->cfg = k;
   {
@@ -427,44 +376,35 @@ extern "C" int glh_create(const glh_config* cfg, glh_ctx** out) {
   c->keys_cap = pt_keys_count(k.max_search_dim, k.max_search_dim);  // with the reflected border
   c->sse_cap = c->search_cap;
   const size_t NBmax = (N + BLK - 1) / BLK;
-  int rc = GLH_OK;
-  auto A = [&](int r) {
-    if (rc == GLH_OK) rc = r;
-  };
-  hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    delete c;
-    return fail(GLH_E_HIP, "hipStreamCreate failed: %s", hipGetErrorString(e));
-  }
+  CHK(c->stream.create());
   for (int i = 0; i < 2; ++i) {
-    A(dalloc(&c->particles[i], P * N * 6));
-    A(dalloc(&c->weights[i], P * N));
+    CHK(c->particles[i].alloc(P * N * 6));
+    CHK(c->weights[i].alloc(P * N));
   }
-  A(dalloc(&c->motion, P * GLH_MOTION_FULL_LEN));
-  A(dalloc(&c->uv, O * P * N * 2));
-  A(dalloc(&c->bbox_part, O * P * NBmax * 5));
-  A(dalloc(&c->u, P));
-  A(dalloc(&c->mean6, P * 6));
-  A(dalloc(&c->moments, (size_t)k.max_frames * P * 12));
-  A(dalloc(&c->obs_mask, P * O));
-  A(dalloc(&c->active, P));
-  A(dalloc(&c->pt_status, P));
-  A(dalloc(&c->pt_err_frame, P));
-  A(dalloc(&c->obs_status_all, (size_t)k.max_frames * O * P));
-  A(dalloc(&c->box, O * P * 4));
-  A(dalloc(&c->tmpl_box, O * P * 4));
-  A(dalloc(&c->tmpl_hist_n, O * P));
-  A(dalloc(&c->tmpl_valid, O * P));
-  A(dalloc(&c->tmpl_duv, O * P * 2));
-  A(dalloc(&c->tmpl_tile64, O * P * c->tile_cap));
-  A(dalloc(&c->tmpl_tile32, O * P * c->tile_cap));
-  A(dalloc(&c->tmpl_hist_v, O * P * c->tile_cap));
-  A(dalloc(&c->tmpl_hist_q, O * P * c->tile_cap));
-  A(dalloc(&c->search, O * P * (size_t)c->search_cap));
-  A(dalloc(&c->ws_keys, O * P * (size_t)c->keys_cap));
-  A(dalloc(&c->sse, O * P * (size_t)c->sse_cap));
-  // spline LU table for every surface side 4..max_search_dim
-  if (rc == GLH_OK) {
+  CHK(c->motion.alloc(P * GLH_MOTION_FULL_LEN));
+  CHK(c->uv.alloc(O * P * N * 2));
+  CHK(c->bbox_part.alloc(O * P * NBmax * 5));
+  CHK(c->u.alloc(P));
+  CHK(c->mean6.alloc(P * 6));
+  CHK(c->moments.alloc((size_t)k.max_frames * P * 12));
+  CHK(c->obs_mask.alloc(P * O));
+  CHK(c->active.alloc(P));
+  CHK(c->pt_status.alloc(P));
+  CHK(c->pt_err_frame.alloc(P));
+  CHK(c->obs_status_all.alloc((size_t)k.max_frames * O * P));
+  CHK(c->box.alloc(O * P * 4));
+  CHK(c->tmpl_box.alloc(O * P * 4));
+  CHK(c->tmpl_hist_n.alloc(O * P));
+  CHK(c->tmpl_valid.alloc(O * P));
+  CHK(c->tmpl_duv.alloc(O * P * 2));
+  CHK(c->tmpl_tile64.alloc(O * P * c->tile_cap));
+  CHK(c->tmpl_tile32.alloc(O * P * c->tile_cap));
+  CHK(c->tmpl_hist_v.alloc(O * P * c->tile_cap));
+  CHK(c->tmpl_hist_q.alloc(O * P * c->tile_cap));
+  CHK(c->search.alloc(O * P * (size_t)c->search_cap));
+  CHK(c->ws_keys.alloc(O * P * (size_t)c->keys_cap));
+  CHK(c->sse.alloc(O * P * (size_t)c->sse_cap));
+  {  // spline LU table for every surface side 4..max_search_dim
     const int maxn = k.max_search_dim;
     std::vector<int64_t> off(maxn + 1, 0);
     int64_t total = 0;
@@ -474,29 +414,27 @@ extern "C" int glh_create(const glh_config* cfg, glh_ctx** out) {
     }
     std::vector<double> lu((size_t)total);
     for (int n = 4; n <= maxn; ++n) spline_lu(n, lu.data() + off[n]);
-    A(dalloc(&c->lu, (size_t)total));
-    A(dalloc(&c->lu_off, (size_t)maxn + 1));
-    if (rc == GLH_OK) {
-      if (hipMemcpy(c->lu, lu.data(), total * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-          hipMemcpy(c->lu_off, off.data(), (maxn + 1) * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
-        rc = fail(GLH_E_HIP, "upload of the spline LU table failed");
-    }
+    CHK(c->lu.alloc((size_t)total));
+    CHK(c->lu_off.alloc((size_t)maxn + 1));
+    if (hipMemcpy(c->lu, lu.data(), total * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->lu_off, off.data(), (maxn + 1) * sizeof(int64_t), hipMemcpyHostToDevice) != hipSuccess)
+      return fail(GLH_E_HIP, "upload of the spline LU table failed");
   }
-  if (rc == GLH_OK) {
+  {
     std::vector<double> inv((size_t)spline_inverse_off(GLH_SPL_DENSE_MAX + 1));
     for (int n = 4; n <= GLH_SPL_DENSE_MAX; ++n) spline_inverse(n, inv.data() + spline_inverse_off(n));
-    A(dalloc(&c->spl_inv, inv.size()));
-    if (rc == GLH_OK && hipMemcpy(c->spl_inv, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-      rc = fail(GLH_E_HIP, "upload of the spline inverse table failed");
+    CHK(c->spl_inv.alloc(inv.size()));
+    if (hipMemcpy(c->spl_inv, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      return fail(GLH_E_HIP, "upload of the spline inverse table failed");
   }
-  if (rc == GLH_OK) {
+  {
     std::vector<double> tab(16 * GLH_NPOLY);
     basis_poly_table(tab.data());
-    A(dalloc(&c->poly, tab.size()));
-    if (rc == GLH_OK && hipMemcpy(c->poly, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
-      rc = fail(GLH_E_HIP, "upload of the spline basis table failed");
+    CHK(c->poly.alloc(tab.size()));
+    if (hipMemcpy(c->poly, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)
+      return fail(GLH_E_HIP, "upload of the spline basis table failed");
   }
-  if (rc == GLH_OK) {
+  {
     // kernels that may use more than the default 64 KB of dynamic LDS
     hipError_t e1 = hipFuncSetAttribute((const void*)k_resample, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
     hipError_t e2 = hipFuncSetAttribute((const void*)k_ssd, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
@@ -508,15 +446,9 @@ extern "C" int glh_create(const glh_config* cfg, glh_ctx** out) {
       if (e != hipSuccess) e4 = e;
     }
     if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess || e4 != hipSuccess)
-      rc = fail(GLH_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
+      return fail(GLH_E_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed");
   }
-  if (rc != GLH_OK) {
-    std::string keep = g_err;
-    glh_destroy(c);
-    g_err = keep;
-    return rc;
-  }
-  *out = c;
+  *out = made.release();
   return GLH_OK;
 }
 
@@ -560,8 +492,8 @@ extern "C" int glh_observer_init(glh_ctx* c, int o, int n_images, int width, int
   if (!(sigma > 0.0)) return fail(GLH_E_INVALID, "sigma must be > 0");
   HIPCHK(hipSetDevice(c->cfg.device_id));
   Observer& ob = c->obs[o];
-  dfree(ob.cams);
-  for (auto& p : ob.owned) dfree(p);
+  ob.cams.reset();
+  ob.owned.clear();  // (frees the frames of an earlier init)
   ob.n_images = n_images;
   ob.width = width;
   ob.height = height;
@@ -569,8 +501,8 @@ extern "C" int glh_observer_init(glh_ctx* c, int o, int n_images, int width, int
   ob.bits = 8;
   ob.sigma = sigma;
   ob.frames.assign(n_images, nullptr);
-  ob.owned.assign(n_images, nullptr);
-  CHK(dalloc(&ob.cams, (size_t)n_images));
+  ob.owned.resize(n_images);
+  CHK(ob.cams.alloc((size_t)n_images));
   return GLH_OK;
 }
 
@@ -622,10 +554,23 @@ extern "C" int glh_observer_upload_frame(glh_ctx* c, int o, int image, const uin
   if (!pixels || image < 0 || image >= ob.n_images) return fail(GLH_E_INVALID, "bad frame index %d", image);
   HIPCHK(hipSetDevice(c->cfg.device_id));
   size_t bytes = ob.frame_bytes();
-  if (!ob.owned[image]) CHK(dalloc(&ob.owned[image], bytes));
+  if (!ob.owned[image]) CHK(ob.owned[image].alloc(bytes));
   HIPCHK(hipMemcpyAsync(ob.owned[image], pixels, bytes, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   ob.frames[image] = ob.owned[image];
+  return GLH_OK;
+}
+
+// The copy stream and the event that marks its latest upload come together, on the first async or pinned upload: a
+// failure between the two leaves neither behind.
+static int open_copy_stream(glh_ctx* c) {
+  if (c->copy_stream) return GLH_OK;
+  Stream s;
+  Event done;
+  CHK(s.create());
+  CHK(done.create(hipEventDisableTiming));
+  c->copy_stream = std::move(s);
+  c->upload_done = std::move(done);
   return GLH_OK;
 }
 
@@ -638,27 +583,18 @@ extern "C" int glh_observer_upload_frame_async(glh_ctx* c, int o, int image, con
   if (!pixels || image < 0 || image >= ob.n_images) return fail(GLH_E_INVALID, "bad frame index %d", image);
   HIPCHK(hipSetDevice(c->cfg.device_id));
   const size_t bytes = ob.frame_bytes();
-  if (!c->copy_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->upload_done, hipEventDisableTiming));
-  }
+  CHK(open_copy_stream(c));
   const int k = c->stage_next;
   c->stage_next = (k + 1) % glh_ctx::NSTAGE;
   if (c->stage_busy[k]) {  // the copy that last used this slot has to be over before it is overwritten
     HIPCHK(hipEventSynchronize(c->stage_done[k]));
     c->stage_busy[k] = false;
   }
-  if (c->stage_bytes[k] < bytes) {
-    if (c->stage[k]) HIPCHK(hipHostFree(c->stage[k]));
-    c->stage[k] = nullptr;
-    c->stage_bytes[k] = 0;
-    HIPCHK(hipHostMalloc((void**)&c->stage[k], bytes, hipHostMallocDefault));
-    c->stage_bytes[k] = bytes;
-  }
-  if (!c->stage_done[k]) HIPCHK(hipEventCreateWithFlags(&c->stage_done[k], hipEventDisableTiming));
-  memcpy(c->stage[k], pixels, bytes);
-  if (!ob.owned[image]) CHK(dalloc(&ob.owned[image], bytes));
-  HIPCHK(hipMemcpyAsync(ob.owned[image], c->stage[k], bytes, hipMemcpyHostToDevice, c->copy_stream));
+  CHK(c->stage[k].reserve(bytes));
+  if (!c->stage_done[k]) CHK(c->stage_done[k].create(hipEventDisableTiming));
+  memcpy(c->stage[k].get(), pixels, bytes);
+  if (!ob.owned[image]) CHK(ob.owned[image].alloc(bytes));
+  HIPCHK(hipMemcpyAsync(ob.owned[image], c->stage[k].get(), bytes, hipMemcpyHostToDevice, c->copy_stream));
   HIPCHK(hipEventRecord(c->stage_done[k], c->copy_stream));
   HIPCHK(hipEventRecord(c->upload_done, c->copy_stream));
   c->stage_busy[k] = true;
@@ -701,15 +637,12 @@ extern "C" int glh_observer_upload_frame_pinned(glh_ctx* c, int o, int image, co
   if (!pixels || !ticket || image < 0 || image >= ob.n_images) return fail(GLH_E_INVALID, "bad frame index %d", image);
   HIPCHK(hipSetDevice(c->cfg.device_id));
   const size_t bytes = ob.frame_bytes();
-  if (!c->copy_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->upload_done, hipEventDisableTiming));
-  }
+  CHK(open_copy_stream(c));
   const int64_t t = c->pin_next;
   if (t - c->pin_completed >= glh_ctx::NPIN) CHK(pin_poll(c, t - glh_ctx::NPIN));  // (its event is about to be reused)
-  hipEvent_t& e = c->pin_ev[t % glh_ctx::NPIN];
-  if (!e) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  if (!ob.owned[image]) CHK(dalloc(&ob.owned[image], bytes));
+  Event& e = c->pin_ev[t % glh_ctx::NPIN];
+  if (!e) CHK(e.create(hipEventDisableTiming));
+  if (!ob.owned[image]) CHK(ob.owned[image].alloc(bytes));
   HIPCHK(hipMemcpyAsync(ob.owned[image], pixels, bytes, hipMemcpyHostToDevice, c->copy_stream));
   HIPCHK(hipEventRecord(e, c->copy_stream));
   HIPCHK(hipEventRecord(c->upload_done, c->copy_stream));
@@ -733,7 +666,7 @@ extern "C" int glh_observer_set_frame_device(glh_ctx* c, int o, int image, const
   CHK(check_obs(c, o));
   Observer& ob = c->obs[o];
   if (!dev || image < 0 || image >= ob.n_images) return fail(GLH_E_INVALID, "bad frame index %d", image);
-  dfree(ob.owned[image]);
+  ob.owned[image].reset();  // (the caller's memory is borrowed: `owned` stays null and nothing here frees it)
   ob.frames[image] = (const uint8_t*)dev;
   return GLH_OK;
 }
@@ -783,13 +716,12 @@ extern "C" int glh_begin_sequence(glh_ctx* c, int P, int N, int tw, int th) {
   if (c->plan_N != N) {
     PairwisePlan pl;
     pairwise_plan(N, pl);
-    dfree(c->leaf_off); dfree(c->leaf_len); dfree(c->sum_ops); dfree(c->level_off); dfree(c->roots);
-    c->plan_N = 0;
-    CHK(dalloc(&c->leaf_off, pl.leaf_off.size()));
-    CHK(dalloc(&c->leaf_len, pl.leaf_len.size()));
-    CHK(dalloc(&c->sum_ops, pl.ops.size()));
-    CHK(dalloc(&c->level_off, pl.level_off.size()));
-    CHK(dalloc(&c->roots, pl.roots.size()));
+    c->plan_N = 0;  // (no plan while its arrays are replaced: a failure half way leaves none marked valid)
+    CHK(c->leaf_off.alloc(pl.leaf_off.size()));
+    CHK(c->leaf_len.alloc(pl.leaf_len.size()));
+    CHK(c->sum_ops.alloc(pl.ops.size()));
+    CHK(c->level_off.alloc(pl.level_off.size()));
+    CHK(c->roots.alloc(pl.roots.size()));
     HIPCHK(hipMemcpy(c->leaf_off, pl.leaf_off.data(), pl.leaf_off.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(c->leaf_len, pl.leaf_len.data(), pl.leaf_len.size() * 4, hipMemcpyHostToDevice));
     if (!pl.ops.empty()) HIPCHK(hipMemcpy(c->sum_ops, pl.ops.data(), pl.ops.size() * 4, hipMemcpyHostToDevice));
@@ -906,7 +838,7 @@ extern "C" int glh_set_raster(glh_ctx* c, int which, const double* z, int nx, in
   if (!z && !r.z) return GLH_OK;  // (no raster before, none now: nothing to wait for -- the usual call of every run)
   HIPCHK(hipSetDevice(c->cfg.device_id));
   HIPCHK(hipStreamSynchronize(c->stream));
-  dfree(r.z); dfree(r.gx); dfree(r.gy);
+  r.z.reset(), r.gx.reset(), r.gy.reset();
   r.dev = RasterDev{};
   r.hgx.clear();
   r.hgy.clear();
@@ -918,9 +850,9 @@ extern "C" int glh_set_raster(glh_ctx* c, int which, const double* z, int nx, in
   if (which == GLH_RASTER_DEM_SIGMA)
     for (size_t i = 0; i < (size_t)nx * ny && c->fast_bad_node == 0.0; ++i)
       if (sigma_outside_fast_domain(z[i])) c->fast_bad_node = z[i];
-  CHK(dalloc(&r.z, (size_t)nx * ny));
-  CHK(dalloc(&r.gx, (size_t)nx));
-  CHK(dalloc(&r.gy, (size_t)ny));
+  CHK(r.z.alloc((size_t)nx * ny));
+  CHK(r.gx.alloc((size_t)nx));
+  CHK(r.gy.alloc((size_t)ny));
   HIPCHK(hipMemcpy(r.z, z, (size_t)nx * ny * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(r.gx, gx, (size_t)nx * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(r.gy, gy, (size_t)ny * sizeof(double), hipMemcpyHostToDevice));
@@ -995,7 +927,7 @@ extern "C" int glh_set_extra_log_likelihoods(glh_ctx* c, const double* ll) {
   CHK(need_seq(c));
   c->have_extra = ll != nullptr;
   if (!ll) return GLH_OK;
-  if (!c->extra_ll) CHK(dalloc(&c->extra_ll, (size_t)c->cfg.max_points * c->cfg.max_particles));
+  if (!c->extra_ll) CHK(c->extra_ll.alloc((size_t)c->cfg.max_points * c->cfg.max_particles));
   UPLOAD(c->extra_ll, ll, (size_t)c->P * c->N, double);
   return GLH_OK;
 }
@@ -1089,24 +1021,20 @@ extern "C" int glh_set_debug(glh_ctx* c, int keep) {
   if (keep < 0 || keep > 2) return fail(GLH_E_INVALID, "keep must be 0, 1 or 2");
   c->keep_sse = keep == 1;
   c->keep_idx = keep != 0;
-  if (keep == 2 && !c->idx) CHK(dalloc(&c->idx, (size_t)c->cfg.max_points * c->cfg.max_particles));
+  if (keep == 2 && !c->idx) CHK(c->idx.alloc((size_t)c->cfg.max_points * c->cfg.max_particles));
   if (keep == 1) {
     if (!c->sse_copy)
-      CHK(dalloc(&c->sse_copy, (size_t)c->cfg.n_observers * c->cfg.max_points * (size_t)c->sse_cap));
-    if (!c->idx) CHK(dalloc(&c->idx, (size_t)c->cfg.max_points * c->cfg.max_particles));
+      CHK(c->sse_copy.alloc((size_t)c->cfg.n_observers * c->cfg.max_points * (size_t)c->sse_cap));
+    if (!c->idx) CHK(c->idx.alloc((size_t)c->cfg.max_points * c->cfg.max_particles));
     if (!c->ll_dbg)
-      CHK(dalloc(&c->ll_dbg, (size_t)c->cfg.n_observers * c->cfg.max_points * c->cfg.max_particles));
+      CHK(c->ll_dbg.alloc((size_t)c->cfg.n_observers * c->cfg.max_points * c->cfg.max_particles));
   }
   return GLH_OK;
 }
 
 // staging of host-fed random numbers (parity mode)
 static int stage_normals(glh_ctx* c, const double* host, size_t count) {
-  if (count > c->normals_cap) {
-    dfree(c->normals);
-    CHK(dalloc(&c->normals, count));
-    c->normals_cap = count;
-  }
+  CHK(c->normals.reserve(count));
   HIPCHK(hipMemcpyAsync(c->normals, host, count * sizeof(double), hipMemcpyHostToDevice, c->stream));
   // the host buffer may be reused by the caller right away
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -1172,10 +1100,10 @@ static void fill_obs(glh_ctx* c, int o, int image, ObsFrame* f) {
 // 16-bit frames: the zeroed per-point key histograms the staged tile kernels of observer `o` count into
 static int prepare_bins16(glh_ctx* c, int o, bool search_tiles = false) {
   if (c->obs[o].bits >= 16 && !c->fwork)  // 16-bit and float frames: two tile-sized arrays of doubles per point
-    CHK(dalloc(&c->fwork, (size_t)c->cfg.max_points * 2 * c->cfg.max_search_dim * c->cfg.max_search_dim));
+    CHK(c->fwork.alloc((size_t)c->cfg.max_points * 2 * c->cfg.max_search_dim * c->cfg.max_search_dim));
   if (c->obs[o].bits != 16 || search_tiles) return GLH_OK;  // (search tiles are ranked; only templates count into bins)
   const size_t per = (size_t)(65535 * 3 + 1);
-  if (!c->bins16) CHK(dalloc(&c->bins16, (size_t)c->cfg.max_points * per));
+  if (!c->bins16) CHK(c->bins16.alloc((size_t)c->cfg.max_points * per));
   HIPCHK(hipMemsetAsync(c->bins16, 0, (size_t)c->P * (65535 * c->obs[o].channels + 1) * sizeof(uint32_t), c->stream));
   return GLH_OK;
 }
@@ -1489,12 +1417,12 @@ extern "C" int glh_resample_method(glh_ctx* c, int method, int rng_mode, const d
   if (method != GLH_RESAMPLE_SYSTEMATIC && method != GLH_RESAMPLE_STRATIFIED && method != GLH_RESAMPLE_CHOICE &&
       method != GLH_RESAMPLE_RESIDUAL)
     return fail(GLH_E_INVALID, "unknown resampling method %d", method);
-  if (method == GLH_RESAMPLE_RESIDUAL && !c->resid_draws) CHK(dalloc(&c->resid_draws, (size_t)c->cfg.max_points));
+  if (method == GLH_RESAMPLE_RESIDUAL && !c->resid_draws) CHK(c->resid_draws.alloc((size_t)c->cfg.max_points));
   const bool per_particle = method != GLH_RESAMPLE_SYSTEMATIC;
   if (rng_mode == GLH_RNG_HOST) {
     if (!u) return fail(GLH_E_INVALID, "GLH_RNG_HOST needs u (%s)", per_particle ? "[P][N]" : "[P]");
     if (per_particle) {
-      if (!c->uj) CHK(dalloc(&c->uj, (size_t)c->cfg.max_points * c->cfg.max_particles));
+      if (!c->uj) CHK(c->uj.alloc((size_t)c->cfg.max_points * c->cfg.max_particles));
       HIPCHK(hipMemcpyAsync(c->uj, u, (size_t)c->P * c->N * sizeof(double), hipMemcpyHostToDevice, c->stream));
     } else {
       HIPCHK(hipMemcpyAsync(c->u, u, (size_t)c->P * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1603,7 +1531,7 @@ static int fused_step(glh_ctx* c, int frame, double tau, const int32_t* images, 
   a.poly = c->poly;
   a.idx_out = c->keep_idx ? c->idx : nullptr;
   for (int b = 0; b < 2; ++b)
-    if (!c->uidx[b]) CHK(dalloc(&c->uidx[b], (size_t)c->cfg.max_points * c->cfg.max_particles));
+    if (!c->uidx[b]) CHK(c->uidx[b].alloc((size_t)c->cfg.max_points * c->cfg.max_particles));
   a.uidx_in = c->compact ? c->uidx[c->cur] : nullptr;
   a.uidx_out = c->uidx[c->cur ^ 1];
   a.stamps = c->stamps ? c->stamps + (size_t)pt0 * PT_NSTAMP : nullptr;  // (indexed by the launch's own block index)
@@ -1694,7 +1622,7 @@ extern "C" int glh_record_covariances(glh_ctx* c, int frame) {
   if (frame < 0 || frame >= c->cfg.max_frames) return fail(GLH_E_INVALID, "frame %d outside [0, max_frames)", frame);
   if (!c->covariances) {
     const size_t n = (size_t)c->cfg.max_frames * c->cfg.max_points * 36;
-    CHK(dalloc(&c->covariances, n));
+    CHK(c->covariances.alloc(n));
     hipLaunchKernelGGL(k_fill_f64, dim3(256), dim3(256), 0, c->stream, c->covariances, n, (double)NAN);
     HIPCHK(hipGetLastError());
   }
@@ -1783,13 +1711,11 @@ extern "C" int glh_track(glh_ctx* c, int n_frames, const int32_t* frames, const 
     return rc;
   }
   HIPCHK(hipSetDevice(c->cfg.device_id));
-  if (!c->ev_fork) HIPCHK(hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
+  if (!c->ev_fork) CHK(c->ev_fork.create(hipEventDisableTiming));
   hipStream_t on[4] = {c->stream, nullptr, nullptr, nullptr};
   for (int q = 1; q < ns; ++q) {
-    if (!c->extra_streams[q - 1]) {
-      HIPCHK(hipStreamCreateWithFlags(&c->extra_streams[q - 1], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->ev_join[q - 1], hipEventDisableTiming));
-    }
+    if (!c->extra_streams[q - 1]) CHK(c->extra_streams[q - 1].create());
+    if (!c->ev_join[q - 1]) CHK(c->ev_join[q - 1].create(hipEventDisableTiming));
     on[q] = c->extra_streams[q - 1];
   }
   // the other streams start behind everything enqueued so far, and the context's stream ends behind them
@@ -1836,28 +1762,22 @@ extern "C" int glh_track_covariances(glh_ctx* c, int on) {
 extern "C" int glh_measure_copy_bandwidth(glh_ctx* c, uint64_t bytes, int iters, double* gbps) {
   if (!c || !gbps || bytes == 0 || iters <= 0) return fail(GLH_E_INVALID, "bad argument");
   HIPCHK(hipSetDevice(c->cfg.device_id));
-  uint8_t *src = nullptr, *dst = nullptr;
-  CHK(dalloc(&src, (size_t)bytes));
-  if (dalloc(&dst, (size_t)bytes) != GLH_OK) {
-    dfree(src);
-    return GLH_E_NOMEM;
-  }
-  hipEvent_t e0 = nullptr, e1 = nullptr;
+  DevArray<uint8_t> src, dst;
+  CHK(src.alloc((size_t)bytes));
+  CHK(dst.alloc((size_t)bytes));
+  Event e0, e1;
   float ms = 0.0f;
   hipError_t err = hipMemsetAsync(src, 1, bytes, c->stream);
   if (err == hipSuccess) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream);  // warm-up
-  if (err == hipSuccess) err = hipEventCreate(&e0);
-  if (err == hipSuccess) err = hipEventCreate(&e1);
+  // (the two empty owners are filled in place, not by Event::create: a failure stays in `err` and is reported below)
+  if (err == hipSuccess) err = hipEventCreate(&e0.p);
+  if (err == hipSuccess) err = hipEventCreate(&e1.p);
   if (err == hipSuccess) err = hipEventRecord(e0, c->stream);
   for (int k = 0; k < iters && err == hipSuccess; ++k)
     err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream);
   if (err == hipSuccess) err = hipEventRecord(e1, c->stream);
   if (err == hipSuccess) err = hipEventSynchronize(e1);
   if (err == hipSuccess) err = hipEventElapsedTime(&ms, e0, e1);
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  dfree(src);
-  dfree(dst);
   if (err != hipSuccess) return fail(GLH_E_HIP, "copy bandwidth measurement failed: %s", hipGetErrorString(err));
   *gbps = 2.0 * (double)bytes * iters / ((double)ms * 1e-3) / 1e9;
   return GLH_OK;
@@ -1875,8 +1795,8 @@ extern "C" int glh_debug_draws(glh_ctx* c, int kind, uint64_t seed, uint64_t ste
   HIPCHK(hipSetDevice(c->cfg.device_id));
   const size_t per = kind == 0 ? 6 : (kind == 1 ? 3 : 0);
   const size_t count = kind == 2 ? (size_t)c->P : (size_t)c->P * c->N * per;
-  double* buf = nullptr;
-  CHK(dalloc(&buf, count));
+  DevArray<double> buf;
+  CHK(buf.alloc(count));
   DrawsArgs a{};
   a.out = buf;
   a.seed = seed;
@@ -1889,7 +1809,6 @@ extern "C" int glh_debug_draws(glh_ctx* c, int kind, uint64_t seed, uint64_t ste
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipMemcpyAsync(out, buf, count * sizeof(double), hipMemcpyDeviceToHost, c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-  dfree(buf);
   if (e != hipSuccess) return fail(GLH_E_HIP, "glh_debug_draws failed: %s", hipGetErrorString(e));
   return GLH_OK;
 }
@@ -1901,7 +1820,7 @@ extern "C" int glh_debug_phase_stamps(glh_ctx* c, uint64_t* stamps) {
   const size_t n = (size_t)c->P * PT_NSTAMP;
   if (!c->stamps) {
     // first call arms the stamps; the next fused steps record them
-    CHK(dalloc(&c->stamps, (size_t)c->cfg.max_points * PT_NSTAMP));
+    CHK(c->stamps.alloc((size_t)c->cfg.max_points * PT_NSTAMP));
     HIPCHK(hipMemset(c->stamps, 0, (size_t)c->cfg.max_points * PT_NSTAMP * sizeof(unsigned long long)));
     memset(stamps, 0, n * sizeof(uint64_t));
     return GLH_OK;
@@ -1934,8 +1853,8 @@ extern "C" int glh_set_interpolation(glh_ctx* c, int kx, int ky) {
                 GLH_SPL_KMAX);
   HIPCHK(hipSetDevice(c->cfg.device_id));
   for (int q = 0; q < 2; ++q) {
-    dfree(c->glu[q]);
-    dfree(c->glu_off[q]);
+    c->glu[q].reset();
+    c->glu_off[q].reset();
   }
   c->interp_kx = kx;
   c->interp_ky = ky;
@@ -1955,8 +1874,8 @@ extern "C" int glh_set_interpolation(glh_ctx* c, int kx, int ky) {
       for (int n = k + 1; n <= maxn; ++n)
         if (!spline_lu_general(n, k, lu.data() + off[n]))
           return fail(GLH_E_STATE, "spline collocation matrix of size %d, degree %d has support outside its band", n, k);
-      CHK(dalloc(&c->glu[q], (size_t)total));
-      CHK(dalloc(&c->glu_off[q], (size_t)maxn + 1));
+      CHK(c->glu[q].alloc((size_t)total));
+      CHK(c->glu_off[q].alloc((size_t)maxn + 1));
       HIPCHK(hipMemcpy(c->glu[q], lu.data(), (size_t)total * sizeof(double), hipMemcpyHostToDevice));
       HIPCHK(hipMemcpy(c->glu_off[q], off.data(), (size_t)(maxn + 1) * sizeof(int64_t), hipMemcpyHostToDevice));
     }
@@ -1995,13 +1914,7 @@ extern "C" int glh_get_tracks(glh_ctx* c, int frame0, int n_frames, double* mean
     return fail(GLH_E_INVALID, "bad frame range or null output");
   HIPCHK(hipSetDevice(c->cfg.device_id));
   const size_t n = (size_t)n_frames * c->P * 6;
-  if (c->tracks_tmp_n < 2 * n) {
-    dfree(c->tracks_tmp);
-    c->tracks_tmp = nullptr;
-    c->tracks_tmp_n = 0;
-    CHK(dalloc(&c->tracks_tmp, 2 * n));
-    c->tracks_tmp_n = 2 * n;
-  }
+  CHK(c->tracks_tmp.reserve(2 * n));
   hipLaunchKernelGGL(k_tracks_layout, dim3((unsigned)((n + BLK - 1) / BLK)), dim3(BLK), 0, c->stream,
                      c->moments + (size_t)frame0 * c->P * 12, n_frames, c->P, c->tracks_tmp, c->tracks_tmp + n);
   HIPCHK(hipGetLastError());
@@ -2076,8 +1989,7 @@ extern "C" int glh_profile_reset(glh_ctx* c) {
     c->ms[i] = 0;
     c->launches[i] = 0;
     c->launch_ms[i].clear();
-    if (c->span_a[i]) c->pool.push_back(c->span_a[i]);
-    c->span_a[i] = nullptr;
+    if (c->span_a[i]) c->pool.push_back(std::move(c->span_a[i]));  // (which leaves span_a[i] null)
     c->span_ms[i] = 0.f;
   }
   return GLH_OK;
@@ -2138,9 +2050,7 @@ static int comm_free(glh_ctx* c) {
   (void)hipStreamSynchronize(c->stream);
   RcclApi* api = rccl_api();
   if (k->comm && api) (void)api->CommDestroy(k->comm);
-  dfree(k->stage);
-  dfree(k->scalar);
-  delete k;
+  delete k;  // (with its staging and scalar buffers)
   return GLH_OK;
 }
 
@@ -2168,7 +2078,7 @@ extern "C" int glh_comm_init(glh_ctx* c, const char* id, int rank, int world) {
     return fail(GLH_E_COMM, "ncclCommInitRank(rank %d of %d, device %d) failed: %s", rank, world, c->cfg.device_id,
                 api->GetErrorString(r));
   }
-  if (dalloc(&k->scalar, 2) != GLH_OK) {
+  if (k->scalar.alloc(2) != GLH_OK) {
     (void)api->CommDestroy(k->comm);
     delete k;
     return GLH_E_NOMEM;
@@ -2230,23 +2140,15 @@ extern "C" int glh_gather_moments(glh_ctx* c, int root, int frame0, int n_frames
   }
   const size_t mom_doubles = total_pts * (size_t)n_frames * 12;
   const size_t st_off = (mom_doubles * 8 + 15) & ~(size_t)15;  // bytes
-  if (is_root) {
-    const size_t need = st_off + total_pts * 4;
-    if (k->stage_bytes < need) {
-      dfree(k->stage);
-      k->stage_bytes = 0;
-      CHK(dalloc((uint8_t**)&k->stage, need));
-      k->stage_bytes = need;
-    }
-  }
+  if (is_root) CHK(k->stage.reserve(st_off + total_pts * 4));
   const double* mine = c->moments + (size_t)frame0 * c->P * 12;
   NCCLCHK(api, api->GroupStart());
   ncclResult_t r1 = api->Send(mine, (size_t)n_frames * c->P * 12, ncclDouble, root, k->comm, c->stream);
   ncclResult_t r2 = api->Send(c->pt_status, (size_t)c->P, ncclUint32, root, k->comm, c->stream);
   ncclResult_t r3 = ncclSuccess;
   if (is_root) {
-    double* dst = k->stage;
-    uint32_t* sdst = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(k->stage) + st_off);
+    double* dst = k->stage.as<double>();
+    uint32_t* sdst = reinterpret_cast<uint32_t*>(k->stage.as<uint8_t>() + st_off);
     for (int r = 0; r < k->world && r3 == ncclSuccess; ++r) {
       const size_t pr = (size_t)points_per_rank[r];
       r3 = api->Recv(dst, pr * n_frames * 12, ncclDouble, r, k->comm, c->stream);
@@ -2262,9 +2164,9 @@ extern "C" int glh_gather_moments(glh_ctx* c, int root, int frame0, int n_frames
     k->gathered_doubles = mom_doubles;
     k->gathered_points = total_pts;
     k->gathered_status_off = st_off;
-    if (out) HIPCHK(hipMemcpyAsync(out, k->stage, mom_doubles * 8, hipMemcpyDeviceToHost, c->stream));
+    if (out) HIPCHK(hipMemcpyAsync(out, k->stage.p, mom_doubles * 8, hipMemcpyDeviceToHost, c->stream));
     if (out && status)
-      HIPCHK(hipMemcpyAsync(status, reinterpret_cast<uint8_t*>(k->stage) + st_off, total_pts * 4, hipMemcpyDeviceToHost,
+      HIPCHK(hipMemcpyAsync(status, k->stage.as<uint8_t>() + st_off, total_pts * 4, hipMemcpyDeviceToHost,
                             c->stream));
   }
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -2276,12 +2178,12 @@ extern "C" int glh_gather_moments(glh_ctx* c, int root, int frame0, int n_frames
 extern "C" int glh_get_gathered(glh_ctx* c, double* out, uint32_t* status) {
   CHK(need_comm(c));
   Comm* k = c->comm;
-  if (!k->stage || !k->gathered_doubles) return fail(GLH_E_STATE, "no gathered moments on this rank");
+  if (!k->stage.p || !k->gathered_doubles) return fail(GLH_E_STATE, "no gathered moments on this rank");
   if (!out) return fail(GLH_E_INVALID, "out is null");
   HIPCHK(hipSetDevice(c->cfg.device_id));
-  HIPCHK(hipMemcpyAsync(out, k->stage, k->gathered_doubles * 8, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(out, k->stage.p, k->gathered_doubles * 8, hipMemcpyDeviceToHost, c->stream));
   if (status)
-    HIPCHK(hipMemcpyAsync(status, reinterpret_cast<uint8_t*>(k->stage) + k->gathered_status_off, k->gathered_points * 4,
+    HIPCHK(hipMemcpyAsync(status, k->stage.as<uint8_t>() + k->gathered_status_off, k->gathered_points * 4,
                           hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return GLH_OK;

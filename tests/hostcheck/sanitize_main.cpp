@@ -1,5 +1,6 @@
 // sanitize_main.cpp -- TEST-ONLY: the host-side tables and stage math of glimpse_amd/csrc (glh_host.h, glh_math.h,
-// glh_median.h, glh_point_plan.h: what the C ABI builds on the host before every launch, and the inline functions shared with the kernels)
+// glh_median.h, glh_point_plan.h: what the C ABI builds on the host before every launch, and the inline functions shared with the kernels;
+// glh_owned.h: the owner that frees what the C ABI allocates)
 // exercised under AddressSanitizer + UndefinedBehaviorSanitizer on the CPU (GPU sanitizers are not available on the
 // pool).  Built and run by tests/test_hostcheck.py; never part of the product.
 #include <cmath>
@@ -13,6 +14,7 @@
 #include "../../glimpse_amd/csrc/glh_math.h"
 #include "../../glimpse_amd/csrc/glh_median.h"
 #include "../../glimpse_amd/csrc/glh_point_plan.h"
+#include "owner_cases.h"
 #include "plan_sweep.h"
 
 using namespace glh;
@@ -49,6 +51,8 @@ int main() {
     REQUIRE(pt_plan_sweep(32768, &accepted) == 0);
     REQUIRE(accepted > 0);
   }
+  // the owner of every device resource, with a release that counts (owner_cases.h)
+  REQUIRE(owner_cases() == 0);
   // spline tables: LU factors and explicit inverses for every size, inverse * matrix = identity
   for (int n = 4; n <= 64; ++n) {
     std::vector<double> lu(5 * n);

@@ -3,7 +3,8 @@
 // directly.  Arrays of 0 and 1 elements and of 15, 16 and 17 bytes, of two element types, in every order of three: the
 // offsets are those of a sequence of StageLayout::place calls, multiples of 16; put reads exactly count * sizeof(T) from
 // a source that is a heap block of just that size (the sanitizer's red zones lie either side of it) and writes exactly
-// those bytes; an empty array has an offset and copies nothing; the total is StageLayout::size.
+// those bytes; an empty array has an offset and copies nothing; the total is StageLayout::size.  Then the owner that frees
+// every buffer, stream and event of the library (csrc/glh_owned.h), with a release that counts: owner_cases.h.
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../glimpse_amd/csrc/glh_stage_layout.h"
+#include "owner_cases.h"
 
 using namespace glh;
 
@@ -149,6 +151,7 @@ int main() {
   check_sequences();
   check_neighbours();
   check_rooms();
+  EXPECT(owner_cases() == 0);
   if (failures) {
     std::printf("%d failures\n", failures);
     return 1;
